@@ -1,6 +1,7 @@
 """Headline benchmark of the ChimeraLM `predict` hot path on MI355X (contract: see the task description).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--bases 8192] [--precision P]     (N > 1: starts its own ranks)
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -11,8 +12,15 @@ and the per-read logits are all-gathered over RCCL inside the step; the global b
 as BASELINE.json's configs[2]/[3] state (8k-bp reads, batch = 256 at 1/2/4/8 GPUs).
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (longest accumulated device time over the timed
-region, measured with HIP events on the launch stream by the engine's own taps); `cpu_baseline` is the CPU oracle
-(oracle/hyena_oracle.py, a port of the reference path) timed on the host cores of this box on a bounded sample.
+region, measured with HIP events on the launch stream by the engine's own taps).
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` / `ms_per_step` and what the timed region's
+own taps give (`roofline`, `stage_ms_share`, `p50_batch_latency_ms`, the guard's verdict).  `--full` adds the legs that
+cost runs of their own after the timed steps: `cpu_baseline` (the CPU oracle, oracle/hyena_oracle.py, a port of the
+reference path, timed on the host cores of this box on a bounded sample), `fp32_exact_reads_per_s` (the exact-fp32
+engine on the same batches, and for modes without a self-check their distance to it), `pcie_inclusive_reads_per_s` and
+`p50_host_visible_latency_ms`.  `--dump-outputs DIR` writes the logits of the last timed step as DIR/logits.npy (float32,
+the whole global batch); inputs and weights are seeded, so two builds run with the same arguments compare output for output.
 """
 from __future__ import annotations
 
@@ -103,6 +111,16 @@ def synthetic_ids(batch_index: int, batch: int, bases: int) -> np.ndarray:
     return np.concatenate([ids, np.ones((batch, 1), np.uint8)], axis=1)
 
 
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """`--dump-outputs`: every array as out_dir/<name>.npy in float32 (logits: a few KB, far under the 64 MB cap)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(v.nbytes for v in host.values()) <= 64 << 20, "--dump-outputs: over 64 MB"
+    for k, v in host.items():
+        np.save(d / f"{k}.npy", v)
+
+
 def cpu_baseline(bases: int, budget_s: float = 20.0) -> dict:
     from oracle import hyena_oracle as ho
 
@@ -161,6 +179,8 @@ def bench_transformer(a):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"logits": out})
     assert out.shape[0] == a.batch and bool(torch.isfinite(out).all())
     prof = net.profile_read(reset=True) if a.precision != "fp32" else {}
     if rank == 0:
@@ -238,11 +258,16 @@ def main():
     ap.add_argument("--no-guard", action="store_true", help="developer A/B runs (timing-only library builds give wrong logits): selfcheck off")
     ap.add_argument("--mlp-lo", action="store_true", help="fp16c: start at the guard's second level (fc1 / fc2 on hi + lo weights) -- "
                     "what the product runs on weights whose MLP rounding shows; to price that level")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-leg", action="store_true", help="skip the extra exact-fp32 timing (fp32_exact_reads_per_s)")
+    ap.add_argument("--full", action="store_true", help="also run the legs outside the headline: CPU baseline, exact-fp32 leg, "
+                    "PCIe-inclusive rate, host-visible latency")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-fp32-leg", action="store_true", help="--full without the extra exact-fp32 timing (fp32_exact_reads_per_s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's logits as DIR/logits.npy (float32)")
     ap.add_argument("--net", default="hyena", choices=["hyena", "transformer"],
                     help="hyena = the production predict path (the headline metric); transformer = SequenceCNNTransformer")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` by itself: one rank per GPU, started here -- BEFORE anything in this process touches HIP -- under
         # torch.distributed.run on a port that is free now (as `chimeralm_amd predict -g N` does).  Rank 0's JSON line is the
@@ -355,6 +380,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:                 # before the --full legs below reuse logits2[0]
+        dump_outputs(a.dump_outputs, {"logits": out})
     prof = eng.profile_read(reset=True)
     eff = eng.effective_precision(L)                 # what reads of this length ran in, after the guard's verdict(s)
     guard = None
@@ -390,7 +417,7 @@ def main():
     # PCIe-inclusive rate (reported beside `value`, never as it): the same batches start in page-locked HOST memory, are
     # staged as uint8 on the engine's copy stream (clm_stage_ids) one batch ahead of the forward that consumes them
     host_rate = None
-    if world == 1:
+    if world == 1 and a.full:
         from chimeralm_amd._native import DT_U8
         hb = [b.cpu().pin_memory() for b in batches]
         k = max(2, min(a.steps, 6))
@@ -408,16 +435,17 @@ def main():
     assert out.shape[0] == a.batch and (bool(torch.isfinite(out).all()) or os.environ.get("CLM_TIMING_ONLY") == "1")
     # latency as BASELINE.json words it: enqueue of a ready (device-resident) batch -> logits visible on the host, one batch in
     # flight (the throughput loop above keeps the queue full instead)
-    host_logits = torch.empty((hi - lo, 2), dtype=torch.float32).pin_memory()
     host_lat = []
-    for i in range(max(3, min(a.steps, 10))):
-        torch.cuda.synchronize(device)
-        t2 = time.perf_counter()
-        eng.forward(batches[i % n_data], out=logits)
-        host_logits.copy_(logits, non_blocking=True)
-        torch.cuda.synchronize(device)
-        host_lat.append((time.perf_counter() - t2) * 1e3)
-    host_lat.sort()
+    if a.full:
+        host_logits = torch.empty((hi - lo, 2), dtype=torch.float32).pin_memory()
+        for i in range(max(3, min(a.steps, 10))):
+            torch.cuda.synchronize(device)
+            t2 = time.perf_counter()
+            eng.forward(batches[i % n_data], out=logits)
+            host_logits.copy_(logits, non_blocking=True)
+            torch.cuda.synchronize(device)
+            host_lat.append((time.perf_counter() - t2) * 1e3)
+        host_lat.sort()
 
     if rank == 0:
         total_ms = sum(ms for ms, _ in prof.values()) or 1.0
@@ -485,7 +513,7 @@ def main():
         fp32_rate = None
         fp32_leg_error = None
         try:
-            if world == 1 and eff != "fp32" and not a.no_fp32_leg:
+            if world == 1 and a.full and eff != "fp32" and not a.no_fp32_leg:
                 # the exact-fp32 engine on the same batches, so that the driver's run also times the mode that is bit-for-bit the
                 # reference's arithmetic (a few steps: it is ~5x slower)
                 e32 = Engine(device, precision="fp32", chunk_reads=a.chunk_reads)
@@ -511,7 +539,7 @@ def main():
             "metric": f"reads/sec (whole node), {a.bases}-bp reads batch={a.batch}", "value": a.batch * a.steps / elapsed,
             "unit": "reads/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": elapsed / a.steps * 1e3, "ms_per_step_by_rank": rank_ms, "p50_batch_latency_ms": lat[len(lat) // 2],
-            "p50_host_visible_latency_ms": host_lat[len(host_lat) // 2],   # this rank's shard: enqueue -> logits on the host
+            **({"p50_host_visible_latency_ms": host_lat[len(host_lat) // 2]} if a.full else {}),   # this rank's shard: enqueue -> logits on the host
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": eff,
             "dtype_note": DTYPE_NOTE[eff] + ("" if eff == a.precision else f" [requested {a.precision}: the guard fell back]"),
             "data": "synthetic reads (seeded); seeded weights of the production architecture at a realistic logit scale (see `weights`)",
@@ -527,14 +555,13 @@ def main():
                             "gather_ms_p50": gather_ms[len(gather_ms) // 2] if gather_ms else None,
                             "gather_ms_max": gather_ms[-1] if gather_ms else None},
             "guard": guard,
-            "fp32_exact_reads_per_s": fp32_rate,
+            **({"fp32_exact_reads_per_s": fp32_rate, "pcie_inclusive_reads_per_s": host_rate} if a.full else {}),
             **({"fp32_leg_error": fp32_leg_error} if fp32_leg_error else {}),
-            "pcie_inclusive_reads_per_s": host_rate,
             "dense_tflops_per_gpu": 6_423_040 * L * (hi - lo) * a.steps / elapsed / 1e12,
             "stage_ms_share": {k: round(v[0] / total_ms, 4) for k, v in prof.items() if v[1]},
             "roofline": roof,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(a.bases)
             except Exception as exc:  # noqa: BLE001

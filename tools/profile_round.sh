@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py $EXTRA"
+BENCH="python3 $R/bench.py --full $EXTRA"
 
 timeout -k 10 300 $BENCH > "$O/bench_default.json" 2> "$O/bench_default.err"
 echo "[1/7] bench done"; cut -c1-200 "$O/bench_default.json"
