@@ -165,14 +165,11 @@ struct clm_handle {
     int last_B = 0, last_L = 0, last_Lp = 0;
     // debug / profiling
     int stop_layer = -1, stop_stage = -1;
-    bool split_tail = false;      // CLM_DEBUG=split_tail: separate out_proj16 + mlp16 kernels instead of the fused tail (A/B runs)
-    bool no_fuse_next = false;    // CLM_DEBUG=no_fuse_next: separate in_proj / score kernels instead of fusing them into the tail
     bool no_idconv = false;       // CLM_DEBUG=no_idconv: run block 0's in_proj instead of the id-table convolution (A/B runs)
     int conv_flags = 0;           // CLM_DEBUG=conv_oneshot / conv_no_xcd: CONV_* switches of the convolution launchers (A/B runs, tests)
     bool no_lone_peel = false;    // CLM_DEBUG=no_lone_peel: keep the lone last token of 128 k + 1-token reads in a tile of its own (A/B runs)
     bool x3 = false;              // CLM_PREC_F16X3: cfg.precision is PREC_F32 inside the engine, the fused tails run on hi + lo halfs (tail32.hip AR_X3)
     bool unfused_fp32 = false;    // CLM_DEBUG=unfused_fp32: exact fp32 through the separate GEMM kernels of rounds 1-3 (tests cross-check the fused tail)
-    bool force_generic = false;   // CLM_DEBUG=generic_gemm: route 16-bit modes through the generic kernels (A/B runs)
     bool prof = false;
     std::vector<ProfRec> recs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
@@ -405,7 +402,7 @@ int ensure_workspace(clm_handle* h, int Bc, int L, hipStream_t st) {
     need[WS_H] = nb * nl * D * 4;
     need[WS_Z] = nb * D3 * Lp * es;
     need[WS_Y] = nb * D * Lp * es;
-    need[WS_U] = ((prec == PREC_F32 && !fused_fp32(h)) || (prec != PREC_F32 && h->force_generic)) ? nb * DI * nl * es : 0;   // the 1024-wide fc1 output: unfused paths only
+    need[WS_U] = (prec == PREC_F32 && !fused_fp32(h)) ? nb * DI * nl * es : 0;   // the 1024-wide fc1 output: unfused fp32 path only
     need[WS_SCORES] = nb * nl * 4;
     need[WS_STATS] = nb * 2 * 4;
     // pooling partials: [POOL_SPLIT][4][256] per read (unfused fp32 path) or one POOL_PSTRIDE row per tile -- 128 tokens in the
@@ -665,28 +662,34 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     const int prec = effective_prec(h, L), Lp = round_up(L, LP_ALIGN);
     const bool alt32 = prec != h->cfg.precision;              // fp16c engine, short reads: exact-fp32 kernels and packing
     const float eps = h->cfg.ln_eps;
+    // the workspace sized for this chunk
+    auto size_workspace = [&]() -> int {
+        const int rc = ensure_workspace(h, Bc, L, st);
+        if (rc) return rc;
+        h->last_B = Bc; h->last_L = L; h->last_Lp = Lp;
+        if (h->ws_es != elem_size(prec)) {   // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
+            if (h->ws_es) {                  // columns may read as NaN in the other
+                HIPCHK(h, hipMemsetAsync(h->z, 0, h->ws_cap[WS_Z], st));
+                HIPCHK(h, hipMemsetAsync(h->y, 0, h->ws_cap[WS_Y], st));
+            }
+            h->ws_es = elem_size(prec);
+        }
+        return CLM_OK;
+    };
     FilterSet* fs = nullptr;
     const ReversedFilter* kr = nullptr;
     int rc = ensure_filters(h, L, st, &fs, &kr);
     const int S = conv_segments_for(L);
     if (rc) return rc;
-    rc = ensure_workspace(h, Bc, L, st);
+    rc = size_workspace();
     if (rc) return rc;
-    h->last_B = Bc; h->last_L = L; h->last_Lp = Lp;
-    if (h->ws_es != elem_size(prec)) {   // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
-        if (h->ws_es) {                  // columns may read as NaN in the other
-            HIPCHK(h, hipMemsetAsync(h->z, 0, h->ws_cap[WS_Z], st));
-            HIPCHK(h, hipMemsetAsync(h->y, 0, h->ws_cap[WS_Y], st));
-        }
-        h->ws_es = elem_size(prec);
-    }
-    const bool tuned16 = prec != PREC_F32 && (!h->force_generic || prec == PREC_F16C);   // fp16c has no generic kernels
+    const bool tuned16 = prec != PREC_F32;
     // 16-bit modes, no debug stop: block 0 never touches the fp32 embedding rows in HBM --
     // its in_proj is a 16-row table looked up by the convolution and its residual is gathered from the embedding table
-    const bool idpath = tuned16 && !h->no_idconv && !h->split_tail && h->stop_stage < 0;
+    const bool idpath = tuned16 && !h->no_idconv && h->stop_stage < 0;
     // ... and every block's tail kernel goes on, on the tile it has just produced, with LayerNorm-1 + in_proj of the next
     // block (the last block: ln_f + attention scores + pooling partials): no separate in_proj / score launches
-    const bool fuse_next = tuned16 && !h->split_tail && !h->no_fuse_next && h->stop_stage < 0;
+    const bool fuse_next = tuned16 && h->stop_stage < 0;
     // reads of 128 k + 1 tokens (every 8k-bp read: 8192 bases + [SEP]): the last token would be a tile of its own, a whole extra
     // round of the tail kernel for one token per read; it is causally isolated, so a per-read matrix-vector kernel takes it
     const bool peel = fuse_next && !h->no_lone_peel && L > 128 && L % 128 == 1;
@@ -699,27 +702,20 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     // Round 5: tiles wholly inside a read's [PAD] prefix are not computed, their rows come from the all-[PAD] table (pad_prefix.hip).
     // In the fused paths only (the debug / unfused paths keep computing everything), never inside the forward that fills a table,
     // and only for reads long enough to hold a whole prefix tile next to a real token.
-    const int Lmain = (tuned16 && peel) ? L - 1 : L;
-    const bool tail16_path = tuned16 && !h->split_tail;      // the persistent tail kernel runs: it walks the tile list
-    const bool pad_skip = !h->no_pad_skip && !h->capture && L >= 256 && ((tail16_path && fuse_next) || fused32);
+    const int Lmain = peel ? L - 1 : L;
+    const bool pad_skip = !h->no_pad_skip && !h->capture && L >= 256 && (fuse_next || fused32);
     clm_handle::PadTable* ptab = nullptr;
     if (pad_skip) {                                          // (before this chunk's ids land in the workspace: the build runs through it)
         rc = ensure_pad_table(h, prec, x3, L, st, &ptab);
         if (rc) return rc;
-        rc = ensure_workspace(h, Bc, L, st);                 // (the build may have regrown -- never shrunk -- the buffers; cheap when not)
+        rc = size_workspace();                               // (the build may have regrown -- never shrunk -- the buffers; cheap when not)
         if (rc) return rc;
-        h->last_B = Bc; h->last_L = L; h->last_Lp = Lp;
-        if (h->ws_es != elem_size(prec)) {                   // (as above: the build ran in this chunk's own arithmetic, so this is a no-op)
-            HIPCHK(h, hipMemsetAsync(h->z, 0, h->ws_cap[WS_Z], st));
-            HIPCHK(h, hipMemsetAsync(h->y, 0, h->ws_cap[WS_Y], st));
-            h->ws_es = elem_size(prec);
-        }
         rc = ensure_filters(h, L, st, &fs, &kr);             // (the build may have added a filter class: the vector behind fs moved)
         if (rc) return rc;
     }
     // fp16c, round 4: y (every block) and the gated rows of z carry one lo byte per element next to the halfs
-    unsigned char* const ylo = (prec == PREC_F16C && tuned16) ? h->ylo : nullptr;
-    if (zgated && tail16_grid(((peel ? L - 1 : L) + 127) / 128 * Bc) > 1024)
+    unsigned char* const ylo = prec == PREC_F16C ? h->ylo : nullptr;
+    if (zgated && tail16_grid((Lmain + 127) / 128 * Bc) > 1024)
         return fail(h, CLM_E_UNSUPPORTED, "more than 1024 compute units: edge_bnd is sized for 1024 workgroups");
     const void* packed_score = alt32 ? h->packed_score32 : h->packed_score;
     const ScorePoolArgs spa{h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
@@ -734,7 +730,7 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
                      h->ids8, Bc, L, Lp, st, h->bad_ids);
     }
     if (stop_here(h, -1, CLM_STAGE_EMBED)) return CLM_OK;
-    if (tail16_path || pad_skip) launch_pad_tiles(h->ids8, Bc, Lp, Lmain, pad_skip ? 1 : 0, h->pad_p0, h->tile_list, st);
+    if (tuned16 || pad_skip) launch_pad_tiles(h->ids8, Bc, Lp, Lmain, pad_skip ? 1 : 0, h->pad_p0, h->tile_list, st);
     // does block j's (segmented) convolution leave out the segments inside the [PAD] prefix of both reads of a pair (SegPrefix)?  Block 0
     // looks z up by token id, the others read the gated hand-over; reads of S * 8192 + 1 tokens need the table's dot-product sums, which
     // belong to ONE length
@@ -743,20 +739,118 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     int* const pair_partner = h->pad_p0 + 2 * Bc;
     if (pad_skip && S > 1) launch_pair_order(h->pad_p0, Bc, pair_perm, pair_partner, st);
     auto seg_skip_layer = [&](int j) {
-        return pad_skip && S > 1 && tail16_path && fuse_next && !h->capture && (j == 0 ? idpath : zgated) && ptab->gspec[j] != nullptr &&
+        return pad_skip && S > 1 && fuse_next && !h->capture && (j == 0 ? idpath : zgated) && ptab->gspec[j] != nullptr &&
                (!kr || L == ptab->L);
     };
+
+    // 16-bit block tail: out_proj + LN2 + fc1 + GELU + fc2 + both residuals in one kernel (tail16_kernel), with the next block's
+    // LN1 + in_proj or, after the last block, ln_f + scores + pooling partials when fuse_next; then the gated patch, the lone token
+    // and the [PAD] prefix
+    auto tail16 = [&](int i, const LayerW& lw) -> int {
+        StageTimer t(h, st, CLM_STAGE_TAIL);
+        const bool mlpc = prec == PREC_F16C && h->mlp_lo;
+        TailArgs ta{h->y, h->h, lw.w_out, mlpc ? h->packed_mlpc[i][0] : lw.w_fc1, mlpc ? h->packed_mlpc[i][1] : lw.w_fc2, lw.b_out,
+                    lw.ln2_g, lw.ln2_b, lw.b_fc1, lw.b_fc2, Bc, L, Lp,
+                    eps, Lmain, (idpath && i == 0) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"),
+                    nullptr, nullptr, nullptr, nullptr, nullptr, spa};
+        ta.ylo = ylo;
+        ta.mlp_lo = mlpc;
+        ta.tiles = h->tile_list;
+        int next = NEXT_NONE;
+        if (fuse_next && i + 1 < NLAYER) {
+            const LayerW& nx = h->lw[i + 1];
+            ta.n_w = nx.w_in; ta.n_bias = nx.b_in; ta.n_g = nx.ln1_g; ta.n_b = nx.ln1_b; ta.n_z = h->z;
+            next = NEXT_INPROJ;
+            if (zgated) {
+                ta.zg = 1; ta.n_fir = h->fir[i + 1]; ta.edge_bnd = h->edge_bnd;
+                ta.edge_read = peel ? h->edge_read : nullptr;
+                ta.zlo = ylo != nullptr;
+            }
+        } else if (fuse_next) {
+            next = NEXT_SCORE;
+        }
+        launch_tail16(prec, ta, next, st);
+        if (ta.zg) launch_gated_patch(prec, ta, st);        // tokens 0, 1 of the workgroup ranges that start inside a read
+        if (peel) {
+            const std::string p = "bb.layers." + std::to_string(i) + ".", pn = "bb.layers." + std::to_string(i + 1) + ".";
+            const bool last = i + 1 == NLAYER;
+            LoneTokenArgs la{};
+            la.y = h->y; la.h = h->h; la.ids8 = ta.ids8; la.emb = ta.emb;
+            la.w_out = W(h, p + "mixer.out_proj.weight"); la.b_out = lw.b_out; la.ln2_g = lw.ln2_g; la.ln2_b = lw.ln2_b;
+            la.w_fc1 = W(h, p + "mlp.fc1.weight"); la.b_fc1 = lw.b_fc1; la.w_fc2 = W(h, p + "mlp.fc2.weight"); la.b_fc2 = lw.b_fc2;
+            la.last = last;
+            if (last) {
+                la.n_g = W(h, "bb.ln_f.weight"); la.n_b = W(h, "bb.ln_f.bias");
+                la.att_w1 = W(h, "head.attention.0.weight"); la.att_b1 = W(h, "head.attention.0.bias");
+                la.att_w2 = W(h, "head.attention.2.weight"); la.att_b2 = W(h, "head.attention.2.bias");
+                la.scores = h->scores; la.partial = h->partial;
+            } else {
+                const LayerW& nx = h->lw[i + 1];
+                la.n_g = nx.ln1_g; la.n_b = nx.ln1_b; la.n_w = W(h, pn + "mixer.in_proj.weight"); la.n_bias = nx.b_in; la.n_z = h->z;
+                if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read; }
+            }
+            la.ws = h->lone_ws;
+            la.B = Bc; la.L = L; la.Lp = Lp; la.ntiles = (L + 127) / 128; la.eps = eps;
+            la.ylo = ylo; la.zlo = ta.zlo;
+            launch_lone_token(prec, la, st);
+        }
+        // the [PAD] prefix: what this block leaves for the next stage, copied out of (capture) or in from (pad_skip) the table
+        const int nrow16 = ta.zg ? 2 * D : D3, nlo = ta.zlo ? 2 * D : 0;
+        if (h->capture && fuse_next) {
+            if (next == NEXT_INPROJ) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * elem_size(prec), hipMemcpyDeviceToDevice, st));
+            else {
+                HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)((L + 127) / 128) * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+            }
+        } else if (pad_skip) {
+            if (next == NEXT_INPROJ)      // (rows of segments the next convolution will not read are not copied)
+                launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, Lmain, (int)elem_size(prec), nrow16, nlo, st,
+                                     seg_skip_layer(i + 1) ? S : 0, pair_partner);
+            else
+                launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, (L + 127) / 128, Lmain, st);
+        }
+        return CLM_OK;
+    };
+
+    // exact fp32 / fp16x3 block tail (tail32.hip), the next block's in_proj or -- the last block -- ln_f + pooling scores + per-tile
+    // pooling partials on the tile still on chip (T32_SCORE); then the [PAD] prefix
+    auto tail32 = [&](int i, const LayerW& lw, bool idconv) -> int {
+        StageTimer t(h, st, CLM_STAGE_TAIL);
+        const LayerW* nx = i + 1 < NLAYER ? &(x3 ? h->lwx[i + 1] : (alt32 ? h->lw32[i + 1] : h->lw[i + 1])) : nullptr;
+        const int nt32 = (L + T32_TILE - 1) / T32_TILE;
+        const Tail32Score ts{x3 ? h->packed_score32x : h->packed_score32t, W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
+                             W(h, "head.attention.2.bias"), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores, h->partial};
+        launch_tail32(reinterpret_cast<const float*>(h->y), h->h, lw.t_out, lw.t_fc1, lw.t_fc2, nx ? nx->t_in : nullptr, lw.b_out,
+                      lw.b_fc1, lw.b_fc2, nx ? nx->b_in : nullptr, lw.ln2_g, lw.ln2_b, nx ? nx->ln1_g : nullptr,
+                      nx ? nx->ln1_b : nullptr, reinterpret_cast<float*>(h->z), Bc, L, Lp, eps, st, x3, pad_skip ? h->pad_p0 : nullptr,
+                      nx ? nullptr : &ts, (i == 0 && idconv) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"));
+        if (h->capture) {
+            if (nx) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * 4, hipMemcpyDeviceToDevice, st));
+            else {
+                HIPCHK(h, hipMemcpyAsync(h->capture->hfin, h->h, (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)nt32 * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+            }
+        } else if (pad_skip) {
+            if (nx) launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, L, 4, D3, 0, st);
+            else {
+                launch_prefix_fill_h(h->pad_p0, h->h, ptab->hfin, Bc, L, L, st);
+                launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, nt32, L, st, 128 / T32_TILE);
+            }
+        }
+        return CLM_OK;
+    };
+
     for (int i = 0; i < NLAYER; ++i) {
         const LayerW& lw = x3 ? h->lwx[i] : (alt32 ? h->lw32[i] : h->lw[i]);
         // block 0 in the 16-bit modes: its in_proj output is a function of the token id alone, the convolution looks it
         // up (ztab), single-shot and segmented kernel alike -- unless a debug stop asks for z itself or CLM_DEBUG=no_idconv
         // (exact fp32 with the fused tail, single-shot convolution: the same table -- it is fp32 -- so block 0 needs no in_proj launch)
-        const bool idconv = i == 0 && (idpath || (tuned16 && !h->no_idconv && !stop_here(h, 0, CLM_STAGE_INPROJ)) ||
-                                       (fused32 && S == 1 && !h->no_idconv));
+        const bool idconv = i == 0 && !h->no_idconv && ((tuned16 && !stop_here(h, 0, CLM_STAGE_INPROJ)) || (fused32 && S == 1));
         if (!idconv && !(fuse_next && i > 0) && !(fused32 && i > 0)) {
             StageTimer t(h, st, CLM_STAGE_INPROJ);
             if (tuned16) launch_inproj16(prec, h->h, lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z, Bc, L, Lp, eps, st);
-            else launch_inproj(prec, h->h, lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z, Bc, L, Lp, eps, st);
+            else launch_inproj(h->h, lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z, Bc, L, Lp, eps, st);
         }
         if (stop_here(h, i, CLM_STAGE_INPROJ)) return CLM_OK;
         {
@@ -791,113 +885,26 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         }
         if (stop_here(h, i, CLM_STAGE_CONV)) return CLM_OK;
         const bool stop_mid = stop_here(h, i, CLM_STAGE_OUTPROJ);
-        if (tuned16 && !h->split_tail && !stop_mid) {   // out_proj + LN2 + fc1 + GELU + fc2 + both residuals: one kernel
-            StageTimer t(h, st, CLM_STAGE_TAIL);
-            const bool mlpc = prec == PREC_F16C && h->mlp_lo;
-            TailArgs ta{h->y, h->h, lw.w_out, mlpc ? h->packed_mlpc[i][0] : lw.w_fc1, mlpc ? h->packed_mlpc[i][1] : lw.w_fc2, lw.b_out,
-                        lw.ln2_g, lw.ln2_b, lw.b_fc1, lw.b_fc2, Bc, L, Lp,
-                        eps, peel ? L - 1 : L, (idpath && i == 0) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"),
-                        nullptr, nullptr, nullptr, nullptr, nullptr, spa};
-            ta.ylo = ylo;
-            ta.mlp_lo = mlpc;
-            ta.tiles = h->tile_list;
-            int next = NEXT_NONE;
-            if (fuse_next && i + 1 < NLAYER) {
-                const LayerW& nx = h->lw[i + 1];
-                ta.n_w = nx.w_in; ta.n_bias = nx.b_in; ta.n_g = nx.ln1_g; ta.n_b = nx.ln1_b; ta.n_z = h->z;
-                next = NEXT_INPROJ;
-                if (zgated) {
-                    ta.zg = 1; ta.n_fir = h->fir[i + 1]; ta.edge_bnd = h->edge_bnd;
-                    ta.edge_read = peel ? h->edge_read : nullptr;
-                    ta.zlo = ylo != nullptr;
-                }
-            } else if (fuse_next) {
-                next = NEXT_SCORE;
-            }
-            launch_tail16(prec, ta, next, st);
-            if (ta.zg) launch_gated_patch(prec, ta, st);        // tokens 0, 1 of the workgroup ranges that start inside a read
-            if (peel) {
-                const std::string p = "bb.layers." + std::to_string(i) + ".", pn = "bb.layers." + std::to_string(i + 1) + ".";
-                const bool last = i + 1 == NLAYER;
-                LoneTokenArgs la{};
-                la.y = h->y; la.h = h->h; la.ids8 = ta.ids8; la.emb = ta.emb;
-                la.w_out = W(h, p + "mixer.out_proj.weight"); la.b_out = lw.b_out; la.ln2_g = lw.ln2_g; la.ln2_b = lw.ln2_b;
-                la.w_fc1 = W(h, p + "mlp.fc1.weight"); la.b_fc1 = lw.b_fc1; la.w_fc2 = W(h, p + "mlp.fc2.weight"); la.b_fc2 = lw.b_fc2;
-                la.last = last;
-                if (last) {
-                    la.n_g = W(h, "bb.ln_f.weight"); la.n_b = W(h, "bb.ln_f.bias");
-                    la.att_w1 = W(h, "head.attention.0.weight"); la.att_b1 = W(h, "head.attention.0.bias");
-                    la.att_w2 = W(h, "head.attention.2.weight"); la.att_b2 = W(h, "head.attention.2.bias");
-                    la.scores = h->scores; la.partial = h->partial;
-                } else {
-                    const LayerW& nx = h->lw[i + 1];
-                    la.n_g = nx.ln1_g; la.n_b = nx.ln1_b; la.n_w = W(h, pn + "mixer.in_proj.weight"); la.n_bias = nx.b_in; la.n_z = h->z;
-                    if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read; }
-                }
-                la.ws = h->lone_ws;
-                la.B = Bc; la.L = L; la.Lp = Lp; la.ntiles = (L + 127) / 128; la.eps = eps;
-                la.ylo = ylo; la.zlo = ta.zlo;
-                launch_lone_token(prec, la, st);
-            }
-            // the [PAD] prefix: what this block leaves for the next stage, copied out of (capture) or in from (pad_skip) the table
-            const int nrow16 = ta.zg ? 2 * D : D3, nlo = ta.zlo ? 2 * D : 0;
-            if (h->capture && fuse_next) {
-                if (next == NEXT_INPROJ) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * elem_size(prec), hipMemcpyDeviceToDevice, st));
-                else {
-                    HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                    HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)((L + 127) / 128) * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
-                }
-            } else if (pad_skip) {
-                if (next == NEXT_INPROJ)      // (rows of segments the next convolution will not read are not copied)
-                    launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, Lmain, (int)elem_size(prec), nrow16, nlo, st,
-                                         seg_skip_layer(i + 1) ? S : 0, pair_partner);
-                else
-                    launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, (L + 127) / 128, Lmain, st);
-            }
+        if (tuned16 && !stop_mid) {
+            rc = tail16(i, lw);
+            if (rc) return rc;
         } else if (fused32) {
-            StageTimer t(h, st, CLM_STAGE_TAIL);
-            const LayerW* nx = i + 1 < NLAYER ? &(x3 ? h->lwx[i + 1] : (alt32 ? h->lw32[i + 1] : h->lw[i + 1])) : nullptr;
-            // the last block: ln_f + pooling scores + per-tile pooling partials on the tile still on chip (tail32.hip T32_SCORE)
-            const int nt32 = (L + T32_TILE - 1) / T32_TILE;
-            const Tail32Score ts{x3 ? h->packed_score32x : h->packed_score32t, W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                                 W(h, "head.attention.2.bias"), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores, h->partial};
-            launch_tail32(reinterpret_cast<const float*>(h->y), h->h, lw.t_out, lw.t_fc1, lw.t_fc2, nx ? nx->t_in : nullptr, lw.b_out,
-                          lw.b_fc1, lw.b_fc2, nx ? nx->b_in : nullptr, lw.ln2_g, lw.ln2_b, nx ? nx->ln1_g : nullptr,
-                          nx ? nx->ln1_b : nullptr, reinterpret_cast<float*>(h->z), Bc, L, Lp, eps, st, x3, pad_skip ? h->pad_p0 : nullptr,
-                          nx ? nullptr : &ts, (i == 0 && idconv) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"));
-            if (h->capture) {
-                if (nx) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * 4, hipMemcpyDeviceToDevice, st));
-                else {
-                    HIPCHK(h, hipMemcpyAsync(h->capture->hfin, h->h, (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
-                    HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                    HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)nt32 * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
-                }
-            } else if (pad_skip) {
-                if (nx) launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, L, 4, D3, 0, st);
-                else {
-                    launch_prefix_fill_h(h->pad_p0, h->h, ptab->hfin, Bc, L, L, st);
-                    launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, nt32, L, st, 128 / T32_TILE);
-                }
-            }
-        } else {
+            rc = tail32(i, lw, idconv);
+            if (rc) return rc;
+        } else {   // the separate kernels: a debug stop after out_proj (16-bit modes), the unfused exact-fp32 path
             {
                 StageTimer t(h, st, CLM_STAGE_OUTPROJ);
                 if (tuned16) launch_outproj16(prec, h->y, lw.w_out, lw.b_out, h->h, Bc, L, Lp, st);
-                else launch_outproj(prec, h->y, lw.w_out, lw.b_out, h->h, Bc, L, Lp, st);
+                else launch_outproj(h->y, lw.w_out, lw.b_out, h->h, Bc, L, Lp, st);
             }
             if (stop_mid) return CLM_OK;
-            if (tuned16) {   // fc1 + GELU + fc2 + residual fused
-                StageTimer t(h, st, CLM_STAGE_MLP);
-                launch_mlp16(prec, h->h, lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, lw.w_fc2, lw.b_fc2, Bc, L, eps, st);
-            } else {
-                {
-                    StageTimer t(h, st, CLM_STAGE_FC1);
-                    launch_fc1(prec, h->h, lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, h->u, Bc, L, eps, st);
-                }
-                if (stop_here(h, i, CLM_STAGE_FC1)) return CLM_OK;
-                StageTimer t(h, st, CLM_STAGE_FC2);
-                launch_fc2(prec, h->u, lw.w_fc2, lw.b_fc2, h->h, Bc, L, st);
+            {
+                StageTimer t(h, st, CLM_STAGE_FC1);
+                launch_fc1(h->h, lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, h->u, Bc, L, eps, st);
             }
+            if (stop_here(h, i, CLM_STAGE_FC1)) return CLM_OK;
+            StageTimer t(h, st, CLM_STAGE_FC2);
+            launch_fc2(h->u, lw.w_fc2, lw.b_fc2, h->h, Bc, L, st);
         }
         if (stop_here(h, i, CLM_STAGE_FC2) || (tuned16 && stop_here(h, i, CLM_STAGE_FC1))) return CLM_OK;
     }
@@ -916,7 +923,7 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     } else {
         {
             StageTimer t(h, st, CLM_STAGE_SCORE);
-            launch_score(prec, h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
+            launch_score(h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
                          W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"), W(h, "head.attention.2.bias"),
                          h->scores, Bc, L, eps, st);
         }
@@ -973,11 +980,8 @@ int clm_create(const clm_config* cfg, int device, clm_handle** out) {
     clm_handle* h = new clm_handle();
     // developer switches (A/B runs, tests): ONE variable, CLM_DEBUG, a comma-separated list read when a handle is created
     // (clm_common.h debug_flag) -- no product behaviour hangs on the environment
-    h->force_generic = debug_flag("generic_gemm");     // 16-bit modes through the generic kernels
     h->unfused_fp32 = debug_flag("unfused_fp32");      // exact fp32 through the separate GEMM kernels instead of tail32_kernel
-    h->no_fuse_next = debug_flag("no_fuse_next");      // separate in_proj / score kernels instead of fusing them into the tail
     h->no_idconv = debug_flag("no_idconv");            // block 0's in_proj instead of the id-table convolution
-    h->split_tail = debug_flag("split_tail");          // separate out_proj16 + mlp16 kernels instead of the fused tail
     h->no_lone_peel = debug_flag("no_lone_peel");      // the lone last token of 128 k + 1-token reads in a tile of its own
     if (debug_flag("conv_oneshot")) h->conv_flags |= CONV_ONESHOT;
     if (debug_flag("conv_no_xcd")) h->conv_flags |= CONV_NO_XCD;

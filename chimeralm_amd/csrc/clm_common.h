@@ -8,8 +8,6 @@
 #include <cstdio>
 #include <type_traits>
 
-#include "clm_lab.h"
-
 namespace clm {
 
 // model constants fixed by the reference (chimeralm/models/lm.py:19-31)
@@ -105,7 +103,6 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 // two at a time: the element-wise part maps onto v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32
 using f32x2 = float __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_tanh2(f32x2 x) {
-    if constexpr (lab::NOGELU) return x * 0.5f;
     f32x2 p = x * (GELU_A + GELU_B * (x * x));
     f32x2 d = {1.0f + __builtin_amdgcn_exp2f(p.x), 1.0f + __builtin_amdgcn_exp2f(p.y)};
     f32x2 r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
@@ -128,10 +125,6 @@ constexpr int LO2_E8M0 = 127 - 10;
 //  an operand of v_fma_mix_f32, not converted back first: (x - h) S = fma(h, -S, x S); 12 instructions per four values where
 //  the plain form took 20, and every LayerNorm tile, z row and y row of fp16c pays them per element)
 __device__ __forceinline__ unsigned lo8_pack4(float x0, float x1, float x2, float x3, u16x4& h) {
-    if constexpr (lab::NOLOPACK) {      // timing-only: the halfs alone
-        h = u16x4{from_float<f16_t>(x0).bits, from_float<f16_t>(x1).bits, from_float<f16_t>(x2).bits, from_float<f16_t>(x3).bits};
-        return 0u;
-    }
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     typedef float f2 __attribute__((ext_vector_type(2)));
     const h2 a = __builtin_convertvector(f2{x0, x1}, h2), b = __builtin_convertvector(f2{x2, x3}, h2);
@@ -155,23 +148,23 @@ __device__ __forceinline__ void lo8_unpack4(unsigned w, float (&d)[4]) {
 // developer switches: is `name` in the comma-separated environment variable CLM_DEBUG?  (clm_api.hip; A/B runs and tests only)
 bool debug_flag(const char* name);
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, DEVICE): a C-ABI client may hold handles on several GPUs in
-// one process, so every launch site keeps one bit per device instead of a once-per-process flag (a handle on a second
-// device launched its > 64-KiB-LDS kernels without the attribute).  CLM_SET_LDS(kernel pointer, bytes) before the launch.
-inline void ensure_lds_attr(const void* kern, size_t lds, std::atomic<unsigned long long>& done) {
+// Launch of a kernel with dynamic LDS.  hipFuncAttributeMaxDynamicSharedMemorySize (needed above 64 KiB) is a property of
+// (kernel, DEVICE): a C-ABI client may hold handles on several GPUs in one process, so each kernel keeps one bit per device that
+// has its attribute.  One instantiation per kernel, hence one set of bits per kernel (a launcher
+// templated on the kernel's TYPE shared them between kernels of one signature).  Every kernel is launched with one LDS size.
+template <auto Kern, class... A>
+void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    static std::atomic<unsigned long long> done{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_relaxed) & bit) return;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
-    else std::fprintf(stderr, "chimeralm_hip: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %zu) failed on device %d: %s\n", lds, dev, hipGetErrorString(e));
+    if (!(done.load(std::memory_order_relaxed) & bit)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+        else std::fprintf(stderr, "chimeralm_hip: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %zu) failed on device %d: %s\n", lds, dev, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
 }
-#define CLM_SET_LDS(kern, lds)                                                             \
-    do {                                                                                   \
-        static std::atomic<unsigned long long> clm_lds_done_{0};                           \
-        ::clm::ensure_lds_attr(reinterpret_cast<const void*>(kern), (lds), clm_lds_done_); \
-    } while (0)
 
 // ---- kernel launchers (definitions in the .hip files); all are asynchronous on `st` --------------------
 // PREC_F16C ("fp16c"): fp16 activations x weights held as hi + lo (in_proj, out_proj, score layer; the MLP weights are plain fp16
@@ -225,29 +218,26 @@ void launch_enc32(const float* att, float* h, const void* w_o, const void* w1, c
                   const float* b1, const float* b2, const float* b_qkv, const float* ln1_g, const float* ln1_b, const float* ln2_g,
                   const float* ln2_b, float* qkv, size_t M, float eps, hipStream_t st, bool x3 = false);
 
-// GEMM family (gemm.hip).  `prec` selects compute dtype; T16 activations are bf16/f16 (or fp32 for PREC_F32).
+// GEMM family (gemm.hip): exact fp32, the unfused path (CLM_DEBUG=unfused_fp32, debug stops); activations fp32.
 // z  = in_proj(LN1(h))      -> channel-major [B, 768, Lp]
-void launch_inproj(int prec, const float* h, const float* g, const float* b, const void* w, const float* bias, void* z,
+void launch_inproj(const float* h, const float* g, const float* b, const void* w, const float* bias, void* z,
                    int B, int L, int Lp, float eps, hipStream_t st);
 // h += out_proj(y^T)        y channel-major [B, 256, Lp]
-void launch_outproj(int prec, const void* y, const void* w, const float* bias, float* h, int B, int L, int Lp,
+void launch_outproj(const void* y, const void* w, const float* bias, float* h, int B, int L, int Lp,
                     hipStream_t st);
 // u  = gelu_tanh(fc1(LN2(h)))  token-major [B, L, 1024]
-void launch_fc1(int prec, const float* h, const float* g, const float* b, const void* w, const float* bias, void* u,
+void launch_fc1(const float* h, const float* g, const float* b, const void* w, const float* bias, void* u,
                 int B, int L, float eps, hipStream_t st);
 // h += fc2(u)
-void launch_fc2(int prec, const void* u, const void* w, const float* bias, float* h, int B, int L, hipStream_t st);
+void launch_fc2(const void* u, const void* w, const float* bias, float* h, int B, int L, hipStream_t st);
 // scores[b,t] = w2 . gelu_erf(W1 LNf(h) + b1) + b2
-void launch_score(int prec, const float* h, const float* g, const float* b, const void* w1, const float* b1,
+void launch_score(const float* h, const float* g, const float* b, const void* w1, const float* b1,
                   const float* w2, const float* b2, float* scores, int B, int L, float eps, hipStream_t st);
 // tuned 16-bit kernels (gemm16.hip); prec must be PREC_BF16 or PREC_F16
 void launch_inproj16(int prec, const float* h, const float* g, const float* b, const void* w, const float* bias,
                      void* z, int B, int L, int Lp, float eps, hipStream_t st);
 void launch_outproj16(int prec, const void* y, const void* w, const float* bias, float* h, int B, int L, int Lp,
                       hipStream_t st);
-// h += fc2(gelu_tanh(fc1(LN2(h)))) in one kernel (hidden activations stay on chip)
-void launch_mlp16(int prec, float* h, const float* g, const float* b, const void* w1, const float* b1, const void* w2,
-                  const float* b2, int B, int L, float eps, hipStream_t st);
 // second half of a block in one kernel: h = r + fc2(gelu(fc1(LN2(r)))), r = h + out_proj(y^T)
 struct ScorePoolArgs {
     const float* h;           // [B, L, 256]

@@ -205,52 +205,42 @@ template <int PREC, int ASRC, int EPI, int K, int N>
 static void launch_gemm(const GemmArgs& a, hipStream_t st) {
     using C = CT<PREC>;
     constexpr size_t lds = (size_t)C::BM * C::RS * sizeof(typename C::elem);
-    auto kern = gemm_kernel<PREC, ASRC, EPI, K, N>;
-    CLM_SET_LDS(kern, lds);
-    dim3 grid((a.L + C::BM - 1) / C::BM, a.B), block(256);
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+    launch_lds<gemm_kernel<PREC, ASRC, EPI, K, N>>(dim3((a.L + C::BM - 1) / C::BM, a.B), dim3(256), lds, st, a);
 }
 
-#define CLM_DISPATCH_PREC(prec, ASRC, EPI, K, N, args, st)                         \
-    do {                                                                           \
-        if ((prec) == PREC_F32) launch_gemm<PREC_F32, ASRC, EPI, K, N>(args, st);  \
-        else if ((prec) == PREC_BF16) launch_gemm<PREC_BF16, ASRC, EPI, K, N>(args, st); \
-        else launch_gemm<PREC_F16, ASRC, EPI, K, N>(args, st);                     \
-    } while (0)
-
-void launch_inproj(int prec, const float* h, const float* g, const float* b, const void* w, const float* bias, void* z,
+void launch_inproj(const float* h, const float* g, const float* b, const void* w, const float* bias, void* z,
                    int B, int L, int Lp, float eps, hipStream_t st) {
     GemmArgs a{};
     a.h_in = h; a.ln_g = g; a.ln_b = b; a.w = w; a.bias = bias; a.out = z; a.B = B; a.L = L; a.Lp = Lp; a.eps = eps;
-    CLM_DISPATCH_PREC(prec, A_LN, E_CM, D, D3, a, st);
+    launch_gemm<PREC_F32, A_LN, E_CM, D, D3>(a, st);
 }
 
-void launch_outproj(int prec, const void* y, const void* w, const float* bias, float* h, int B, int L, int Lp,
+void launch_outproj(const void* y, const void* w, const float* bias, float* h, int B, int L, int Lp,
                     hipStream_t st) {
     GemmArgs a{};
     a.a_in = y; a.w = w; a.bias = bias; a.h_out = h; a.B = B; a.L = L; a.Lp = Lp;
-    CLM_DISPATCH_PREC(prec, A_CM, E_RESID, D, D, a, st);
+    launch_gemm<PREC_F32, A_CM, E_RESID, D, D>(a, st);
 }
 
-void launch_fc1(int prec, const float* h, const float* g, const float* b, const void* w, const float* bias, void* u,
+void launch_fc1(const float* h, const float* g, const float* b, const void* w, const float* bias, void* u,
                 int B, int L, float eps, hipStream_t st) {
     GemmArgs a{};
     a.h_in = h; a.ln_g = g; a.ln_b = b; a.w = w; a.bias = bias; a.out = u; a.B = B; a.L = L; a.Lp = 0; a.eps = eps;
-    CLM_DISPATCH_PREC(prec, A_LN, E_GELU_TM, D, DI, a, st);
+    launch_gemm<PREC_F32, A_LN, E_GELU_TM, D, DI>(a, st);
 }
 
-void launch_fc2(int prec, const void* u, const void* w, const float* bias, float* h, int B, int L, hipStream_t st) {
+void launch_fc2(const void* u, const void* w, const float* bias, float* h, int B, int L, hipStream_t st) {
     GemmArgs a{};
     a.a_in = u; a.w = w; a.bias = bias; a.h_out = h; a.B = B; a.L = L; a.Lp = 0;
-    CLM_DISPATCH_PREC(prec, A_TM, E_RESID, DI, D, a, st);
+    launch_gemm<PREC_F32, A_TM, E_RESID, DI, D>(a, st);
 }
 
-void launch_score(int prec, const float* h, const float* g, const float* b, const void* w1, const float* b1,
+void launch_score(const float* h, const float* g, const float* b, const void* w1, const float* b1,
                   const float* w2, const float* b2, float* scores, int B, int L, float eps, hipStream_t st) {
     GemmArgs a{};
     a.h_in = h; a.ln_g = g; a.ln_b = b; a.w = w1; a.bias = b1; a.w2 = w2; a.b2 = b2; a.scores = scores;
     a.B = B; a.L = L; a.Lp = 0; a.eps = eps;
-    CLM_DISPATCH_PREC(prec, A_LN, E_SCORE, D, D, a, st);
+    launch_gemm<PREC_F32, A_LN, E_SCORE, D, D>(a, st);
 }
 
 }  // namespace clm

@@ -2,7 +2,6 @@
 //
 //   in_proj16   z = in_proj(LN1(h))                      reference: HyenaOperator.in_proj after HyenaBlock.norm1
 //   out_proj16  h += out_proj(y^T)                                   HyenaOperator.out_proj + residual
-//   mlp16       h += fc2(gelu_tanh(fc1(LN2(h))))                     HyenaBlock.norm2 + HyenaMlp + residual
 //   
 //
 // What the first version got wrong (rocprofv3, profiles/r01_*): its epilogues issued one 2- or 4-byte global store
@@ -221,7 +220,7 @@ __device__ __forceinline__ void zg_store_rows(const f32x16 (&a)[4], typename CT<
     for (int i = 0; i < 8; ++i) {
         const int row = i * 4 + (lane >> 4);
         const uint4 v = *reinterpret_cast<const uint4*>(zs + row * RSOUT + col8);
-        if (in_row && (!lab::NOZSTORE || v.x == 0x12345678u)) *reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8) = v;
+        if (in_row) *reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8) = v;
     }
     __builtin_amdgcn_sched_barrier(0);
 }
@@ -263,7 +262,7 @@ __device__ __forceinline__ void inproj_blocks_gated(const typename CT<PREC>::ele
         if (gt.tail_bnd && lhalf) m.edge_bnd[((size_t)(gt.w + 1) * 2 + 0) * D3 + q * 256 + c] = tl;
         if (gt.head_bnd && !lhalf) m.edge_bnd[((size_t)gt.w * 2 + 1) * D3 + q * 256 + c] = hd;
         if (gt.read_tail && lhalf) m.edge_read[(size_t)b * D3 + q * 256 + c] = tl;
-        if constexpr (!lab::NOFIR) zg_fir_inplace<PREC>(acc, firq, p2, p3, lane);
+        zg_fir_inplace<PREC>(acc, firq, p2, p3, lane);
         // x1f waits for vf through a whole MFMA phase in which both accumulators, two weight sets and the fragment ring are live
         // (hipcc spilled 8 .. 26 of its registers to scratch, behind vmcnt waits): its upper half (tokens 64 .. 127) waits in the
         // wave's staging tile instead -- unused until g is staged -- as eight conflict-free 16-byte rows per lane
@@ -364,11 +363,10 @@ __device__ __forceinline__ void zg_store_half(const f32x16 (&a)[4], f16_t* zs, v
         for (int i = 0; i < 4; ++i) {
             const int row = i * 8 + (lane >> 3);
             const uint4 v = *reinterpret_cast<const uint4*>(zs + row * RSH + col8);
-            if (in_row && (!lab::NOZSTORE || v.x == 0x12345678u)) *reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8) = v;
+            if (in_row) *reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8) = v;
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (lab::NOZLO) return;
     unsigned char* z8 = reinterpret_cast<unsigned char*>(zs);
 #pragma unroll
     for (int m2 = 0; m2 < 2; ++m2)
@@ -431,7 +429,7 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         history(q, c, hs, p2, p3);
         leave_tail(q, c, hs, make_float2(accx[3][14], accx[3][15]));
         leave_head(q, c, make_float2(accx[0][0], accx[0][1]));
-        if constexpr (!lab::NOFIR) zg_fir_inplace<PREC>(accx, firq, p2, p3, lane);
+        zg_fir_inplace<PREC>(accx, firq, p2, p3, lane);
         // x1f is COMPLETE here: left alone hipcc sinks the filter arithmetic of the upper row tiles to their first use, behind
         // both halves of v, and carries the 16 lane-exchange results through those MFMA phases instead -- nine of them in scratch
 #pragma unroll
@@ -457,7 +455,7 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         phase_tm<PREC, K, K, false, false, decltype(hook2), PREC_SAME, true, 0, 2>(As, wp, q, 0, wp, q, 0, wave, lane, bs, accv, hook2, 2, Al);
         history(q, c, hs, p2, p3);
         leave_head(q, c, make_float2(accv[0][0], accv[0][1]));
-        if constexpr (!lab::NOFIR) zg_fir_range<0, 2>(accv, firq, p2, p3, lane);
+        zg_fir_range<0, 2>(accv, firq, p2, p3, lane);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -467,7 +465,7 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         for (int r = 0; r < 16; ++r) accv[2][r] = 0.f, accv[3][r] = 0.f;
         phase_tm<PREC, K, K, false, false, NoHook, PREC_SAME, true, 2, 2>(As, wp, q, 0, wp, 0, 0, wave, lane, bs, accv, NoHook(), 0, Al);
         leave_tail(q, c, hs, make_float2(accv[3][14], accv[3][15]));
-        if constexpr (!lab::NOFIR) zg_fir_range<2, 2>(accv, firq, p2, p3, lane);
+        zg_fir_range<2, 2>(accv, firq, p2, p3, lane);
 #pragma unroll
         for (int mt = 2; mt < 4; ++mt)
 #pragma unroll
@@ -483,20 +481,15 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         const int c = wave * 32 + lrow_e;
         auto hook2 = [&](int step) {
             if (step == 4) firq = m.n_fir[c * 3 + q];
-            if constexpr (!lab::YLATE) hook(step);
+            hook(step);
         };
         phase_tm<PREC, K, K, false, false, decltype(hook2), PREC_SAME, true>(As, wp, q, 0, wp, ZG_ORDER[0], 0, wave, lane, bs, accx, hook2, 4, Al);
-        if constexpr (lab::YLATE) {
-            hook(4);
-            hook(5);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         float* hs = halo + ((wave * 3 + q) * 32 + lrow_e) * 2;
         float p2, p3;
         history(q, c, hs, p2, p3);
         leave_tail(q, c, hs, make_float2(accx[3][14], accx[3][15]));
         leave_head(q, c, make_float2(accx[0][0], accx[0][1]));
-        if constexpr (!lab::NOFIR) zg_fir_inplace<PREC>(accx, firq, p2, p3, lane);
+        zg_fir_inplace<PREC>(accx, firq, p2, p3, lane);
         zg_store_half<0>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
         zg_store_half<1>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
     }
@@ -580,73 +573,6 @@ __global__ __launch_bounds__(512) void out_proj16_kernel(GemmArgs a) {
     phase_km<PREC, K, K>(Ys, wp, 0, 0, wp, 0, 0, wave, lane, bs, acc);
     __syncthreads();                                       // every wave is done reading Ys: reuse it as the staging tile
     resid_epilogue(a.h_out, a.bias, acc, b, t0, L, wave, lane, reinterpret_cast<float*>(smem));
-}
-
-// ================================================================================================ fused MLP
-struct MlpArgs {
-    float* h;                 // residual stream [B, L, 256], read (LN2) and updated in place
-    const float *ln_g, *ln_b;
-    const void *w1, *w2;      // packed fc1 [1024 x 256], fc2 [256 x 1024]
-    const float *b1, *b2;
-    int B, L;
-    float eps;
-};
-
-// One workgroup per 128-token tile.  Two variants were measured and rejected (r01 notes in HISTORY.md): a persistent
-// loop that prefetches the next tile's rows during the epilogue, and taking the residual as the accumulator's initial
-// value through an LDS half-tile (store-only epilogue): the extra barriers / LDS traffic / register pressure cost more
-// than the 1 KiB/token re-read they save (4.0 ms vs 3.25 ms per 64 reads for this stage).
-template <int PREC>
-__global__ __launch_bounds__(512) void mlp16_kernel(MlpArgs m) {
-    using elem = typename CT<PREC>::elem;
-    using frag = u16x8;
-    constexpr int BM = 128, NCH = DI / 256;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    elem* As = reinterpret_cast<elem*>(smem);              // LN2(h) tile   [128][RS16]
-    elem* Hs = As + BM * RS16;                              // gelu(fc1) chunk [128][RS16] (256 hidden units)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 31, lhalf = lane >> 5;
-    const int b = blockIdx.y, t0 = blockIdx.x * BM, L = m.L;
-    const frag* w1 = reinterpret_cast<const frag*>(m.w1);
-    const frag* w2 = reinterpret_cast<const frag*>(m.w2);
-    f32x16 acc1[4], acc2[4];
-    frag bs[2][1][SETK];
-
-    load_set<PREC, D, 1>(w1, 0, 0, 0, wave, lane, bs[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    {
-        GemmArgs a{};
-        a.h_in = m.h; a.ln_g = m.ln_g; a.ln_b = m.ln_b; a.L = L; a.eps = m.eps;
-        stage_a_tile<PREC, A_LN, D, 8>(a, As, b, t0, 0);
-    }
-    __syncthreads();
-    zero_acc(acc2);
-#pragma unroll 1
-    for (int j = 0; j < NCH; ++j) {
-        // ---- fc1, hidden units [256 j, 256 j + 256): rows = hidden unit, cols = token
-        zero_acc(acc1);
-        phase_tm<PREC, D, DI, true>(As, w1, j, 0, w2, 0, j, wave, lane, bs, acc1);
-        // ---- GELU -> Hs[token][hidden]: every wave must be done reading the previous chunk
-        __syncthreads();
-        {
-            const float* b1 = m.b1 + j * 256 + wave * 32 + 4 * lhalf;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 bb = *reinterpret_cast<const float4*>(b1 + 8 * q);
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const f32x2 g0 = gelu_tanh2(f32x2{acc1[mt][4 * q + 0] + bb.x, acc1[mt][4 * q + 1] + bb.y});
-                    const f32x2 g1 = gelu_tanh2(f32x2{acc1[mt][4 * q + 2] + bb.z, acc1[mt][4 * q + 3] + bb.w});
-                    u16x4 pk = {to_bits<PREC>(g0.x), to_bits<PREC>(g0.y), to_bits<PREC>(g1.x), to_bits<PREC>(g1.y)};
-                    *reinterpret_cast<u16x4*>(Hs + (mt * 32 + lrow) * RS16 + wave * 32 + 8 * q + 4 * lhalf) = pk;
-                }
-            }
-        }
-        __syncthreads();
-        // ---- fc2, reduction chunk j: rows = output feature, cols = token
-        phase_tm<PREC, DI, D, true>(Hs, w2, 0, j, w1, j + 1 < NCH ? j + 1 : 0, 0, wave, lane, bs, acc2);
-    }
-    __syncthreads();                                       // As / Hs are dead: reuse them as the staging tiles
-    resid_epilogue(m.h, m.b2, acc2, b, t0, L, wave, lane, reinterpret_cast<float*>(smem));
 }
 
 // ================================================================================================ score + pool
@@ -790,11 +716,6 @@ constexpr int TAIL_NSTAMP = 28;      // 0..20 phase boundaries, 21..26 the six h
 // the 32 token rows of one accumulator tile
 __device__ __forceinline__ void tail_load_resid_piece(const TailArgs& m, float4 (&hv)[4], int mt, int b, int t0, int wave,
                                                       int lrow, int lhalf) {
-    if constexpr (lab::NORESID) {      // timing-only: no residual rows (what the loads at the tile boundary cost)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) hv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
     const int t = t0 + mt * 32 + lrow, tc = t < m.L ? t : 0;
     const float* row = m.ids8 ? m.emb + (size_t)m.ids8[(size_t)b * m.Lp + tc] * D + wave * 32 + 4 * lhalf
                               : m.h + ((size_t)b * m.L + tc) * D + wave * 32 + 4 * lhalf;
@@ -825,14 +746,9 @@ __device__ __forceinline__ void tail_load_y_piece(const TailArgs& m, uint4 (&yx)
 // (8 lines per instruction, 4-way conflicted writes) was no faster than the first either.  The loads themselves are what the
 // plane costs (0.85 of 1.2 ms per step, profiles/r04_timing_only.txt), whatever their shape.
 // thread -> (4-channel column, 16-token run) of the y lo tile
-__device__ __forceinline__ int ylo_cg(int tid) { return lab::YLO_MAP64 ? (tid & 63) : (tid & 15) + 16 * ((tid >> 6) & 3); }
-__device__ __forceinline__ int ylo_tk(int tid) { return lab::YLO_MAP64 ? (tid >> 6) * 16 : 16 * (((tid >> 4) & 3) + 4 * (tid >> 8)); }
+__device__ __forceinline__ int ylo_cg(int tid) { return (tid & 15) + 16 * ((tid >> 6) & 3); }
+__device__ __forceinline__ int ylo_tk(int tid) { return 16 * (((tid >> 4) & 3) + 4 * (tid >> 8)); }
 __device__ __forceinline__ void tail_load_ylo(const TailArgs& m, uint4 (&yl)[4], int b, int t0, int tid) {
-    if constexpr (lab::YLO_NOLOAD) {     // timing-only: zeros instead of the four loads (garbage would be NaN bytes: another clock)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) yl[r] = make_uint4(0, 0, 0, 0);
-        return;
-    }
     const int cg = ylo_cg(tid), tk = ylo_tk(tid), tkc = t0 + tk < m.Lp ? tk : 0;   // clamped, masked at the LDS store
     const unsigned char* src = m.ylo + ((size_t)b * D + 4 * cg) * m.Lp + t0 + tkc;
 #pragma unroll
@@ -852,8 +768,8 @@ __device__ __forceinline__ void tail_stage_ylo(unsigned char* Aly, const uint4 (
         const unsigned d3 = a == 0 ? yl[3].x : a == 1 ? yl[3].y : a == 2 ? yl[3].z : yl[3].w;
         const unsigned x0 = __builtin_amdgcn_perm(d1, d0, 0x05010400u), x1 = __builtin_amdgcn_perm(d1, d0, 0x07030602u);
         const unsigned y0 = __builtin_amdgcn_perm(d3, d2, 0x05010400u), y1 = __builtin_amdgcn_perm(d3, d2, 0x07030602u);
-        const unsigned o[4] = {lab::YLO_NOPERM ? d0 : __builtin_amdgcn_perm(y0, x0, 0x05040100u), lab::YLO_NOPERM ? d1 : __builtin_amdgcn_perm(y0, x0, 0x07060302u),
-                               lab::YLO_NOPERM ? d2 : __builtin_amdgcn_perm(y1, x1, 0x05040100u), lab::YLO_NOPERM ? d3 : __builtin_amdgcn_perm(y1, x1, 0x07060302u)};
+        const unsigned o[4] = {__builtin_amdgcn_perm(y0, x0, 0x05040100u), __builtin_amdgcn_perm(y0, x0, 0x07060302u),
+                               __builtin_amdgcn_perm(y1, x1, 0x05040100u), __builtin_amdgcn_perm(y1, x1, 0x07060302u)};
 #pragma unroll
         for (int e = 0; e < 4; ++e) *reinterpret_cast<unsigned*>(dst + (4 * a + e) * RSL) = in_row ? o[e] : 0u;
     }
@@ -947,7 +863,7 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
     uint4 yx[8];                                           // y tile pieces of this thread
     // fp16c, round 4: y comes as hi + lo bytes; the lo plane is staged into a token-major tile behind the y tile (under As / Hs,
     // dead during out_proj) and adds the activations' lo term to out_proj (compute_km LO2)
-    constexpr bool LOY = PREC == PREC_F16C && !lab::NOYLO;
+    constexpr bool LOY = PREC == PREC_F16C;
     uint4 yl[LOY ? 4 : 1];
     unsigned char* Aly = smem + (size_t)D * RSKM * 2;
     static_assert((size_t)D * RSKM * 2 % 16 == 0 && (size_t)D * RSKM * 2 + 128 * RSL <= (size_t)2 * BM * RS16 * 2, "y lo tile fits behind the y tile");
@@ -1004,7 +920,7 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
             }
         }
     }
-    phase_km<PREC, D, D, PF, LOY && !lab::YLO_NOMFMA>(Ys, wo, 0, 0, w1, 0, 0, wave, lane, bs, acc2, Aly);   // (first fc1 set requested under the last set)
+    phase_km<PREC, D, D, PF, LOY>(Ys, wo, 0, 0, w1, 0, 0, wave, lane, bs, acc2, Aly);   // (first fc1 set requested under the last set)
     CLM_STAMP_AT(2);
     // ---- 2./3. LayerNorm-2 of r straight from the accumulators -> As (16-bit)
     ln_acc_to_tile<PREC>(acc2, P1, P2, m.ln_g, m.ln_b, m.eps, As, t0, L, wave, lrow, lhalf);
@@ -1161,17 +1077,12 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
 }
 
 // ================================================================================================ launchers
-template <typename Kern, typename Args>
-static void launch16_inst(Kern kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args& args) {
-    CLM_SET_LDS(kern, lds);                                  // (one static per instantiation of this launcher = per kernel)
-    hipLaunchKernelGGL(kern, grid, block, lds, st, args);
-}
 // one instantiation per 16-bit arithmetic mode (bf16, fp16, fp16 with hi + lo weights)
-#define CLM_LAUNCH16(prec, KERN, grid, block, lds, st, args)                                  \
-    do {                                                                                      \
-        if ((prec) == PREC_BF16) launch16_inst(KERN<PREC_BF16>, grid, block, lds, st, args);  \
-        else if ((prec) == PREC_F16C) launch16_inst(KERN<PREC_F16C>, grid, block, lds, st, args); \
-        else launch16_inst(KERN<PREC_F16>, grid, block, lds, st, args);                       \
+#define CLM_LAUNCH16(prec, KERN, ...)                                           \
+    do {                                                                        \
+        if ((prec) == PREC_BF16) launch_lds<KERN<PREC_BF16>>(__VA_ARGS__);      \
+        else if ((prec) == PREC_F16C) launch_lds<KERN<PREC_F16C>>(__VA_ARGS__); \
+        else launch_lds<KERN<PREC_F16>>(__VA_ARGS__);                           \
     } while (0)
 
 void launch_inproj16(int prec, const float* h, const float* g, const float* bta, const void* w, const float* bias,
@@ -1191,15 +1102,6 @@ void launch_outproj16(int prec, const void* y, const void* w, const float* bias,
     static_assert(lds >= (size_t)D * RSKM * 2, "k-major tile must fit");
     dim3 grid((L + 127) / 128, B), block(512);
     CLM_LAUNCH16(prec, out_proj16_kernel, grid, block, lds, st, a);
-}
-
-void launch_mlp16(int prec, float* h, const float* g, const float* bta, const void* w1, const float* b1, const void* w2,
-                  const float* b2, int B, int L, float eps, hipStream_t st) {
-    MlpArgs m{h, g, bta, w1, w2, b1, b2, B, L, eps};
-    constexpr size_t lds = (size_t)2 * 128 * RS16 * 2;
-    dim3 grid((L + 127) / 128, B), block(512);
-    // (fp16c: LayerNorm-2 + fc1 + GELU + fc2 is the plain fp16 kernel on fp16-packed weights, as inside tail16_kernel)
-    CLM_LAUNCH16(prec == PREC_F16C ? (int)PREC_F16 : prec, mlp16_kernel, grid, block, lds, st, m);
 }
 
 // developer stamps (CLM_DEBUG=stamp): per-phase mean cycles of wave 0 over all workgroups, printed by clm_destroy
@@ -1254,8 +1156,7 @@ void tail16_dump_stamps() {
 template <int PREC, int NEXT, bool ZG = false, bool MLPC = false>
 static void launch_tail_inst(const TailArgs& m, dim3 grid, size_t lds, hipStream_t st) {
     if (ZG) lds += (size_t)(ZG_HALO_FLOATS - D3) * 4;        // the stash takes the in_proj bias table's place and 3 KiB more
-    CLM_SET_LDS((tail16_kernel<PREC, false, NEXT, ZG, MLPC>), lds);
-    hipLaunchKernelGGL((tail16_kernel<PREC, false, NEXT, ZG, MLPC>), grid, dim3(512), lds, st, m, (unsigned long long*)nullptr);
+    launch_lds<tail16_kernel<PREC, false, NEXT, ZG, MLPC>>(grid, dim3(512), lds, st, m, (unsigned long long*)nullptr);
 }
 
 static int tail_cus() {
@@ -1294,14 +1195,8 @@ void launch_tail16(int prec, const TailArgs& m, int next, hipStream_t st) {
             s_stamp_wgs = wgs;
         }
         (void)hipMemsetAsync(s_stamp_buf, 0, wgs * TAIL_NSTAMP * 8, st);
-        if (zg) {
-            constexpr size_t ldz = lds + (size_t)(ZG_HALO_FLOATS - D3) * 4;
-            CLM_SET_LDS((tail16_kernel<PREC_F16C, true, NEXT_INPROJ, true>), ldz);
-            hipLaunchKernelGGL((tail16_kernel<PREC_F16C, true, NEXT_INPROJ, true>), grid, block, ldz, st, m, s_stamp_buf);
-        } else {
-            CLM_SET_LDS((tail16_kernel<PREC_F16C, true, NEXT_INPROJ>), lds);
-            hipLaunchKernelGGL((tail16_kernel<PREC_F16C, true, NEXT_INPROJ>), grid, block, lds, st, m, s_stamp_buf);
-        }
+        if (zg) launch_lds<tail16_kernel<PREC_F16C, true, NEXT_INPROJ, true>>(grid, block, lds + (size_t)(ZG_HALO_FLOATS - D3) * 4, st, m, s_stamp_buf);
+        else launch_lds<tail16_kernel<PREC_F16C, true, NEXT_INPROJ>>(grid, block, lds, st, m, s_stamp_buf);
         return;
     }
     if (prec == PREC_F16C && m.mlp_lo) {                       // fc1 / fc2 on hi + lo weights too (the guard's second level)

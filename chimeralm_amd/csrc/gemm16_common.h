@@ -37,19 +37,17 @@ __device__ __forceinline__ unsigned short to_bits(float v) {
 // LO2 (fp16c only): the activations' lo tile `Al` (RSL, lo_pos) adds a third term per row tile and 64-deep group.
 // MT0, NMT (fp16c only): the row tiles [MT0, MT0 + NMT) of the 128-token tile instead of all four (the gated in_proj stage runs its
 // v block in two 64-token halves: half the accumulator registers at a time).
-template <int PREC, bool ROWS_N, int AHEAD = 4, bool LO2_ = false, int MT0 = 0, int NMT = 4>
+template <int PREC, bool ROWS_N, int AHEAD = 4, bool LO2 = false, int MT0 = 0, int NMT = 4>
 __device__ __forceinline__ void compute_tm(const typename CT<PREC>::elem* As, int part, int lrow, int lhalf,
                                            const u16x8 (&src)[1][SETK], f32x16 (&acc)[4], const unsigned char* Al = nullptr) {
-    static_assert(!LO2_ || PREC == PREC_F16C, "activation lo tiles exist in the compensated mode only");
+    static_assert(!LO2 || PREC == PREC_F16C, "activation lo tiles exist in the compensated mode only");
     static_assert((MT0 == 0 && NMT == 4) || PREC == PREC_F16C, "row-tile ranges are implemented for the compensated mode");
-    constexpr bool LO2 = LO2_ && !lab::NOLO2;
     // Explicitly software-pipelined over the 4*KPS (k-step, row tile) items: the A fragment of item i + AHEAD is requested
     // before the MFMA(s) of item i (ring of AHEAD + 1 fragments), and that order is pinned with sched_group_barrier.  Left to
     // itself hipcc serialises `ds_read -> s_waitcnt lgkmcnt(0) -> mfma` wherever registers are tight (fc1: both accumulators
     // and two half-sets live), and every MFMA then pays a full LDS latency: fc1 ran at half the rate of fc2.
     constexpr int FR = WFR<PREC>, KP = KPS<PREC>, NI = 4 * KP, R = AHEAD + 1;
     const typename CT<PREC>::elem* a0 = As + lrow * RS16 + part * KP * 16 + lhalf * 8;
-#define CLM_A_OFF(x) (lab::A0 ? 0 : (x))
     if constexpr (PREC == PREC_F16C) {
         // Compensated mode.  Items run ROW-TILE major (mt = i >> 2, k-step = i & 3): a row tile's four activation fragments feed
         // four fp16 MFMAs with the hi fragments and, their upper bytes gathered as e5m2 as they pass (8 registers, two v_perm_b32
@@ -77,12 +75,12 @@ __device__ __forceinline__ void compute_tm(const typename CT<PREC>::elem* As, in
             }
         }
 #pragma unroll
-        for (int i = 0; i < AHEAD; ++i) afc[i % R] = *reinterpret_cast<const u16x8*>(a0 + CLM_A_OFF((MT0 + (i >> 2)) * 32 * RS16 + (i & 3) * 16));
+        for (int i = 0; i < AHEAD; ++i) afc[i % R] = *reinterpret_cast<const u16x8*>(a0 + (MT0 + (i >> 2)) * 32 * RS16 + (i & 3) * 16);
 #pragma unroll
         for (int i = 0; i < NIR; ++i) {
             if (i + AHEAD < NIR) {
                 const int n = i + AHEAD;
-                afc[n % R] = *reinterpret_cast<const u16x8*>(a0 + CLM_A_OFF((MT0 + (n >> 2)) * 32 * RS16 + (n & 3) * 16));
+                afc[n % R] = *reinterpret_cast<const u16x8*>(a0 + (MT0 + (n >> 2)) * 32 * RS16 + (n & 3) * 16);
             }
             const int mt = MT0 + (i >> 2), ks = i & 3;
             if constexpr (LO2) {
@@ -94,12 +92,10 @@ __device__ __forceinline__ void compute_tm(const typename CT<PREC>::elem* As, in
             }
             if (ROWS_N) acc[mt] = mfma<PREC>(src[0][ks], afc[i % R], acc[mt]);
             else acc[mt] = mfma<PREC>(afc[i % R], src[0][ks], acc[mt]);
-            if constexpr (!lab::NOLO) {
-                int w0, w1;
-                frag_to_e5m2t(afc[i % R], w0, w1);
-                a8[2 * ks] = w0, a8[2 * ks + 1] = w1;
-                if (ks == 3) acc[mt] = mfma_lo8<ROWS_N>(w8, a8, acc[mt]);
-            }
+            int w0, w1;
+            frag_to_e5m2t(afc[i % R], w0, w1);
+            a8[2 * ks] = w0, a8[2 * ks + 1] = w1;
+            if (ks == 3) acc[mt] = mfma_lo8<ROWS_N>(w8, a8, acc[mt]);
             if constexpr (LO2) {
                 if (ks == 3) acc[mt] = mfma_lo2<ROWS_N>(w8h, alo, acc[mt]);
             }
@@ -111,10 +107,8 @@ __device__ __forceinline__ void compute_tm(const typename CT<PREC>::elem* As, in
             if (i + AHEAD < NIR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             if (LO2 && (i & 3) == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if constexpr (!lab::NOLO) {
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-                if ((i & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            }
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+            if ((i & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             if (LO2 && (i & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         }
         return;
@@ -144,11 +138,10 @@ __device__ __forceinline__ void compute_tm(const typename CT<PREC>::elem* As, in
 
 // Same, A operand taken from the k-major tile Ys[k][token] with the transposing read: a 16-lane group reads a
 // 4(k) x 16(token) block and lane i receives token i's four k values (cdna_hip_programming.md T10).
-template <int PREC, bool LO2_ = false>
+template <int PREC, bool LO2 = false>
 __device__ __forceinline__ void compute_km(const typename CT<PREC>::elem* Ys, int part, int lane,
                                            const u16x8 (&src)[1][SETK], f32x16 (&acc)[4], const unsigned char* Al = nullptr) {
-    static_assert(!LO2_ || PREC == PREC_F16C, "activation lo tiles exist in the compensated mode only");
-    constexpr bool LO2 = LO2_ && !lab::NOLO2;
+    static_assert(!LO2 || PREC == PREC_F16C, "activation lo tiles exist in the compensated mode only");
     constexpr int FR = WFR<PREC>, KP = KPS<PREC>;
     const int li = lane & 15, g1 = (lane >> 4) & 1, h = lane >> 5, q = li >> 2, p = li & 3;
     const typename CT<PREC>::elem* base = Ys + (8 * h + q) * RSKM + 16 * g1 + 4 * p;
@@ -254,7 +247,7 @@ __device__ __forceinline__ void phase_tm(const typename CT<PREC>::elem* As, cons
         }
         if constexpr (p % (NP / 2) == 0) hook(hook0 + p / (NP / 2));
         __builtin_amdgcn_sched_barrier(0);
-        compute_tm<PREC, ROWS_N, lab::AHEAD, LO2, MT0, NMT>(As, p, lrow, lhalf, bs[p & 1], acc, Al);
+        compute_tm<PREC, ROWS_N, 4, LO2, MT0, NMT>(As, p, lrow, lhalf, bs[p & 1], acc, Al);
         __builtin_amdgcn_sched_barrier(0);
     });
 }
@@ -302,30 +295,6 @@ __device__ __forceinline__ void ln_acc_to_tile(f32x16 (&acc2)[4], float* P1, flo
     static_assert(!LO || PREC == PREC_F16C, "activation lo tiles exist in the compensated mode only");
     constexpr int BM = 128;
     float mean[4], rstd[4];
-    if constexpr (lab::NOLN) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) mean[mt] = 0.f, rstd[mt] = 1.f;
-        __syncthreads();
-    } else if constexpr (lab::LN1PASS) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += acc2[mt][r], q = fmaf(acc2[mt][r], acc2[mt][r], q);
-            s += __shfl_xor(s, 32, 64);
-            q += __shfl_xor(q, 32, 64);
-            if (lhalf == 0) P1[wave * BM + mt * 32 + lrow] = s, P2[wave * BM + mt * 32 + lrow] = q;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            float s = 0.f, q = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s += P1[w * BM + mt * 32 + lrow], q += P2[w * BM + mt * 32 + lrow];
-            mean[mt] = s * (1.0f / D);
-            rstd[mt] = 1.0f / sqrtf(fmaxf(q * (1.0f / D) - mean[mt] * mean[mt], 0.f) + eps);
-        }
-    } else {
     // the two-exchange form: mean first, then the deviations about it.  (ONE exchange -- every lane leaves the sum of its 16 values
     // and their squared deviations about its own mean, combined exactly after Chan et al. -- was built and MEASURED SLOWER in round 3:
     // 22.76 vs 22.45 ms of tail kernel per step; the statistics cost VALU + LDS instructions, not barriers.  HISTORY.md section 4.9.)
@@ -363,7 +332,6 @@ __device__ __forceinline__ void ln_acc_to_tile(f32x16 (&acc2)[4], float* P1, flo
 #pragma unroll
         for (int w = 0; w < 8; ++w) v += P2[w * BM + mt * 32 + lrow];
         rstd[mt] = 1.0f / sqrtf(v * (1.0f / D) + eps);
-    }
     }
     const float* gp = g + wave * 32 + 4 * lhalf;
     const float* bp = bta + wave * 32 + 4 * lhalf;

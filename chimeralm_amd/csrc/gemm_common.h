@@ -339,14 +339,10 @@ __device__ __forceinline__ void load_set(const typename CT<PREC>::frag* wp, int 
                                          typename CT<PREC>::frag (&dst)[NT][SETK]) {
     constexpr int KSTEPS = 256 / CT<PREC>::MFMA_K, KSTEPS_ALL = K / CT<PREC>::MFMA_K;
     constexpr int FR = CT<PREC>::MFMA_K == 16 ? WFR<PREC> : 1, KP = SETK / FR;
-    if constexpr (lab::NOW) {
-        if (kc != 0 || part != 0) return;
-    }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const typename CT<PREC>::frag* p =
             wp + ((size_t)(nb * 8 + wave * NT + nt) * KSTEPS_ALL + kc * KSTEPS + part * KP) * (FR * 64) + lane;
-        if constexpr (lab::W0) p = wp + (size_t)(wave * NT + nt) * KSTEPS_ALL * (FR * 64) + lane;
 #pragma unroll
         for (int ks = 0; ks < SETK; ++ks)
             if (PREC != PREC_F16C || ks < 6) dst[nt][ks] = p[(size_t)ks * 64];     // compensated mode: slots 6, 7 are unused

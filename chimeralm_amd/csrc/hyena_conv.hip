@@ -1130,8 +1130,6 @@ static void launch_conv_pers_inst(const void* z, void* y, const float2* kf, cons
                                   const float* ztab, int use_xcd, hipStream_t st, unsigned char* ylo = nullptr) {
     using P = Plan<14>;
     constexpr size_t lds = (size_t)2 * padded_size(P::N) * sizeof(float) + 256;
-    auto kern = hyena_conv_pers_kernel<T, IDS, GATED, LO>;
-    CLM_SET_LDS(kern, lds);
     static const int cus = [] {
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1139,8 +1137,8 @@ static void launch_conv_pers_inst(const void* z, void* y, const float2* kf, cons
     }();
     const int n_units = ((B + 1) / 2) * D;
     dim3 grid(n_units < cus ? n_units : cus), block(P::NT);
-    hipLaunchKernelGGL(kern, grid, block, lds, st, reinterpret_cast<const T*>(z), reinterpret_cast<T*>(y), kf, tw, ktime, short_w,
-                       short_b, B, L, Lp, ids8, ztab, use_xcd, ylo);
+    launch_lds<hyena_conv_pers_kernel<T, IDS, GATED, LO>>(grid, block, lds, st, reinterpret_cast<const T*>(z), reinterpret_cast<T*>(y), kf,
+                                                         tw, ktime, short_w, short_b, B, L, Lp, ids8, ztab, use_xcd, ylo);
 }
 
 // (Round 2 built the 16384-point convolution of 8k reads as two 8192-point problems over the even / odd bins -- hyena_conv_eo_kernel --
@@ -1693,12 +1691,11 @@ static void launch_conv_seg_inst(const void* z, void* y, const float2* kf, int K
                               int use_xcd, hipStream_t st, unsigned char* ylo = nullptr, const SegPrefix& pfx = SegPrefix{}) {
     using P = Plan<14>;
     constexpr size_t lds = (size_t)2 * padded_size(P::N) * sizeof(float) + 256;   // + the 3x16 id table
-    auto kern = hyena_conv_seg_kernel<T, LONE, IDS, GATED, LO>;
-    CLM_SET_LDS(kern, lds);
     static_assert(D % XCDS == 0, "channels split evenly over the XCDs");
     dim3 grid(((B + 1) / 2) * D), block(P::NT);
-    hipLaunchKernelGGL(kern, grid, block, lds, st, reinterpret_cast<const T*>(z), reinterpret_cast<T*>(y), kf, KS, tw,
-                       short_w, short_b, gscratch, B, L, Lp, S, krev, krev_stride, ids8, ztab, use_xcd, ylo, pfx);
+    launch_lds<hyena_conv_seg_kernel<T, LONE, IDS, GATED, LO>>(grid, block, lds, st, reinterpret_cast<const T*>(z), reinterpret_cast<T*>(y),
+                                                              kf, KS, tw, short_w, short_b, gscratch, B, L, Lp, S, krev, krev_stride,
+                                                              ids8, ztab, use_xcd, ylo, pfx);
 }
 // LO: fp16c (T = f16_t) with a lo plane for y -- the gated rows then carry lo bytes too
 template <typename T, bool LO = false>
@@ -1833,14 +1830,6 @@ void conv_dump_stamps() {
         if (k != 6) std::fprintf(stderr, "  %-14s %9.0f  %5.1f %%\n", names[k], sum[k] / (n ? n : 1), 100.0 * sum[k] / (n ? n : 1) / tot);
 }
 
-// one launch site = one static: the dynamic-LDS attribute is set once per kernel instantiation and device
-#define CLM_CONV_LAUNCH(KERN, ...)                                    \
-    do {                                                              \
-        auto kern_ = KERN;                                            \
-        CLM_SET_LDS(kern_, lds);                                      \
-        hipLaunchKernelGGL(kern_, grid, block, lds, st, __VA_ARGS__); \
-    } while (0)
-
 // LO: fp16c (T = f16_t) with a lo plane for y -- the gated rows then carry lo bytes too
 template <int LOGN, typename T, bool LO = false>
 static void launch_conv_t(const void* z, void* y, const float2* kf, const float2* tw, const float* ktime,
@@ -1856,14 +1845,14 @@ static void launch_conv_t(const void* z, void* y, const float2* kf, const float2
     const float* const no_tab = nullptr;
     if constexpr (!std::is_same<T, float>::value) {
         if (gated && !ids8) {
-            CLM_CONV_LAUNCH((hyena_conv_kernel<LOGN, T, false, false, true, LO>), zt, yt, kf, tw, ktime, short_w, short_b, B, L, Lp,
-                            no_stamps, no_ids, no_tab, ylo);
+            launch_lds<hyena_conv_kernel<LOGN, T, false, false, true, LO>>(grid, block, lds, st, zt, yt, kf, tw, ktime, short_w, short_b,
+                                                                            B, L, Lp, no_stamps, no_ids, no_tab, ylo);
             return;
         }
     }
     if (ids8) {     // block 0: z looked up by token id (exact fp32 too, round 4: its block 0 then needs no in_proj launch)
-        CLM_CONV_LAUNCH((hyena_conv_kernel<LOGN, T, false, true, false, LO>), (const T*)nullptr, yt, kf, tw, ktime, short_w, short_b,
-                        B, L, Lp, no_stamps, ids8, ztab, ylo);
+        launch_lds<hyena_conv_kernel<LOGN, T, false, true, false, LO>>(grid, block, lds, st, (const T*)nullptr, yt, kf, tw, ktime, short_w,
+                                                                       short_b, B, L, Lp, no_stamps, ids8, ztab, ylo);
         return;
     }
     if constexpr (LOGN == 14 && std::is_same<T, f16_t>::value && !LO) {
@@ -1876,13 +1865,13 @@ static void launch_conv_t(const void* z, void* y, const float2* kf, const float2
                 s_conv_stamp_wgs = wgs;
             }
             (void)hipMemsetAsync(s_conv_stamp_buf, 0, wgs * CONV_NSTAMP * 8, st);
-            CLM_CONV_LAUNCH((hyena_conv_kernel<LOGN, T, true>), zt, yt, kf, tw, ktime, short_w, short_b, B, L, Lp, s_conv_stamp_buf,
-                            no_ids, no_tab, (unsigned char*)nullptr);
+            launch_lds<hyena_conv_kernel<LOGN, T, true>>(grid, block, lds, st, zt, yt, kf, tw, ktime, short_w, short_b, B, L, Lp,
+                                                          s_conv_stamp_buf, no_ids, no_tab, (unsigned char*)nullptr);
             return;
         }
     }
-    CLM_CONV_LAUNCH((hyena_conv_kernel<LOGN, T, false, false, false, LO>), zt, yt, kf, tw, ktime, short_w, short_b, B, L, Lp, no_stamps,
-                    no_ids, no_tab, ylo);
+    launch_lds<hyena_conv_kernel<LOGN, T, false, false, false, LO>>(grid, block, lds, st, zt, yt, kf, tw, ktime, short_w, short_b, B, L,
+                                                                    Lp, no_stamps, no_ids, no_tab, ylo);
 }
 
 template <int LOGN>

@@ -757,12 +757,6 @@ void launch_pack_f32t(const float* w, void* out, int n, int k, hipStream_t st) {
     hipLaunchKernelGGL(pack_f32t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, reinterpret_cast<f32x4*>(out), n, k);
 }
 
-// one instantiation per kernel: the dynamic-LDS attribute is set once per kernel and device
-template <auto Kern, typename Args>
-static void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args& m) {
-    CLM_SET_LDS(Kern, lds);
-    hipLaunchKernelGGL(Kern, grid, block, lds, st, m);
-}
 // x3: the products as three fp16 MFMAs on hi + lo halfs (weights from launch_pack_x3) instead of the fp32 MFMA.
 // score != null (the last block; w_in_next must be null): ln_f + pooling scores + per-64-token-tile pooling partials follow on the tile.
 void launch_tail32(const float* y, float* h, const void* w_out, const void* w_fc1, const void* w_fc2, const void* w_in_next,

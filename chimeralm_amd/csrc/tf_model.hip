@@ -13,7 +13,7 @@
 // attention is attention.hip.  Data layout, one batch of B reads (L tokens -> L3 = L / 8 positions, M = B * L3 rows):
 //   x1 [B, L/2, 256], x2 [B, L/4, 256], x3 [B, L3, 256]     16-bit, token-major          conv stack
 //   h  [M, 256] fp32 (residual stream, post-norm: always a LayerNorm output)   hx [M, 256] 16-bit copy = next GEMM operand
-//   qkv [M, 768], att [M, 256], u [M, 1024]                  16-bit
+//   qkv [M, 768], att [M, 256]                               16-bit
 // The convolution is a GEMM with K = 3 * 256: one 130-row tile of the input (1 halo row each side) feeds three passes with the
 // row offset 0 / 1 / 2 and the weight slice W[:, :, dk]; ReLU and the max-pool happen on the accumulator quads (4 consecutive
 // positions of one channel) before anything is written.
@@ -152,15 +152,11 @@ struct LinArgs {
     const void* a;            // [M, K] 16-bit, token-major
     const void* w;            // packed [N, K]
     const float* bias;        // [N]
-    void* out16;              // E_ACT: [M, N] 16-bit
-    float* h;                 // E_RES_LN: residual in, LayerNorm(residual + a W^T + bias) out, [M, 256] fp32
-    void* hx;                 // E_RES_LN: 16-bit copy of the new h
-    const float *ln_g, *ln_b;
+    void* out16;              // [M, N] 16-bit
     size_t M;
-    float eps;
     int relu;
 };
-enum { E_ACT = 0, E_RES_LN = 1 };
+enum { E_ACT = 0 };           // bias (+ ReLU) -> 16-bit rows: the one epilogue (the layer's later products run in enc_ffn16_kernel)
 
 template <int PREC>
 __device__ __forceinline__ void stage_rows16(const typename CT<PREC>::elem* a, size_t row0, size_t M, int K, int kc,
@@ -277,40 +273,21 @@ template <int PREC, int EPI, int K, int N>
 __global__ __launch_bounds__(512) void linear16_kernel(LinArgs m) {
     using elem = typename CT<PREC>::elem;
     using frag = u16x8;
-    static_assert(K % 256 == 0 && N % 256 == 0, "256-wide chunks");
-    static_assert(EPI == E_ACT ? K == 256 : N == 256, "E_ACT keeps one activation tile; E_RES_LN normalises one 256-wide row");
+    static_assert(EPI == E_ACT && K == 256 && N % 256 == 0, "one activation tile, 256-wide output chunks");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     elem* As = reinterpret_cast<elem*>(smem);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 31, lhalf = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t row0 = (size_t)blockIdx.x * 128;
     const elem* a = reinterpret_cast<const elem*>(m.a);
     const frag* wp = reinterpret_cast<const frag*>(m.w);
     f32x16 acc[4];
     frag bs[2][1][SETK];
-    if constexpr (EPI == E_ACT) {
-        elem* zs = As + 128 * RS16 + wave * 128 * ZRS;        // wave-private [128 tokens][32 features]
-        load_set<PREC, K, 1>(wp, 0, 0, 0, wave, lane, bs[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        stage_rows16<PREC>(a, row0, m.M, K, 0, As, tid);
-        __syncthreads();
-        act_blocks<PREC, N>(As, zs, wp, m.bias, reinterpret_cast<elem*>(m.out16), row0, m.M, m.relu != 0, bs, acc);
-    } else {
-        float* P1 = reinterpret_cast<float*>(smem + (size_t)2 * 128 * RS16 * 2);   // tables behind the 128 KiB staging area
-        float* P2 = P1 + 16 * 128;
-        zero_acc(acc);
-        load_set<PREC, K, 1>(wp, 0, 0, 0, wave, lane, bs[0]);
-#pragma unroll 1
-        for (int kc = 0; kc < K / 256; ++kc) {                 // (bs[0] holds the chunk's first set: requested a chunk ahead)
-            load_set<PREC, K, 1>(wp, 0, kc, 1, wave, lane, bs[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kc > 0) __syncthreads();                       // every wave is done with the previous chunk of the tile
-            stage_rows16<PREC>(a, row0, m.M, K, kc, As, tid);
-            __syncthreads();
-            phase_tm<PREC, K, K, true, true>(As, wp, 0, kc, wp, 0, kc + 1 < K / 256 ? kc + 1 : 0, wave, lane, bs, acc);
-        }
-        const int l_valid = res_ln<PREC>(acc, m.bias, m.h, m.ln_g, m.ln_b, m.eps, row0, m.M, As, P1, P2);
-        store_h_hx<PREC>(acc, m.h, reinterpret_cast<elem*>(m.hx), row0, l_valid, smem, As);
-    }
+    elem* zs = As + 128 * RS16 + wave * 128 * ZRS;            // wave-private [128 tokens][32 features]
+    load_set<PREC, K, 1>(wp, 0, 0, 0, wave, lane, bs[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    stage_rows16<PREC>(a, row0, m.M, K, 0, As, tid);
+    __syncthreads();
+    act_blocks<PREC, N>(As, zs, wp, m.bias, reinterpret_cast<elem*>(m.out16), row0, m.M, m.relu != 0, bs, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ fused feed-forward
@@ -488,9 +465,9 @@ struct clm_tf_handle {
     bool finalized = false;
     // workspace
     size_t cap_rows = 0, cap_tok = 0, cap_B = 0;            // cap_B: reads `pooled` has rows for (it scales with B alone)
-    size_t cap16[7] = {};                         // bytes of x1, x2, x3, hx, qkv, att, u
+    size_t cap16[6] = {};                         // bytes of x1, x2, x3, hx, qkv, att
     unsigned char* ids8 = nullptr;
-    void *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *hx = nullptr, *qkv = nullptr, *att = nullptr, *u = nullptr;
+    void *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *hx = nullptr, *qkv = nullptr, *att = nullptr;
     float *h = nullptr, *scores = nullptr, *pooled = nullptr;
     bool referee = false;                         // inside clm_tf_selfcheck's second pass: an fp16x3 handle runs its exact-fp32 kernels
     bool arith_x3 = false;                        // CLM_PREC_F16X3: prec is PREC_F32, the fused fp32-path kernels run on hi + lo halfs
@@ -573,22 +550,13 @@ std::map<std::string, std::vector<int64_t>> tf_expected(int n_layers) {
 }
 
 void tf_free_ws(clm_tf_handle* h) {
-    for (void* p : {(void*)h->ids8, h->x1, h->x2, h->x3, h->hx, h->qkv, h->att, h->u, (void*)h->h, (void*)h->scores,
+    for (void* p : {(void*)h->ids8, h->x1, h->x2, h->x3, h->hx, h->qkv, h->att, (void*)h->h, (void*)h->scores,
                     (void*)h->pooled, (void*)h->ws32})
         if (p) (void)hipFree(p);
-    h->ids8 = nullptr; h->x1 = h->x2 = h->x3 = h->hx = h->qkv = h->att = h->u = nullptr;
+    h->ids8 = nullptr; h->x1 = h->x2 = h->x3 = h->hx = h->qkv = h->att = nullptr;
     h->h = h->scores = h->pooled = h->ws32 = nullptr;
     h->cap_rows = h->cap_tok = h->cap_ws32 = h->cap_B = 0;
     for (size_t& c : h->cap16) c = 0;
-}
-
-template <int PREC, int EPI, int K, int N>
-void tf_launch_linear(const tf::LinArgs& a, hipStream_t st) {
-    constexpr size_t lds = EPI == tf::E_ACT ? (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2
-                                            : (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
-    auto kern = tf::linear16_kernel<PREC, EPI, K, N>;
-    CLM_SET_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + 127) / 128)), dim3(512), lds, st, a);
 }
 
 template <int PREC>
@@ -601,64 +569,40 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
     launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8, B, L, Lp, st);      // ids of any dtype -> clamped uint8
     constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
     {
-        auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
-        auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
-        CLM_SET_LDS(k1, conv_lds);
-        CLM_SET_LDS(k2, conv_lds);
-        hipLaunchKernelGGL(k1, dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8, Lp, W("embedding.weight"),
-                           (const elem*)nullptr, h->packed.at("cnn.0"), W("cnn.0.bias"), (elem*)h->x1, L, L1);
-        hipLaunchKernelGGL(k2, dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                           (const float*)nullptr, (const elem*)h->x1, h->packed.at("cnn.3"), W("cnn.3.bias"), (elem*)h->x2, L1, L2);
-        hipLaunchKernelGGL(k2, dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                           (const float*)nullptr, (const elem*)h->x2, h->packed.at("cnn.6"), W("cnn.6.bias"), (elem*)h->x3, L2, L3);
+        constexpr auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
+        constexpr auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
+        launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8, Lp, W("embedding.weight"),
+                       (const elem*)nullptr, h->packed.at("cnn.0"), W("cnn.0.bias"), (elem*)h->x1, L, L1);
+        launch_lds<k2>(dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
+                       (const float*)nullptr, (const elem*)h->x1, h->packed.at("cnn.3"), W("cnn.3.bias"), (elem*)h->x2, L1, L2);
+        launch_lds<k2>(dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
+                       (const float*)nullptr, (const elem*)h->x2, h->packed.at("cnn.6"), W("cnn.6.bias"), (elem*)h->x3, L2, L3);
     }
     hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const elem*)h->x3,
                        W("pos_encoder.pe"), W("norm.weight"), W("norm.bias"), h->h, (elem*)h->hx, M, L3, 1e-5f);
     delete tconv;
     for (int i = 0; i < h->n_layers; ++i) {
         const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
-        tf::LinArgs a{};
-        a.M = M; a.eps = 1e-5f;
-        // (the unfused A/B forms read the attention output as ONE 16-bit plane: not for fp16c, whose out_proj takes two)
-        static const bool unfused_ffn_env = debug_flag("tf_unfused_ffn");
-        const bool unfused_ffn = unfused_ffn_env && PREC != PREC_F16C;
-        if (i == 0 || unfused_ffn) {   // later layers: computed at the end of the previous layer's feed-forward kernel
+        if (i == 0) {   // later layers: computed at the end of the previous layer's feed-forward kernel
             TfTimer t(h, st, 2);
-            a.a = h->hx; a.w = h->packed.at(p + "in"); a.bias = W(p + "self_attn.in_proj_bias"); a.out16 = h->qkv; a.relu = 0;
-            tf_launch_linear<PREC, tf::E_ACT, D, tf::TQKV>(a, st);
+            const tf::LinArgs a{h->hx, h->packed.at(p + "in"), W(p + "self_attn.in_proj_bias"), h->qkv, M, 0};
+            constexpr size_t lds = (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2;
+            launch_lds<tf::linear16_kernel<PREC, tf::E_ACT, D, tf::TQKV>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, a);
         }
         {
             TfTimer t(h, st, 1);
             launch_attention_fwd(PREC, h->qkv, h->att, B, L3, st, PREC == PREC_F16C);   // fp16c: hi and lo planes (attention.hip)
         }
         TfTimer tl(h, st, 2);
-        static const bool unfused_layer_env = debug_flag("tf_unfused_layer");
-        const bool unfused_layer = unfused_layer_env && PREC != PREC_F16C;
-        const bool whole_layer = !unfused_layer && !unfused_ffn;   // out_proj + LN1 at the head of the feed-forward kernel
-        if (!whole_layer) {
-            a.a = h->att; a.w = h->packed.at(p + "out"); a.bias = W(p + "self_attn.out_proj.bias"); a.h = h->h; a.hx = h->hx;
-            a.ln_g = W(p + "norm1.weight"); a.ln_b = W(p + "norm1.bias");
-            tf_launch_linear<PREC, tf::E_RES_LN, D, D>(a, st);
-        }
-        if (!unfused_ffn) {
-            const bool more = i + 1 < h->n_layers;
-            const std::string pn = "transformer_encoder.layers." + std::to_string(i + 1) + ".";
-            tf::FfnArgs f{h->hx, h->packed.at(p + "ff1"), h->packed.at(p + "ff2"), W(p + "linear1.bias"), W(p + "linear2.bias"),
-                          W(p + "norm2.weight"), W(p + "norm2.bias"), h->h, h->hx, M, 1e-5f,
-                          more ? h->packed.at(pn + "in") : nullptr, more ? W(pn + "self_attn.in_proj_bias") : nullptr, h->qkv,
-                          whole_layer ? h->att : nullptr, h->packed.at(p + "out"), W(p + "self_attn.out_proj.bias"),
-                          W(p + "norm1.weight"), W(p + "norm1.bias")};
-            constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
-            auto kern = tf::enc_ffn16_kernel<PREC>;
-            CLM_SET_LDS(kern, lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
-        } else {
-            a.a = h->hx; a.w = h->packed.at(p + "ff1"); a.bias = W(p + "linear1.bias"); a.out16 = h->u; a.relu = 1;
-            tf_launch_linear<PREC, tf::E_ACT, D, tf::TFF>(a, st);
-            a.a = h->u; a.w = h->packed.at(p + "ff2"); a.bias = W(p + "linear2.bias");
-            a.ln_g = W(p + "norm2.weight"); a.ln_b = W(p + "norm2.bias");
-            tf_launch_linear<PREC, tf::E_RES_LN, tf::TFF, D>(a, st);
-        }
+        // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel
+        const bool more = i + 1 < h->n_layers;
+        const std::string pn = "transformer_encoder.layers." + std::to_string(i + 1) + ".";
+        const tf::FfnArgs f{h->hx, h->packed.at(p + "ff1"), h->packed.at(p + "ff2"), W(p + "linear1.bias"), W(p + "linear2.bias"),
+                            W(p + "norm2.weight"), W(p + "norm2.bias"), h->h, h->hx, M, 1e-5f,
+                            more ? h->packed.at(pn + "in") : nullptr, more ? W(pn + "self_attn.in_proj_bias") : nullptr, h->qkv,
+                            h->att, h->packed.at(p + "out"), W(p + "self_attn.out_proj.bias"), W(p + "norm1.weight"), W(p + "norm1.bias")};
+        constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
+        launch_lds<tf::enc_ffn16_kernel<PREC>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
     }
     {
         TfTimer t(h, st, 3);
@@ -866,14 +810,14 @@ static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype,
         return hipGetLastError() == hipSuccess ? CLM_OK : tf_fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
     }
     {   // the 16-bit activations, each buffer grown on its own (x1 / x2 scale with B * (L / 2), B * (L / 4), not with M)
-        const size_t need[7] = {(size_t)B * (L / 2) * D * 2, (size_t)B * (L / 4) * D * 2, M * D * 2, M * D * 2, M * tf::TQKV * 2,
-                                M * D * 2 * (h->prec == PREC_F16C ? 2 : 1) /* hi + lo planes */, M * tf::TFF * 2};
-        void** buf[7] = {&h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att, &h->u};
+        const size_t need[6] = {(size_t)B * (L / 2) * D * 2, (size_t)B * (L / 4) * D * 2, M * D * 2, M * D * 2, M * tf::TQKV * 2,
+                                M * D * 2 * (h->prec == PREC_F16C ? 2 : 1) /* hi + lo planes */};
+        void** buf[6] = {&h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att};
         bool grow = false;
-        for (int i = 0; i < 7; ++i) grow |= need[i] > h->cap16[i];
+        for (int i = 0; i < 6; ++i) grow |= need[i] > h->cap16[i];
         if (grow) {
             TFCHK(h, hipDeviceSynchronize());
-            for (int i = 0; i < 7; ++i)
+            for (int i = 0; i < 6; ++i)
                 if (need[i] > h->cap16[i]) {
                     if (*buf[i]) (void)hipFree(*buf[i]);
                     *buf[i] = nullptr; h->cap16[i] = 0;
