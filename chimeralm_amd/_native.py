@@ -21,7 +21,7 @@ PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "bf16": PREC_BF16, "fp16": PREC
 STAGES = ["embed", "ln1_in_proj", "short_long_conv", "out_proj", "ln2_fc1_gelu", "fc2", "lnf_pool_score",
           "softmax_pool", "head_mlp", "filter", "out_proj_ln2_mlp", "ln2_mlp"]
 N_STAGES = len(STAGES)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class ClmConfig(C.Structure):
@@ -79,6 +79,13 @@ SYMBOLS = {
     "clm_tf_profile_read": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "clm_tf_last_error": (C.c_char_p, [_H]),
     "clm_tf_destroy": (C.c_int, [_H]),
+    "clm_cnn_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_H)]),
+    "clm_cnn_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "clm_cnn_finalize": (C.c_int, [_H]),
+    "clm_cnn_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "clm_cnn_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "clm_cnn_last_error": (C.c_char_p, [_H]),
+    "clm_cnn_destroy": (C.c_int, [_H]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

@@ -212,6 +212,11 @@ void launch_pack_f32t(const float* w /*[n][k]*/, void* out /*n * k floats*/, int
 // SequenceCNNTransformer, exact fp32 (tail32.hip conv32_kernel): Conv1d(k = 3, padding = 1) + ReLU + MaxPool1d(2); w = three taps
 // [dk][co][ci], each packed by launch_pack_f32t
 void launch_conv32(const float* x, const void* w, const float* bias, float* out, int B, int Lin, hipStream_t st, bool x3 = false);
+// DNAConvNet blocks 1 and 2 (tail32.hip): Conv1d k = 7 "same" + bias + BatchNorm (scale / shift) + GELU(erf) + MaxPool1d(4), weights
+// [dk][co][ci] with each tap packed by launch_pack_f32t (x3: launch_pack_x3).  partial = true: per-64-row-tile channel sums of the
+// pooled rows -> out [B, ceil((Lin / 4) / 16), 256] instead of the rows themselves
+void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const float* bn_scale, const float* bn_shift, float* out,
+                      bool partial, int B, int Lin, hipStream_t st, bool x3);
 // SequenceCNNTransformer, exact fp32 (tail32.hip enc32_kernel): att == null: qkv of the rows of h as they are; otherwise one encoder
 // layer after its attention (out_proj + LN1 + FFN + LN2 on h in place) and, w_qkv != null, the next layer's in_proj into qkv
 void launch_enc32(const float* att, float* h, const void* w_o, const void* w1, const void* w2, const void* w_qkv, const float* b_o,

@@ -1,0 +1,407 @@
+// cnn.hip -- DNAConvNet forward on MI355X: kernels + engine + C ABI (clm_cnn_*).
+//
+// Reference: /root/reference/chimeralm/models/components/cnn.py (configured by configs/model/cnn.yaml: vocab 12, embedding 256,
+// num_filters [256, 256, 256], kernel_sizes [7, 7, 7], pool_sizes [4, 4, 4], hidden 512, 2 classes), eval mode:
+//   x = Embedding(12, 256)(ids)                         pads are ordinary tokens, no mask
+//   3 x [Conv1d(256, 256, 7, padding "same"), BatchNorm1d (running stats), GELU (erf), MaxPool1d(4), Dropout]   L -> L/4 -> L/16 -> L/64
+//   AdaptiveAvgPool1d(1) ; Linear(256, 512), BatchNorm1d, GELU, Dropout, Linear(512, 2)
+//
+// Four launches per batch (ids -> clamped bytes, then):
+//   block 0   cnn_block0_kernel: the input is an embedding of 12 ids, so conv(embed(x))[t] = b + sum_dk T[dk][x[t + dk - 3]] with the
+//             table T[dk][tok] = W[:, :, dk] . E[tok] (7 x 12 x 256 floats, computed in fp64 at finalize, held in LDS); a position
+//             outside the read contributes nothing (row 12 of the LDS table is zero -- not E[4]: a loaded pad row need not be zero).
+//             Bias, BatchNorm, GELU on each of the 4 positions of a window, then the max; writes [B, L/4, 256] fp32.
+//   block 1   cnn_gemm7_kernel (tail32.hip): implicit GEMM, K = 7 x 256, on the fp32 MFMA or as fp16x3; writes [B, L/16, 256].
+//   block 2   the same kernel; instead of its rows, per-64-row-tile channel sums of its pooled rows -> [B, tiles, 256].
+//   head      cnn_head_kernel: the tiles' sums in a fixed order / (L/64), fc.0, BatchNorm, GELU, fc.4 -> logits [B, 2].
+// No atomics: every reduction has a fixed order, so the forward is bitwise deterministic and a read's logits do not depend on the
+// batch it is in.  BatchNorm is applied as y = x * scale + shift with scale = g / sqrt(var + eps), shift = b - mean * scale, both
+// computed in fp64 at finalize (not folded into the weights).
+#include <cmath>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "chimeralm_hip.h"
+#include "clm_common.h"
+
+namespace clm {
+namespace cnn {
+
+constexpr int VOC = 12;            // embedding rows
+constexpr int K = 7, HALO = 3;     // taps, "same" padding on each side
+constexpr int TROWS = VOC + 1;     // LDS table rows per tap: the 12 ids + a zero row for positions outside the read
+constexpr int HID = 512;           // fc hidden
+constexpr int PT0 = 128;           // block 0: pooled positions per workgroup (512 tokens)
+constexpr int ROWS2 = 16;          // block 2: pooled rows per 64-row tile of cnn_gemm7_kernel
+constexpr float BN_EPS = 1e-5f;
+
+// ------------------------------------------------------------------------------------------------ block 0
+// grid (tiles, B), 512 threads: thread = (channel tid & 255, half tid >> 8 of the tile's pooled positions).
+__global__ __launch_bounds__(512) void cnn_block0_kernel(const unsigned char* __restrict__ ids8, int Lp, const float* __restrict__ table,
+                                                         const float* __restrict__ bias, const float* __restrict__ bn_scale,
+                                                         const float* __restrict__ bn_shift, float* __restrict__ out, int L) {
+    extern __shared__ __attribute__((aligned(16))) float smem_c0[];
+    float* Ts = smem_c0;                                       // [K][TROWS][256]
+    int* idl = reinterpret_cast<int*>(Ts + K * TROWS * D);     // [4 PT0 + 2 HALO]: LDS row of token 4 p0 - 3 + i
+    const int tid = threadIdx.x, b = blockIdx.y, p0 = blockIdx.x * PT0, L4 = L / 4;
+    for (int i = tid; i < K * TROWS * D / 4; i += 512) {
+        const int row = i / (D / 4), dk = row / TROWS, tok = row % TROWS, c4 = i % (D / 4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tok < VOC) v = *reinterpret_cast<const float4*>(table + ((size_t)dk * VOC + tok) * D + 4 * c4);
+        *reinterpret_cast<float4*>(Ts + (size_t)row * D + 4 * c4) = v;
+    }
+    const int base = 4 * p0 - HALO;
+    for (int i = tid; i < 4 * PT0 + 2 * HALO; i += 512) {
+        const int t = base + i;
+        int id = VOC;                                          // outside [0, L): the zero row
+        if (t >= 0 && t < L) {
+            id = ids8[(size_t)b * Lp + t];
+            id = id < VOC ? id : VOC - 1;                      // (ids8 holds [0, 16); ids past the vocabulary clamp to its last row)
+        }
+        idl[i] = id;
+    }
+    __syncthreads();
+    const int c = tid & (D - 1), half = tid >> 8;
+    const float bc = bias[c], sc = bn_scale[c], sh = bn_shift[c];
+    const float* Tc = Ts + c;
+    const int pend = p0 + PT0 < L4 ? p0 + PT0 : L4;
+#pragma unroll 1
+    for (int p = p0 + half * (PT0 / 2); p < pend && p < p0 + (half + 1) * (PT0 / 2); ++p) {
+        const int* id = idl + 4 * (p - p0);                    // token 4 p + j + dk - 3  ->  id[j + dk]
+        int r[4 + K - 1];
+#pragma unroll
+        for (int i = 0; i < 4 + K - 1; ++i) r[i] = id[i] * D;
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = bc;
+#pragma unroll
+            for (int dk = 0; dk < K; ++dk) v += Tc[dk * TROWS * D + r[j + dk]];
+            m = fmaxf(m, gelu_erf(v * sc + sh));
+        }
+        out[((size_t)b * L4 + p) * D + c] = m;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ head
+// one workgroup of 512 threads per read: mean of block 2's pooled rows, fc.0 (weights transposed [256][512]: coalesced), BN, GELU,
+// fc.4; fixed reduction orders throughout
+__global__ __launch_bounds__(512) void cnn_head_kernel(const float* __restrict__ partial, int tiles, int L64, const float* __restrict__ w0t,
+                                                       const float* __restrict__ b0, const float* __restrict__ s1, const float* __restrict__ h1,
+                                                       const float* __restrict__ w4, const float* __restrict__ b4, float* __restrict__ pooled,
+                                                       float* __restrict__ logits) {
+    __shared__ float P[D];
+    __shared__ float red[2][8];
+    const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < D) {
+        const float* src = partial + (size_t)b * tiles * D + tid;
+        float s = 0.f;
+        for (int i = 0; i < tiles; ++i) s += src[(size_t)i * D];
+        s = s / (float)L64;
+        P[tid] = s;
+        pooled[(size_t)b * D + tid] = s;
+    }
+    __syncthreads();
+    float a = b0[tid];
+#pragma unroll 8
+    for (int c = 0; c < D; ++c) a = fmaf(w0t[(size_t)c * HID + tid], P[c], a);
+    const float g = gelu_erf(a * s1[tid] + h1[tid]);
+    const float r0 = wave_sum(g * w4[tid]), r1 = wave_sum(g * w4[HID + tid]);
+    if (lane == 0) {
+        red[0][wave] = r0;
+        red[1][wave] = r1;
+    }
+    __syncthreads();
+    if (tid < NCLS) {
+        const float* r = red[tid];
+        logits[(size_t)b * NCLS + tid] = (((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))) + b4[tid];
+    }
+}
+
+}  // namespace cnn
+}  // namespace clm
+
+// ================================================================================================ engine + C ABI
+using namespace clm;
+
+struct clm_cnn_handle {
+    int device = 0;
+    bool x3 = false;                              // CLM_PREC_F16X3 handle
+    bool x3_active = false;                       // ... and its block 1 / 2 weights are inside the packing's range (finalize)
+    std::string err;
+    std::map<std::string, float*> w;              // fp32 device copies by reference key
+    std::map<std::string, float*> dev;            // finalize products: table, packed taps, BN scale / shift, fc.0 transposed
+    bool finalized = false;
+    size_t cap_tok = 0, cap_x1 = 0, cap_x2 = 0, cap_part = 0, cap_B = 0;
+    unsigned char* ids8 = nullptr;
+    float *x1 = nullptr, *x2 = nullptr, *part = nullptr, *pooled = nullptr;
+    int last_B = 0, last_L = 0;
+};
+
+namespace {
+
+std::string g_cnn_create_error;
+
+int cnn_fail(clm_cnn_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg; else g_cnn_create_error = msg;
+    return code;
+}
+#define CNNCHK(h, call)                                                                             \
+    do {                                                                                            \
+        hipError_t e_ = (call);                                                                     \
+        if (e_ != hipSuccess) return cnn_fail(h, CLM_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+std::map<std::string, std::vector<int64_t>> cnn_expected() {
+    std::map<std::string, std::vector<int64_t>> e;
+    e["embedding.weight"] = {cnn::VOC, D};
+    for (int i = 0; i < 3; ++i) {
+        const std::string p = "conv_blocks." + std::to_string(i) + ".";
+        e[p + "0.weight"] = {D, D, cnn::K};
+        e[p + "0.bias"] = {D};
+        for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[p + "1." + s] = {D};
+    }
+    e["fc.0.weight"] = {cnn::HID, D};
+    e["fc.0.bias"] = {cnn::HID};
+    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[std::string("fc.1.") + s] = {cnn::HID};
+    e["fc.4.weight"] = {NCLS, cnn::HID};
+    e["fc.4.bias"] = {NCLS};
+    return e;
+}
+
+bool is_batches_tracked(const std::string& k) {
+    const std::string s = "num_batches_tracked";
+    return k.size() >= s.size() && k.compare(k.size() - s.size(), s.size(), s) == 0;
+}
+
+int cnn_host(clm_cnn_handle* h, const std::string& k, std::vector<float>& out) {
+    const std::vector<int64_t> shp = cnn_expected().at(k);     // (a copy: the map is a temporary)
+    size_t n = 1;
+    for (int64_t s : shp) n *= (size_t)s;
+    out.resize(n);
+    CNNCHK(h, hipMemcpy(out.data(), h->w.at(k), n * 4, hipMemcpyDeviceToHost));
+    return CLM_OK;
+}
+
+int cnn_upload(clm_cnn_handle* h, const std::string& name, const void* src, size_t bytes) {
+    float* d = nullptr;
+    CNNCHK(h, hipMalloc((void**)&d, bytes));
+    CNNCHK(h, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    h->dev[name] = d;
+    return CLM_OK;
+}
+
+// BatchNorm1d in eval mode as scale / shift, computed in fp64 and rounded once
+int cnn_bn(clm_cnn_handle* h, const std::string& p, const std::string& name, int n) {
+    std::vector<float> g, b, m, v;
+    int rc;
+    if ((rc = cnn_host(h, p + "weight", g)) || (rc = cnn_host(h, p + "bias", b)) || (rc = cnn_host(h, p + "running_mean", m)) ||
+        (rc = cnn_host(h, p + "running_var", v)))
+        return rc;
+    std::vector<float> sc(n), sh(n);
+    for (int i = 0; i < n; ++i) {
+        const double s = (double)g[i] / std::sqrt((double)v[i] + (double)cnn::BN_EPS);
+        sc[i] = (float)s;
+        sh[i] = (float)((double)b[i] - (double)m[i] * s);
+    }
+    if ((rc = cnn_upload(h, name + ".scale", sc.data(), (size_t)n * 4))) return rc;
+    return cnn_upload(h, name + ".shift", sh.data(), (size_t)n * 4);
+}
+
+void cnn_free_ws(clm_cnn_handle* h) {
+    for (void* p : {(void*)h->ids8, (void*)h->x1, (void*)h->x2, (void*)h->part, (void*)h->pooled})
+        if (p) (void)hipFree(p);
+    h->ids8 = nullptr; h->x1 = h->x2 = h->part = h->pooled = nullptr;
+    h->cap_tok = h->cap_x1 = h->cap_x2 = h->cap_part = h->cap_B = 0;
+}
+
+template <typename T>
+int cnn_grow(clm_cnn_handle* h, T*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return CLM_OK;
+    CNNCHK(h, hipDeviceSynchronize());
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    CNNCHK(h, hipMalloc((void**)&p, bytes));
+    cap = bytes;
+    return CLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int clm_cnn_create(int device, int precision, clm_cnn_handle** out) {
+    if (!out) return cnn_fail(nullptr, CLM_E_INVALID, "clm_cnn_create: bad argument");
+    if (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)
+        return cnn_fail(nullptr, CLM_E_INVALID, "clm_cnn_create: precision must be CLM_PREC_F32 (exact) or CLM_PREC_F16X3");
+    if (hipSetDevice(device) != hipSuccess) return cnn_fail(nullptr, CLM_E_HIP, "clm_cnn_create: hipSetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return cnn_fail(nullptr, CLM_E_UNSUPPORTED, "clm_cnn_create: this engine is built for gfx950 (MI355X) only");
+    clm_cnn_handle* h = new clm_cnn_handle();
+    h->device = device;
+    h->x3 = precision == CLM_PREC_F16X3;
+    *out = h;
+    return CLM_OK;
+}
+
+int clm_cnn_load_weight(clm_cnn_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
+    if (!h || !key || !data || !shape || ndim < 0) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: null argument");
+    std::string k(key);
+    if (k.rfind("net.", 0) == 0) k = k.substr(4);
+    if (is_batches_tracked(k)) return CLM_OK;                  // BatchNorm's step counter: not used in eval mode
+    if (dtype != CLM_DT_F32) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: fp32 tensors only");
+    const auto exp = cnn_expected();
+    auto it = exp.find(k);
+    if (it == exp.end()) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: unknown key " + k);
+    if (it->second != std::vector<int64_t>(shape, shape + ndim)) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: wrong shape for " + k);
+    size_t n = 1;
+    for (int64_t s : it->second) n *= (size_t)s;
+    CNNCHK(h, hipSetDevice(h->device));
+    if (h->w.count(k)) { (void)hipFree(h->w[k]); h->w.erase(k); }
+    float* d = nullptr;
+    CNNCHK(h, hipMalloc((void**)&d, n * 4));
+    CNNCHK(h, hipMemcpy(d, data, n * 4, hipMemcpyDefault));
+    h->w[k] = d;
+    h->finalized = false;
+    return CLM_OK;
+}
+
+int clm_cnn_finalize(clm_cnn_handle* h) {
+    if (!h) return CLM_E_INVALID;
+    CNNCHK(h, hipSetDevice(h->device));
+    for (const auto& kv : cnn_expected())
+        if (!h->w.count(kv.first)) return cnn_fail(h, CLM_E_MISSING, "clm_cnn_finalize: missing weight " + kv.first);
+    CNNCHK(h, hipDeviceSynchronize());
+    for (auto& kv : h->dev) (void)hipFree(kv.second);
+    h->dev.clear();
+    h->finalized = false;
+    int rc;
+    // block 0's table T[dk][tok][co] = sum_ci W[co][ci][dk] E[tok][ci], in fp64
+    {
+        std::vector<float> E, W;
+        if ((rc = cnn_host(h, "embedding.weight", E)) || (rc = cnn_host(h, "conv_blocks.0.0.weight", W))) return rc;
+        std::vector<float> T((size_t)cnn::K * cnn::VOC * D);
+        for (int dk = 0; dk < cnn::K; ++dk)
+            for (int tok = 0; tok < cnn::VOC; ++tok)
+                for (int co = 0; co < D; ++co) {
+                    double s = 0.0;
+                    for (int ci = 0; ci < D; ++ci) s += (double)W[((size_t)co * D + ci) * cnn::K + dk] * (double)E[(size_t)tok * D + ci];
+                    T[((size_t)dk * cnn::VOC + tok) * D + co] = (float)s;
+                }
+        if ((rc = cnn_upload(h, "table", T.data(), T.size() * 4))) return rc;
+    }
+    // blocks 1 and 2: [co][ci][dk] -> seven taps [co][ci], each packed for the MFMA.  fp16x3 packs w x 2^10 as fp16 hi + lo, which
+    // saturates for |w| >= 64: such weights run in the exact-fp32 packing instead (chimeralm_amd/cnn.py reports it)
+    std::vector<std::vector<float>> Wb(2);
+    float wmax = 0.f;
+    for (int i = 1; i <= 2; ++i) {
+        if ((rc = cnn_host(h, "conv_blocks." + std::to_string(i) + ".0.weight", Wb[i - 1]))) return rc;
+        for (float v : Wb[i - 1]) wmax = std::fmax(wmax, std::fabs(v));
+    }
+    h->x3_active = h->x3 && wmax < 64.f;
+    {
+        float* split = nullptr;
+        CNNCHK(h, hipMalloc((void**)&split, (size_t)cnn::K * D * D * 4));
+        std::vector<float> hs((size_t)cnn::K * D * D);
+        for (int i = 1; i <= 2; ++i) {
+            const std::vector<float>& W = Wb[i - 1];
+            for (int dk = 0; dk < cnn::K; ++dk)
+                for (int co = 0; co < D; ++co)
+                    for (int ci = 0; ci < D; ++ci) hs[((size_t)dk * D + co) * D + ci] = W[((size_t)co * D + ci) * cnn::K + dk];
+            CNNCHK(h, hipMemcpy(split, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+            float* q = nullptr;
+            CNNCHK(h, hipMalloc((void**)&q, (size_t)cnn::K * D * D * 4));
+            for (int dk = 0; dk < cnn::K; ++dk) {
+                if (h->x3_active) launch_pack_x3(split + (size_t)dk * D * D, q + (size_t)dk * D * D, D, D, 0);
+                else launch_pack_f32t(split + (size_t)dk * D * D, q + (size_t)dk * D * D, D, D, 0);
+            }
+            h->dev["conv" + std::to_string(i)] = q;
+            CNNCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next block
+        }
+        (void)hipFree(split);
+    }
+    for (int i = 0; i < 3; ++i)
+        if ((rc = cnn_bn(h, "conv_blocks." + std::to_string(i) + ".1.", "bn" + std::to_string(i), D))) return rc;
+    if ((rc = cnn_bn(h, "fc.1.", "bnfc", cnn::HID))) return rc;
+    {
+        std::vector<float> W0;
+        if ((rc = cnn_host(h, "fc.0.weight", W0))) return rc;
+        std::vector<float> W0t((size_t)D * cnn::HID);
+        for (int j = 0; j < cnn::HID; ++j)
+            for (int c = 0; c < D; ++c) W0t[(size_t)c * cnn::HID + j] = W0[(size_t)j * D + c];
+        if ((rc = cnn_upload(h, "fc0t", W0t.data(), W0t.size() * 4))) return rc;
+    }
+    CNNCHK(h, hipDeviceSynchronize());
+    h->finalized = true;
+    return CLM_OK;
+}
+
+int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                    void* stream) {
+    if (!h) return CLM_E_INVALID;
+    if (!h->finalized) return cnn_fail(h, CLM_E_STATE, "clm_cnn_forward before clm_cnn_finalize");
+    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: bad argument");
+    if (L < 64)
+        return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: DNAConvNet needs reads of at least 64 tokens (three max-pools of 4; "
+                                          "the reference raises 'Invalid computed output size: 0'), got L = " + std::to_string(L));
+    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
+        return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: ids dtype must be i64, i32 or u8");
+    CNNCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int Lp = (L + 63) / 64 * 64, L4 = L / 4, L16 = L4 / 4, L64 = L16 / 4;
+    const int tiles2 = (L64 + cnn::ROWS2 - 1) / cnn::ROWS2;
+    int rc;
+    if ((rc = cnn_grow(h, h->ids8, h->cap_tok, (size_t)B * Lp)) || (rc = cnn_grow(h, h->x1, h->cap_x1, (size_t)B * L4 * D * 4)) ||
+        (rc = cnn_grow(h, h->x2, h->cap_x2, (size_t)B * L16 * D * 4)) || (rc = cnn_grow(h, h->part, h->cap_part, (size_t)B * tiles2 * D * 4)) ||
+        (rc = cnn_grow(h, h->pooled, h->cap_B, (size_t)B * D * 4)))
+        return rc;
+    auto W = [&](const std::string& k) { return h->w.at(k); };
+    auto P = [&](const std::string& k) { return h->dev.at(k); };
+    launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8, B, L, Lp, st);   // ids of any dtype -> clamped bytes
+    {
+        const size_t lds = (size_t)cnn::K * cnn::TROWS * D * 4 + (size_t)(4 * cnn::PT0 + 2 * cnn::HALO) * 4;
+        launch_lds<cnn::cnn_block0_kernel>(dim3((unsigned)((L4 + cnn::PT0 - 1) / cnn::PT0), (unsigned)B), dim3(512), lds, st, h->ids8, Lp,
+                                           P("table"), W("conv_blocks.0.0.bias"), P("bn0.scale"), P("bn0.shift"), h->x1, L);
+    }
+    launch_cnn_gemm7(h->x1, P("conv1"), W("conv_blocks.1.0.bias"), P("bn1.scale"), P("bn1.shift"), h->x2, false, B, L4, st, h->x3_active);
+    launch_cnn_gemm7(h->x2, P("conv2"), W("conv_blocks.2.0.bias"), P("bn2.scale"), P("bn2.shift"), h->part, true, B, L16, st, h->x3_active);
+    hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, h->part, tiles2, L64, P("fc0t"), W("fc.0.bias"),
+                       P("bnfc.scale"), P("bnfc.shift"), W("fc.4.weight"), W("fc.4.bias"), h->pooled, logits_out);
+    h->last_B = B; h->last_L = L;
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CLM_OK : cnn_fail(h, CLM_E_HIP, std::string("clm_cnn_forward: launch failed: ") + hipGetErrorString(e));
+}
+
+int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, size_t bytes) {
+    if (!h || !name || !host_out) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: bad argument");
+    CNNCHK(h, hipSetDevice(h->device));
+    CNNCHK(h, hipDeviceSynchronize());
+    const std::string n(name);
+    const size_t B = (size_t)h->last_B, L4 = (size_t)(h->last_L / 4), L16 = L4 / 4;
+    const void* src = nullptr;
+    size_t have = 0;
+    if (n == "block0") { src = h->x1; have = B * L4 * D * 4; }
+    else if (n == "block1") { src = h->x2; have = B * L16 * D * 4; }
+    else if (n == "pooled") { src = h->pooled; have = B * D * 4; }
+    else return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: unknown name " + n);
+    if (bytes > have) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: more bytes requested than the last forward produced");
+    CNNCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    return CLM_OK;
+}
+
+const char* clm_cnn_last_error(const clm_cnn_handle* h) { return h ? h->err.c_str() : g_cnn_create_error.c_str(); }
+
+int clm_cnn_destroy(clm_cnn_handle* h) {
+    if (!h) return CLM_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    cnn_free_ws(h);
+    for (auto& kv : h->w) (void)hipFree(kv.second);
+    for (auto& kv : h->dev) (void)hipFree(kv.second);
+    delete h;
+    return CLM_OK;
+}
+
+}  // extern "C"

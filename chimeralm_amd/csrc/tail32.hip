@@ -1,6 +1,7 @@
 // tail32.hip -- the fused kernels of the exact-fp32 engine and of its fp16x3 form (round 4):
 //   tail32_kernel   Hyena block tail (this comment)                          enc32_kernel   SequenceCNNTransformer encoder layer
 //   conv32_kernel   the transformer's CNN stem (conv k = 3 + ReLU + pool)     pack_f32t / pack_x3 kernels: the weight packings
+//   cnn_gemm7_kernel  DNAConvNet blocks 1 and 2 (conv k = 7 + BatchNorm + GELU + pool of 4; cnn.hip)
 // all on one 64-token tile, one weight-set pipeline and one MFMA loop, instantiated for two arithmetics (AR_F32: the fp32 MFMA;
 // AR_X3: every operand as two halfs, three fp16 MFMAs per product -- see ARITH below).  The fp32 / x3 attention lives in tf_fp32.hip.
 //
@@ -715,6 +716,105 @@ __global__ __launch_bounds__(512) void conv32_kernel(Conv32Args m) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// DNAConvNet, blocks 1 and 2: Conv1d(256 -> 256, k = 7, padding "same") + eval BatchNorm + GELU(erf) + MaxPool1d(4)   (cnn.hip)
+// The same implicit GEMM as conv32_kernel with K = 7 x 256: rows t0 - 3 .. t0 + 66 of the block's input (zero outside [0, Lin)) lie
+// in LDS once and tap dk reads them shifted by dk rows.  Epilogue per element: bias, then the BatchNorm as a per-channel scale and
+// shift (fp32, computed in fp64 at finalize), then GELU -- all on every position, since neither BN nor GELU commutes with the max --
+// then the max over the 4 positions of a pooling window, which are 4 adjacent lanes (two lane exchanges).
+// POOLSUM (block 2): the pooled rows are not stored; the tile's per-channel sum over its pooled rows < Lout goes to
+// partial[b][tile][256] in a fixed order (the head kernel finishes the mean).
+struct CnnConvArgs {
+    const float* x;           // [B, Lin, 256]
+    const f32x4* w;           // [7] x packed [256, 256]
+    const float *bias, *bn_scale, *bn_shift;
+    float* out;               // [B, Lin / 4, 256]  or  partial [B, tiles_x, 256] (POOLSUM)
+    int B, Lin, tiles_x;
+};
+
+constexpr int CNN_K = 7, CNN_HALO = 3;
+
+template <bool POOLSUM, int AR = AR_F32>
+__global__ __launch_bounds__(512) void cnn_gemm7_kernel(CnnConvArgs m) {
+    constexpr float WSI = WUNSCALE<AR>;
+    extern __shared__ __attribute__((aligned(16))) float smem32[];
+    float* Xs = smem32;                                     // [70][RS32]: row r = position t0 - 3 + r
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lrow = lane & 31, lhalf = lane >> 5;
+    const int b = (int)blockIdx.x / m.tiles_x, tile = (int)blockIdx.x % m.tiles_x, t0 = tile * BM32, Lin = m.Lin, Lout = Lin / 4;
+    f32x4 ws[2][KS_SET];
+    f32x16 acc[2];
+    load_wset(wset_ptr(m.w, 0, D / 8, 0, wave, lane), ws[0]);
+    {
+        const float* src = m.x + (size_t)b * Lin * D + lane * 4;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const int r = wave + 8 * i, t = t0 - CNN_HALO + r;
+            if (r < BM32 + 2 * CNN_HALO) {
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
+                tile_store4<AR>(Xs, r, lane * 4, v);
+            }
+        }
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    __syncthreads();
+    static_for<0, CNN_K>([&](auto dkc) {
+        constexpr int dk = decltype(dkc)::value;
+        const f32x4* wdk = m.w + (size_t)dk * (D * D / 4);
+        const f32x4* nxt = wset_ptr(dk + 1 < CNN_K ? m.w + (size_t)(dk + 1) * (D * D / 4) : m.w, 0, D / 8, 0, wave, lane);
+        product256<false, AR>(Xs + dk * RS32, wdk, 0, D / 8, 0, nxt, wave, lane, ws, acc);
+    });
+    const int c0 = wave * 32 + 4 * lhalf;
+    f32x4 sum[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 bb = *reinterpret_cast<const float4*>(m.bias + c0 + 8 * q);
+        const float4 sc = *reinterpret_cast<const float4*>(m.bn_scale + c0 + 8 * q);
+        const float4 sh = *reinterpret_cast<const float4*>(m.bn_shift + c0 + 8 * q);
+        const float bq[4] = {bb.x, bb.y, bb.z, bb.w}, sq[4] = {sc.x, sc.y, sc.z, sc.w}, hq[4] = {sh.x, sh.y, sh.z, sh.w};
+        sum[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = gelu_erf((acc[mt][4 * q + e] * WSI + bq[e]) * sq[e] + hq[e]);
+                v[e] = fmaxf(v[e], __shfl_xor(v[e], 1, 64));    // positions 4 p .. 4 p + 3: lanes 4 p .. 4 p + 3 of the half-wave
+                v[e] = fmaxf(v[e], __shfl_xor(v[e], 2, 64));
+            }
+            const int pos = (t0 + mt * 32 + lrow) >> 2;
+            if constexpr (POOLSUM) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sum[q][e] += ((lrow & 3) == 0 && pos < Lout) ? v[e] : 0.f;
+            } else {
+                if ((lrow & 3) == 0 && pos < Lout)
+                    *reinterpret_cast<float4*>(m.out + ((size_t)b * Lout + pos) * D + c0 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+    }
+    if constexpr (POOLSUM) {
+        // the 8 window leaders of each half-wave (lanes 0, 4, .., 28; the others hold 0) in a fixed tree, then lane 0 / 32 writes
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float s = sum[q][e];
+                s += __shfl_xor(s, 4, 64);
+                s += __shfl_xor(s, 8, 64);
+                s += __shfl_xor(s, 16, 64);
+                sum[q][e] = s;
+            }
+        if (lrow == 0) {
+            float* po = m.out + ((size_t)b * m.tiles_x + tile) * D + c0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(po + 8 * q) = make_float4(sum[q][0], sum[q][1], sum[q][2], sum[q][3]);
+        }
+    }
+}
+
 // W [N][K] row-major fp32 -> [N / 256][8 waves][K / 8 k-steps][64 lanes] float4: lane (lrow, lhalf) of wave w holds
 // W[nb * 256 + w * 32 + lrow][8 s + 4 lhalf + 0..3]
 __global__ __launch_bounds__(256) void pack_f32t_kernel(const float* __restrict__ w, f32x4* __restrict__ out, int N, int K) {
@@ -808,6 +908,24 @@ void launch_conv32(const float* x, const void* w, const float* bias, float* out,
     const dim3 grid((unsigned)(m.tiles_x * B)), block(512);
     if (x3) launch_lds<conv32_kernel<AR_X3>>(grid, block, lds, st, m);
     else launch_lds<conv32_kernel<AR_F32>>(grid, block, lds, st, m);
+}
+
+// DNAConvNet block 1 / 2 (cnn.hip): x [B, Lin, 256] -> maxpool4(gelu(bn(conv1d_k7(x) + bias))) -> out [B, Lin / 4, 256], or with
+// `partial` the per-64-row-tile channel sums of those pooled rows -> partial [B, ceil(Lin / 4 / 16), 256]; w: seven taps, each
+// packed by launch_pack_f32t (x3: launch_pack_x3)
+void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const float* bn_scale, const float* bn_shift, float* out,
+                      bool partial, int B, int Lin, hipStream_t st, bool x3) {
+    const int Lout = Lin / 4;
+    CnnConvArgs m{x, reinterpret_cast<const f32x4*>(w), bias, bn_scale, bn_shift, out, B, Lin, (4 * Lout + BM32 - 1) / BM32};
+    const size_t lds = (size_t)(BM32 + 2 * CNN_HALO) * RS32 * sizeof(float);
+    const dim3 grid((unsigned)(m.tiles_x * B)), block(512);
+    if (partial) {
+        if (x3) launch_lds<cnn_gemm7_kernel<true, AR_X3>>(grid, block, lds, st, m);
+        else launch_lds<cnn_gemm7_kernel<true, AR_F32>>(grid, block, lds, st, m);
+    } else {
+        if (x3) launch_lds<cnn_gemm7_kernel<false, AR_X3>>(grid, block, lds, st, m);
+        else launch_lds<cnn_gemm7_kernel<false, AR_F32>>(grid, block, lds, st, m);
+    }
 }
 
 }  // namespace clm

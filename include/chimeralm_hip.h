@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CLM_ABI_VERSION 5
+#define CLM_ABI_VERSION 6
 
 /* error codes */
 #define CLM_OK 0
@@ -211,6 +211,32 @@ int clm_tf_profile_enable(clm_tf_handle* h, int on);
 int clm_tf_profile_read(clm_tf_handle* h, double* ms_out /*[4]*/, int64_t* spans_out /*[4]*/, int reset);
 const char* clm_tf_last_error(const clm_tf_handle* h);
 int clm_tf_destroy(clm_tf_handle* h);
+
+/* ---- DNAConvNet (ABI 6) ----------------------------------------------------------------------------------------------
+ * The reference's CNN classifier (/root/reference/chimeralm/models/components/cnn.py, configs/model/cnn.yaml: vocab 12, embedding 256,
+ * three blocks of Conv1d(256, 256, 7, padding "same") + BatchNorm1d + GELU + MaxPool1d(4), mean over positions, Linear(256, 512) +
+ * BatchNorm1d + GELU + Linear(512, 2)) in eval mode, behind the same `net` boundary: forward(input_ids[B, L]) -> logits fp32 [B, 2].
+ * Same conventions as the clm_tf_* calls; weights under the reference module's state_dict keys (with or without `net.`), fp32
+ * only; `*.num_batches_tracked` is accepted and ignored.
+ *   precision   CLM_PREC_F32 (exact fp32 MFMA) or CLM_PREC_F16X3 (blocks 1 and 2 as three fp16 MFMAs on hi + lo halfs); anything
+ *               else is CLM_E_INVALID.  The fp16x3 weight packing saturates for |w| >= 64: if a block-1 / block-2 weight is that
+ *               large, clm_cnn_finalize packs that handle's weights for the exact-fp32 kernels instead.  Block 0 (an fp64 table of
+ *               embedding x taps) and the head are fp32 in both modes.
+ *   L >= 64     (three max-pools of 4; the reference raises for shorter reads), otherwise CLM_E_INVALID.
+ *   ids         i64, i32 or u8; an id outside [0, 12) is clamped into it (no read outside the table; the reference's nn.Embedding
+ *               would raise IndexError).
+ * The forward is bitwise deterministic (no atomics) and a read's logits do not depend on the other reads of its batch.
+ * clm_cnn_debug_fetch names (the last forward): "block0" fp32 [B, L/4, 256], "block1" fp32 [B, L/16, 256], "pooled" fp32 [B, 256]
+ * (the mean of block 2's output). */
+typedef struct clm_cnn_handle clm_cnn_handle;
+int clm_cnn_create(int device, int precision, clm_cnn_handle** out);
+int clm_cnn_load_weight(clm_cnn_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
+int clm_cnn_finalize(clm_cnn_handle* h);
+int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                    void* stream);
+int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, size_t bytes);
+const char* clm_cnn_last_error(const clm_cnn_handle* h); /* h may be NULL: error of the last failed clm_cnn_create */
+int clm_cnn_destroy(clm_cnn_handle* h);
 
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
