@@ -36,7 +36,7 @@ bool debug_flag(const char* name) {
 namespace {
 
 struct Tensor {
-    float* d = nullptr;
+    DevBuf d;
     std::vector<int64_t> shape;
     size_t numel = 0;
     bool loaded = false;
@@ -51,14 +51,12 @@ struct Tensor {
 constexpr int KEY_LONG = 100;
 struct ReversedFilter {           // conv_lone_tail(L): [256][stride] per layer, one per such L (16385, 24577, 32769)
     int L = 0, stride = 0;
-    float* p[NLAYER] = {};
+    DevBuf p[NLAYER];
 };
 struct FilterSet {
     int key = 0, Lf = 0, logn = 0, KS = 1;   // Lf taps; KS partition spectra per channel in kf ([256][KS][N])
-    float* ktime[NLAYER] = {};
-    float2* kf[NLAYER] = {};
-    float2* tw = nullptr;
-    float2* kfp[NLAYER] = {};     // 16384-point class only: kf lane-packed for the persistent kernel (launch_spectrum_lanepack)
+    DevBuf ktime[NLAYER], kf[NLAYER], tw;
+    DevBuf kfp[NLAYER];           // 16384-point class only: kf lane-packed for the persistent kernel (launch_spectrum_lanepack)
     std::vector<ReversedFilter> krev;
 };
 
@@ -66,8 +64,6 @@ struct ProfRec {
     int stage;
     hipEvent_t e0, e1;
 };
-
-std::string g_create_error;
 
 }  // namespace
 
@@ -78,21 +74,21 @@ struct clm_handle {
     std::map<std::string, Tensor> w;
     bool finalized = false;
     // packed / derived weights
-    void* packed[NLAYER][4] = {};
-    void* packed_score = nullptr;
+    DevBuf packed[NLAYER][4];
+    DevBuf packed_score;
     // 16-bit handles: exact-fp32 packing of the same weights (fp16c's reads shorter than f16c_min_len, clm_selfcheck, clm_set_fallback)
-    void* packed32[NLAYER][4] = {};
-    void* packed32t[NLAYER][4] = {};   // exact fp32, the fused tail's packing (tail32.hip): in_proj, out_proj, fc1, fc2
+    DevBuf packed32[NLAYER][4];
+    DevBuf packed32t[NLAYER][4];       // exact fp32, the fused tail's packing (tail32.hip): in_proj, out_proj, fc1, fc2
     // the same weights as hi + lo halfs (launch_pack_x3; tail32.hip AR_X3): the arithmetic of a CLM_PREC_F16X3 handle AND, round 5,
     // of every 16-bit handle's short reads and first fall-back level -- lwx = the handle's fp32-path LayerW with these
-    void* packed32x[NLAYER][4] = {};
+    DevBuf packed32x[NLAYER][4];
     LayerW lwx[NLAYER] = {};
     bool referee = false;              // inside clm_selfcheck's second pass: exact fp32, whatever the handle's mode or fall-back level
-    void* packed_score32 = nullptr;
-    void *packed_score32t = nullptr, *packed_score32x = nullptr;   // attention.0.weight in the fused tail's packings (tail32.hip T32_SCORE)
+    DevBuf packed_score32;
+    DevBuf packed_score32t, packed_score32x;   // attention.0.weight in the fused tail's packings (tail32.hip T32_SCORE)
     LayerW lw32[NLAYER]{};
     // PREC_F16C: fc1 / fc2 packed as hi + lo as well (the mode's second level, clm_set_mlp_compensation; lw.w_fc1 / w_fc2 are plain fp16)
-    void* packed_mlpc[NLAYER][2] = {};
+    DevBuf packed_mlpc[NLAYER][2];
     bool mlp_lo = false;
     int f16c_min_len = 2048;
     // clm_selfcheck / clm_set_fallback: the exact-fp32 kernels of the same handle as referee of, and replacement for, the 16-bit path
@@ -100,12 +96,10 @@ struct clm_handle {
     // clm_set_fallback: 0 = the handle's own mode; 1 = the next arithmetic INSIDE the gate (a 16-bit handle: fp16x3 -- fp32-class
     // results at about twice the exact rate; an fp16x3 handle: exact fp32); 2 = exact fp32 on every handle
     int fallback = 0;
-    float* sc_logits = nullptr;   // [2][sc_cap][2] device: logits of the two passes of a self-check
-    int sc_cap = 0;
+    DevBuf sc_logits;             // [2][B][2] fp32: logits of the two passes of a self-check
     // host batches: two device staging buffers fed by the handle's own copy stream
     struct Stage {
-        void* buf = nullptr;
-        size_t cap = 0;
+        DevBuf buf;
         int dtype = 0, B = 0, L = 0;
         int64_t stride = 0;
         hipEvent_t copied = nullptr, consumed = nullptr;
@@ -114,52 +108,48 @@ struct clm_handle {
     hipStream_t copy_stream = nullptr;
     int next_stage = 0;
     int* bad_ids = nullptr;       // host-mapped flag the id kernels set for a token id outside [0, vocab_rows)
-    float* ztab = nullptr;        // [16][768] block-0 in_proj rows per token id (16-bit modes)
+    DevBuf ztab;                  // [16][768] block-0 in_proj rows per token id (16-bit modes)
     // gated hand-over of z (TailArgs::zg): filter constants per layer, raw rows either side of the tail kernel's workgroup-range
     // boundaries, raw rows of every read's last two tiled tokens
-    float4* fir[NLAYER] = {};
-    float2* edge_bnd = nullptr;
-    float2* edge_read = nullptr;
-    int edge_read_cap = 0;
+    DevBuf fir[NLAYER];           // float4 [256][3]
+    DevBuf edge_bnd, edge_read;   // float2
     bool raw_z = false;           // CLM_DEBUG=raw_z: the fused in_proj stage writes x0 | x1 | v as before round 3 (A/B runs, tests)
-    unsigned char* ids8 = nullptr;   // workspace: clamped ids [B][Lp]
-    float* head_t[5] = {};
+    DevBuf head_t[5];
     LayerW lw[NLAYER]{};
     HeadW hw{};
     std::vector<FilterSet> filters;
     uint64_t clock = 0;
-    // workspace (one chunk of reads)
-    size_t ws_cap[15] = {};       // bytes of each workspace buffer (ensure_workspace: WS_H .. WS_TILES)
+    // workspace (one chunk of reads; ensure_workspace)
     size_t ws_es = 0;             // element size z / y were last written with
-    float* h = nullptr;
-    void *z = nullptr, *y = nullptr, *u = nullptr;
-    float *scores = nullptr, *stats = nullptr, *partial = nullptr, *pooled = nullptr, *lone_ws = nullptr;
-    float2* gscratch = nullptr;                     // segment spectra of the long-read convolution
-    unsigned char* ylo = nullptr;                   // PREC_F16C: lo bytes of y [B][256][Lp] (round 4, clm_common.h lo8_pack4)
+    DevBuf h;                     // fp32 residual stream
+    DevBuf z, y, u;
+    DevBuf scores, stats, partial, pooled, lone_ws;   // fp32
+    DevBuf gscratch;                                // float2: segment spectra of the long-read convolution
+    DevBuf ylo;                                     // PREC_F16C: lo bytes of y [B][256][Lp] (round 4, clm_common.h lo8_pack4)
+    DevBuf ids8;                                    // clamped ids [B][Lp]
     // Round 5, the [PAD] prefix of left-padded batches (pad_prefix.hip): per read the 128-token tiles wholly inside its leading run
     // of [PAD], the list of tiles the tail kernels compute, and per arithmetic one table of what an all-[PAD] read leaves behind
-    int* pad_p0 = nullptr;                          // [B]
-    int* tile_list = nullptr;                       // [1 + B * tiles_x]
+    DevBuf pad_p0;                                  // int [B]
+    DevBuf tile_list;                               // int [1 + B * tiles_x]
     struct PadTable {
         int prec = -1;                              // the arithmetic it was computed in (effective precision, fp16c's level, fp32 path: x3?)
         bool mlp_lo = false, x3 = false;
         int L = 0, Lp = 0;                          // tokens of the all-[PAD] read, row pitch of its z blocks
-        void* z[NLAYER] = {};                       // [i], i >= 1: the z block layer i's convolution reads ([D3][Lp] elements incl. lo planes)
-        float* scores = nullptr;                    // [L] pooling scores                                   (16-bit fused path)
-        float* partial = nullptr;                   // [ceil(L / 128)][POOL_PSTRIDE] pooling partials       (16-bit fused path)
-        float* hfin = nullptr;                      // [L][256] the last block's residual rows              (fp32 path; its partials: per 64 tokens)
+        DevBuf z[NLAYER];                           // [i], i >= 1: the z block layer i's convolution reads ([D3][Lp] elements incl. lo planes)
+        DevBuf scores;                              // fp32 [L] pooling scores                              (16-bit fused path)
+        DevBuf partial;                             // fp32 [ceil(L / 128)][POOL_PSTRIDE] pooling partials  (16-bit fused path)
+        DevBuf hfin;                                // fp32 [L][256] the last block's residual rows         (fp32 path; its partials: per 64 tokens)
         // 16-bit fused path, tables of long reads (S = segments of L > 1): per block the segment spectra of the all-[PAD] read's
         // gated signal ([256][S][N], the one read's convolution scratch as it stood) and the running per-thread sums of the last
         // token's dot product -- segments inside the [PAD] prefix of both reads of a pair are not transformed (hyena_conv.hip SegPrefix)
         int S = 1;
-        float2* gspec[NLAYER] = {};
-        float* dots[NLAYER] = {};
+        DevBuf gspec[NLAYER];                       // float2
+        DevBuf dots[NLAYER];                        // fp32
     };
     std::vector<PadTable> pad_tables;
     PadTable* capture = nullptr;                    // inside the forward that fills a table
-    unsigned char* pad_ids = nullptr;               // device, all PAD_ID: the table read's ids
-    size_t pad_ids_cap = 0;
-    float* pad_logits = nullptr;                    // device [2]: that read's logits (unused)
+    DevBuf pad_ids;                                 // all PAD_ID: the table read's ids
+    DevBuf pad_logits;                              // fp32 [2]: that read's logits (unused)
     bool no_pad_skip = false;                       // CLM_DEBUG=no_pad_skip: every tile of every read is computed (A/B runs, tests)
     bool no_seg_skip = false;                       // CLM_DEBUG=no_seg_skip: ... but every segment of the long-read convolution is transformed
     int last_B = 0, last_L = 0, last_Lp = 0;
@@ -178,19 +168,6 @@ struct clm_handle {
 };
 
 namespace {
-
-int fail(clm_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-
-#define HIPCHK(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess)                                                                             \
-            return fail(h, CLM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
-    } while (0)
 
 size_t elem_size(int prec) { return prec == PREC_F32 ? 4 : 2; }
 // The arithmetic a chunk of L-token reads runs in.  fp16c keeps fp16 activation operands; their roundings are independent
@@ -293,143 +270,46 @@ __global__ void convert_to_f32_kernel(const void* in, float* out, size_t n, int 
         out[i] = to_float(reinterpret_cast<const f16_t*>(in)[i]);
 }
 
-void free_filter_set(FilterSet& f) {
-    for (int i = 0; i < NLAYER; ++i) {
-        if (f.ktime[i]) (void)hipFree(f.ktime[i]);
-        if (f.kf[i]) (void)hipFree(f.kf[i]);
-        if (f.kfp[i]) (void)hipFree(f.kfp[i]);
-        f.kfp[i] = nullptr;
-        for (auto& r : f.krev)
-            if (r.p[i]) (void)hipFree(r.p[i]);
-        f.ktime[i] = nullptr;
-        f.kf[i] = nullptr;
-    }
-    f.krev.clear();
-    if (f.tw) (void)hipFree(f.tw);
-    f.tw = nullptr;
-}
-
-void free_filters(clm_handle* h) {
-    for (auto& f : h->filters) free_filter_set(f);
-    h->filters.clear();
-}
-
-// The per-chunk workspace: twelve buffers, each with its own capacity in bytes and grown on its own -- a call needs Bc x (its
-// own length) of each, and chunk_for() bounds that product whatever the read length, so a handle that has seen 256 x 8k-token and
-// 32 x 32k-token batches holds the larger of the two needs per buffer, not 256 x 32k (the round-2 shape bookkeeping did).
-enum { WS_H, WS_Z, WS_Y, WS_U, WS_SCORES, WS_STATS, WS_PARTIAL, WS_POOLED, WS_GSCRATCH, WS_IDS8, WS_LONE, WS_EDGE_READ, WS_YLO, WS_P0, WS_TILES, WS_N };
-static_assert(WS_N == sizeof(clm_handle::ws_cap) / sizeof(size_t), "one capacity per buffer");
-void** ws_slot(clm_handle* h, int i) {
-    switch (i) {
-        case WS_H: return (void**)&h->h;
-        case WS_Z: return &h->z;
-        case WS_Y: return &h->y;
-        case WS_U: return &h->u;
-        case WS_SCORES: return (void**)&h->scores;
-        case WS_STATS: return (void**)&h->stats;
-        case WS_PARTIAL: return (void**)&h->partial;
-        case WS_POOLED: return (void**)&h->pooled;
-        case WS_GSCRATCH: return (void**)&h->gscratch;
-        case WS_IDS8: return (void**)&h->ids8;
-        case WS_LONE: return (void**)&h->lone_ws;
-        case WS_YLO: return (void**)&h->ylo;
-        case WS_P0: return (void**)&h->pad_p0;
-        case WS_TILES: return (void**)&h->tile_list;
-        default: return (void**)&h->edge_read;
-    }
-}
-
-void free_workspace(clm_handle* h) {
-    for (int i = 0; i < WS_N; ++i) {
-        void** p = ws_slot(h, i);
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        h->ws_cap[i] = 0;
-    }
-    h->ws_es = 0;
-}
-
-void free_packed(clm_handle* h) {
-    for (int i = 0; i < NLAYER; ++i)
-        for (int j = 0; j < 4; ++j)
-        {
-            if (h->packed[i][j]) { (void)hipFree(h->packed[i][j]); h->packed[i][j] = nullptr; }
-            if (h->packed32[i][j]) { (void)hipFree(h->packed32[i][j]); h->packed32[i][j] = nullptr; }
-            if (h->packed32t[i][j]) { (void)hipFree(h->packed32t[i][j]); h->packed32t[i][j] = nullptr; }
-            if (h->packed32x[i][j]) { (void)hipFree(h->packed32x[i][j]); h->packed32x[i][j] = nullptr; }
-            if (j < 2 && h->packed_mlpc[i][j]) { (void)hipFree(h->packed_mlpc[i][j]); h->packed_mlpc[i][j] = nullptr; }
-        }
-    if (h->packed_score) { (void)hipFree(h->packed_score); h->packed_score = nullptr; }
-    if (h->packed_score32) { (void)hipFree(h->packed_score32); h->packed_score32 = nullptr; }
-    if (h->packed_score32t) { (void)hipFree(h->packed_score32t); h->packed_score32t = nullptr; }
-    if (h->packed_score32x) { (void)hipFree(h->packed_score32x); h->packed_score32x = nullptr; }
-    if (h->ztab) { (void)hipFree(h->ztab); h->ztab = nullptr; }
-    for (int i = 0; i < NLAYER; ++i)
-        if (h->fir[i]) { (void)hipFree(h->fir[i]); h->fir[i] = nullptr; }
-    for (int j = 0; j < 5; ++j)
-        if (h->head_t[j]) { (void)hipFree(h->head_t[j]); h->head_t[j] = nullptr; }
-}
-
-void free_pad_table_spectra(clm_handle::PadTable& t) {
-    for (int i = 0; i < NLAYER; ++i) {
-        if (t.gspec[i]) (void)hipFree(t.gspec[i]);
-        if (t.dots[i]) (void)hipFree(t.dots[i]);
-        t.gspec[i] = nullptr; t.dots[i] = nullptr;
-    }
-}
-
-void free_pad_tables(clm_handle* h) {
-    for (auto& t : h->pad_tables) {
-        free_pad_table_spectra(t);
-        for (int i = 0; i < NLAYER; ++i)
-            if (t.z[i]) (void)hipFree(t.z[i]);
-        if (t.scores) (void)hipFree(t.scores);
-        if (t.partial) (void)hipFree(t.partial);
-        if (t.hfin) (void)hipFree(t.hfin);
-    }
-    h->pad_tables.clear();
-}
-
-const float* W(clm_handle* h, const std::string& key) { return h->w[key].d; }
+const float* W(clm_handle* h, const std::string& key) { return h->w[key].d.get<float>(); }
 
 // exact fp32 runs its block tails fused (tail32.hip) unless a debug stop wants an intermediate or CLM_DEBUG=unfused_fp32 asks
 bool fused_fp32(const clm_handle* h) { return !h->unfused_fp32 && h->stop_stage < 0; }
 
+// The per-chunk workspace: buffers grown each on its own -- a call needs Bc x (its own length) of each, and chunk_for() bounds that
+// product whatever the read length, so a handle that has seen 256 x 8k-token and 32 x 32k-token batches holds the larger of the two
+// needs per buffer, not 256 x 32k (the round-2 shape bookkeeping did).
 int ensure_workspace(clm_handle* h, int Bc, int L, hipStream_t st) {
     const int prec = effective_prec(h, L);                   // (honours the self-check's referee pass and the fallback)
     const size_t es = elem_size(prec), Lp = (size_t)round_up(L, LP_ALIGN), nb = (size_t)Bc, nl = (size_t)L;
-    size_t need[WS_N] = {};
-    need[WS_H] = nb * nl * D * 4;
-    need[WS_Z] = nb * D3 * Lp * es;
-    need[WS_Y] = nb * D * Lp * es;
-    need[WS_U] = (prec == PREC_F32 && !fused_fp32(h)) ? nb * DI * nl * es : 0;   // the 1024-wide fc1 output: unfused fp32 path only
-    need[WS_SCORES] = nb * nl * 4;
-    need[WS_STATS] = nb * 2 * 4;
-    // pooling partials: [POOL_SPLIT][4][256] per read (unfused fp32 path) or one POOL_PSTRIDE row per tile -- 128 tokens in the
-    // 16-bit tail kernel, T32_TILE = 64 in the exact / fp16x3 one
-    need[WS_PARTIAL] = nb * std::max((size_t)POOL_SPLIT * 4 * D, (size_t)((nl + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE) * 4;
-    need[WS_POOLED] = nb * D * 4;
-    need[WS_LONE] = lone_token_ws_floats((int)nb) * 4;
-    need[WS_IDS8] = nb * Lp;
-    need[WS_EDGE_READ] = nb * D3 * sizeof(float2);
-    need[WS_YLO] = h->cfg.precision == PREC_F16C ? nb * D * Lp : 0;
-    need[WS_P0] = 3 * nb * sizeof(int);                     // p0 | pair order | pair partner (pad_prefix.hip)
-    need[WS_TILES] = (1 + nb * ((nl + 127) / 128)) * sizeof(int);
-    if (conv_segments_for(L) > 1) need[WS_GSCRATCH] = ((nb + 1) / 2) * D * (size_t)conv_segments_for(L) * 16384 * sizeof(float2);
+    const size_t S = conv_segments_for(L) > 1 ? (size_t)conv_segments_for(L) : 0;
+    struct { DevBuf& buf; size_t need; bool zero; } ws[] = {   // zero: padding columns [L, Lp) must never hold NaN garbage
+        {h->h, nb * nl * D * 4, false},
+        {h->z, nb * D3 * Lp * es, true},
+        {h->y, nb * D * Lp * es, true},
+        {h->u, (prec == PREC_F32 && !fused_fp32(h)) ? nb * DI * nl * es : 0, false},   // the 1024-wide fc1 output: unfused fp32 path only
+        {h->scores, nb * nl * 4, false},
+        {h->stats, nb * 2 * 4, false},
+        // pooling partials: [POOL_SPLIT][4][256] per read (unfused fp32 path) or one POOL_PSTRIDE row per tile -- 128 tokens in the
+        // 16-bit tail kernel, T32_TILE = 64 in the exact / fp16x3 one
+        {h->partial, nb * std::max((size_t)POOL_SPLIT * 4 * D, (size_t)((nl + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE) * 4, false},
+        {h->pooled, nb * D * 4, false},
+        {h->gscratch, ((nb + 1) / 2) * D * S * 16384 * sizeof(float2), false},
+        {h->ids8, nb * Lp, false},
+        {h->lone_ws, lone_token_ws_floats((int)nb) * 4, false},
+        {h->edge_read, nb * D3 * sizeof(float2), false},
+        {h->ylo, h->cfg.precision == PREC_F16C ? nb * D * Lp : 0, true},
+        {h->pad_p0, 3 * nb * sizeof(int), false},                     // p0 | pair order | pair partner (pad_prefix.hip)
+        {h->tile_list, (1 + nb * ((nl + 127) / 128)) * sizeof(int), false},
+    };
     bool grow = false;
-    for (int i = 0; i < WS_N; ++i) grow |= need[i] > h->ws_cap[i];
-    if (!h->edge_bnd) HIPCHK(h, hipMalloc((void**)&h->edge_bnd, (size_t)1024 * 2 * D3 * sizeof(float2)));   // >= any grid (one workgroup per CU)
+    for (auto& w : ws) grow |= w.need > w.buf.bytes();
+    if (!h->edge_bnd) HIPCHK(h, h->edge_bnd.alloc((size_t)1024 * 2 * D3 * sizeof(float2)));   // >= any grid (one workgroup per CU)
     if (!grow) return CLM_OK;
     HIPCHK(h, hipStreamSynchronize(st));
-    for (int i = 0; i < WS_N; ++i) {
-        if (need[i] <= h->ws_cap[i]) continue;
-        void** p = ws_slot(h, i);
-        if (*p) HIPCHK(h, hipFree(*p));
-        *p = nullptr;
-        h->ws_cap[i] = 0;
-        HIPCHK(h, hipMalloc(p, need[i]));
-        h->ws_cap[i] = need[i];
-        if (i == WS_Z || i == WS_Y || i == WS_YLO) HIPCHK(h, hipMemset(*p, 0, need[i]));   // padding columns [L, Lp) must never hold NaN garbage
+    for (auto& w : ws) {
+        if (w.need <= w.buf.bytes()) continue;
+        HIPCHK(h, w.buf.reserve(w.need));
+        if (w.zero) HIPCHK(h, hipMemset(w.buf.get(), 0, w.need));
     }
     return CLM_OK;
 }
@@ -453,41 +333,41 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
         f.logn = logn;
         f.Lf = S > 1 ? h->cfg.max_seq_len : std::min(N / 2 + 1, h->cfg.max_seq_len);
         f.KS = S > 1 ? conv_segments_for(h->cfg.max_seq_len) : 1;
-        double2* scratch = nullptr;
-        HIPCHK(h, hipMalloc((void**)&scratch, (size_t)D * N * sizeof(double2)));
-        HIPCHK(h, hipMalloc((void**)&f.tw, (size_t)(N / 2) * sizeof(float2)));
-        launch_twiddles(f.tw, logn, st);
+        DevBuf scratch;
+        HIPCHK(h, scratch.alloc((size_t)D * N * sizeof(double2)));
+        HIPCHK(h, f.tw.alloc((size_t)(N / 2) * sizeof(float2)));
+        launch_twiddles(f.tw.get<float2>(), logn, st);
         for (int i = 0; i < NLAYER; ++i) {
-            HIPCHK(h, hipMalloc((void**)&f.ktime[i], (size_t)f.Lf * D * 4));
-            HIPCHK(h, hipMalloc((void**)&f.kf[i], (size_t)D * f.KS * N * sizeof(float2)));
+            HIPCHK(h, f.ktime[i].alloc((size_t)f.Lf * D * 4));
+            HIPCHK(h, f.kf[i].alloc((size_t)D * f.KS * N * sizeof(float2)));
+            float* const kt = f.ktime[i].get<float>();
+            float2* const kf = f.kf[i].get<float2>();
             std::string p = "bb.layers." + std::to_string(i) + ".mixer.filter_fn.";
             launch_filter(W(h, p + "pos_emb.z"), W(h, p + "pos_emb.t"), W(h, p + "implicit_filter.0.weight"),
                           W(h, p + "implicit_filter.0.bias"), W(h, p + "implicit_filter.1.freq"),
                           W(h, p + "implicit_filter.2.weight"), W(h, p + "implicit_filter.2.bias"),
                           W(h, p + "implicit_filter.4.weight"), W(h, p + "implicit_filter.4.bias"),
-                          W(h, p + "implicit_filter.6.weight"), W(h, p + "modulation.deltas"), f.ktime[i], f.Lf, st);
+                          W(h, p + "implicit_filter.6.weight"), W(h, p + "modulation.deltas"), kt, f.Lf, st);
             if (S == 1) {
-                launch_filter_spectrum(f.ktime[i], W(h, p + "bias"), f.kf[i], scratch, f.Lf, logn, 0, f.Lf, -1, st);
+                launch_filter_spectrum(kt, W(h, p + "bias"), kf, scratch.get<double2>(), f.Lf, logn, 0, f.Lf, -1, st);
                 if (logn == 14) {                            // (round 5: the exact / fp16x3 engine's fp32 rows take the persistent kernel too)
-                    HIPCHK(h, hipMalloc((void**)&f.kfp[i], (size_t)D * N * sizeof(float2)));
-                    launch_spectrum_lanepack(f.kf[i], f.kfp[i], 1, 0, st);
+                    HIPCHK(h, f.kfp[i].alloc((size_t)D * N * sizeof(float2)));
+                    launch_spectrum_lanepack(kf, f.kfp[i].get<float2>(), 1, 0, st);
                 }
             } else {   // kf [256][KS][N], lane-packed for the segmented kernel: one launch per partition, through a temporary
-                float2* tmp = nullptr;
-                HIPCHK(h, hipMalloc((void**)&tmp, (size_t)D * N * sizeof(float2)));
+                DevBuf tmp;
+                HIPCHK(h, tmp.alloc((size_t)D * N * sizeof(float2)));
                 for (int j = 0; j < f.KS; ++j) {
-                    launch_filter_spectrum(f.ktime[i], W(h, p + "bias"), tmp, scratch, f.Lf, logn, j * SEG_LEN, SEG_LEN,
-                                           (j - 1) * SEG_LEN, st);
-                    launch_spectrum_lanepack(tmp, f.kf[i], f.KS, j, st);
+                    launch_filter_spectrum(kt, W(h, p + "bias"), tmp.get<float2>(), scratch.get<double2>(), f.Lf, logn, j * SEG_LEN,
+                                           SEG_LEN, (j - 1) * SEG_LEN, st);
+                    launch_spectrum_lanepack(tmp.get<float2>(), kf, f.KS, j, st);
                 }
-                HIPCHK(h, hipStreamSynchronize(st));
-                HIPCHK(h, hipFree(tmp));
+                HIPCHK(h, hipStreamSynchronize(st));         // (before `tmp` is freed)
             }
         }
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipStreamSynchronize(st));
-        HIPCHK(h, hipFree(scratch));
-        h->filters.push_back(f);
+        HIPCHK(h, hipStreamSynchronize(st));                 // (before `scratch` is freed)
+        h->filters.push_back(std::move(f));
         fs = &h->filters.back();
     }
     if (conv_lone_tail(L)) {               // the reversed taps [0, L) of the dot product for the lone last token
@@ -499,10 +379,10 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
             r.stride = round_up(L, 8);
             for (int i = 0; i < NLAYER; ++i) {
                 std::string p = "bb.layers." + std::to_string(i) + ".mixer.filter_fn.";
-                HIPCHK(h, hipMalloc((void**)&r.p[i], (size_t)D * r.stride * 4));
-                launch_filter_reversed(fs->ktime[i], W(h, p + "bias"), r.p[i], L, r.stride, st);
+                HIPCHK(h, r.p[i].alloc((size_t)D * r.stride * 4));
+                launch_filter_reversed(fs->ktime[i].get<float>(), W(h, p + "bias"), r.p[i].get<float>(), L, r.stride, st);
             }
-            fs->krev.push_back(r);
+            fs->krev.push_back(std::move(r));
             *krev_out = &fs->krev.back();
         }
     }
@@ -598,12 +478,6 @@ int ensure_pad_table(clm_handle* h, int prec, bool x3, int L, hipStream_t st, cl
     for (size_t k = 0; k < h->pad_tables.size(); ++k) {      // a shorter table of the same arithmetic is replaced
         auto& t = h->pad_tables[k];
         if (t.prec == prec && t.x3 == x3 && t.mlp_lo == (prec == PREC_F16C && h->mlp_lo)) {
-            free_pad_table_spectra(t);
-            for (int i = 0; i < NLAYER; ++i)
-                if (t.z[i]) (void)hipFree(t.z[i]);
-            if (t.scores) (void)hipFree(t.scores);
-            if (t.partial) (void)hipFree(t.partial);
-            if (t.hfin) (void)hipFree(t.hfin);
             h->pad_tables.erase(h->pad_tables.begin() + (long)k);
             break;
         }
@@ -612,44 +486,35 @@ int ensure_pad_table(clm_handle* h, int prec, bool x3, int L, hipStream_t st, cl
     t.prec = prec; t.x3 = x3; t.mlp_lo = prec == PREC_F16C && h->mlp_lo;
     t.L = LT; t.Lp = round_up(LT, LP_ALIGN);
     const size_t es = elem_size(prec);
-    for (int i = 1; i < NLAYER; ++i) HIPCHK(h, hipMalloc(&t.z[i], (size_t)D3 * t.Lp * es));
+    for (int i = 1; i < NLAYER; ++i) HIPCHK(h, t.z[i].alloc((size_t)D3 * t.Lp * es));
     // (the exact path: partials per 64-token tile, and the final residual rows as well -- clm_debug_fetch("hidden") shows them)
-    if (prec == PREC_F32) HIPCHK(h, hipMalloc((void**)&t.hfin, (size_t)LT * D * 4));
-    HIPCHK(h, hipMalloc((void**)&t.scores, (size_t)LT * 4));
-    HIPCHK(h, hipMalloc((void**)&t.partial, (size_t)((LT + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE * 4));
+    if (prec == PREC_F32) HIPCHK(h, t.hfin.alloc((size_t)LT * D * 4));
+    HIPCHK(h, t.scores.alloc((size_t)LT * 4));
+    HIPCHK(h, t.partial.alloc((size_t)((LT + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE * 4));
     t.S = conv_segments_for(LT);
     if (t.S > 1 && prec != PREC_F32 && !h->no_seg_skip)           // (the 16-bit fused path's segmented convolution skips prefix segments)
         for (int i = 0; i < NLAYER; ++i) {
-            HIPCHK(h, hipMalloc((void**)&t.gspec[i], (size_t)D * t.S * 16384 * sizeof(float2)));
-            HIPCHK(h, hipMalloc((void**)&t.dots[i], (size_t)D * (t.S - 1) * SEG_DOT_THREADS * 4));
-            HIPCHK(h, hipMemsetAsync(t.dots[i], 0, (size_t)D * (t.S - 1) * SEG_DOT_THREADS * 4, st));
+            HIPCHK(h, t.gspec[i].alloc((size_t)D * t.S * 16384 * sizeof(float2)));
+            HIPCHK(h, t.dots[i].alloc((size_t)D * (t.S - 1) * SEG_DOT_THREADS * 4));
+            HIPCHK(h, hipMemsetAsync(t.dots[i].get(), 0, t.dots[i].bytes(), st));
         }
-    if ((size_t)t.Lp > h->pad_ids_cap) {
-        if (h->pad_ids) HIPCHK(h, hipFree(h->pad_ids));
-        h->pad_ids = nullptr; h->pad_ids_cap = 0;
-        HIPCHK(h, hipMalloc((void**)&h->pad_ids, (size_t)t.Lp));
-        h->pad_ids_cap = (size_t)t.Lp;
-        HIPCHK(h, hipMemsetAsync(h->pad_ids, PAD_ID, (size_t)t.Lp, st));
+    if ((size_t)t.Lp > h->pad_ids.bytes()) {
+        HIPCHK(h, h->pad_ids.reserve((size_t)t.Lp));
+        HIPCHK(h, hipMemsetAsync(h->pad_ids.get(), PAD_ID, (size_t)t.Lp, st));
     }
-    if (!h->pad_logits) HIPCHK(h, hipMalloc((void**)&h->pad_logits, NCLS * 4));
-    h->pad_tables.push_back(t);
+    if (!h->pad_logits) HIPCHK(h, h->pad_logits.alloc(NCLS * 4));
+    h->pad_tables.push_back(std::move(t));
     clm_handle::PadTable* tp = &h->pad_tables.back();
     const int force = h->force_prec;
     const bool prof = h->prof;
     h->force_prec = prec;                                    // (fp16c: the class length may lie on the other side of the length switch)
     h->prof = false;
     h->capture = tp;
-    const int rc = forward_chunk(h, h->pad_ids, CLM_DT_U8, t.Lp, 1, LT, h->pad_logits, st);
+    const int rc = forward_chunk(h, h->pad_ids.get(), CLM_DT_U8, tp->Lp, 1, LT, h->pad_logits.get<float>(), st);
     h->capture = nullptr;
     h->prof = prof;
     h->force_prec = force;
     if (rc) {
-        free_pad_table_spectra(*tp);
-        for (int i = 0; i < NLAYER; ++i)
-            if (tp->z[i]) (void)hipFree(tp->z[i]);
-        if (tp->scores) (void)hipFree(tp->scores);
-        if (tp->partial) (void)hipFree(tp->partial);
-        if (tp->hfin) (void)hipFree(tp->hfin);
         h->pad_tables.pop_back();
         return rc;
     }
@@ -669,8 +534,8 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         h->last_B = Bc; h->last_L = L; h->last_Lp = Lp;
         if (h->ws_es != elem_size(prec)) {   // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
             if (h->ws_es) {                  // columns may read as NaN in the other
-                HIPCHK(h, hipMemsetAsync(h->z, 0, h->ws_cap[WS_Z], st));
-                HIPCHK(h, hipMemsetAsync(h->y, 0, h->ws_cap[WS_Y], st));
+                HIPCHK(h, hipMemsetAsync(h->z.get(), 0, h->z.bytes(), st));
+                HIPCHK(h, hipMemsetAsync(h->y.get(), 0, h->y.bytes(), st));
             }
             h->ws_es = elem_size(prec);
         }
@@ -714,32 +579,32 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         if (rc) return rc;
     }
     // fp16c, round 4: y (every block) and the gated rows of z carry one lo byte per element next to the halfs
-    unsigned char* const ylo = prec == PREC_F16C ? h->ylo : nullptr;
+    unsigned char* const ylo = prec == PREC_F16C ? h->ylo.get<unsigned char>() : nullptr;
     if (zgated && tail16_grid((Lmain + 127) / 128 * Bc) > 1024)
         return fail(h, CLM_E_UNSUPPORTED, "more than 1024 compute units: edge_bnd is sized for 1024 workgroups");
-    const void* packed_score = alt32 ? h->packed_score32 : h->packed_score;
-    const ScorePoolArgs spa{h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
+    const void* packed_score = alt32 ? h->packed_score32.get() : h->packed_score.get();
+    const ScorePoolArgs spa{h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
                             W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                            W(h, "head.attention.2.bias"), h->scores, h->partial, Bc, L, (L + 127) / 128, eps};
+                            W(h, "head.attention.2.bias"), h->scores.get<float>(), h->partial.get<float>(), Bc, L, (L + 127) / 128, eps};
     {
         StageTimer t(h, st, CLM_STAGE_EMBED);
         // (exact / fp16x3 engine, one-shot convolution: block 0 reads z from the id table and its tail gathers the residual rows from
         //  the embedding table -- h is first written by that tail kernel, as in the 16-bit id path)
         const bool id32 = fused32 && S == 1 && !h->no_idconv;
-        launch_embed(ids, ids_dtype, row_stride, W(h, "bb.embeddings.word_embeddings.weight"), (idpath || id32) ? nullptr : h->h,
-                     h->ids8, Bc, L, Lp, st, h->bad_ids);
+        launch_embed(ids, ids_dtype, row_stride, W(h, "bb.embeddings.word_embeddings.weight"), (idpath || id32) ? nullptr : h->h.get<float>(),
+                     h->ids8.get<unsigned char>(), Bc, L, Lp, st, h->bad_ids);
     }
     if (stop_here(h, -1, CLM_STAGE_EMBED)) return CLM_OK;
-    if (tuned16 || pad_skip) launch_pad_tiles(h->ids8, Bc, Lp, Lmain, pad_skip ? 1 : 0, h->pad_p0, h->tile_list, st);
+    if (tuned16 || pad_skip) launch_pad_tiles(h->ids8.get<unsigned char>(), Bc, Lp, Lmain, pad_skip ? 1 : 0, h->pad_p0.get<int>(), h->tile_list.get<int>(), st);
     // does block j's (segmented) convolution leave out the segments inside the [PAD] prefix of both reads of a pair (SegPrefix)?  Block 0
     // looks z up by token id, the others read the gated hand-over; reads of S * 8192 + 1 tokens need the table's dot-product sums, which
     // belong to ONE length
     // (with it the pairs of those convolutions are formed by descending prefix: perm / partner live behind p0)
-    int* const pair_perm = h->pad_p0 + Bc;
-    int* const pair_partner = h->pad_p0 + 2 * Bc;
-    if (pad_skip && S > 1) launch_pair_order(h->pad_p0, Bc, pair_perm, pair_partner, st);
+    int* const pair_perm = h->pad_p0.get<int>() + Bc;
+    int* const pair_partner = h->pad_p0.get<int>() + 2 * Bc;
+    if (pad_skip && S > 1) launch_pair_order(h->pad_p0.get<int>(), Bc, pair_perm, pair_partner, st);
     auto seg_skip_layer = [&](int j) {
-        return pad_skip && S > 1 && fuse_next && !h->capture && (j == 0 ? idpath : zgated) && ptab->gspec[j] != nullptr &&
+        return pad_skip && S > 1 && fuse_next && !h->capture && (j == 0 ? idpath : zgated) && ptab->gspec[j] &&
                (!kr || L == ptab->L);
     };
 
@@ -749,21 +614,21 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     auto tail16 = [&](int i, const LayerW& lw) -> int {
         StageTimer t(h, st, CLM_STAGE_TAIL);
         const bool mlpc = prec == PREC_F16C && h->mlp_lo;
-        TailArgs ta{h->y, h->h, lw.w_out, mlpc ? h->packed_mlpc[i][0] : lw.w_fc1, mlpc ? h->packed_mlpc[i][1] : lw.w_fc2, lw.b_out,
+        TailArgs ta{h->y.get(), h->h.get<float>(), lw.w_out, mlpc ? h->packed_mlpc[i][0].get() : lw.w_fc1, mlpc ? h->packed_mlpc[i][1].get() : lw.w_fc2, lw.b_out,
                     lw.ln2_g, lw.ln2_b, lw.b_fc1, lw.b_fc2, Bc, L, Lp,
-                    eps, Lmain, (idpath && i == 0) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"),
+                    eps, Lmain, (idpath && i == 0) ? h->ids8.get<unsigned char>() : nullptr, W(h, "bb.embeddings.word_embeddings.weight"),
                     nullptr, nullptr, nullptr, nullptr, nullptr, spa};
         ta.ylo = ylo;
         ta.mlp_lo = mlpc;
-        ta.tiles = h->tile_list;
+        ta.tiles = h->tile_list.get<int>();
         int next = NEXT_NONE;
         if (fuse_next && i + 1 < NLAYER) {
             const LayerW& nx = h->lw[i + 1];
-            ta.n_w = nx.w_in; ta.n_bias = nx.b_in; ta.n_g = nx.ln1_g; ta.n_b = nx.ln1_b; ta.n_z = h->z;
+            ta.n_w = nx.w_in; ta.n_bias = nx.b_in; ta.n_g = nx.ln1_g; ta.n_b = nx.ln1_b; ta.n_z = h->z.get();
             next = NEXT_INPROJ;
             if (zgated) {
-                ta.zg = 1; ta.n_fir = h->fir[i + 1]; ta.edge_bnd = h->edge_bnd;
-                ta.edge_read = peel ? h->edge_read : nullptr;
+                ta.zg = 1; ta.n_fir = h->fir[i + 1].get<float4>(); ta.edge_bnd = h->edge_bnd.get<float2>();
+                ta.edge_read = peel ? h->edge_read.get<float2>() : nullptr;
                 ta.zlo = ylo != nullptr;
             }
         } else if (fuse_next) {
@@ -775,7 +640,7 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
             const std::string p = "bb.layers." + std::to_string(i) + ".", pn = "bb.layers." + std::to_string(i + 1) + ".";
             const bool last = i + 1 == NLAYER;
             LoneTokenArgs la{};
-            la.y = h->y; la.h = h->h; la.ids8 = ta.ids8; la.emb = ta.emb;
+            la.y = h->y.get(); la.h = h->h.get<float>(); la.ids8 = ta.ids8; la.emb = ta.emb;
             la.w_out = W(h, p + "mixer.out_proj.weight"); la.b_out = lw.b_out; la.ln2_g = lw.ln2_g; la.ln2_b = lw.ln2_b;
             la.w_fc1 = W(h, p + "mlp.fc1.weight"); la.b_fc1 = lw.b_fc1; la.w_fc2 = W(h, p + "mlp.fc2.weight"); la.b_fc2 = lw.b_fc2;
             la.last = last;
@@ -783,13 +648,13 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
                 la.n_g = W(h, "bb.ln_f.weight"); la.n_b = W(h, "bb.ln_f.bias");
                 la.att_w1 = W(h, "head.attention.0.weight"); la.att_b1 = W(h, "head.attention.0.bias");
                 la.att_w2 = W(h, "head.attention.2.weight"); la.att_b2 = W(h, "head.attention.2.bias");
-                la.scores = h->scores; la.partial = h->partial;
+                la.scores = h->scores.get<float>(); la.partial = h->partial.get<float>();
             } else {
                 const LayerW& nx = h->lw[i + 1];
-                la.n_g = nx.ln1_g; la.n_b = nx.ln1_b; la.n_w = W(h, pn + "mixer.in_proj.weight"); la.n_bias = nx.b_in; la.n_z = h->z;
-                if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read; }
+                la.n_g = nx.ln1_g; la.n_b = nx.ln1_b; la.n_w = W(h, pn + "mixer.in_proj.weight"); la.n_bias = nx.b_in; la.n_z = h->z.get();
+                if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read.get<float2>(); }
             }
-            la.ws = h->lone_ws;
+            la.ws = h->lone_ws.get<float>();
             la.B = Bc; la.L = L; la.Lp = Lp; la.ntiles = (L + 127) / 128; la.eps = eps;
             la.ylo = ylo; la.zlo = ta.zlo;
             launch_lone_token(prec, la, st);
@@ -797,17 +662,17 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         // the [PAD] prefix: what this block leaves for the next stage, copied out of (capture) or in from (pad_skip) the table
         const int nrow16 = ta.zg ? 2 * D : D3, nlo = ta.zlo ? 2 * D : 0;
         if (h->capture && fuse_next) {
-            if (next == NEXT_INPROJ) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * elem_size(prec), hipMemcpyDeviceToDevice, st));
+            if (next == NEXT_INPROJ) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1].get(), h->z.get(), (size_t)D3 * Lp * elem_size(prec), hipMemcpyDeviceToDevice, st));
             else {
-                HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)((L + 127) / 128) * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->scores.get<float>(), h->scores.get<float>(), (size_t)L * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->partial.get<float>(), h->partial.get<float>(), (size_t)((L + 127) / 128) * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
             }
         } else if (pad_skip) {
             if (next == NEXT_INPROJ)      // (rows of segments the next convolution will not read are not copied)
-                launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, Lmain, (int)elem_size(prec), nrow16, nlo, st,
+                launch_prefix_fill_z(h->pad_p0.get<int>(), h->z.get(), ptab->z[i + 1].get(), Bc, Lp, ptab->Lp, Lmain, (int)elem_size(prec), nrow16, nlo, st,
                                      seg_skip_layer(i + 1) ? S : 0, pair_partner);
             else
-                launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, (L + 127) / 128, Lmain, st);
+                launch_prefix_fill_pool(h->pad_p0.get<int>(), h->scores.get<float>(), h->partial.get<float>(), ptab->scores.get<float>(), ptab->partial.get<float>(), Bc, L, (L + 127) / 128, Lmain, st);
         }
         return CLM_OK;
     };
@@ -818,24 +683,24 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         StageTimer t(h, st, CLM_STAGE_TAIL);
         const LayerW* nx = i + 1 < NLAYER ? &(x3 ? h->lwx[i + 1] : (alt32 ? h->lw32[i + 1] : h->lw[i + 1])) : nullptr;
         const int nt32 = (L + T32_TILE - 1) / T32_TILE;
-        const Tail32Score ts{x3 ? h->packed_score32x : h->packed_score32t, W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                             W(h, "head.attention.2.bias"), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores, h->partial};
-        launch_tail32(reinterpret_cast<const float*>(h->y), h->h, lw.t_out, lw.t_fc1, lw.t_fc2, nx ? nx->t_in : nullptr, lw.b_out,
+        const Tail32Score ts{x3 ? h->packed_score32x.get() : h->packed_score32t.get(), W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
+                             W(h, "head.attention.2.bias"), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores.get<float>(), h->partial.get<float>()};
+        launch_tail32(h->y.get<float>(), h->h.get<float>(), lw.t_out, lw.t_fc1, lw.t_fc2, nx ? nx->t_in : nullptr, lw.b_out,
                       lw.b_fc1, lw.b_fc2, nx ? nx->b_in : nullptr, lw.ln2_g, lw.ln2_b, nx ? nx->ln1_g : nullptr,
-                      nx ? nx->ln1_b : nullptr, reinterpret_cast<float*>(h->z), Bc, L, Lp, eps, st, x3, pad_skip ? h->pad_p0 : nullptr,
-                      nx ? nullptr : &ts, (i == 0 && idconv) ? h->ids8 : nullptr, W(h, "bb.embeddings.word_embeddings.weight"));
+                      nx ? nx->ln1_b : nullptr, h->z.get<float>(), Bc, L, Lp, eps, st, x3, pad_skip ? h->pad_p0.get<int>() : nullptr,
+                      nx ? nullptr : &ts, (i == 0 && idconv) ? h->ids8.get<unsigned char>() : nullptr, W(h, "bb.embeddings.word_embeddings.weight"));
         if (h->capture) {
-            if (nx) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1], h->z, (size_t)D3 * Lp * 4, hipMemcpyDeviceToDevice, st));
+            if (nx) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1].get(), h->z.get(), (size_t)D3 * Lp * 4, hipMemcpyDeviceToDevice, st));
             else {
-                HIPCHK(h, hipMemcpyAsync(h->capture->hfin, h->h, (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->scores, h->scores, (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->partial, h->partial, (size_t)nt32 * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->hfin.get<float>(), h->h.get<float>(), (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->scores.get<float>(), h->scores.get<float>(), (size_t)L * 4, hipMemcpyDeviceToDevice, st));
+                HIPCHK(h, hipMemcpyAsync(h->capture->partial.get<float>(), h->partial.get<float>(), (size_t)nt32 * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
             }
         } else if (pad_skip) {
-            if (nx) launch_prefix_fill_z(h->pad_p0, h->z, ptab->z[i + 1], Bc, Lp, ptab->Lp, L, 4, D3, 0, st);
+            if (nx) launch_prefix_fill_z(h->pad_p0.get<int>(), h->z.get(), ptab->z[i + 1].get(), Bc, Lp, ptab->Lp, L, 4, D3, 0, st);
             else {
-                launch_prefix_fill_h(h->pad_p0, h->h, ptab->hfin, Bc, L, L, st);
-                launch_prefix_fill_pool(h->pad_p0, h->scores, h->partial, ptab->scores, ptab->partial, Bc, L, nt32, L, st, 128 / T32_TILE);
+                launch_prefix_fill_h(h->pad_p0.get<int>(), h->h.get<float>(), ptab->hfin.get<float>(), Bc, L, L, st);
+                launch_prefix_fill_pool(h->pad_p0.get<int>(), h->scores.get<float>(), h->partial.get<float>(), ptab->scores.get<float>(), ptab->partial.get<float>(), Bc, L, nt32, L, st, 128 / T32_TILE);
             }
         }
         return CLM_OK;
@@ -849,37 +714,37 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         const bool idconv = i == 0 && !h->no_idconv && ((tuned16 && !stop_here(h, 0, CLM_STAGE_INPROJ)) || (fused32 && S == 1));
         if (!idconv && !(fuse_next && i > 0) && !(fused32 && i > 0)) {
             StageTimer t(h, st, CLM_STAGE_INPROJ);
-            if (tuned16) launch_inproj16(prec, h->h, lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z, Bc, L, Lp, eps, st);
-            else launch_inproj(h->h, lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z, Bc, L, Lp, eps, st);
+            if (tuned16) launch_inproj16(prec, h->h.get<float>(), lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z.get(), Bc, L, Lp, eps, st);
+            else launch_inproj(h->h.get<float>(), lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z.get(), Bc, L, Lp, eps, st);
         }
         if (stop_here(h, i, CLM_STAGE_INPROJ)) return CLM_OK;
         {
             StageTimer t(h, st, CLM_STAGE_CONV);
             if (S == 1)
-                launch_hyena_conv(prec, h->z, h->y, fs->kf[i], fs->tw, fs->ktime[i], lw.short_w, lw.short_b, Bc, L, Lp,
-                                  fs->logn, idconv ? h->ids8 : nullptr, idconv ? h->ztab : nullptr, st,
-                                  h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), fs->kfp[i], ylo);
+                launch_hyena_conv(prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->tw.get<float2>(), fs->ktime[i].get<float>(), lw.short_w, lw.short_b, Bc, L, Lp,
+                                  fs->logn, idconv ? h->ids8.get<unsigned char>() : nullptr, idconv ? h->ztab.get<float>() : nullptr, st,
+                                  h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), fs->kfp[i].get<float2>(), ylo);
             else {
                 // [PAD]-prefix reuse: segments inside the prefix of both reads of a pair come from the table (SegPrefix).  Reads of
                 // S * 8192 + 1 tokens carry the last token's dot product through the segments: its table sums belong to ONE length
                 SegPrefix pfx;
                 if (h->capture && h->capture->gspec[i]) {
-                    pfx.dots_out = kr ? h->capture->dots[i] : nullptr;
+                    pfx.dots_out = kr ? h->capture->dots[i].get<float>() : nullptr;
                     pfx.dots_segs = h->capture->S - 1;
                 } else if (seg_skip_layer(i)) {
-                    pfx.p0 = h->pad_p0;
+                    pfx.p0 = h->pad_p0.get<int>();
                     pfx.perm = pair_perm;
-                    pfx.tab = ptab->gspec[i];
+                    pfx.tab = ptab->gspec[i].get<float2>();
                     pfx.tab_segs = ptab->S;
-                    pfx.dots_in = ptab->dots[i];
+                    pfx.dots_in = ptab->dots[i].get<float>();
                     pfx.dots_segs = ptab->S - 1;
                 }
-                launch_hyena_conv_seg(prec, h->z, h->y, fs->kf[i], fs->KS, fs->tw, lw.short_w, lw.short_b, h->gscratch, Bc,
-                                      L, Lp, S, kr ? kr->p[i] : nullptr, kr ? kr->stride : 0, idconv ? h->ids8 : nullptr,
-                                      idconv ? h->ztab : nullptr, st, h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), ylo, pfx);
+                launch_hyena_conv_seg(prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->KS, fs->tw.get<float2>(), lw.short_w, lw.short_b, h->gscratch.get<float2>(), Bc,
+                                      L, Lp, S, kr ? kr->p[i].get<float>() : nullptr, kr ? kr->stride : 0, idconv ? h->ids8.get<unsigned char>() : nullptr,
+                                      idconv ? h->ztab.get<float>() : nullptr, st, h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), ylo, pfx);
                 if (h->capture && h->capture->gspec[i]) {   // (one read = pair 0: [256][S][N] at the head of the scratch), then pair form
-                    HIPCHK(h, hipMemcpyAsync(h->capture->gspec[i], h->gscratch, (size_t)D * S * 16384 * sizeof(float2), hipMemcpyDeviceToDevice, st));
-                    launch_spectra_pair_form(h->capture->gspec[i], S, st);
+                    HIPCHK(h, hipMemcpyAsync(h->capture->gspec[i].get<float2>(), h->gscratch.get<float2>(), (size_t)D * S * 16384 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+                    launch_spectra_pair_form(h->capture->gspec[i].get<float2>(), S, st);
                 }
             }
         }
@@ -894,47 +759,47 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
         } else {   // the separate kernels: a debug stop after out_proj (16-bit modes), the unfused exact-fp32 path
             {
                 StageTimer t(h, st, CLM_STAGE_OUTPROJ);
-                if (tuned16) launch_outproj16(prec, h->y, lw.w_out, lw.b_out, h->h, Bc, L, Lp, st);
-                else launch_outproj(h->y, lw.w_out, lw.b_out, h->h, Bc, L, Lp, st);
+                if (tuned16) launch_outproj16(prec, h->y.get(), lw.w_out, lw.b_out, h->h.get<float>(), Bc, L, Lp, st);
+                else launch_outproj(h->y.get(), lw.w_out, lw.b_out, h->h.get<float>(), Bc, L, Lp, st);
             }
             if (stop_mid) return CLM_OK;
             {
                 StageTimer t(h, st, CLM_STAGE_FC1);
-                launch_fc1(h->h, lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, h->u, Bc, L, eps, st);
+                launch_fc1(h->h.get<float>(), lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, h->u.get(), Bc, L, eps, st);
             }
             if (stop_here(h, i, CLM_STAGE_FC1)) return CLM_OK;
             StageTimer t(h, st, CLM_STAGE_FC2);
-            launch_fc2(h->u, lw.w_fc2, lw.b_fc2, h->h, Bc, L, st);
+            launch_fc2(h->u.get(), lw.w_fc2, lw.b_fc2, h->h.get<float>(), Bc, L, st);
         }
         if (stop_here(h, i, CLM_STAGE_FC2) || (tuned16 && stop_here(h, i, CLM_STAGE_FC1))) return CLM_OK;
     }
     if (tuned16) {   // score + pooling partials in one pass over h, merged by the classifier kernel
         if (!fuse_next) {
             StageTimer t(h, st, CLM_STAGE_SCORE);
-            launch_score_pool16(prec, h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
+            launch_score_pool16(prec, h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
                                 W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                                W(h, "head.attention.2.bias"), h->scores, h->partial, Bc, L, eps, st);
+                                W(h, "head.attention.2.bias"), h->scores.get<float>(), h->partial.get<float>(), Bc, L, eps, st);
         }
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_tiles(h->partial, (L + 127) / 128, h->hw, h->pooled, logits, Bc, st);
+        launch_head_tiles(h->partial.get<float>(), (L + 127) / 128, h->hw, h->pooled.get<float>(), logits, Bc, st);
     } else if (fused32) {   // scores and per-tile pooling partials came out of the last block's tail kernel
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_tiles(h->partial, (L + T32_TILE - 1) / T32_TILE, h->hw, h->pooled, logits, Bc, st);
+        launch_head_tiles(h->partial.get<float>(), (L + T32_TILE - 1) / T32_TILE, h->hw, h->pooled.get<float>(), logits, Bc, st);
     } else {
         {
             StageTimer t(h, st, CLM_STAGE_SCORE);
-            launch_score(h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
+            launch_score(h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
                          W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"), W(h, "head.attention.2.bias"),
-                         h->scores, Bc, L, eps, st);
+                         h->scores.get<float>(), Bc, L, eps, st);
         }
         {
             StageTimer t(h, st, CLM_STAGE_POOL);
-            launch_softmax_stats(h->scores, h->stats, Bc, L, st);
-            launch_pool(h->h, W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores, h->stats, h->partial, Bc, L, eps,
+            launch_softmax_stats(h->scores.get<float>(), h->stats.get<float>(), Bc, L, st);
+            launch_pool(h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores.get<float>(), h->stats.get<float>(), h->partial.get<float>(), Bc, L, eps,
                         st);
         }
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_mlp(h->partial, h->hw, h->pooled, logits, Bc, st);
+        launch_head_mlp(h->partial.get<float>(), h->hw, h->pooled.get<float>(), logits, Bc, st);
     }
     HIPCHK(h, hipGetLastError());
     return CLM_OK;
@@ -960,23 +825,16 @@ int clm_default_config(clm_config* c) {
 }
 
 int clm_create(const clm_config* cfg, int device, clm_handle** out) {
-    if (!cfg || !out) return fail(nullptr, CLM_E_INVALID, "clm_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(clm_config)) return fail(nullptr, CLM_E_INVALID, "clm_config size mismatch");
+    if (!cfg || !out) return fail<clm_handle>(nullptr, CLM_E_INVALID, "clm_create: null argument");
+    if (cfg->struct_size != (int32_t)sizeof(clm_config)) return fail<clm_handle>(nullptr, CLM_E_INVALID, "clm_config size mismatch");
     if (cfg->d_model != D || cfg->n_layer != NLAYER || cfg->d_inner != DI || cfg->vocab_rows != VOCAB ||
         cfg->filter_order != FORDER || cfg->emb_dim != EMB || cfg->head_hidden != HH || cfg->n_classes != NCLS)
-        return fail(nullptr, CLM_E_UNSUPPORTED,
-                    "only the HyenaDNA-small-32k + 512-wide attention-pooling head of chimeralm/models/lm.py is built");
+        return fail<clm_handle>(nullptr, CLM_E_UNSUPPORTED,
+                                "only the HyenaDNA-small-32k + 512-wide attention-pooling head of chimeralm/models/lm.py is built");
     if (cfg->precision < CLM_PREC_F32 || cfg->precision > CLM_PREC_F16X3 || cfg->chunk_reads < 1 ||
         cfg->max_seq_len < 2)
-        return fail(nullptr, CLM_E_INVALID, "clm_create: bad precision / chunk_reads / max_seq_len");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fail(nullptr, CLM_E_HIP, "clm_create: no such HIP device " + std::to_string(device));
-    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, CLM_E_HIP, "hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(nullptr, CLM_E_HIP, "hipGetDeviceProperties failed");
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(nullptr, CLM_E_UNSUPPORTED, std::string("this engine is built for gfx950 (MI355X) only, found ") + prop.gcnArchName);
+        return fail<clm_handle>(nullptr, CLM_E_INVALID, "clm_create: bad precision / chunk_reads / max_seq_len");
+    if (int rc = use_gfx950<clm_handle>(device, "clm_create")) return rc;
     clm_handle* h = new clm_handle();
     // developer switches (A/B runs, tests): ONE variable, CLM_DEBUG, a comma-separated list read when a handle is created
     // (clm_common.h debug_flag) -- no product behaviour hangs on the environment
@@ -992,7 +850,7 @@ int clm_create(const clm_config* cfg, int device, clm_handle** out) {
     if (cfg->precision == CLM_PREC_F16X3) {             // an exact-fp32 engine whose fused tails multiply hi + lo halfs
         h->x3 = true;
         h->cfg.precision = CLM_PREC_F32;
-        if (h->unfused_fp32) { delete h; return fail(nullptr, CLM_E_UNSUPPORTED, "CLM_PREC_F16X3 exists in the fused tail kernels only (CLM_DEBUG=unfused_fp32 is set)"); }
+        if (h->unfused_fp32) { delete h; return fail<clm_handle>(nullptr, CLM_E_UNSUPPORTED, "CLM_PREC_F16X3 exists in the fused tail kernels only (CLM_DEBUG=unfused_fp32 is set)"); }
     }
     h->device = device;
     if (hipHostMalloc((void**)&h->bad_ids, sizeof(int), hipHostMallocMapped) == hipSuccess) *h->bad_ids = 0;
@@ -1024,19 +882,18 @@ int clm_load_weight(clm_handle* h, const char* key, const void* data, int dtype,
     for (auto v : shp) n *= (size_t)v;
     HIPCHK(h, hipSetDevice(h->device));
     Tensor& t = h->w[ck];
-    if (!t.d) HIPCHK(h, hipMalloc((void**)&t.d, n * 4));
+    if (!t.d) HIPCHK(h, t.d.alloc(n * 4));
     t.shape = shp;
     t.numel = n;
     if (dtype == CLM_DT_F32) {
-        HIPCHK(h, hipMemcpy(t.d, data, n * 4, hipMemcpyDefault));
+        HIPCHK(h, hipMemcpy(t.d.get(), data, n * 4, hipMemcpyDefault));
     } else if (dtype == CLM_DT_F64 || dtype == CLM_DT_BF16 || dtype == CLM_DT_F16) {
         size_t es = dtype == CLM_DT_F64 ? 8 : 2;
-        void* stage = nullptr;
-        HIPCHK(h, hipMalloc(&stage, n * es));
-        HIPCHK(h, hipMemcpy(stage, data, n * es, hipMemcpyDefault));
-        hipLaunchKernelGGL(convert_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.d, n, dtype);
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, hipFree(stage));
+        DevBuf stage;
+        HIPCHK(h, stage.alloc(n * es));
+        HIPCHK(h, hipMemcpy(stage.get(), data, n * es, hipMemcpyDefault));
+        hipLaunchKernelGGL(convert_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage.get(), t.d.get<float>(), n, dtype);
+        HIPCHK(h, hipDeviceSynchronize());                    // (before `stage` is freed)
     } else {
         return fail(h, CLM_E_INVALID, "clm_load_weight: dtype must be f32/f64/bf16/f16");
     }
@@ -1053,37 +910,36 @@ int clm_finalize(clm_handle* h) {
         if (it == h->w.end() || !it->second.loaded) return fail(h, CLM_E_MISSING, "missing weight: " + s.key);
     }
     HIPCHK(h, hipDeviceSynchronize());
-    free_packed(h);
-    free_filters(h);
-    free_pad_tables(h);                                      // (functions of the weights)
+    h->filters.clear();                                      // (functions of the weights; each packing below replaces its own)
+    h->pad_tables.clear();
     const int prec = h->cfg.precision;
     // hi + lo halfs of the tail weights: an fp16x3 handle's own arithmetic; a 16-bit handle's short reads and first fall-back level
     const bool pack_x3 = (h->x3 || prec != PREC_F32) && !h->unfused_fp32;
     hipStream_t st = 0;
-    auto pack_as = [&](int pr, const std::string& key, int n, int k, void** out) -> int {
-        HIPCHK(h, hipMalloc(out, packed_weight_bytes(pr, n, k)));
-        HIPCHK(h, hipMemsetAsync(*out, 0, packed_weight_bytes(pr, n, k), st));
-        launch_pack_weight(pr, W(h, key), *out, n, k, st);
+    auto pack_as = [&](int pr, const std::string& key, int n, int k, DevBuf& out) -> int {
+        HIPCHK(h, out.alloc(packed_weight_bytes(pr, n, k)));
+        HIPCHK(h, hipMemsetAsync(out.get(), 0, out.bytes(), st));
+        launch_pack_weight(pr, W(h, key), out.get(), n, k, st);
         return CLM_OK;
     };
-    auto pack = [&](const std::string& key, int n, int k, void** out) -> int { return pack_as(prec, key, n, k, out); };
+    auto pack = [&](const std::string& key, int n, int k, DevBuf& out) -> int { return pack_as(prec, key, n, k, out); };
     for (int i = 0; i < NLAYER; ++i) {
         std::string p = "bb.layers." + std::to_string(i) + ".";
         int rc;
-        if ((rc = pack(p + "mixer.in_proj.weight", D3, D, &h->packed[i][0]))) return rc;
-        if ((rc = pack(p + "mixer.out_proj.weight", D, D, &h->packed[i][1]))) return rc;
+        if ((rc = pack(p + "mixer.in_proj.weight", D3, D, h->packed[i][0]))) return rc;
+        if ((rc = pack(p + "mixer.out_proj.weight", D, D, h->packed[i][1]))) return rc;
         // (fp16c: the two MLP products run on plain fp16 weights -- tail16_kernel, MLP_PREC)
         const int mlp_prec = prec == PREC_F16C ? (int)PREC_F16 : prec;
-        if ((rc = pack_as(mlp_prec, p + "mlp.fc1.weight", DI, D, &h->packed[i][2]))) return rc;
-        if ((rc = pack_as(mlp_prec, p + "mlp.fc2.weight", D, DI, &h->packed[i][3]))) return rc;
+        if ((rc = pack_as(mlp_prec, p + "mlp.fc1.weight", DI, D, h->packed[i][2]))) return rc;
+        if ((rc = pack_as(mlp_prec, p + "mlp.fc2.weight", D, DI, h->packed[i][3]))) return rc;
         if (prec == PREC_F16C) {
-            if ((rc = pack_as(PREC_F16C, p + "mlp.fc1.weight", DI, D, &h->packed_mlpc[i][0]))) return rc;
-            if ((rc = pack_as(PREC_F16C, p + "mlp.fc2.weight", D, DI, &h->packed_mlpc[i][1]))) return rc;
+            if ((rc = pack_as(PREC_F16C, p + "mlp.fc1.weight", DI, D, h->packed_mlpc[i][0]))) return rc;
+            if ((rc = pack_as(PREC_F16C, p + "mlp.fc2.weight", D, DI, h->packed_mlpc[i][1]))) return rc;
         }
         LayerW& lw = h->lw[i];
         lw.ln1_g = W(h, p + "norm1.weight"); lw.ln1_b = W(h, p + "norm1.bias");
         lw.ln2_g = W(h, p + "norm2.weight"); lw.ln2_b = W(h, p + "norm2.bias");
-        lw.w_in = h->packed[i][0]; lw.w_out = h->packed[i][1]; lw.w_fc1 = h->packed[i][2]; lw.w_fc2 = h->packed[i][3];
+        lw.w_in = h->packed[i][0].get(); lw.w_out = h->packed[i][1].get(); lw.w_fc1 = h->packed[i][2].get(); lw.w_fc2 = h->packed[i][3].get();
         lw.b_in = W(h, p + "mixer.in_proj.bias"); lw.b_out = W(h, p + "mixer.out_proj.bias");
         lw.b_fc1 = W(h, p + "mlp.fc1.bias"); lw.b_fc2 = W(h, p + "mlp.fc2.bias");
         lw.short_w = W(h, p + "mixer.short_filter.weight"); lw.short_b = W(h, p + "mixer.short_filter.bias");
@@ -1092,63 +948,63 @@ int clm_finalize(clm_handle* h) {
             struct { const char* key; int n, k; } tw[4] = {{"mixer.in_proj.weight", D3, D}, {"mixer.out_proj.weight", D, D},
                                                            {"mlp.fc1.weight", DI, D}, {"mlp.fc2.weight", D, DI}};
             for (int j = 0; j < 4; ++j) {
-                HIPCHK(h, hipMalloc(&h->packed32t[i][j], (size_t)tw[j].n * tw[j].k * 4));
-                launch_pack_f32t(W(h, p + tw[j].key), h->packed32t[i][j], tw[j].n, tw[j].k, st);
+                HIPCHK(h, h->packed32t[i][j].alloc((size_t)tw[j].n * tw[j].k * 4));
+                launch_pack_f32t(W(h, p + tw[j].key), h->packed32t[i][j].get(), tw[j].n, tw[j].k, st);
                 if (pack_x3) {
-                    HIPCHK(h, hipMalloc(&h->packed32x[i][j], (size_t)tw[j].n * tw[j].k * 4));
-                    launch_pack_x3(W(h, p + tw[j].key), h->packed32x[i][j], tw[j].n, tw[j].k, st);
+                    HIPCHK(h, h->packed32x[i][j].alloc((size_t)tw[j].n * tw[j].k * 4));
+                    launch_pack_x3(W(h, p + tw[j].key), h->packed32x[i][j].get(), tw[j].n, tw[j].k, st);
                 }
             }
-            lw.t_in = h->packed32t[i][0]; lw.t_out = h->packed32t[i][1]; lw.t_fc1 = h->packed32t[i][2]; lw.t_fc2 = h->packed32t[i][3];
+            lw.t_in = h->packed32t[i][0].get(); lw.t_out = h->packed32t[i][1].get(); lw.t_fc1 = h->packed32t[i][2].get(); lw.t_fc2 = h->packed32t[i][3].get();
         }
         if (prec != PREC_F32) {   // the exact-fp32 packing next to the 16-bit one: fp16c's short reads, clm_selfcheck, clm_set_fallback
-            if ((rc = pack_as(PREC_F32, p + "mixer.in_proj.weight", D3, D, &h->packed32[i][0]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mixer.out_proj.weight", D, D, &h->packed32[i][1]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mlp.fc1.weight", DI, D, &h->packed32[i][2]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mlp.fc2.weight", D, DI, &h->packed32[i][3]))) return rc;
+            if ((rc = pack_as(PREC_F32, p + "mixer.in_proj.weight", D3, D, h->packed32[i][0]))) return rc;
+            if ((rc = pack_as(PREC_F32, p + "mixer.out_proj.weight", D, D, h->packed32[i][1]))) return rc;
+            if ((rc = pack_as(PREC_F32, p + "mlp.fc1.weight", DI, D, h->packed32[i][2]))) return rc;
+            if ((rc = pack_as(PREC_F32, p + "mlp.fc2.weight", D, DI, h->packed32[i][3]))) return rc;
             h->lw32[i] = lw;
-            h->lw32[i].w_in = h->packed32[i][0]; h->lw32[i].w_out = h->packed32[i][1];
-            h->lw32[i].w_fc1 = h->packed32[i][2]; h->lw32[i].w_fc2 = h->packed32[i][3];
+            h->lw32[i].w_in = h->packed32[i][0].get(); h->lw32[i].w_out = h->packed32[i][1].get();
+            h->lw32[i].w_fc1 = h->packed32[i][2].get(); h->lw32[i].w_fc2 = h->packed32[i][3].get();
         }
         if (pack_x3) {            // the fp32 path's LayerW with the fused tail's weights as hi + lo halfs
             h->lwx[i] = prec != PREC_F32 ? h->lw32[i] : lw;
-            h->lwx[i].t_in = h->packed32x[i][0]; h->lwx[i].t_out = h->packed32x[i][1];
-            h->lwx[i].t_fc1 = h->packed32x[i][2]; h->lwx[i].t_fc2 = h->packed32x[i][3];
+            h->lwx[i].t_in = h->packed32x[i][0].get(); h->lwx[i].t_out = h->packed32x[i][1].get();
+            h->lwx[i].t_fc1 = h->packed32x[i][2].get(); h->lwx[i].t_fc2 = h->packed32x[i][3].get();
         }
     }
     {
         int rc;
-        if ((rc = pack("head.attention.0.weight", D, D, &h->packed_score))) return rc;
-        if (prec != PREC_F32 && (rc = pack_as(PREC_F32, "head.attention.0.weight", D, D, &h->packed_score32))) return rc;
-        HIPCHK(h, hipMalloc(&h->packed_score32t, (size_t)D * D * 4));
-        launch_pack_f32t(W(h, "head.attention.0.weight"), h->packed_score32t, D, D, st);
+        if ((rc = pack("head.attention.0.weight", D, D, h->packed_score))) return rc;
+        if (prec != PREC_F32 && (rc = pack_as(PREC_F32, "head.attention.0.weight", D, D, h->packed_score32))) return rc;
+        HIPCHK(h, h->packed_score32t.alloc((size_t)D * D * 4));
+        launch_pack_f32t(W(h, "head.attention.0.weight"), h->packed_score32t.get(), D, D, st);
         if (pack_x3) {
-            HIPCHK(h, hipMalloc(&h->packed_score32x, (size_t)D * D * 4));
-            launch_pack_x3(W(h, "head.attention.0.weight"), h->packed_score32x, D, D, st);
+            HIPCHK(h, h->packed_score32x.alloc((size_t)D * D * 4));
+            launch_pack_x3(W(h, "head.attention.0.weight"), h->packed_score32x.get(), D, D, st);
         }
     }
     if (prec != PREC_F32)
         for (int i = 0; i < NLAYER; ++i) {
-            HIPCHK(h, hipMalloc((void**)&h->fir[i], (size_t)D * 3 * sizeof(float4)));
-            launch_fir_table(h->lw[i].short_w, h->lw[i].short_b, h->lw[i].b_in, h->fir[i], st);
+            HIPCHK(h, h->fir[i].alloc((size_t)D * 3 * sizeof(float4)));
+            launch_fir_table(h->lw[i].short_w, h->lw[i].short_b, h->lw[i].b_in, h->fir[i].get<float4>(), st);
         }
-    HIPCHK(h, hipMalloc((void**)&h->ztab, (size_t)VOCAB * D3 * 4));
+    HIPCHK(h, h->ztab.alloc((size_t)VOCAB * D3 * 4));
     launch_ztab(W(h, "bb.embeddings.word_embeddings.weight"), W(h, "bb.layers.0.norm1.weight"),
                 W(h, "bb.layers.0.norm1.bias"), W(h, "bb.layers.0.mixer.in_proj.weight"),
-                W(h, "bb.layers.0.mixer.in_proj.bias"), h->ztab, h->cfg.ln_eps, st);
+                W(h, "bb.layers.0.mixer.in_proj.bias"), h->ztab.get<float>(), h->cfg.ln_eps, st);
     struct { const char* key; int rows, cols; } tr[5] = {
         {"head.classifier.0.weight", HH, D}, {"head.classifier.3.weight", HH, HH},
         {"head.classifier.6.layers.0.weight", HH, HH}, {"head.classifier.6.layers.3.weight", HH, HH},
         {"head.output_layer.weight", NCLS, HH}};
     for (int j = 0; j < 5; ++j) {
-        HIPCHK(h, hipMalloc((void**)&h->head_t[j], (size_t)tr[j].rows * tr[j].cols * 4));
-        launch_transpose(W(h, tr[j].key), h->head_t[j], tr[j].rows, tr[j].cols, st);
+        HIPCHK(h, h->head_t[j].alloc((size_t)tr[j].rows * tr[j].cols * 4));
+        launch_transpose(W(h, tr[j].key), h->head_t[j].get<float>(), tr[j].rows, tr[j].cols, st);
     }
-    h->hw.w0t = h->head_t[0]; h->hw.b0 = W(h, "head.classifier.0.bias");
-    h->hw.w3t = h->head_t[1]; h->hw.b3 = W(h, "head.classifier.3.bias");
-    h->hw.w60t = h->head_t[2]; h->hw.b60 = W(h, "head.classifier.6.layers.0.bias");
-    h->hw.w63t = h->head_t[3]; h->hw.b63 = W(h, "head.classifier.6.layers.3.bias");
-    h->hw.wot = h->head_t[4]; h->hw.bo = W(h, "head.output_layer.bias");
+    h->hw.w0t = h->head_t[0].get<float>(); h->hw.b0 = W(h, "head.classifier.0.bias");
+    h->hw.w3t = h->head_t[1].get<float>(); h->hw.b3 = W(h, "head.classifier.3.bias");
+    h->hw.w60t = h->head_t[2].get<float>(); h->hw.b60 = W(h, "head.classifier.6.layers.0.bias");
+    h->hw.w63t = h->head_t[3].get<float>(); h->hw.b63 = W(h, "head.classifier.6.layers.3.bias");
+    h->hw.wot = h->head_t[4].get<float>(); h->hw.bo = W(h, "head.output_layer.bias");
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
@@ -1208,16 +1064,11 @@ int clm_stage_ids(clm_handle* h, const void* host_ids, int ids_dtype, int64_t id
         HIPCHK(h, hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
     }
     if (s.used) HIPCHK(h, hipStreamWaitEvent(h->copy_stream, s.consumed, 0));   // the forward that read this buffer is done
-    if (bytes > s.cap) {
-        if (s.buf) {
-            HIPCHK(h, hipEventSynchronize(s.consumed));
-            HIPCHK(h, hipFree(s.buf));
-            s.buf = nullptr;
-        }
-        HIPCHK(h, hipMalloc(&s.buf, bytes));
-        s.cap = bytes;
+    if (bytes > s.buf.bytes()) {
+        if (s.buf) HIPCHK(h, hipEventSynchronize(s.consumed));
+        HIPCHK(h, s.buf.reserve(bytes));
     }
-    HIPCHK(h, hipMemcpyAsync(s.buf, host_ids, bytes, hipMemcpyHostToDevice, h->copy_stream));
+    HIPCHK(h, hipMemcpyAsync(s.buf.get(), host_ids, bytes, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(h, hipEventRecord(s.copied, h->copy_stream));
     s.dtype = ids_dtype; s.B = B; s.L = L; s.stride = ids_row_stride;
     s.pending = true;
@@ -1234,7 +1085,7 @@ int clm_forward_staged(clm_handle* h, int staged, float* logits_out, void* strea
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(h, hipStreamWaitEvent(st, s.copied, 0));
-    const int rc = clm_forward(h, s.buf, s.dtype, s.stride, s.B, s.L, logits_out, stream);
+    const int rc = clm_forward(h, s.buf.get(), s.dtype, s.stride, s.B, s.L, logits_out, stream);
     // whatever happened, the buffer is no longer "staged and waiting": a failed forward must not wedge it for good
     s.pending = false;
     s.used = true;
@@ -1269,12 +1120,9 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
     *max_abs_diff = 0.f;
     if (labels_differ) *labels_differ = 0;
     if (h->cfg.precision == PREC_F32 && !h->x3) return CLM_OK;   // the handle IS the referee
-    if (B > h->sc_cap) {
+    if ((size_t)2 * B * NCLS * 4 > h->sc_logits.bytes()) {
         HIPCHK(h, hipStreamSynchronize(st));
-        if (h->sc_logits) HIPCHK(h, hipFree(h->sc_logits));
-        h->sc_logits = nullptr;
-        HIPCHK(h, hipMalloc((void**)&h->sc_logits, (size_t)2 * B * NCLS * 4));
-        h->sc_cap = B;
+        HIPCHK(h, h->sc_logits.reserve((size_t)2 * B * NCLS * 4));
     }
     // pass 0: the arithmetic the handle's mode runs reads of this length in (whatever clm_set_fallback says); pass 1: exact fp32
     const int mode_prec = (h->cfg.precision == PREC_F16C && L < h->f16c_min_len) ? (int)PREC_F32 : h->cfg.precision;
@@ -1291,7 +1139,7 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
         for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
             const int Bc = B - b0 < chunk ? B - b0 : chunk;
             const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * ids_row_stride * ies;
-            rc = forward_chunk(h, p, ids_dtype, ids_row_stride, Bc, L, h->sc_logits + ((size_t)pass * h->sc_cap + b0) * NCLS, st);
+            rc = forward_chunk(h, p, ids_dtype, ids_row_stride, Bc, L, h->sc_logits.get<float>() + ((size_t)pass * B + b0) * NCLS, st);
         }
     }
     h->force_prec = -1;
@@ -1299,12 +1147,12 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
     h->prof = prof;
     h->fallback = fallback;
     if (rc) return rc;
-    std::vector<float> host((size_t)2 * h->sc_cap * NCLS);
-    HIPCHK(h, hipMemcpyAsync(host.data(), h->sc_logits, host.size() * 4, hipMemcpyDeviceToHost, st));
+    std::vector<float> host((size_t)2 * B * NCLS);
+    HIPCHK(h, hipMemcpyAsync(host.data(), h->sc_logits.get<float>(), host.size() * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     float worst = 0.f;
     int differ = 0;
-    (void)clm_logit_deviation(host.data(), host.data() + (size_t)h->sc_cap * NCLS, B, NCLS, &worst, &differ);
+    (void)clm_logit_deviation(host.data(), host.data() + (size_t)B * NCLS, B, NCLS, &worst, &differ);
     *max_abs_diff = worst;
     if (labels_differ) *labels_differ = differ;
     return CLM_OK;
@@ -1375,17 +1223,17 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
     const void* src = nullptr;
     size_t have = 0;
     std::string n(name);
-    if (n == "hidden" || n == "h") { src = h->h; have = B * L * D * 4; }
-    else if (n == "z") { src = h->z; have = B * D3 * Lp * es; }
-    else if (n == "y") { src = h->y; have = B * D * Lp * es; }
-    else if (n == "u") { src = h->u; have = B * L * DI * es; }
-    else if (n == "scores") { src = h->scores; have = B * L * 4; }
-    else if (n == "pooled") { src = h->pooled; have = B * D * 4; }
+    if (n == "hidden" || n == "h") { src = h->h.get<float>(); have = B * L * D * 4; }
+    else if (n == "z") { src = h->z.get(); have = B * D3 * Lp * es; }
+    else if (n == "y") { src = h->y.get(); have = B * D * Lp * es; }
+    else if (n == "u") { src = h->u.get(); have = B * L * DI * es; }
+    else if (n == "scores") { src = h->scores.get<float>(); have = B * L * 4; }
+    else if (n == "pooled") { src = h->pooled.get<float>(); have = B * D * 4; }
     else if (n.rfind("filter.", 0) == 0) {
         int i = std::atoi(n.c_str() + 7);
         const int key = conv_segments_for((int)L) > 1 ? KEY_LONG : conv_logn_for((int)L);
         for (auto& f : h->filters)          // the first L taps of the class's filter (they do not depend on L)
-            if (f.key == key && i >= 0 && i < NLAYER && (int)L <= f.Lf) { src = f.ktime[i]; have = L * D * 4; }
+            if (f.key == key && i >= 0 && i < NLAYER && (int)L <= f.Lf) { src = f.ktime[i].get(); have = L * D * 4; }
     }
     if (!src) return fail(h, CLM_E_INVALID, "clm_debug_fetch: unknown or empty buffer " + n);
     if (bytes > have) return fail(h, CLM_E_INVALID, "clm_debug_fetch: " + n + " holds only " + std::to_string(have) + " bytes");
@@ -1427,7 +1275,7 @@ const char* clm_profile_stage_name(int stage) {
     return (stage >= 0 && stage < CLM_N_STAGES) ? names[stage] : "?";
 }
 
-const char* clm_last_error(const clm_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* clm_last_error(const clm_handle* h) { return h ? h->err.c_str() : create_error<clm_handle>().c_str(); }
 
 int clm_destroy(clm_handle* h) {
     if (!h) return CLM_OK;
@@ -1437,24 +1285,13 @@ int clm_destroy(clm_handle* h) {
     conv_dump_stamps();
     for (auto& r : h->recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto& e : h->free_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    free_workspace(h);
-    free_filters(h);
-    free_packed(h);
-    free_pad_tables(h);
-    if (h->pad_ids) (void)hipFree(h->pad_ids);
-    if (h->pad_logits) (void)hipFree(h->pad_logits);
-    if (h->sc_logits) (void)hipFree(h->sc_logits);
-    if (h->edge_bnd) (void)hipFree(h->edge_bnd);
     for (auto& sg : h->stage) {
-        if (sg.buf) (void)hipFree(sg.buf);
         if (sg.copied) (void)hipEventDestroy(sg.copied);
         if (sg.consumed) (void)hipEventDestroy(sg.consumed);
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->bad_ids) (void)hipHostFree(h->bad_ids);
-    for (auto& kv : h->w)
-        if (kv.second.d) (void)hipFree(kv.second.d);
-    delete h;
+    delete h;                                                // (its device buffers free themselves)
     return CLM_OK;
 }
 

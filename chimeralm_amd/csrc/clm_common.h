@@ -6,7 +6,13 @@
 
 #include <atomic>
 #include <cstdio>
+#include <map>
+#include <string>
 #include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "chimeralm_hip.h"
 
 namespace clm {
 
@@ -164,6 +170,98 @@ void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
         else std::fprintf(stderr, "chimeralm_hip: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %zu) failed on device %d: %s\n", lds, dev, hipGetErrorString(e));
     }
     hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+}
+
+// ---- host side of the engine handles (clm_api.hip, tf_model.hip, cnn.hip) ------------------------------------------------------
+// One device allocation and its size, freed by its owner.  Nothing here synchronises: whoever replaces memory that queued kernels
+// may still read synchronises first.
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(n_, o.n_);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t bytes) {              // what it held is freed first
+        reset();
+        const hipError_t e = hipMalloc(&p_, bytes);
+        if (e == hipSuccess) n_ = bytes;
+        else p_ = nullptr;
+        return e;
+    }
+    hipError_t reserve(size_t bytes) { return bytes > n_ ? alloc(bytes) : hipSuccess; }   // grows, never shrinks
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    size_t bytes() const { return n_; }
+    template <class T = void>
+    T* get() const { return static_cast<T*>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+
+  private:
+    void* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The last error of a handle is its `err`; before a handle exists (its *_create), one string per handle type.
+template <class H>
+std::string& create_error() {
+    static std::string s;
+    return s;
+}
+template <class H>
+int fail(H* h, int code, const std::string& msg) {
+    (h ? h->err : create_error<H>()) = msg;
+    return code;
+}
+#define HIPCHK(h, expr)                                                                                   \
+    do {                                                                                                  \
+        const hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) return clm::fail(h, CLM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// *_create: `device` exists, is made current and is a gfx950
+template <class H>
+int use_gfx950(int device, const char* who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": no such HIP device " + std::to_string(device));
+    if (hipSetDevice(device) != hipSuccess) return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": hipSetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
+        return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": hipGetDeviceProperties failed");
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail<H>(nullptr, CLM_E_UNSUPPORTED, std::string(who) + ": this engine is built for gfx950 (MI355X) only, found " + prop.gcnArchName);
+    return CLM_OK;
+}
+
+// An fp32 tensor `k` of `expected` (key -> shape) into the handle's `w`: a device copy, replacing the one loaded before
+template <class H>
+int load_f32(H* h, const char* who, const std::map<std::string, std::vector<int64_t>>& expected, const std::string& k, const void* data,
+             const int64_t* shape, int ndim) {
+    const auto it = expected.find(k);
+    if (it == expected.end()) return fail(h, CLM_E_INVALID, std::string(who) + ": unknown key " + k);
+    if (it->second != std::vector<int64_t>(shape, shape + ndim)) return fail(h, CLM_E_INVALID, std::string(who) + ": wrong shape for " + k);
+    size_t n = 1;
+    for (int64_t s : it->second) n *= (size_t)s;
+    HIPCHK(h, hipSetDevice(h->device));
+    h->w.erase(k);
+    DevBuf d;
+    HIPCHK(h, d.alloc(n * 4));
+    HIPCHK(h, hipMemcpy(d.get(), data, n * 4, hipMemcpyDefault));
+    h->w.emplace(k, std::move(d));
+    h->finalized = false;
+    return CLM_OK;
 }
 
 // ---- kernel launchers (definitions in the .hip files); all are asynchronous on `st` --------------------

@@ -130,28 +130,14 @@ struct clm_cnn_handle {
     bool x3 = false;                              // CLM_PREC_F16X3 handle
     bool x3_active = false;                       // ... and its block 1 / 2 weights are inside the packing's range (finalize)
     std::string err;
-    std::map<std::string, float*> w;              // fp32 device copies by reference key
-    std::map<std::string, float*> dev;            // finalize products: table, packed taps, BN scale / shift, fc.0 transposed
+    std::map<std::string, DevBuf> w;              // fp32 device copies by reference key
+    std::map<std::string, DevBuf> dev;            // finalize products: table, packed taps, BN scale / shift, fc.0 transposed
     bool finalized = false;
-    size_t cap_tok = 0, cap_x1 = 0, cap_x2 = 0, cap_part = 0, cap_B = 0;
-    unsigned char* ids8 = nullptr;
-    float *x1 = nullptr, *x2 = nullptr, *part = nullptr, *pooled = nullptr;
+    DevBuf ids8, x1, x2, part, pooled;            // workspace (clm_cnn_forward)
     int last_B = 0, last_L = 0;
 };
 
 namespace {
-
-std::string g_cnn_create_error;
-
-int cnn_fail(clm_cnn_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_cnn_create_error = msg;
-    return code;
-}
-#define CNNCHK(h, call)                                                                             \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return cnn_fail(h, CLM_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 std::map<std::string, std::vector<int64_t>> cnn_expected() {
     std::map<std::string, std::vector<int64_t>> e;
@@ -180,15 +166,15 @@ int cnn_host(clm_cnn_handle* h, const std::string& k, std::vector<float>& out) {
     size_t n = 1;
     for (int64_t s : shp) n *= (size_t)s;
     out.resize(n);
-    CNNCHK(h, hipMemcpy(out.data(), h->w.at(k), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(out.data(), h->w.at(k).get(), n * 4, hipMemcpyDeviceToHost));
     return CLM_OK;
 }
 
 int cnn_upload(clm_cnn_handle* h, const std::string& name, const void* src, size_t bytes) {
-    float* d = nullptr;
-    CNNCHK(h, hipMalloc((void**)&d, bytes));
-    CNNCHK(h, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    h->dev[name] = d;
+    DevBuf d;
+    HIPCHK(h, d.alloc(bytes));
+    HIPCHK(h, hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
+    h->dev[name] = std::move(d);
     return CLM_OK;
 }
 
@@ -209,36 +195,15 @@ int cnn_bn(clm_cnn_handle* h, const std::string& p, const std::string& name, int
     return cnn_upload(h, name + ".shift", sh.data(), (size_t)n * 4);
 }
 
-void cnn_free_ws(clm_cnn_handle* h) {
-    for (void* p : {(void*)h->ids8, (void*)h->x1, (void*)h->x2, (void*)h->part, (void*)h->pooled})
-        if (p) (void)hipFree(p);
-    h->ids8 = nullptr; h->x1 = h->x2 = h->part = h->pooled = nullptr;
-    h->cap_tok = h->cap_x1 = h->cap_x2 = h->cap_part = h->cap_B = 0;
-}
-
-template <typename T>
-int cnn_grow(clm_cnn_handle* h, T*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return CLM_OK;
-    CNNCHK(h, hipDeviceSynchronize());
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    CNNCHK(h, hipMalloc((void**)&p, bytes));
-    cap = bytes;
-    return CLM_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int clm_cnn_create(int device, int precision, clm_cnn_handle** out) {
-    if (!out) return cnn_fail(nullptr, CLM_E_INVALID, "clm_cnn_create: bad argument");
+    if (!out) return fail<clm_cnn_handle>(nullptr, CLM_E_INVALID, "clm_cnn_create: bad argument");
     if (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)
-        return cnn_fail(nullptr, CLM_E_INVALID, "clm_cnn_create: precision must be CLM_PREC_F32 (exact) or CLM_PREC_F16X3");
-    if (hipSetDevice(device) != hipSuccess) return cnn_fail(nullptr, CLM_E_HIP, "clm_cnn_create: hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return cnn_fail(nullptr, CLM_E_UNSUPPORTED, "clm_cnn_create: this engine is built for gfx950 (MI355X) only");
+        return fail<clm_cnn_handle>(nullptr, CLM_E_INVALID, "clm_cnn_create: precision must be CLM_PREC_F32 (exact) or CLM_PREC_F16X3");
+    if (int rc = use_gfx950<clm_cnn_handle>(device, "clm_cnn_create")) return rc;
     clm_cnn_handle* h = new clm_cnn_handle();
     h->device = device;
     h->x3 = precision == CLM_PREC_F16X3;
@@ -247,34 +212,20 @@ int clm_cnn_create(int device, int precision, clm_cnn_handle** out) {
 }
 
 int clm_cnn_load_weight(clm_cnn_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
-    if (!h || !key || !data || !shape || ndim < 0) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: null argument");
+    if (!h || !key || !data || !shape || ndim < 0) return fail(h, CLM_E_INVALID, "clm_cnn_load_weight: null argument");
     std::string k(key);
     if (k.rfind("net.", 0) == 0) k = k.substr(4);
     if (is_batches_tracked(k)) return CLM_OK;                  // BatchNorm's step counter: not used in eval mode
-    if (dtype != CLM_DT_F32) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: fp32 tensors only");
-    const auto exp = cnn_expected();
-    auto it = exp.find(k);
-    if (it == exp.end()) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: unknown key " + k);
-    if (it->second != std::vector<int64_t>(shape, shape + ndim)) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_load_weight: wrong shape for " + k);
-    size_t n = 1;
-    for (int64_t s : it->second) n *= (size_t)s;
-    CNNCHK(h, hipSetDevice(h->device));
-    if (h->w.count(k)) { (void)hipFree(h->w[k]); h->w.erase(k); }
-    float* d = nullptr;
-    CNNCHK(h, hipMalloc((void**)&d, n * 4));
-    CNNCHK(h, hipMemcpy(d, data, n * 4, hipMemcpyDefault));
-    h->w[k] = d;
-    h->finalized = false;
-    return CLM_OK;
+    if (dtype != CLM_DT_F32) return fail(h, CLM_E_INVALID, "clm_cnn_load_weight: fp32 tensors only");
+    return load_f32(h, "clm_cnn_load_weight", cnn_expected(), k, data, shape, ndim);
 }
 
 int clm_cnn_finalize(clm_cnn_handle* h) {
     if (!h) return CLM_E_INVALID;
-    CNNCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     for (const auto& kv : cnn_expected())
-        if (!h->w.count(kv.first)) return cnn_fail(h, CLM_E_MISSING, "clm_cnn_finalize: missing weight " + kv.first);
-    CNNCHK(h, hipDeviceSynchronize());
-    for (auto& kv : h->dev) (void)hipFree(kv.second);
+        if (!h->w.count(kv.first)) return fail(h, CLM_E_MISSING, "clm_cnn_finalize: missing weight " + kv.first);
+    HIPCHK(h, hipDeviceSynchronize());
     h->dev.clear();
     h->finalized = false;
     int rc;
@@ -302,25 +253,25 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
     }
     h->x3_active = h->x3 && wmax < 64.f;
     {
-        float* split = nullptr;
-        CNNCHK(h, hipMalloc((void**)&split, (size_t)cnn::K * D * D * 4));
+        DevBuf split;
+        HIPCHK(h, split.alloc((size_t)cnn::K * D * D * 4));
         std::vector<float> hs((size_t)cnn::K * D * D);
         for (int i = 1; i <= 2; ++i) {
             const std::vector<float>& W = Wb[i - 1];
             for (int dk = 0; dk < cnn::K; ++dk)
                 for (int co = 0; co < D; ++co)
                     for (int ci = 0; ci < D; ++ci) hs[((size_t)dk * D + co) * D + ci] = W[((size_t)co * D + ci) * cnn::K + dk];
-            CNNCHK(h, hipMemcpy(split, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-            float* q = nullptr;
-            CNNCHK(h, hipMalloc((void**)&q, (size_t)cnn::K * D * D * 4));
+            HIPCHK(h, hipMemcpy(split.get(), hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+            DevBuf q;
+            HIPCHK(h, q.alloc((size_t)cnn::K * D * D * 4));
             for (int dk = 0; dk < cnn::K; ++dk) {
-                if (h->x3_active) launch_pack_x3(split + (size_t)dk * D * D, q + (size_t)dk * D * D, D, D, 0);
-                else launch_pack_f32t(split + (size_t)dk * D * D, q + (size_t)dk * D * D, D, D, 0);
+                const float* tap = split.get<float>() + (size_t)dk * D * D;
+                if (h->x3_active) launch_pack_x3(tap, q.get<float>() + (size_t)dk * D * D, D, D, 0);
+                else launch_pack_f32t(tap, q.get<float>() + (size_t)dk * D * D, D, D, 0);
             }
-            h->dev["conv" + std::to_string(i)] = q;
-            CNNCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next block
+            h->dev["conv" + std::to_string(i)] = std::move(q);
+            HIPCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next block, and freed after the last
         }
-        (void)hipFree(split);
     }
     for (int i = 0; i < 3; ++i)
         if ((rc = cnn_bn(h, "conv_blocks." + std::to_string(i) + ".1.", "bn" + std::to_string(i), D))) return rc;
@@ -333,7 +284,7 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
             for (int c = 0; c < D; ++c) W0t[(size_t)c * cnn::HID + j] = W0[(size_t)j * D + c];
         if ((rc = cnn_upload(h, "fc0t", W0t.data(), W0t.size() * 4))) return rc;
     }
-    CNNCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
     return CLM_OK;
 }
@@ -341,66 +292,67 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
 int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
                     void* stream) {
     if (!h) return CLM_E_INVALID;
-    if (!h->finalized) return cnn_fail(h, CLM_E_STATE, "clm_cnn_forward before clm_cnn_finalize");
-    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: bad argument");
+    if (!h->finalized) return fail(h, CLM_E_STATE, "clm_cnn_forward before clm_cnn_finalize");
+    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return fail(h, CLM_E_INVALID, "clm_cnn_forward: bad argument");
     if (L < 64)
-        return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: DNAConvNet needs reads of at least 64 tokens (three max-pools of 4; "
+        return fail(h, CLM_E_INVALID, "clm_cnn_forward: DNAConvNet needs reads of at least 64 tokens (three max-pools of 4; "
                                           "the reference raises 'Invalid computed output size: 0'), got L = " + std::to_string(L));
     if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return cnn_fail(h, CLM_E_INVALID, "clm_cnn_forward: ids dtype must be i64, i32 or u8");
-    CNNCHK(h, hipSetDevice(h->device));
+        return fail(h, CLM_E_INVALID, "clm_cnn_forward: ids dtype must be i64, i32 or u8");
+    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Lp = (L + 63) / 64 * 64, L4 = L / 4, L16 = L4 / 4, L64 = L16 / 4;
     const int tiles2 = (L64 + cnn::ROWS2 - 1) / cnn::ROWS2;
-    int rc;
-    if ((rc = cnn_grow(h, h->ids8, h->cap_tok, (size_t)B * Lp)) || (rc = cnn_grow(h, h->x1, h->cap_x1, (size_t)B * L4 * D * 4)) ||
-        (rc = cnn_grow(h, h->x2, h->cap_x2, (size_t)B * L16 * D * 4)) || (rc = cnn_grow(h, h->part, h->cap_part, (size_t)B * tiles2 * D * 4)) ||
-        (rc = cnn_grow(h, h->pooled, h->cap_B, (size_t)B * D * 4)))
-        return rc;
-    auto W = [&](const std::string& k) { return h->w.at(k); };
-    auto P = [&](const std::string& k) { return h->dev.at(k); };
-    launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8, B, L, Lp, st);   // ids of any dtype -> clamped bytes
+    const size_t need[5] = {(size_t)B * Lp, (size_t)B * L4 * D * 4, (size_t)B * L16 * D * 4, (size_t)B * tiles2 * D * 4, (size_t)B * D * 4};
+    DevBuf* buf[5] = {&h->ids8, &h->x1, &h->x2, &h->part, &h->pooled};
+    for (int i = 0; i < 5; ++i)
+        if (need[i] > buf[i]->bytes()) {
+            HIPCHK(h, hipDeviceSynchronize());
+            HIPCHK(h, buf[i]->reserve(need[i]));
+        }
+    auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
+    auto P = [&](const std::string& k) { return h->dev.at(k).get<float>(); };
+    unsigned char* const ids8 = h->ids8.get<unsigned char>();
+    float *const x1 = h->x1.get<float>(), *const x2 = h->x2.get<float>(), *const part = h->part.get<float>();
+    launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, ids8, B, L, Lp, st);   // ids of any dtype -> clamped bytes
     {
         const size_t lds = (size_t)cnn::K * cnn::TROWS * D * 4 + (size_t)(4 * cnn::PT0 + 2 * cnn::HALO) * 4;
-        launch_lds<cnn::cnn_block0_kernel>(dim3((unsigned)((L4 + cnn::PT0 - 1) / cnn::PT0), (unsigned)B), dim3(512), lds, st, h->ids8, Lp,
-                                           P("table"), W("conv_blocks.0.0.bias"), P("bn0.scale"), P("bn0.shift"), h->x1, L);
+        launch_lds<cnn::cnn_block0_kernel>(dim3((unsigned)((L4 + cnn::PT0 - 1) / cnn::PT0), (unsigned)B), dim3(512), lds, st, ids8, Lp,
+                                           P("table"), W("conv_blocks.0.0.bias"), P("bn0.scale"), P("bn0.shift"), x1, L);
     }
-    launch_cnn_gemm7(h->x1, P("conv1"), W("conv_blocks.1.0.bias"), P("bn1.scale"), P("bn1.shift"), h->x2, false, B, L4, st, h->x3_active);
-    launch_cnn_gemm7(h->x2, P("conv2"), W("conv_blocks.2.0.bias"), P("bn2.scale"), P("bn2.shift"), h->part, true, B, L16, st, h->x3_active);
-    hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, h->part, tiles2, L64, P("fc0t"), W("fc.0.bias"),
-                       P("bnfc.scale"), P("bnfc.shift"), W("fc.4.weight"), W("fc.4.bias"), h->pooled, logits_out);
+    launch_cnn_gemm7(x1, P("conv1"), W("conv_blocks.1.0.bias"), P("bn1.scale"), P("bn1.shift"), x2, false, B, L4, st, h->x3_active);
+    launch_cnn_gemm7(x2, P("conv2"), W("conv_blocks.2.0.bias"), P("bn2.scale"), P("bn2.shift"), part, true, B, L16, st, h->x3_active);
+    hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, part, tiles2, L64, P("fc0t"), W("fc.0.bias"),
+                       P("bnfc.scale"), P("bnfc.shift"), W("fc.4.weight"), W("fc.4.bias"), h->pooled.get<float>(), logits_out);
     h->last_B = B; h->last_L = L;
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : cnn_fail(h, CLM_E_HIP, std::string("clm_cnn_forward: launch failed: ") + hipGetErrorString(e));
+    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_cnn_forward: launch failed: ") + hipGetErrorString(e));
 }
 
 int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, size_t bytes) {
-    if (!h || !name || !host_out) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: bad argument");
-    CNNCHK(h, hipSetDevice(h->device));
-    CNNCHK(h, hipDeviceSynchronize());
+    if (!h || !name || !host_out) return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
     const std::string n(name);
     const size_t B = (size_t)h->last_B, L4 = (size_t)(h->last_L / 4), L16 = L4 / 4;
     const void* src = nullptr;
     size_t have = 0;
-    if (n == "block0") { src = h->x1; have = B * L4 * D * 4; }
-    else if (n == "block1") { src = h->x2; have = B * L16 * D * 4; }
-    else if (n == "pooled") { src = h->pooled; have = B * D * 4; }
-    else return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: unknown name " + n);
-    if (bytes > have) return cnn_fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: more bytes requested than the last forward produced");
-    CNNCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    if (n == "block0") { src = h->x1.get(); have = B * L4 * D * 4; }
+    else if (n == "block1") { src = h->x2.get(); have = B * L16 * D * 4; }
+    else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; }
+    else return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: unknown name " + n);
+    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: more bytes requested than the last forward produced");
+    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
     return CLM_OK;
 }
 
-const char* clm_cnn_last_error(const clm_cnn_handle* h) { return h ? h->err.c_str() : g_cnn_create_error.c_str(); }
+const char* clm_cnn_last_error(const clm_cnn_handle* h) { return h ? h->err.c_str() : create_error<clm_cnn_handle>().c_str(); }
 
 int clm_cnn_destroy(clm_cnn_handle* h) {
     if (!h) return CLM_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    cnn_free_ws(h);
-    for (auto& kv : h->w) (void)hipFree(kv.second);
-    for (auto& kv : h->dev) (void)hipFree(kv.second);
-    delete h;
+    delete h;                                                  // (its device buffers free themselves)
     return CLM_OK;
 }
 

@@ -459,28 +459,24 @@ using namespace clm;
 struct clm_tf_handle {
     int device = 0, prec = PREC_F16, n_layers = 12;
     std::string err;
-    std::map<std::string, float*> w;              // fp32 device copies by reference key
+    std::map<std::string, DevBuf> w;              // fp32 device copies by reference key
     std::map<std::string, std::vector<int64_t>> shape;
-    std::map<std::string, void*> packed;
+    std::map<std::string, DevBuf> packed;
     bool finalized = false;
-    // workspace
-    size_t cap_rows = 0, cap_tok = 0, cap_B = 0;            // cap_B: reads `pooled` has rows for (it scales with B alone)
-    size_t cap16[6] = {};                         // bytes of x1, x2, x3, hx, qkv, att
-    unsigned char* ids8 = nullptr;
-    void *x1 = nullptr, *x2 = nullptr, *x3 = nullptr, *hx = nullptr, *qkv = nullptr, *att = nullptr;
-    float *h = nullptr, *scores = nullptr, *pooled = nullptr;
+    // workspace (tf_run)
+    DevBuf ids8;
+    DevBuf x1, x2, x3, hx, qkv, att;              // 16-bit activations
+    DevBuf h, scores, pooled;                     // fp32; pooled [B][256] scales with B alone
     bool referee = false;                         // inside clm_tf_selfcheck's second pass: an fp16x3 handle runs its exact-fp32 kernels
     bool arith_x3 = false;                        // CLM_PREC_F16X3: prec is PREC_F32, the fused fp32-path kernels run on hi + lo halfs
     bool unfused_fp32 = false;                    // CLM_DEBUG=unfused_fp32 at creation: the separate fp32 launches of round 2 (tests cross-check the fused kernels)
-    float* ws32 = nullptr;                        // fp32 mode: activations of tf_fp32.hip
-    size_t cap_ws32 = 0;
+    DevBuf ws32;                                  // fp32 mode: activations of tf_fp32.hip
     int last_B = 0, last_L3 = 0;
     // clm_tf_set_fallback (as clm_set_fallback): 0 = the handle's mode; 1 = the next arithmetic inside the gate (16-bit handle: the
     // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
     int fallback = 0;
     bool have_x3 = false;                         // the "x3.*" packings exist (fp16x3 and 16-bit handles, fused kernels only)
-    float* sc_logits = nullptr;                   // clm_tf_selfcheck: [2][cap] device logits of the two forwards
-    int sc_cap = 0;
+    DevBuf sc_logits;                             // clm_tf_selfcheck: [2][B][2] fp32 logits of the two forwards
     // profiling taps (clm_tf_profile_*): HIP events on the launch stream around each stage, stages: 0 conv stack + pe/LN,
     // 1 attention, 2 encoder layer kernel (out_proj + LN1 + FFN + LN2 + next QKV; the unfused pieces count here too), 3 pooling head
     bool prof = false;
@@ -490,8 +486,6 @@ struct clm_tf_handle {
 };
 
 namespace {
-
-std::string g_tf_create_error;
 
 struct TfTimer {                                   // RAII: one event pair per stage span when profiling is on
     clm_tf_handle* h;
@@ -510,16 +504,6 @@ struct TfTimer {                                   // RAII: one event pair per s
         h->recs.push_back({stage, {e0, e1}});
     }
 };
-
-int tf_fail(clm_tf_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else g_tf_create_error = msg;
-    return code;
-}
-#define TFCHK(h, call)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) return tf_fail(h, CLM_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 std::string tf_canon(const char* key) {
     std::string k(key);
@@ -549,66 +533,57 @@ std::map<std::string, std::vector<int64_t>> tf_expected(int n_layers) {
     return e;
 }
 
-void tf_free_ws(clm_tf_handle* h) {
-    for (void* p : {(void*)h->ids8, h->x1, h->x2, h->x3, h->hx, h->qkv, h->att, (void*)h->h, (void*)h->scores,
-                    (void*)h->pooled, (void*)h->ws32})
-        if (p) (void)hipFree(p);
-    h->ids8 = nullptr; h->x1 = h->x2 = h->x3 = h->hx = h->qkv = h->att = nullptr;
-    h->h = h->scores = h->pooled = h->ws32 = nullptr;
-    h->cap_rows = h->cap_tok = h->cap_ws32 = h->cap_B = 0;
-    for (size_t& c : h->cap16) c = 0;
-}
-
 template <int PREC>
 int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t stride, int B, int L, float* logits, hipStream_t st) {
     using elem = typename CT<PREC>::elem;
     const int L1 = L / 2, L2 = L1 / 2, L3 = L2 / 2, Lp = (L + 63) / 64 * 64;
     const size_t M = (size_t)B * L3;
-    auto W = [&](const std::string& k) { return h->w.at(k); };
+    auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
+    auto P = [&](const std::string& k) { return h->packed.at(k).get(); };
     TfTimer* tconv = new TfTimer(h, st, 0);
-    launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8, B, L, Lp, st);      // ids of any dtype -> clamped uint8
+    launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);   // ids of any dtype -> clamped uint8
     constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
     {
         constexpr auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
         constexpr auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
-        launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8, Lp, W("embedding.weight"),
-                       (const elem*)nullptr, h->packed.at("cnn.0"), W("cnn.0.bias"), (elem*)h->x1, L, L1);
+        launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8.get<unsigned char>(), Lp, W("embedding.weight"),
+                       (const elem*)nullptr, P("cnn.0"), W("cnn.0.bias"), h->x1.get<elem>(), L, L1);
         launch_lds<k2>(dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                       (const float*)nullptr, (const elem*)h->x1, h->packed.at("cnn.3"), W("cnn.3.bias"), (elem*)h->x2, L1, L2);
+                       (const float*)nullptr, h->x1.get<const elem>(), P("cnn.3"), W("cnn.3.bias"), h->x2.get<elem>(), L1, L2);
         launch_lds<k2>(dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                       (const float*)nullptr, (const elem*)h->x2, h->packed.at("cnn.6"), W("cnn.6.bias"), (elem*)h->x3, L2, L3);
+                       (const float*)nullptr, h->x2.get<const elem>(), P("cnn.6"), W("cnn.6.bias"), h->x3.get<elem>(), L2, L3);
     }
-    hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const elem*)h->x3,
-                       W("pos_encoder.pe"), W("norm.weight"), W("norm.bias"), h->h, (elem*)h->hx, M, L3, 1e-5f);
+    hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, h->x3.get<const elem>(),
+                       W("pos_encoder.pe"), W("norm.weight"), W("norm.bias"), h->h.get<float>(), h->hx.get<elem>(), M, L3, 1e-5f);
     delete tconv;
     for (int i = 0; i < h->n_layers; ++i) {
         const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
         if (i == 0) {   // later layers: computed at the end of the previous layer's feed-forward kernel
             TfTimer t(h, st, 2);
-            const tf::LinArgs a{h->hx, h->packed.at(p + "in"), W(p + "self_attn.in_proj_bias"), h->qkv, M, 0};
+            const tf::LinArgs a{h->hx.get(), P(p + "in"), W(p + "self_attn.in_proj_bias"), h->qkv.get(), M, 0};
             constexpr size_t lds = (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2;
             launch_lds<tf::linear16_kernel<PREC, tf::E_ACT, D, tf::TQKV>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, a);
         }
         {
             TfTimer t(h, st, 1);
-            launch_attention_fwd(PREC, h->qkv, h->att, B, L3, st, PREC == PREC_F16C);   // fp16c: hi and lo planes (attention.hip)
+            launch_attention_fwd(PREC, h->qkv.get(), h->att.get(), B, L3, st, PREC == PREC_F16C);   // fp16c: hi and lo planes (attention.hip)
         }
         TfTimer tl(h, st, 2);
         // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel
         const bool more = i + 1 < h->n_layers;
         const std::string pn = "transformer_encoder.layers." + std::to_string(i + 1) + ".";
-        const tf::FfnArgs f{h->hx, h->packed.at(p + "ff1"), h->packed.at(p + "ff2"), W(p + "linear1.bias"), W(p + "linear2.bias"),
-                            W(p + "norm2.weight"), W(p + "norm2.bias"), h->h, h->hx, M, 1e-5f,
-                            more ? h->packed.at(pn + "in") : nullptr, more ? W(pn + "self_attn.in_proj_bias") : nullptr, h->qkv,
-                            h->att, h->packed.at(p + "out"), W(p + "self_attn.out_proj.bias"), W(p + "norm1.weight"), W(p + "norm1.bias")};
+        const tf::FfnArgs f{h->hx.get(), P(p + "ff1"), P(p + "ff2"), W(p + "linear1.bias"), W(p + "linear2.bias"),
+                            W(p + "norm2.weight"), W(p + "norm2.bias"), h->h.get<float>(), h->hx.get(), M, 1e-5f,
+                            more ? P(pn + "in") : nullptr, more ? W(pn + "self_attn.in_proj_bias") : nullptr, h->qkv.get(),
+                            h->att.get(), P(p + "out"), W(p + "self_attn.out_proj.bias"), W(p + "norm1.weight"), W(p + "norm1.bias")};
         constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
         launch_lds<tf::enc_ffn16_kernel<PREC>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
     }
     {
         TfTimer t(h, st, 3);
-        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h, W("attn_pool.weight"), W("attn_pool.bias"),
+        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), W("attn_pool.weight"), W("attn_pool.bias"),
                            W("classifier.0.weight"), W("classifier.0.bias"), W("classifier.3.weight"), W("classifier.3.bias"),
-                           h->scores, h->pooled, logits, L3);
+                           h->scores.get<float>(), h->pooled.get<float>(), logits, L3);
     }
     h->last_B = B; h->last_L3 = L3;
     return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
@@ -619,15 +594,12 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
 extern "C" {
 
 int clm_tf_create(int device, int precision, int n_layers, clm_tf_handle** out) {
-    if (!out || n_layers < 1 || n_layers > 64) return tf_fail(nullptr, CLM_E_INVALID, "clm_tf_create: bad argument");
+    if (!out || n_layers < 1 || n_layers > 64) return fail<clm_tf_handle>(nullptr, CLM_E_INVALID, "clm_tf_create: bad argument");
     if (precision != CLM_PREC_F16 && precision != CLM_PREC_BF16 && precision != CLM_PREC_F32 && precision != CLM_PREC_F16C &&
         precision != CLM_PREC_F16X3)
-        return tf_fail(nullptr, CLM_E_UNSUPPORTED,
+        return fail<clm_tf_handle>(nullptr, CLM_E_UNSUPPORTED,
                        "clm_tf_create: precision must be fp32 (exact, the reference's arithmetic), fp16x3, fp16c, fp16 or bf16");
-    if (hipSetDevice(device) != hipSuccess) return tf_fail(nullptr, CLM_E_HIP, "clm_tf_create: hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return tf_fail(nullptr, CLM_E_UNSUPPORTED, "clm_tf_create: this engine is built for gfx950 (MI355X) only");
+    if (int rc = use_gfx950<clm_tf_handle>(device, "clm_tf_create")) return rc;
     clm_tf_handle* h = new clm_tf_handle();
     h->unfused_fp32 = debug_flag("unfused_fp32");
     h->device = device;
@@ -635,7 +607,7 @@ int clm_tf_create(int device, int precision, int n_layers, clm_tf_handle** out) 
     h->arith_x3 = precision == CLM_PREC_F16X3;
     if (h->arith_x3 && h->unfused_fp32) {
         delete h;
-        return tf_fail(nullptr, CLM_E_UNSUPPORTED, "clm_tf_create: fp16x3 exists in the fused kernels only (CLM_DEBUG=unfused_fp32 is set)");
+        return fail<clm_tf_handle>(nullptr, CLM_E_UNSUPPORTED, "clm_tf_create: fp16x3 exists in the fused kernels only (CLM_DEBUG=unfused_fp32 is set)");
     }
     h->prec = precision == CLM_PREC_BF16 ? PREC_BF16 : (precision == CLM_PREC_F32 || h->arith_x3) ? PREC_F32 : precision == CLM_PREC_F16C ? PREC_F16C
                                                                                                                                    : PREC_F16;
@@ -645,38 +617,26 @@ int clm_tf_create(int device, int precision, int n_layers, clm_tf_handle** out) 
 }
 
 int clm_tf_load_weight(clm_tf_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
-    if (!h || !key || !data || !shape) return tf_fail(h, CLM_E_INVALID, "clm_tf_load_weight: null argument");
-    if (dtype != CLM_DT_F32) return tf_fail(h, CLM_E_INVALID, "clm_tf_load_weight: fp32 tensors only");
+    if (!h || !key || !data || !shape) return fail(h, CLM_E_INVALID, "clm_tf_load_weight: null argument");
+    if (dtype != CLM_DT_F32) return fail(h, CLM_E_INVALID, "clm_tf_load_weight: fp32 tensors only");
     const std::string k = tf_canon(key);
     std::vector<int64_t> shp(shape, shape + ndim);
+    auto exp = tf_expected(h->n_layers);
     if (k == "pos_encoder.pe") {                               // buffer [1, max_len, 256]
-        if (ndim != 3 || shp[0] != 1 || shp[2] != D) return tf_fail(h, CLM_E_INVALID, "pos_encoder.pe: expected [1, max_len, 256]");
-    } else {
-        const auto exp = tf_expected(h->n_layers);
-        auto it = exp.find(k);
-        if (it == exp.end()) return tf_fail(h, CLM_E_INVALID, "clm_tf_load_weight: unknown key " + k);
-        if (it->second != shp) return tf_fail(h, CLM_E_INVALID, "clm_tf_load_weight: wrong shape for " + k);
+        if (ndim != 3 || shp[0] != 1 || shp[2] != D) return fail(h, CLM_E_INVALID, "pos_encoder.pe: expected [1, max_len, 256]");
+        exp[k] = shp;
     }
-    size_t n = 1;
-    for (int64_t s : shp) n *= (size_t)s;
-    TFCHK(h, hipSetDevice(h->device));
-    if (h->w.count(k)) { (void)hipFree(h->w[k]); h->w.erase(k); }
-    float* d = nullptr;
-    TFCHK(h, hipMalloc((void**)&d, n * 4));
-    TFCHK(h, hipMemcpy(d, data, n * 4, hipMemcpyDefault));
-    h->w[k] = d;
+    if (int rc = load_f32(h, "clm_tf_load_weight", exp, k, data, shape, ndim)) return rc;
     h->shape[k] = shp;
-    h->finalized = false;
     return CLM_OK;
 }
 
 int clm_tf_finalize(clm_tf_handle* h) {
     if (!h) return CLM_E_INVALID;
-    TFCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     for (const auto& kv : tf_expected(h->n_layers))
-        if (!h->w.count(kv.first)) return tf_fail(h, CLM_E_MISSING, "clm_tf_finalize: missing weight " + kv.first);
-    if (!h->w.count("pos_encoder.pe")) return tf_fail(h, CLM_E_MISSING, "clm_tf_finalize: missing buffer pos_encoder.pe");
-    for (auto& kv : h->packed) (void)hipFree(kv.second);
+        if (!h->w.count(kv.first)) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing weight " + kv.first);
+    if (!h->w.count("pos_encoder.pe")) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing buffer pos_encoder.pe");
     h->packed.clear();
     h->have_x3 = (h->arith_x3 || h->prec != PREC_F32) && !h->unfused_fp32;
     // exact fp32 (the handle's own mode, or the referee / fall-back of a 16-bit handle): the dense layers of the encoder in the fused
@@ -686,72 +646,72 @@ int clm_tf_finalize(clm_tf_handle* h) {
         struct { const char* name; const char* key; int n, k; } tw[4] = {{"in", "self_attn.in_proj_weight", tf::TQKV, D}, {"out", "self_attn.out_proj.weight", D, D},
                                                                          {"ff1", "linear1.weight", tf::TFF, D}, {"ff2", "linear2.weight", D, tf::TFF}};
         for (auto& e : tw) {
-            void* q = nullptr;
-            TFCHK(h, hipMalloc(&q, (size_t)e.n * e.k * 4));
-            launch_pack_f32t(h->w.at(p + e.key), q, e.n, e.k, 0);
-            h->packed[t + e.name] = q;
+            DevBuf q;
+            HIPCHK(h, q.alloc((size_t)e.n * e.k * 4));
+            launch_pack_f32t(h->w.at(p + e.key).get<float>(), q.get(), e.n, e.k, 0);
+            h->packed[t + e.name] = std::move(q);
             if (h->have_x3) {                                 // fp16x3 (a handle's mode, or a 16-bit handle's first fall-back level): the same weights as hi + lo halfs ("x3." keys); "t32." = the referee
-                void* qx = nullptr;
-                TFCHK(h, hipMalloc(&qx, (size_t)e.n * e.k * 4));
-                launch_pack_x3(h->w.at(p + e.key), qx, e.n, e.k, 0);
-                h->packed["x3." + std::to_string(i) + "." + e.name] = qx;
+                DevBuf qx;
+                HIPCHK(h, qx.alloc((size_t)e.n * e.k * 4));
+                launch_pack_x3(h->w.at(p + e.key).get<float>(), qx.get(), e.n, e.k, 0);
+                h->packed["x3." + std::to_string(i) + "." + e.name] = std::move(qx);
             }
         }
     }
     {   // ... and the three taps of each CNN-stem convolution ([co][ci][3] -> [3][co][ci], each tap packed)
-        float* split32 = nullptr;
-        TFCHK(h, hipMalloc((void**)&split32, (size_t)3 * D * D * 4));
+        DevBuf split;
+        HIPCHK(h, split.alloc((size_t)3 * D * D * 4));
+        float* const split32 = split.get<float>();
         for (int i : {0, 3, 6}) {
             const std::string name = "cnn." + std::to_string(i);
-            hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight"), split32);
-            float* q = nullptr;
-            TFCHK(h, hipMalloc((void**)&q, (size_t)3 * D * D * 4));
-            for (int dk = 0; dk < 3; ++dk) launch_pack_f32t(split32 + (size_t)dk * D * D, q + (size_t)dk * D * D, D, D, 0);
-            h->packed["t32." + name] = q;
+            hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight").get<float>(), split32);
+            DevBuf q;
+            HIPCHK(h, q.alloc((size_t)3 * D * D * 4));
+            for (int dk = 0; dk < 3; ++dk) launch_pack_f32t(split32 + (size_t)dk * D * D, q.get<float>() + (size_t)dk * D * D, D, D, 0);
+            h->packed["t32." + name] = std::move(q);
             if (h->have_x3) {
-                float* qx = nullptr;
-                TFCHK(h, hipMalloc((void**)&qx, (size_t)3 * D * D * 4));
-                for (int dk = 0; dk < 3; ++dk) launch_pack_x3(split32 + (size_t)dk * D * D, qx + (size_t)dk * D * D, D, D, 0);
-                h->packed["x3." + name] = qx;
+                DevBuf qx;
+                HIPCHK(h, qx.alloc((size_t)3 * D * D * 4));
+                for (int dk = 0; dk < 3; ++dk) launch_pack_x3(split32 + (size_t)dk * D * D, qx.get<float>() + (size_t)dk * D * D, D, D, 0);
+                h->packed["x3." + name] = std::move(qx);
             }
-            TFCHK(h, hipDeviceSynchronize());                 // `split32` is reused by the next layer
+            HIPCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next layer, and freed after the last
         }
-        (void)hipFree(split32);
     }
     if (h->prec == PREC_F32) {
-        TFCHK(h, hipDeviceSynchronize());
+        HIPCHK(h, hipDeviceSynchronize());
         h->finalized = true;
         return CLM_OK;
     }
-    auto pack = [&](const std::string& name, const float* w, int n, int k) -> int {
-        void* p = nullptr;
-        TFCHK(h, hipMalloc(&p, packed_weight_bytes(h->prec, n, k)));
-        launch_pack_weight(h->prec, w, p, n, k, 0);
-        h->packed[name] = p;
+    auto pack = [&](const std::string& name, const std::string& key, int n, int k) -> int {
+        DevBuf p;
+        HIPCHK(h, p.alloc(packed_weight_bytes(h->prec, n, k)));
+        launch_pack_weight(h->prec, h->w.at(key).get<float>(), p.get(), n, k, 0);
+        h->packed[name] = std::move(p);
         return CLM_OK;
     };
-    float* split = nullptr;
-    TFCHK(h, hipMalloc((void**)&split, (size_t)3 * D * D * 4));
+    DevBuf split;
+    HIPCHK(h, split.alloc((size_t)3 * D * D * 4));
     for (int i : {0, 3, 6}) {
         const std::string name = "cnn." + std::to_string(i);
-        hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight"), split);
-        void* p = nullptr;
-        TFCHK(h, hipMalloc(&p, 3 * packed_weight_bytes(h->prec, D, D)));
+        hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight").get<float>(), split.get<float>());
+        DevBuf p;
+        HIPCHK(h, p.alloc(3 * packed_weight_bytes(h->prec, D, D)));
         for (int dk = 0; dk < 3; ++dk)
-            launch_pack_weight(h->prec, split + (size_t)dk * D * D, (char*)p + dk * packed_weight_bytes(h->prec, D, D), D, D, 0);
-        TFCHK(h, hipDeviceSynchronize());                     // `split` is reused by the next layer
-        h->packed[name] = p;
+            launch_pack_weight(h->prec, split.get<float>() + (size_t)dk * D * D, p.get<char>() + dk * packed_weight_bytes(h->prec, D, D), D, D, 0);
+        HIPCHK(h, hipDeviceSynchronize());                     // `split` is reused by the next layer, and freed after the last
+        h->packed[name] = std::move(p);
     }
-    (void)hipFree(split);
+    split.reset();
     for (int i = 0; i < h->n_layers; ++i) {
         const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
         int rc;
-        if ((rc = pack(p + "in", h->w.at(p + "self_attn.in_proj_weight"), tf::TQKV, D))) return rc;
-        if ((rc = pack(p + "out", h->w.at(p + "self_attn.out_proj.weight"), D, D))) return rc;
-        if ((rc = pack(p + "ff1", h->w.at(p + "linear1.weight"), tf::TFF, D))) return rc;
-        if ((rc = pack(p + "ff2", h->w.at(p + "linear2.weight"), D, tf::TFF))) return rc;
+        if ((rc = pack(p + "in", p + "self_attn.in_proj_weight", tf::TQKV, D))) return rc;
+        if ((rc = pack(p + "out", p + "self_attn.out_proj.weight", D, D))) return rc;
+        if ((rc = pack(p + "ff1", p + "linear1.weight", tf::TFF, D))) return rc;
+        if ((rc = pack(p + "ff2", p + "linear2.weight", D, tf::TFF))) return rc;
     }
-    TFCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
     return CLM_OK;
 }
@@ -767,88 +727,76 @@ static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype,
                   float* logits_out, hipStream_t st) {
     const int L3 = L / 8;
     const size_t M = (size_t)B * L3, tok = (size_t)B * ((L + 63) / 64 * 64);
-    if (M > h->cap_rows || tok > h->cap_tok) {                // shared pieces: ids, residual stream, pooling scores
-        TFCHK(h, hipDeviceSynchronize());
-        tf_free_ws(h);
-        TFCHK(h, hipMalloc((void**)&h->ids8, tok));
-        TFCHK(h, hipMalloc((void**)&h->h, M * D * 4));
-        TFCHK(h, hipMalloc((void**)&h->scores, M * 4));
-        h->cap_rows = M; h->cap_tok = tok;
+    if (tok > h->ids8.bytes() || M * D * 4 > h->h.bytes() || M * 4 > h->scores.bytes()) {   // shared pieces: ids, residual stream, pooling scores
+        HIPCHK(h, hipDeviceSynchronize());
+        for (DevBuf* b : {&h->ids8, &h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att, &h->h, &h->scores, &h->pooled, &h->ws32})
+            b->reset();                                        // (the whole workspace: what is regrown below follows this shape)
+        HIPCHK(h, h->ids8.alloc(tok));
+        HIPCHK(h, h->h.alloc(M * D * 4));
+        HIPCHK(h, h->scores.alloc(M * 4));
     }
-    if ((size_t)B > h->cap_B) {                               // pooled [B][256]: its own capacity -- a batch of MORE, SHORTER reads fits
-        TFCHK(h, hipDeviceSynchronize());                     // cap_rows / cap_tok and must still regrow this one
-        if (h->pooled) (void)hipFree(h->pooled);
-        h->pooled = nullptr; h->cap_B = 0;
-        TFCHK(h, hipMalloc((void**)&h->pooled, (size_t)B * D * 4));
-        h->cap_B = (size_t)B;
+    if ((size_t)B * D * 4 > h->pooled.bytes()) {               // pooled [B][256] on its own -- a batch of MORE, SHORTER reads fits the
+        HIPCHK(h, hipDeviceSynchronize());                     // shared pieces and must still regrow this one
+        HIPCHK(h, h->pooled.reserve((size_t)B * D * 4));
     }
     if (prec32) {
-        const size_t need = tf32_workspace_floats(B, L);
-        if (need > h->cap_ws32) {
-            TFCHK(h, hipDeviceSynchronize());
-            if (h->ws32) (void)hipFree(h->ws32);
-            h->ws32 = nullptr; h->cap_ws32 = 0;
-            TFCHK(h, hipMalloc((void**)&h->ws32, need * 4));
-            h->cap_ws32 = need;
+        const size_t need = tf32_workspace_floats(B, L) * 4;
+        if (need > h->ws32.bytes()) {
+            HIPCHK(h, hipDeviceSynchronize());
+            HIPCHK(h, h->ws32.reserve(need));
         }
         const int Lp = (L + 63) / 64 * 64;
-        launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8, B, L, Lp, st);
+        launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);
         // hi + lo halfs on the fp32 path: an fp16x3 handle unless told to fall back; a 16-bit handle at fall-back level 1
         const bool use_x3 = tf_fp32_path_is_x3(h);
         auto get = [](void* ctx, const std::string& k) -> const float* {     // "t32.*": the fused kernels' packed weights ("x3.*" in fp16x3)
             auto* hh = static_cast<clm_tf_handle*>(ctx);
-            if (k.rfind("t32.", 0) != 0) return hh->w.at(k);
-            return static_cast<const float*>(hh->packed.at(tf_fp32_path_is_x3(hh) ? "x3." + k.substr(4) : k));
+            if (k.rfind("t32.", 0) != 0) return hh->w.at(k).get<float>();
+            return hh->packed.at(tf_fp32_path_is_x3(hh) ? "x3." + k.substr(4) : k).get<const float>();
         };
-        if (tf32_forward(h->ids8, Lp, B, L, h->n_layers, h->ws32, h->h, get, h, st, h->unfused_fp32, use_x3))
-            return tf_fail(h, CLM_E_HIP, std::string("clm_tf_forward (fp32): ") + hipGetErrorString(hipGetLastError()));
-        auto W = [&](const std::string& k) { return h->w.at(k); };
-        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h, W("attn_pool.weight"), W("attn_pool.bias"),
+        if (tf32_forward(h->ids8.get<unsigned char>(), Lp, B, L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), get, h, st, h->unfused_fp32, use_x3))
+            return fail(h, CLM_E_HIP, std::string("clm_tf_forward (fp32): ") + hipGetErrorString(hipGetLastError()));
+        auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
+        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), W("attn_pool.weight"), W("attn_pool.bias"),
                            W("classifier.0.weight"), W("classifier.0.bias"), W("classifier.3.weight"), W("classifier.3.bias"),
-                           h->scores, h->pooled, logits_out, L3);
+                           h->scores.get<float>(), h->pooled.get<float>(), logits_out, L3);
         h->last_B = B; h->last_L3 = L3;
-        return hipGetLastError() == hipSuccess ? CLM_OK : tf_fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
+        return hipGetLastError() == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
     }
     {   // the 16-bit activations, each buffer grown on its own (x1 / x2 scale with B * (L / 2), B * (L / 4), not with M)
         const size_t need[6] = {(size_t)B * (L / 2) * D * 2, (size_t)B * (L / 4) * D * 2, M * D * 2, M * D * 2, M * tf::TQKV * 2,
                                 M * D * 2 * (h->prec == PREC_F16C ? 2 : 1) /* hi + lo planes */};
-        void** buf[6] = {&h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att};
+        DevBuf* buf[6] = {&h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att};
         bool grow = false;
-        for (int i = 0; i < 6; ++i) grow |= need[i] > h->cap16[i];
+        for (int i = 0; i < 6; ++i) grow |= need[i] > buf[i]->bytes();
         if (grow) {
-            TFCHK(h, hipDeviceSynchronize());
-            for (int i = 0; i < 6; ++i)
-                if (need[i] > h->cap16[i]) {
-                    if (*buf[i]) (void)hipFree(*buf[i]);
-                    *buf[i] = nullptr; h->cap16[i] = 0;
-                    TFCHK(h, hipMalloc(buf[i], need[i]));
-                    h->cap16[i] = need[i];
-                }
+            HIPCHK(h, hipDeviceSynchronize());
+            for (int i = 0; i < 6; ++i) HIPCHK(h, buf[i]->reserve(need[i]));
         }
     }
     const int rc = h->prec == PREC_BF16   ? tf_forward_t<PREC_BF16>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st)
                    : h->prec == PREC_F16C ? tf_forward_t<PREC_F16C>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st)
                                           : tf_forward_t<PREC_F16>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st);
-    if (rc) return tf_fail(h, rc, std::string("clm_tf_forward: ") + hipGetErrorString(hipGetLastError()));
+    if (rc) return fail(h, rc, std::string("clm_tf_forward: ") + hipGetErrorString(hipGetLastError()));
     return CLM_OK;
 }
 
 static int tf_check_args(clm_tf_handle* h, const char* who, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L) {
-    if (!h->finalized) return tf_fail(h, CLM_E_STATE, std::string(who) + " before clm_tf_finalize");
-    if (!ids || B < 1 || L < 8 || ids_row_stride < L) return tf_fail(h, CLM_E_INVALID, std::string(who) + ": bad argument (L >= 8)");
+    if (!h->finalized) return fail(h, CLM_E_STATE, std::string(who) + " before clm_tf_finalize");
+    if (!ids || B < 1 || L < 8 || ids_row_stride < L) return fail(h, CLM_E_INVALID, std::string(who) + ": bad argument (L >= 8)");
     if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return tf_fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
+        return fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
     if ((int64_t)(L / 8) > h->shape.at("pos_encoder.pe")[1])
-        return tf_fail(h, CLM_E_INVALID, std::string(who) + ": Sequence too long (" + std::to_string(L / 8) + " > max_len of pos_encoder.pe)");
+        return fail(h, CLM_E_INVALID, std::string(who) + ": Sequence too long (" + std::to_string(L / 8) + " > max_len of pos_encoder.pe)");
     return CLM_OK;
 }
 
 int clm_tf_forward(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
                    void* stream) {
     if (!h) return CLM_E_INVALID;
-    if (!logits_out) return tf_fail(h, CLM_E_INVALID, "clm_tf_forward: bad argument (L >= 8)");
+    if (!logits_out) return fail(h, CLM_E_INVALID, "clm_tf_forward: bad argument (L >= 8)");
     if (int rc = tf_check_args(h, "clm_tf_forward", ids, ids_dtype, ids_row_stride, B, L)) return rc;
-    TFCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     return tf_run(h, h->prec == PREC_F32 || h->fallback > 0, ids, ids_dtype, ids_row_stride, B, L, logits_out,
                   reinterpret_cast<hipStream_t>(stream));
 }
@@ -859,21 +807,18 @@ int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t i
                      float* max_abs_diff_out, int* labels_differ_out) {
     if (!h) return CLM_E_INVALID;
     if (int rc = tf_check_args(h, "clm_tf_selfcheck", ids, ids_dtype, ids_row_stride, B, L)) return rc;
-    if (B > 4096) return tf_fail(h, CLM_E_INVALID, "clm_tf_selfcheck: at most 4096 reads per call");
-    TFCHK(h, hipSetDevice(h->device));
+    if (B > 4096) return fail(h, CLM_E_INVALID, "clm_tf_selfcheck: at most 4096 reads per call");
+    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float diff = 0.f;
     int differ = 0;
     if (h->prec != PREC_F32 || h->arith_x3) {                  // (an fp16x3 handle: its own exact-fp32 kernels are the referee)
-        if (B > h->sc_cap) {
-            TFCHK(h, hipDeviceSynchronize());
-            if (h->sc_logits) (void)hipFree(h->sc_logits);
-            h->sc_logits = nullptr; h->sc_cap = 0;
-            TFCHK(h, hipMalloc((void**)&h->sc_logits, (size_t)2 * B * NCLS * 4));
-            h->sc_cap = B;
+        if ((size_t)2 * B * NCLS * 4 > h->sc_logits.bytes()) {
+            HIPCHK(h, hipDeviceSynchronize());
+            HIPCHK(h, h->sc_logits.reserve((size_t)2 * B * NCLS * 4));
         }
-        float* lm = h->sc_logits;
-        float* lx = h->sc_logits + (size_t)h->sc_cap * NCLS;
+        float* lm = h->sc_logits.get<float>();
+        float* lx = lm + (size_t)B * NCLS;
         const int fallback = h->fallback;
         h->fallback = 0;                                       // the MODE is on trial, whatever clm_tf_set_fallback says
         const int rc1 = tf_run(h, h->arith_x3, ids, ids_dtype, ids_row_stride, B, L, lm, st);
@@ -884,9 +829,9 @@ int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t i
         h->referee = false;
         if (rc2) return rc2;
         std::vector<float> a((size_t)B * NCLS), b((size_t)B * NCLS);
-        TFCHK(h, hipMemcpyAsync(a.data(), lm, a.size() * 4, hipMemcpyDeviceToHost, st));
-        TFCHK(h, hipMemcpyAsync(b.data(), lx, b.size() * 4, hipMemcpyDeviceToHost, st));
-        TFCHK(h, hipStreamSynchronize(st));
+        HIPCHK(h, hipMemcpyAsync(a.data(), lm, a.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(b.data(), lx, b.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
         (void)clm_logit_deviation(a.data(), b.data(), B, NCLS, &diff, &differ);   // (shared with clm_selfcheck: a non-finite logit is sticky +inf)
     }
     if (max_abs_diff_out) *max_abs_diff_out = diff;
@@ -896,25 +841,25 @@ int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t i
 
 int clm_tf_set_fallback(clm_tf_handle* h, int on) {
     if (!h) return CLM_E_INVALID;
-    if (on < 0 || on > 2) return tf_fail(h, CLM_E_INVALID, "clm_tf_set_fallback: level must be 0, 1 or 2");
+    if (on < 0 || on > 2) return fail(h, CLM_E_INVALID, "clm_tf_set_fallback: level must be 0, 1 or 2");
     h->fallback = (h->prec == PREC_F32 && !h->arith_x3) ? 0 : on;
     return CLM_OK;
 }
 
 int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_t bytes) {
-    if (!h || !name || !host_out) return tf_fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: bad argument");
-    TFCHK(h, hipSetDevice(h->device));
-    TFCHK(h, hipDeviceSynchronize());
+    if (!h || !name || !host_out) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: bad argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
     const std::string n(name);
     const size_t M = (size_t)h->last_B * h->last_L3;
     const void* src = nullptr;
     size_t have = 0;
-    if (n == "hidden") { src = h->h; have = M * D * 4; }
-    else if (n == "scores") { src = h->scores; have = M * 4; }
-    else if (n == "pooled") { src = h->pooled; have = (size_t)h->last_B * D * 4; }
-    else return tf_fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: unknown name " + n);
-    if (bytes > have) return tf_fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: more bytes requested than the last forward produced");
-    TFCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    if (n == "hidden") { src = h->h.get(); have = M * D * 4; }
+    else if (n == "scores") { src = h->scores.get(); have = M * 4; }
+    else if (n == "pooled") { src = h->pooled.get(); have = (size_t)h->last_B * D * 4; }
+    else return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: unknown name " + n);
+    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: more bytes requested than the last forward produced");
+    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
     return CLM_OK;
 }
 
@@ -926,8 +871,8 @@ int clm_tf_profile_enable(clm_tf_handle* h, int on) {
 
 int clm_tf_profile_read(clm_tf_handle* h, double* ms_out /*[4]*/, int64_t* spans_out /*[4]*/, int reset) {
     if (!h) return CLM_E_INVALID;
-    TFCHK(h, hipSetDevice(h->device));
-    TFCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
     for (auto& r : h->recs) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, r.second.first, r.second.second) == hipSuccess) {
@@ -946,18 +891,14 @@ int clm_tf_profile_read(clm_tf_handle* h, double* ms_out /*[4]*/, int64_t* spans
     return CLM_OK;
 }
 
-const char* clm_tf_last_error(const clm_tf_handle* h) { return h ? h->err.c_str() : g_tf_create_error.c_str(); }
+const char* clm_tf_last_error(const clm_tf_handle* h) { return h ? h->err.c_str() : create_error<clm_tf_handle>().c_str(); }
 
 int clm_tf_destroy(clm_tf_handle* h) {
     if (!h) return CLM_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
-    tf_free_ws(h);
-    if (h->sc_logits) (void)hipFree(h->sc_logits);
     for (auto& r : h->recs) { (void)hipEventDestroy(r.second.first); (void)hipEventDestroy(r.second.second); }
-    for (auto& kv : h->w) (void)hipFree(kv.second);
-    for (auto& kv : h->packed) (void)hipFree(kv.second);
-    delete h;
+    delete h;                                                  // (its device buffers free themselves)
     return CLM_OK;
 }
 
