@@ -22,6 +22,7 @@ STAGES = ["embed", "ln1_in_proj", "short_long_conv", "out_proj", "ln2_fc1_gelu",
           "softmax_pool", "head_mlp", "filter", "out_proj_ln2_mlp", "ln2_mlp"]
 N_STAGES = len(STAGES)
 ABI_VERSION = 6
+MAMBA_SEQ, MAMBA_SP = 0, 1            # clm_mamba_create variants (CLM_MAMBA_SEQ, CLM_MAMBA_SP)
 
 
 class ClmConfig(C.Structure):
@@ -86,6 +87,14 @@ SYMBOLS = {
     "clm_cnn_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_cnn_last_error": (C.c_char_p, [_H]),
     "clm_cnn_destroy": (C.c_int, [_H]),
+    "clm_mamba_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    "clm_mamba_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "clm_mamba_finalize": (C.c_int, [_H]),
+    "clm_mamba_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_void_p]),
+    "clm_mamba_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "clm_mamba_last_error": (C.c_char_p, [_H]),
+    "clm_mamba_destroy": (C.c_int, [_H]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

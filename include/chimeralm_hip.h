@@ -238,6 +238,46 @@ int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, siz
 const char* clm_cnn_last_error(const clm_cnn_handle* h); /* h may be NULL: error of the last failed clm_cnn_create */
 int clm_cnn_destroy(clm_cnn_handle* h);
 
+/* ---- Mamba2 classifiers (ABI 6, additive) -----------------------------------------------------------------------------
+ * The reference's two Mamba nets (chimeralm/models/components/mamba.py) in eval mode, behind the same `net`
+ * boundary: forward(input_ids[B, L], second argument) -> logits fp32 [B, 2].
+ *   CLM_MAMBA_SEQ  MambaSequenceClassification (configs/model/mamba.yaml: d 256, 12 layers, d_state 16, expand 2):
+ *                  LayerNorm(Linear(E[id] + pos_embedding[t])), then h += Mamba2(h) per layer; `mask` [B, L] (the reference's
+ *                  `attention_mask`, optional) multiplies h after the front and after every residual add.  L > model_max_length
+ *                  is CLM_E_INVALID.
+ *   CLM_MAMBA_SP   MambaSequenceClassificationSP (configs/model/mambasp.yaml: d 512, 3 layers, d_state 128, expand 3): h = E[id];
+ *                  `mask` is ignored, as the reference ignores its second argument; any L.
+ * Both: pooled = (mean_t h + max_t h) / 2 over all L positions, pooler Linear + GELU, classifier Linear + GELU + Linear.  Mamba2 is
+ * mamba_ssm 2.x's with its defaults (ngroups 1, gated RMSNorm after the gate, per-head D, no projection bias, conv bias, zero
+ * initial state); tests/mamba_reference.py states its arithmetic.
+ * Same conventions as the clm_cnn_* calls; weights under the reference module's state_dict keys (with or without `net.`), fp32 only.
+ *   create      variant, precision, d_model (256 or 512), n_layers (>= 1), d_state (16, 32, 64 or 128), expand (d_inner = expand x
+ *               d_model), headdim (64), model_max_length (CLM_MAMBA_SEQ: the positional table's length; ignored otherwise).
+ *               Anything else is CLM_E_INVALID.
+ *   precision   CLM_PREC_F32 (exact fp32 MFMA) or CLM_PREC_F16X3 (the projections as three fp16 MFMAs on hi + lo halfs).  The
+ *               fp16x3 weight packing saturates for |w| >= 64 (out_proj counted with norm.weight folded in): then finalize packs
+ *               that handle's weights for the exact-fp32 kernels.  An activation beyond fp16's range entering an fp16x3 projection
+ *               makes that tile's outputs NaN (the caller reruns the batch on an fp32 handle).  The scan, the norms and the head
+ *               are fp32 in both modes.
+ *   ids         i64, i32 or u8; an id outside [0, 12) is clamped into it.
+ *   mask        fp32 [B, mask_row_stride] device pointer or NULL.
+ * Long batches run in chunks of whole reads (the in_proj output of one chunk is bounded at 4 GiB).  The forward is bitwise
+ * deterministic (no atomics) and a read's logits do not depend on the other reads of its batch.
+ * clm_mamba_debug_fetch names (the last forward): "front" fp32 [B, L, d] (the residual stream entering layer 0), "layer0" fp32
+ * [B, L, d] (after layer 0) -- both only while B x L x d x 4 <= 256 MiB -- and "pooled" fp32 [B, d]. */
+#define CLM_MAMBA_SEQ 0
+#define CLM_MAMBA_SP 1
+typedef struct clm_mamba_handle clm_mamba_handle;
+int clm_mamba_create(int device, int variant, int precision, int d_model, int n_layers, int d_state, int expand, int headdim,
+                     int model_max_length, clm_mamba_handle** out);
+int clm_mamba_load_weight(clm_mamba_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
+int clm_mamba_finalize(clm_mamba_handle* h);
+int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, const float* mask,
+                      int64_t mask_row_stride, float* logits_out, void* stream);
+int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out, size_t bytes);
+const char* clm_mamba_last_error(const clm_mamba_handle* h); /* h may be NULL: error of the last failed clm_mamba_create */
+int clm_mamba_destroy(clm_mamba_handle* h);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:
