@@ -18,6 +18,7 @@ DT_F32, DT_F64, DT_BF16, DT_F16, DT_U8, DT_I32, DT_I64 = range(7)
 PREC_F32, PREC_BF16, PREC_F16, PREC_F16C, PREC_F16X3 = 0, 1, 2, 3, 4
 BAM_INPUT_SAM, BAM_KEEP_UNPLACED = 1, 2
 PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "bf16": PREC_BF16, "fp16": PREC_F16, "f16": PREC_F16, "fp16c": PREC_F16C, "fp16x3": PREC_F16X3}
+PREC_NAMES = {PREC_F32: "fp32", PREC_BF16: "bf16", PREC_F16: "fp16", PREC_F16C: "fp16c", PREC_F16X3: "fp16x3"}
 STAGES = ["embed", "ln1_in_proj", "short_long_conv", "out_proj", "ln2_fc1_gelu", "fc2", "lnf_pool_score",
           "softmax_pool", "head_mlp", "filter", "out_proj_ln2_mlp", "ln2_mlp"]
 N_STAGES = len(STAGES)
@@ -68,6 +69,7 @@ SYMBOLS = {
     "clm_set_short_read_len": (C.c_int, [_H, C.c_int]),
     "clm_set_mlp_compensation": (C.c_int, [_H, C.c_int]),
     "clm_attention_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "clm_attention_exact_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "clm_tf_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "clm_tf_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "clm_tf_finalize": (C.c_int, [_H]),
@@ -75,6 +77,7 @@ SYMBOLS = {
     "clm_tf_selfcheck": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_float),
                                    C.POINTER(C.c_int)]),
     "clm_tf_set_fallback": (C.c_int, [_H, C.c_int]),
+    "clm_tf_effective_precision": (C.c_int, [_H]),
     "clm_tf_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_tf_profile_enable": (C.c_int, [_H, C.c_int]),
     "clm_tf_profile_read": (C.c_int, [_H, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),

@@ -159,6 +159,7 @@ struct clm_handle {
     int conv_flags = 0;           // CLM_DEBUG=conv_oneshot / conv_no_xcd: CONV_* switches of the convolution launchers (A/B runs, tests)
     bool no_lone_peel = false;    // CLM_DEBUG=no_lone_peel: keep the lone last token of 128 k + 1-token reads in a tile of its own (A/B runs)
     bool x3 = false;              // CLM_PREC_F16X3: cfg.precision is PREC_F32 inside the engine, the fused tails run on hi + lo halfs (tail32.hip AR_X3)
+    float x3_wmax = 0.f;          // largest |w| of the hi + lo packed weights (clm_finalize; NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32
     bool unfused_fp32 = false;    // CLM_DEBUG=unfused_fp32: exact fp32 through the separate GEMM kernels of rounds 1-3 (tests cross-check the fused tail)
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -425,7 +426,7 @@ int effective_prec(const clm_handle* h, int L) {
 // handle: unless told to fall back; a 16-bit handle (short reads of fp16c, fall-back level 1): unless told to fall back all the
 // way (level 2).  Never inside the referee pass of a self-check, never on an fp32 handle.
 bool fp32_path_is_x3(const clm_handle* h) {
-    if (h->referee) return false;
+    if (h->referee || !(h->x3_wmax < X3_WEIGHT_LIMIT)) return false;   // (weights beyond the packing's range: exact fp32 instead)
     if (h->x3) return h->fallback == 0;
     return h->cfg.precision != PREC_F32 && h->fallback < 2;
 }
@@ -915,6 +916,18 @@ int clm_finalize(clm_handle* h) {
     const int prec = h->cfg.precision;
     // hi + lo halfs of the tail weights: an fp16x3 handle's own arithmetic; a 16-bit handle's short reads and first fall-back level
     const bool pack_x3 = (h->x3 || prec != PREC_F32) && !h->unfused_fp32;
+    h->x3_wmax = 0.f;
+    if (pack_x3) {                // what the hi + lo packing must hold: the four tail products of every block and the score layer
+        std::vector<std::string> keys{"head.attention.0.weight"};
+        for (int i = 0; i < NLAYER; ++i)
+            for (const char* k : {"mixer.in_proj.weight", "mixer.out_proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"})
+                keys.push_back("bb.layers." + std::to_string(i) + "." + k);
+        for (const auto& k : keys) {
+            float m = 0.f;
+            HIPCHK(h, device_max_abs(W(h, k), h->w[k].numel, m));
+            if (m != m || m > h->x3_wmax) h->x3_wmax = m;          // (NaN stays)
+        }
+    }
     hipStream_t st = 0;
     auto pack_as = [&](int pr, const std::string& key, int n, int k, DevBuf& out) -> int {
         HIPCHK(h, out.alloc(packed_weight_bytes(pr, n, k)));

@@ -264,6 +264,22 @@ int load_f32(H* h, const char* who, const std::map<std::string, std::vector<int6
     return CLM_OK;
 }
 
+// fp16x3 packs a weight x 2^10 as fp16 hi + lo (tail32.hip pack_x3_kernel): from |w| = 65504 / 2^10 ~ 63.97 the hi half saturates
+// and the packing no longer holds the weight, so a handle whose x3-packed weights reach this runs its exact-fp32 kernels instead.
+constexpr float X3_WEIGHT_LIMIT = 64.f;
+// Largest |w| of `n` fp32 values in device memory (read back to the host; NaN as soon as one of them is NaN).
+inline hipError_t device_max_abs(const float* d, size_t n, float& out) {
+    std::vector<float> host(n);
+    const hipError_t e = hipMemcpy(host.data(), d, n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    out = 0.f;
+    for (const float x : host) {
+        if (x != x) { out = x; break; }
+        out = __builtin_fabsf(x) > out ? __builtin_fabsf(x) : out;
+    }
+    return hipSuccess;
+}
+
 // ---- kernel launchers (definitions in the .hip files); all are asynchronous on `st` --------------------
 // PREC_F16C ("fp16c"): fp16 activations x weights held as hi + lo (in_proj, out_proj, score layer; the MLP weights are plain fp16
 // since round 3: MLP_PREC, gemm_common.h), hi = fp16(w), lo = e4m3((w - hi) * 2^17): per 64-deep group

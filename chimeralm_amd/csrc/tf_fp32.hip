@@ -544,3 +544,17 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
 }
 
 }  // namespace clm
+
+// The exact attention kernels on their own (chimeralm_hip.h): the launches of tf32_forward, for the tests that hold them to an fp64
+// softmax(q k^T / sqrt(32)) v at shapes and score patterns a whole-model bound cannot resolve.
+extern "C" int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream) {
+    using namespace clm::tf32;
+    if (!qkv || !out || B < 1 || L < 1 || (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)) return CLM_E_INVALID;
+    const int qt = precision == CLM_PREC_F32 ? A32_QT : AX_QT;
+    const size_t grid = (size_t)((L + qt - 1) / qt) * 8 * B;
+    if (grid > 0x7fffffff) return CLM_E_INVALID;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (precision == CLM_PREC_F32) hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)grid), dim3(256), 0, st, qkv, out, L);
+    else hipLaunchKernelGGL(attention_x3_kernel, dim3((unsigned)grid), dim3(256), 0, st, qkv, out, L);
+    return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
+}

@@ -476,6 +476,7 @@ struct clm_tf_handle {
     // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
     int fallback = 0;
     bool have_x3 = false;                         // the "x3.*" packings exist (fp16x3 and 16-bit handles, fused kernels only)
+    float x3_wmax = 0.f;                          // largest |w| they hold (NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32 instead
     DevBuf sc_logits;                             // clm_tf_selfcheck: [2][B][2] fp32 logits of the two forwards
     // profiling taps (clm_tf_profile_*): HIP events on the launch stream around each stage, stages: 0 conv stack + pe/LN,
     // 1 attention, 2 encoder layer kernel (out_proj + LN1 + FFN + LN2 + next QKV; the unfused pieces count here too), 3 pooling head
@@ -639,6 +640,18 @@ int clm_tf_finalize(clm_tf_handle* h) {
     if (!h->w.count("pos_encoder.pe")) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing buffer pos_encoder.pe");
     h->packed.clear();
     h->have_x3 = (h->arith_x3 || h->prec != PREC_F32) && !h->unfused_fp32;
+    h->x3_wmax = 0.f;
+    if (h->have_x3) {             // what the hi + lo packing must hold: the CNN stem and the four dense products of every layer
+        std::vector<std::string> keys{"cnn.0.weight", "cnn.3.weight", "cnn.6.weight"};
+        for (int i = 0; i < h->n_layers; ++i)
+            for (const char* k : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"})
+                keys.push_back("transformer_encoder.layers." + std::to_string(i) + "." + k);
+        for (const auto& k : keys) {
+            float m = 0.f;
+            HIPCHK(h, device_max_abs(h->w.at(k).get<float>(), h->w.at(k).bytes() / 4, m));
+            if (m != m || m > h->x3_wmax) h->x3_wmax = m;          // (NaN stays)
+        }
+    }
     // exact fp32 (the handle's own mode, or the referee / fall-back of a 16-bit handle): the dense layers of the encoder in the fused
     // kernel's packing (tail32.hip enc32_kernel); everything else of tf_fp32.hip reads the fp32 tensors as they are
     for (int i = 0; i < h->n_layers; ++i) {
@@ -717,7 +730,7 @@ int clm_tf_finalize(clm_tf_handle* h) {
 }
 
 static bool tf_fp32_path_is_x3(const clm_tf_handle* h) {
-    if (h->referee || !h->have_x3) return false;
+    if (h->referee || !h->have_x3 || !(h->x3_wmax < X3_WEIGHT_LIMIT)) return false;   // (weights beyond the packing's range: exact fp32)
     return h->arith_x3 ? h->fallback == 0 : h->fallback < 2;
 }
 
@@ -844,6 +857,13 @@ int clm_tf_set_fallback(clm_tf_handle* h, int on) {
     if (on < 0 || on > 2) return fail(h, CLM_E_INVALID, "clm_tf_set_fallback: level must be 0, 1 or 2");
     h->fallback = (h->prec == PREC_F32 && !h->arith_x3) ? 0 : on;
     return CLM_OK;
+}
+
+int clm_tf_effective_precision(const clm_tf_handle* h) {
+    if (!h) return CLM_E_INVALID;
+    if (!h->finalized) return CLM_E_STATE;
+    if (h->prec != PREC_F32 && h->fallback == 0) return h->prec;
+    return tf_fp32_path_is_x3(h) ? CLM_PREC_F16X3 : CLM_PREC_F32;
 }
 
 int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_t bytes) {

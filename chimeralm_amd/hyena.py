@@ -20,6 +20,9 @@ from torch import nn
 
 from .engine import Engine
 
+# |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_finalize)
+X3_WEIGHT_LIMIT = 64.0
+_X3_PACKED = ("mixer.in_proj.weight", "mixer.out_proj.weight", "mlp.fc1.weight", "mlp.fc2.weight", "head.attention.0.weight")
 _SMALL_32K = dict(d_model=256, n_layer=4, d_inner=1024, vocab_rows=16, filter_order=64, emb_dim=5, max_seq_len=32770)
 
 
@@ -197,6 +200,10 @@ class HyenaDna(nn.Module):
     engine fall back for good (logged, RuntimeWarning): to fp16x3, the next-fastest arithmetic inside the gate
     (`clm_set_fallback` level 1; an "fp16x3" module that was asked to check itself falls back to exact fp32).  `selfcheck_report`
     holds what was measured.
+    fp16x3 -- the "fp16x3" mode, fp16c's short reads and the first fall-back level of the 16-bit modes -- packs weights x 2^10 as
+    fp16 halfs, which saturate at |w| >= 64: if an in_proj / out_proj / fc1 / fc2 / score weight is that large (or NaN), the engine
+    runs exact fp32 wherever it would run fp16x3; the module reads that back at every weight load, records it in `precision_report`
+    and logs a warning.
     """
 
     def __init__(self, number_of_classes: int, head: nn.Module, backbone_name: str = "hyenadna-small-32k-seqlen", *,
@@ -218,6 +225,7 @@ class HyenaDna(nn.Module):
         self.selfcheck_tol = float(selfcheck_tol)
         self.selfcheck_every = int(selfcheck_every)
         self.selfcheck_report: dict = {}
+        self.precision_report: dict = {}
         if freeze_backbone:
             for p in self.backbone.parameters():
                 p.requires_grad = False
@@ -256,7 +264,35 @@ class HyenaDna(nn.Module):
             self._batches_since_check = 0
             self._reads_since_check = 0
             self.selfcheck_report = {}
+            self._report_x3(self._engine)
         return self._engine
+
+    def _report_x3(self, eng: Engine) -> None:
+        """`precision_report` of the weights just loaded: the arithmetic the engine runs where this mode uses fp16x3 (see the class
+        docstring), read back from the engine, and a warning when the weights pushed it to exact fp32."""
+        if self.precision == "fp32":
+            self.precision_report = {"precision": "fp32", "fallback": False}
+            return
+        if self.precision in ("fp16x3", "fp16c"):             # its own mode / its short reads (level 0, one-token reads)
+            x3 = eng.effective_precision(1)
+        else:                                                 # fp16 / bf16: only their first fall-back level is fp16x3
+            eng.set_fallback(1)
+            x3 = eng.effective_precision(1)
+            eng.set_fallback(0)
+        ws = [t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)]
+        wmax = max(float(t.detach().abs().max()) for t in ws)
+        fallback = x3 != "fp16x3"
+        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
+        if not fallback:
+            return
+        import logging
+
+        self.precision_report["fallback_precision"] = x3
+        where = {"fp16x3": "", "fp16c": " (its reads below f16c_min_len and its first fall-back level)"}.get(
+            self.precision, " (its first fall-back level)")
+        logging.getLogger("chimeralm_amd").warning(
+            f"chimeralm_amd: HyenaDna precision={self.precision!r} packs weights as fp16 halfs x 2^10 for fp16x3{where}, which "
+            f"saturate at |w| >= {X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so it runs the exact-fp32 kernels there")
 
     # -------------------------------------------------------------------------------- the 16-bit mode on trial
     _SAMPLE_LENGTHS = (4097, 2048, 1024, 512, 256)       # descending: the mode's error grows like 1 / sqrt(L)

@@ -14,7 +14,10 @@ after a weight load (and again every `selfcheck_every`-th batch, for a batch mor
 far, and for the batch after a measurement within 10 % of the threshold) the mode is measured against the exact-fp32 kernels of the
 same engine on seeded reads and on rows of the batch (`clm_tf_selfcheck`); above the threshold the module falls back for good --
 a 16-bit mode to fp16x3, the next-fastest arithmetic inside the tolerance (`clm_tf_set_fallback` level 1), fp16x3 to exact fp32 --
-and says so.  On by default for fp16c.
+and says so.  On by default for fp16c.  fp16x3 -- the default mode, and the first fall-back level of the 16-bit modes -- packs
+weights x 2^10 as fp16 halfs, which saturate at |w| >= 64: if a CNN-stem or encoder weight is that large (or NaN), the engine runs
+exact fp32 wherever it would run fp16x3; the module reads that back at every weight load (`clm_tf_effective_precision`), records
+it in `precision_report` and logs a warning.
 """
 from __future__ import annotations
 
@@ -26,6 +29,11 @@ import torch
 from torch import nn
 
 from . import _native as N
+
+# |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_tf_finalize)
+X3_WEIGHT_LIMIT = 64.0
+_X3_PACKED = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight", "cnn.0.weight",
+              "cnn.3.weight", "cnn.6.weight")
 
 
 class _PosEnc(nn.Module):
@@ -61,6 +69,7 @@ class SequenceCNNTransformer(nn.Module):
         self.selfcheck = (precision == "fp16c") if selfcheck is None else bool(selfcheck)
         self.selfcheck_tol = float(selfcheck_tol)
         self.selfcheck_report: dict = {}
+        self.precision_report: dict = {}
         self.selfcheck_every = int(selfcheck_every)
         self._checked_min_len: int | None = None
         self._checked_max_len: int | None = None
@@ -104,7 +113,41 @@ class SequenceCNNTransformer(nn.Module):
             self._check(lib.clm_tf_set_fallback(self._h, 0))
             self._sig, self._checked_min_len, self._checked_max_len, self._batches_since_check, self.selfcheck_report = sig, None, None, 0, {}
             self._recheck_next = False
+            self._report_x3(lib)
         return lib
+
+    def _arith(self, lib) -> str:
+        """The arithmetic the engine runs a forward in right now (`clm_tf_effective_precision`)."""
+        code = lib.clm_tf_effective_precision(self._h)
+        if code < 0:
+            raise TransformerEngineError(f"clm_tf_effective_precision: error {code}")
+        return N.PREC_NAMES[code]
+
+    def _report_x3(self, lib) -> None:
+        """`precision_report` of the weights just loaded: what the engine runs where this mode uses fp16x3 (its own mode; the first
+        fall-back level of a 16-bit mode), read back from it, and a warning when the weights pushed it to exact fp32."""
+        if self.precision == "fp32":
+            self.precision_report = {"precision": "fp32", "fallback": False}
+            return
+        if self.precision == "fp16x3":
+            x3 = self._arith(lib)
+        else:
+            self._check(lib.clm_tf_set_fallback(self._h, 1))
+            x3 = self._arith(lib)
+            self._check(lib.clm_tf_set_fallback(self._h, 0))
+        ws = [t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)]
+        wmax = max(float(t.detach().abs().max()) for t in ws)
+        fallback = x3 != "fp16x3"
+        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
+        if not fallback:
+            return
+        import logging
+
+        self.precision_report["fallback_precision"] = x3
+        where = "" if self.precision == "fp16x3" else " (its first fall-back level)"
+        logging.getLogger("chimeralm_amd").warning(
+            f"chimeralm_amd: SequenceCNNTransformer precision={self.precision!r} packs weights as fp16 halfs x 2^10 for fp16x3{where}, "
+            f"which saturate at |w| >= {X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so it runs the exact-fp32 kernels there")
 
     # ------------------------------------------------------------------ the 16-bit mode on trial
     def _measure(self, lib, name: str, ids: torch.Tensor) -> float:
@@ -155,11 +198,11 @@ class SequenceCNNTransformer(nn.Module):
         if not worst <= self.selfcheck_tol:                    # (NaN fails too)
             self._check(lib.clm_tf_set_fallback(self._h, 1))
             rep["fallback"] = True
-            rep["fallback_precision"] = "fp32" if self.precision == "fp16x3" else "fp16x3"
+            rep["fallback_precision"] = self._arith(lib)
             import logging
             import warnings
 
-            what = ("exact fp32 (the reference's arithmetic)" if self.precision == "fp16x3" else
+            what = ("exact fp32 (the reference's arithmetic)" if rep["fallback_precision"] == "fp32" else
                     "fp16x3 (every operand as two halfs, three fp16 MFMAs per product: fp32-class logits, about half the rate)")
             msg = (f"chimeralm_amd: SequenceCNNTransformer precision={self.precision!r} differs from the exact-fp32 kernels by "
                    f"{worst:.2e} in the logits on the loaded weights (threshold {self.selfcheck_tol:.1e}); falling back to {what} "

@@ -152,7 +152,9 @@ int clm_check(clm_handle* h, void* stream);
  *                   threshold: chimeralm_amd/hyena.py uses level 1 at 5e-4, half the reference tolerance.)  No effect on a
  *                   CLM_PREC_F32 handle.  Other values: CLM_E_INVALID.
  *   clm_effective_precision  the CLM_PREC_* code reads of L tokens run in right now (CLM_PREC_F16X3 for the short reads of a
- *                   CLM_PREC_F16C handle and for a 16-bit handle at fall-back level 1). */
+ *                   CLM_PREC_F16C handle and for a 16-bit handle at fall-back level 1).  fp16x3 packs weights x 2^10 as fp16 halfs,
+ *                   which saturate at |w| >= 64: on a handle whose in_proj / out_proj / fc1 / fc2 / score weights reach that (or hold
+ *                   a NaN; measured by clm_finalize) every read that would run fp16x3 runs exact fp32, and this says CLM_PREC_F32. */
 int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, void* stream,
                   float* max_abs_diff, int* labels_differ);
 int clm_set_fallback(clm_handle* h, int level);
@@ -180,6 +182,10 @@ int clm_set_mlp_compensation(clm_handle* h, int on);
  *   qkv  device, [B, L, 768] 16-bit, the in_proj output q | k | v per token;  out  device, [B, L, 256] 16-bit, heads concatenated
  *   precision CLM_PREC_F16 or CLM_PREC_BF16 (element type of qkv / out; statistics and accumulation are fp32). */
 int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, void* stream);
+/* The same attention in the arithmetic of the exact path (csrc/tf_fp32.hip; the kernels clm_tf_forward runs there): qkv device fp32
+ * [B, L, 768], out device fp32 [B, L, 256]; precision CLM_PREC_F32 (fp32 products) or CLM_PREC_F16X3 (every operand as fp16 hi + lo,
+ * three fp16 MFMAs per product).  Asynchronous on `stream`; writes nothing beyond out[B * L * 256]. */
+int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream);
 
 /* The whole SequenceCNNTransformer forward (transformer.py:88-104; configuration of configs/model/transformer.yaml:3-12:
  * vocab 12, d_model 256, kernel 3, 8 heads, feed-forward 1024, `n_layers` encoder layers) behind the same `net` boundary as
@@ -203,6 +209,11 @@ int clm_tf_forward(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids
 int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, void* stream,
                      float* max_abs_diff_out, int* labels_differ_out);
 int clm_tf_set_fallback(clm_tf_handle* h, int level);
+/* The CLM_PREC_* code clm_tf_forward runs in right now (after clm_tf_finalize; CLM_E_STATE before): the handle's 16-bit mode, or on
+ * the fp32 path CLM_PREC_F16X3 / CLM_PREC_F32.  fp16x3 packs weights x 2^10 as fp16 halfs, which saturate at |w| >= 64: a handle
+ * whose CNN-stem or encoder weights reach that (or hold a NaN) runs exact fp32 wherever it would run fp16x3 -- its own mode, fall-back
+ * level 1 -- and says CLM_PREC_F32 here.  The Hyena engine does the same (clm_effective_precision). */
+int clm_tf_effective_precision(const clm_tf_handle* h);
 int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_t bytes);
 /* Profiling taps of the 16-bit path (bench.py --net transformer): accumulated HIP-event time on the launch stream and number of
  * spans per stage -- 0 conv stack + positional encoding / LayerNorm, 1 attention, 2 encoder layer kernel (out_proj + LayerNorm-1

@@ -615,6 +615,12 @@ def test_baseline_batch_size_independent_properties(sd, built_lib, prec, B, chun
     pick = sorted({0, max(B // 4 - 1, 0), B // 4, B - max(B // 5, 1), B - 1})
     solo = e.forward(t[pick].contiguous()).cpu()
     assert (solo - a[pick]).abs().max() < 0.5 * TOL[prec]                        # (c)
+    small = Engine("cuda:0", precision=prec, chunk_reads=4)                      # ... and EVERY row against 4-read chunks
+    small.load_state_dict(sd)
+    d_small = (small.forward(t).cpu() - a).abs().max().item()
+    small.close()
+    print(f"{prec} {B} x {L} (chunk {chunk}): every row against 4-read chunks {d_small:.2e}")
+    assert d_small < 0.5 * TOL[prec]
     n_ref = 3 if L <= 8193 else 2                                                # (the oracle takes ~10 s per 32k-token read)
     ref = ho.forward(torch.from_numpy(ids[pick[:n_ref]].astype(np.int64)), sd)   # (d)
     err = (a[pick[:n_ref]] - ref).abs().max()
@@ -626,6 +632,144 @@ def test_baseline_batch_size_independent_properties(sd, built_lib, prec, B, chun
         diff, _ = e.selfcheck(t[max(B - 8, 0):].contiguous())
         assert 0 < diff <= GATE
     e.close()
+
+
+_ORACLE_ROWS: dict = {}
+
+
+def _oracle_rows(ids: np.ndarray, rows: list[int], sd: dict) -> torch.Tensor:
+    """Oracle logits of ids[rows], one read at a time, kept per (weights, read) for the other cases of the module that hold that read."""
+    out = []
+    for r in rows:
+        key = (id(sd), ids[r].tobytes())
+        if key not in _ORACLE_ROWS:
+            _ORACLE_ROWS[key] = ho.forward(torch.from_numpy(ids[r: r + 1].astype(np.int64)), sd)[0]
+        out.append(_ORACLE_ROWS[key])
+    return torch.stack(out)
+
+
+def _bench_ids(B: int, L: int) -> tuple[np.ndarray, list[int]]:
+    """The reads of the bench-shape cases and the rows held to the oracle.  8,193 tokens: 256 reads whose last quarter (192-255) is
+    left-padded with [PAD] runs of varied length, as the collator pads shorter reads; the 32-read case is rows 0-23 and 248-255 of
+    it.  32,769 tokens: 32 reads; the 4-read case is rows 0-2 and 31.  The oracle rows (first, a padded row at index >= 128 or in the
+    last quarter, last) are the same reads in every case of one length."""
+    if L == 8193:
+        ids = _ids(256, L, seed=43)
+        rng = np.random.default_rng(8193)
+        for r in range(192, 256):
+            ids[r, : int(rng.integers(1, L - 64))] = 4
+        if B == 256:
+            return ids, [0, 250, 255]
+        return ids[list(range(24)) + list(range(248, 256))], [0, 26, 31]
+    ids = _ids(32, L, seed=47)
+    return (ids, [0, 31]) if B == 32 else (ids[[0, 1, 2, 31]], [0, 3])
+
+
+@pytest.mark.parametrize("prec,B,chunk,L", [("fp32", 256, 256, 8193), ("fp16x3", 256, 256, 8193), ("fp16x3", 32, 256, 8193),
+                                            ("fp32", 32, 256, 32769), ("fp16x3", 32, 256, 32769), ("fp16x3", 4, 256, 32769)])
+def test_exact_and_fp16x3_at_bench_shapes(sd, built_lib, prec, B, chunk, L):
+    """The two arithmetics the product's safety rests on -- exact fp32 (the referee of every self-check) and fp16x3 (fp16c's short
+    reads and first fall-back level) -- at the bench's shapes in one chunk: 256 x 8,193 is 32,768 persistent-convolution units and
+    6.5 GB of fp32 z rows (byte offsets past 4 GB), 32 x 32,769 the segmented convolution.  (a) finite, bit-identical on a second
+    run; (b) EVERY row equals a handle of 4-read (2 at 32,769) chunks up to the read pairing of the packed FFT; (c) oracle rows within
+    1e-4, labels where the oracle decides them; (d) fp16x3: it runs fp16x3, an exact-fp32 handle agrees on every row, and its
+    self-check on 8 rows spread over the batch passes."""
+    from chimeralm_amd.engine import Engine
+
+    ids, rows = _bench_ids(B, L)
+    t = torch.from_numpy(ids).cuda()
+    e = Engine("cuda:0", precision=prec, chunk_reads=chunk)
+    e.load_state_dict(sd)
+    a = e.forward(t).cpu()
+    assert torch.isfinite(a).all() and torch.equal(a, e.forward(t).cpu())       # (a)
+    small = Engine("cuda:0", precision=prec, chunk_reads=4 if L <= 8193 else 2)
+    small.load_state_dict(sd)
+    d_small = (small.forward(t).cpu() - a).abs().max().item()                   # (b)
+    small.close()
+    ref = _oracle_rows(ids, rows, sd)                                            # (c)
+    err = (a[rows] - ref).abs().max().item()
+    msg = f"{prec} {B} x {L}: every row vs small chunks {d_small:.2e}, rows {rows} vs oracle {err:.2e}"
+    if prec == "fp16x3":                                                         # (d)
+        assert e.effective_precision(L) == "fp16x3"
+        e32 = Engine("cuda:0", precision="fp32", chunk_reads=chunk)
+        e32.load_state_dict(sd)
+        d32 = (e32.forward(t).cpu() - a).abs().max().item()
+        e32.close()
+        sel = sorted({round(i * (B - 1) / 7) for i in range(8)})
+        diff, flips = e.selfcheck(t[sel].contiguous())
+        msg += f", every row vs exact fp32 {d32:.2e}, selfcheck on rows {sel} {diff:.2e}"
+        assert d32 <= 1e-4 and 0 < diff <= 1e-4 and flips == 0, msg
+    print(msg)
+    assert d_small <= 2e-5, msg
+    assert err <= 1e-4, msg
+    decided = (ref[:, 0] - ref[:, 1]).abs() > MARGIN["fp16x3"]
+    assert torch.equal(a[rows].argmax(1)[decided], ref.argmax(1)[decided])
+    e.close()
+
+
+def _big_weight_sd(value: float) -> dict:
+    sdw = ho.make_state_dict(0, head_scale=3.0)
+    sdw["net.backbone.backbone.layers.1.mixer.in_proj.weight"][5, 17] = value
+    return sdw
+
+
+@pytest.mark.parametrize("value", [300.0, 100.0, 63.9])
+def test_fp16x3_weight_range_of_the_engine(built_lib, value):
+    """fp16x3 packs weights x 2^10 as fp16 hi + lo: the hi half saturates from |w| ~ 63.97, the lo half absorbs the rest at reduced
+    precision up to ~128, above that the weight is clamped.  A handle whose x3-packed weights reach 64 runs exact fp32 wherever it
+    would run fp16x3 -- an fp16x3 handle, fp16c's short reads and its first fall-back level -- and says so; just below, it stays."""
+    from chimeralm_amd.engine import Engine
+
+    sdw = _big_weight_sd(value)
+    ids = _ids(3, 1000, seed=61)
+    ref = ho.forward(torch.from_numpy(ids.astype(np.int64)), sdw)
+    t = torch.from_numpy(ids).cuda()
+    want = "fp32" if value >= 64 else "fp16x3"
+    ex = Engine("cuda:0", precision="fp16x3", chunk_reads=4)
+    ex.load_state_dict(sdw)
+    err = (ex.forward(t).cpu() - ref).abs().max().item()
+    msg = [f"fp16x3 handle ({ex.effective_precision(1000)}) {err:.2e}"]
+    assert ex.effective_precision(1000) == want, msg
+    if value >= 64:
+        fc = Engine("cuda:0", precision="fp16c", chunk_reads=4)
+        fc.load_state_dict(sdw)
+        for level in (0, 1):
+            fc.set_fallback(level)
+            err_c = (fc.forward(t).cpu() - ref).abs().max().item()
+            msg.append(f"fp16c level {level} ({fc.effective_precision(1000)}) {err_c:.2e}")
+            assert fc.effective_precision(1000) == "fp32", msg
+            assert err_c <= 1e-4, msg
+        fc.close()
+    print(f"|w| = {value}: |logits - oracle| " + ", ".join(msg))
+    assert err <= 1e-4, msg
+    ex.close()
+
+
+@pytest.mark.parametrize("prec", ["fp16x3", "fp16c"])
+def test_fp16x3_weight_range_of_the_module(built_lib, caplog, prec):
+    """`HyenaDna` reads the engine's arithmetic back at the weight load: a warning naming exact fp32 and a `precision_report` of what
+    runs where the mode would use fp16x3; weights inside the range report no fall-back."""
+    from chimeralm_amd import lm
+
+    sdw = _big_weight_sd(300.0)
+    ids = _ids(3, 1000, seed=61)
+    ref = ho.forward(torch.from_numpy(ids.astype(np.int64)), sdw)
+    model = lm.ChimeraLM.new(precision=prec, chunk_reads=4)
+    model.load_state_dict(sdw, strict=True)
+    with caplog.at_level("WARNING", logger="chimeralm_amd"):
+        got, _ = model.predict_step({"input_ids": torch.from_numpy(ids).cuda(), "labels": torch.full((3,), -1)}, 0)
+    rep = model.net.precision_report
+    assert rep["precision"] == prec and rep["fallback"] is True and rep["fallback_precision"] == "fp32" and rep["max_abs_weight"] == 300.0
+    assert any("exact-fp32" in r.getMessage() and prec in r.getMessage() for r in caplog.records)
+    if model.net.selfcheck_report.get("fallback"):
+        assert model.net.selfcheck_report["fallback_precision"] == "fp32"
+    err = (got.cpu() - ref).abs().max().item()
+    print(f"HyenaDna {prec} with |w| = 300: |logits - oracle| {err:.2e}, report {rep}")
+    assert err <= (1e-4 if prec == "fp16x3" else GATE)
+    ok = lm.ChimeraLM.new(precision=prec, chunk_reads=4)
+    ok.load_state_dict(ho.make_state_dict(0, head_scale=3.0), strict=True)
+    ok.predict_step({"input_ids": torch.from_numpy(ids).cuda(), "labels": torch.full((3,), -1)}, 0)
+    assert ok.net.precision_report["fallback"] is False and ok.net.precision_report["max_abs_weight"] < 64
 
 
 @pytest.mark.parametrize("wseed,B,L,pads", [(0, 3, 257, 0), (0, 2, 64, 0), (0, 1, 1, 0), (4, 5, 130, 3), (4, 4, 1000, 0), (7, 3, 2049, 5),

@@ -241,3 +241,101 @@ def test_random_shapes_fp16c_against_the_exact_kernels(built_lib):
         assert diff.value < (GATE if L >= 512 else 4e-3), f"{B} x {L}: |fp16c - exact fp32| = {diff.value:.2e}"
     print(f"16 random shapes: worst |fp16c - exact fp32| = {worst:.2e}")
     net.close()
+
+
+_LONG_ORACLE: dict = {}
+
+
+def _long_case(seed, B, L):
+    """Weights, ids (reads 1 and 2 of the padded case left-padded by different runs) and the oracle's logits, encoder output and
+    pooled vector, one read at a time (the score matrices of one read take ~0.5 GB per layer); shared by fp32 and fp16x3."""
+    if (seed, B, L) not in _LONG_ORACLE:
+        sd = to.make_state_dict(seed, to.PRODUCTION, scale=3.0)
+        ids = to.synthetic_ids(200 + seed, B, L)
+        if L % 8:                                              # the ragged case: [PAD] runs as the collator leaves them
+            ids[1, :900] = 4
+            ids[2, :5000] = 4
+        outs = []
+        for r in range(B):
+            trace = {}
+            logit = to.forward(torch.from_numpy(ids[r: r + 1]), sd, trace=trace)
+            outs.append((logit.numpy(), trace["layer11"].numpy(), trace["pooled"].numpy()))
+        _LONG_ORACLE[(seed, B, L)] = (sd, ids, *(np.concatenate(x) for x in zip(*outs)))
+    return _LONG_ORACLE[(seed, B, L)]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16x3"])
+@pytest.mark.parametrize("seed,B,L", [(7, 2, 32768), (8, 3, 32700), (9, 3, 8003)])
+def test_long_context_matches_oracle(built_lib, prec, seed, B, L):
+    """The checks of `test_forward_matches_oracle` at the benched context: 4,096 attention positions (32 query tiles, whole key
+    tiles), 4,087 (32 query tiles, ragged last key tile, padded reads) and 1,000 (8 query tiles, ragged)."""
+    sd, ids, ref, ref_h, ref_p = _long_case(seed, B, L)
+    net = _model(sd, prec)
+    t = torch.from_numpy(ids).cuda()
+    got = net(t).cpu().numpy()
+    assert np.isfinite(got).all()
+    err = np.abs(got - ref).max()
+    err_h = np.abs(net.debug_fetch("hidden", (B, L // 8, 256)) - ref_h).max()
+    err_p = np.abs(net.debug_fetch("pooled", (B, 256)) - ref_p).max()
+    msg = f"{prec} B={B} L={L} ({L // 8} positions): |logits - oracle| = {err:.2e}, |hidden - oracle| = {err_h:.2e}, |pooled| {err_p:.2e}"
+    if prec == "fp16x3":
+        from chimeralm_amd import _native as N
+        d = net._measure(N.load(), "test", t)
+        msg += f", clm_tf_selfcheck {d:.2e}"
+        assert 0 < d <= TOL[prec], msg
+    print(msg)
+    assert err < TOL[prec] and err_h < TOL_HIDDEN[prec] and err_p < TOL_HIDDEN[prec], msg
+    decided = np.abs(ref[:, 0] - ref[:, 1]) > 2 * TOL[prec]
+    assert (got.argmax(1)[decided] == ref.argmax(1)[decided]).all()
+    net.close()
+
+
+def test_fp16x3_bench_line_rows_are_independent(built_lib):
+    """The benched transformer line, 32 x 32,768 in fp16x3 (4,096 positions through attention_x3_kernel): bit-identical on a second
+    run, rows run alone equal their batch rows bit for bit (no operation mixes reads), and exact fp32 agrees on all 32 rows."""
+    sd = to.make_state_dict(0, to.PRODUCTION, scale=3.0)
+    t = torch.from_numpy(to.synthetic_ids(110, 32, 32768)).cuda()
+    net = _model(sd, "fp16x3")
+    a = net(t).cpu()
+    assert torch.isfinite(a).all() and torch.equal(a, net(t).cpu())
+    for r in (0, 15, 31):
+        assert torch.equal(net(t[r: r + 1]).cpu(), a[r: r + 1]), f"row {r} alone differs from its batch row"
+    exact = _model(sd, "fp32")
+    d = (exact(t).cpu() - a).abs().max().item()
+    print(f"transformer fp16x3 32 x 32768: every row vs exact fp32 {d:.2e}")
+    assert d <= 1e-4
+    exact.close()
+    net.close()
+
+
+@pytest.mark.parametrize("key", ["transformer_encoder.layers.3.linear1.weight", "cnn.3.weight"])
+def test_fp16x3_weight_range_of_the_transformer(built_lib, caplog, key):
+    """fp16x3 packs weights x 2^10 as fp16 halfs, which saturate at |w| >= 64: with one encoder or CNN-stem weight at 300 the default
+    module runs exact fp32, within fp16x3's bound of the oracle, warns and records it; an fp16c model that falls back names exact
+    fp32 as what it falls back to."""
+    from chimeralm_amd.transformer import SequenceCNNTransformer
+
+    sd = to.make_state_dict(0, to.PRODUCTION, scale=3.0)
+    sd[key].view(-1)[1234] = 300.0
+    ids = to.synthetic_ids(100, 2, 1000)
+    ref = to.forward(torch.from_numpy(ids), sd).numpy()
+    t = torch.from_numpy(ids).cuda()
+    net = SequenceCNNTransformer(vocab_size=12, max_len=32768, num_encoder_layers=12)
+    net.load_state_dict(sd, strict=True)
+    with caplog.at_level("WARNING", logger="chimeralm_amd"):
+        got = net(t).cpu().numpy()
+    rep = net.precision_report
+    assert rep["precision"] == "fp16x3" and rep["fallback"] is True and rep["fallback_precision"] == "fp32" and rep["max_abs_weight"] == 300.0
+    assert any("exact-fp32" in r.getMessage() for r in caplog.records)
+    err = np.abs(got - ref).max()
+    print(f"transformer fp16x3 with {key} = 300: |logits - oracle| {err:.2e}")
+    assert err <= TOL["fp16x3"]
+    net.close()
+    fc = SequenceCNNTransformer(vocab_size=12, max_len=32768, num_encoder_layers=12, precision="fp16c", selfcheck_tol=1e-12)
+    fc.load_state_dict(sd, strict=True)
+    with pytest.warns(RuntimeWarning, match="falling back to exact fp32"):
+        got_c = fc(t).cpu().numpy()
+    assert fc.precision_report["fallback_precision"] == "fp32"
+    assert fc.selfcheck_report["fallback"] is True and fc.selfcheck_report["fallback_precision"] == "fp32"
+    assert np.abs(got_c - ref).max() <= TOL["fp16x3"]
+    fc.close()
