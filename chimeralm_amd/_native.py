@@ -46,6 +46,12 @@ class ClmFeedBatch(C.Structure):              # include/chimeralm_feed.h: struct
                 ("row_stride", C.c_int64), ("ids", C.c_void_p), ("names", C.c_void_p), ("first_index", C.c_int64)]
 
 
+class ClmEvalResult(C.Structure):             # include/chimeralm_hip.h: struct clm_eval_result
+    _fields_ = [(n, C.c_int64) for n in ("tp", "fp", "tn", "fn", "n_valid", "n_ignored", "n_batches", "n_empty_batches",
+                                         "n_invalid_labels", "n_nonfinite")] + [("sum_batch_mean_loss", C.c_double),
+                                                                                ("sum_loss", C.c_double)]
+
+
 # every symbol include/chimeralm_hip.h and include/chimeralm_feed.h declare: name -> (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -98,6 +104,13 @@ SYMBOLS = {
     "clm_mamba_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_mamba_last_error": (C.c_char_p, [_H]),
     "clm_mamba_destroy": (C.c_int, [_H]),
+    "clm_eval_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(_H)]),
+    "clm_eval_update": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "clm_eval_read": (C.c_int, [_H, C.POINTER(ClmEvalResult), C.c_void_p]),
+    "clm_eval_merge": (C.c_int, [_H, C.POINTER(ClmEvalResult)]),
+    "clm_eval_reset": (C.c_int, [_H, C.c_void_p]),
+    "clm_eval_last_error": (C.c_char_p, [_H]),
+    "clm_eval_destroy": (C.c_int, [_H]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

@@ -97,7 +97,8 @@ class BamDataModule:
 
     def setup(self, stage: str | None = None, world_size: int = 1, rank: int = 0) -> None:
         if stage != "predict":
-            raise NotImplementedError("the MI355X engine covers the predict stage only")
+            raise NotImplementedError("the BAM data module covers the predict stage only; labelled reads for the test stage "
+                                      "come from parquet (data=fq, chimeralm_amd.fq.DataModule)")
         if not self.predict_data_path:
             raise ValueError("Predict data path is required for prediction stage.")
         if self.batch_size % world_size != 0:

@@ -1,9 +1,10 @@
-"""`ClassificationLit` for the predict path, mirroring /root/reference/chimeralm/models/basic_module.py.
+"""`ClassificationLit` for the predict and test paths, mirroring /root/reference/chimeralm/models/basic_module.py.
 
-Same constructor (`net, optimizer, scheduler, criterion, *, compile`), `forward(input_ids, input_quals)` (:67-77) and
-`predict_step(batch, batch_idx) -> (logits, labels)` (:177-187).  When `lightning` is importable the class is a
-`LightningModule` (so `Trainer.predict` drives it as in the reference); otherwise a plain `nn.Module` -- the training
-hooks and torchmetrics of the reference (:43-65, :87-175) are out of scope for an inference engine.
+Same constructor (`net, optimizer, scheduler, criterion, *, compile`), `forward(input_ids, input_quals)` (:67-77),
+`predict_step(batch, batch_idx) -> (logits, labels)` (:177-187), `model_step(batch) -> (loss, preds, targets)` (:87-104) and
+`test_step(batch, batch_idx)` (:153-170).  The reference's `test_step` feeds torchmetrics objects on the host; here it queues the
+batch's sums on the device (eval_metrics.EvalMetrics, attached by `Trainer.test`).  When `lightning` is importable the class is a
+`LightningModule`; otherwise a plain `nn.Module` -- the training hooks of the reference are out of scope for an inference engine.
 """
 from __future__ import annotations
 
@@ -25,7 +26,9 @@ class ClassificationLit(_Base):
         if not hasattr(net, "number_of_classes"):
             raise AttributeError("net must expose `number_of_classes` (basic_module.py:43-58)")
         self.net = net
-        self.criterion = criterion
+        # configs/model/*.yaml carry no `criterion` node: the loss of the reference's model files is the default
+        self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()
+        self.test_metrics = None                                # eval_metrics.EvalMetrics while Trainer.test runs
         self.optimizer_factory, self.scheduler_factory, self.compile_flag = optimizer, scheduler, compile
 
     def forward(self, input_ids: torch.Tensor, input_quals: torch.Tensor | None = None) -> torch.Tensor:
@@ -34,6 +37,29 @@ class ClassificationLit(_Base):
     def predict_step(self, batch: dict[str, torch.Tensor], batch_idx: int = 0):
         logits = self.forward(batch["input_ids"], batch.get("input_quals", None))
         return logits, batch["labels"]
+
+    def model_step(self, batch: dict[str, torch.Tensor]):
+        """(loss, preds, targets) of one batch, as the reference computes them: torch ops on the logits' device, for callers that
+        want one batch's numbers.  The test stage does not come through here (`test_step`)."""
+        logits = self.forward(batch["input_ids"], batch.get("input_quals", None))
+        targets = batch["labels"].to(logits.device)
+        loss = self.criterion(logits.reshape(-1, logits.size(-1)), targets.long().view(-1))
+        return loss, torch.argmax(logits, dim=-1), targets
+
+    def test_step(self, batch: dict[str, torch.Tensor], batch_idx: int = 0) -> None:
+        """Forward, then the batch's loss and confusion counts added to `self.test_metrics` by one kernel on the same stream."""
+        if self.test_metrics is None:
+            raise RuntimeError("test_step needs `test_metrics` (an eval_metrics.EvalMetrics); Trainer.test attaches one")
+        logits = self.forward(batch["input_ids"], batch.get("input_quals", None))
+        self.test_metrics.update(logits, batch["labels"].to(logits.device, non_blocking=True))
+
+    def test_criterion(self) -> int:
+        """`ignore_index` of the criterion, if it is the loss the metrics kernel implements; raises otherwise."""
+        c = self.criterion
+        if type(c) is not nn.CrossEntropyLoss or c.weight is not None or c.label_smoothing != 0.0 or c.reduction != "mean":
+            raise NotImplementedError(f"the test stage implements torch.nn.CrossEntropyLoss (no class weights, no label smoothing, "
+                                      f"mean reduction), not {c!r}")
+        return int(c.ignore_index)
 
     # ---- checkpoint loading (reference: PyTorchModelHubMixin.from_pretrained / Lightning ckpt_path) ----
     def load_reference_checkpoint(self, path) -> "ClassificationLit":

@@ -10,6 +10,9 @@ Results leave the device one batch behind: the logits of batch i are copied to p
 forward, the forward of batch i+1 is enqueued, and only then does the host wait for copy i and write its file -- the GPU never
 idles while Python formats read names (the reference syncs on every batch, callbacks.py:107).
 
+`run_test` is the loop of `lightning.Trainer.test` over the same double buffer: `model.test_step(batch)` queues the batch's metric
+update (csrc/eval_metrics.hip) behind its forward, so neither logits nor labels come back and the host waits for nothing per batch.
+
 `run_predict_native` is the same loop fed by the native BAM feeder (csrc/bam_feeder.cpp): a C++ thread decodes, selects,
 tokenises and collates into a ring of page-locked slots; each batch crosses PCIe as uint8 on the engine's copy stream
 (`clm_stage_ids`) while the previous batch is computing, and the slot goes back to the ring once its copy has landed.
@@ -23,15 +26,36 @@ import torch
 from .distributed import LogitsGather
 
 
-def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream) -> dict:
+def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, device_keys: tuple = ()) -> dict:
     out = {}
     with torch.cuda.stream(stream):
         for k, v in batch.items():
             if k == "input_ids":
                 # ids fit a byte (vocabulary 12): 8x less PCIe traffic than the reference's int64 batch
                 v = v.to(torch.uint8).pin_memory().to(device, non_blocking=True)
+            elif k in device_keys:
+                v = v.pin_memory().to(device, non_blocking=True)
             out[k] = v
     return out
+
+
+def _staged_batches(loader, device: torch.device, device_keys: tuple = ()):
+    """The double buffer of the predict and test loops: yields batch i on the device once the compute stream waits for its copy,
+    with batch i+1 already collated on the host and its H2D copy queued on a side stream -- under the forward the caller runs next."""
+    copy_stream = torch.cuda.Stream(device)
+    compute = torch.cuda.current_stream(device)
+    it = iter(loader)
+    nxt = next(it, None)
+    staged = _to_device(nxt, device, copy_stream, device_keys) if nxt is not None else None
+    while staged is not None:
+        compute.wait_stream(copy_stream)
+        cur = staged
+        nxt = next(it, None)                              # host collation of batch i+1 ...
+        staged = _to_device(nxt, device, copy_stream, device_keys) if nxt is not None else None   # ... and its H2D overlap
+        for k, v in cur.items():
+            if k == "input_ids" or k in device_keys:
+                v.record_stream(compute)                  # allocated on the copy stream, read by the caller's kernels
+        yield cur
 
 
 class _Deferred:
@@ -105,22 +129,13 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
     group (RCCL over xGMI when the backend is "nccl"), off the compute stream, and handed to `on_batch(batch_idx, tensor)` one
     batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows)."""
     model.eval()
-    copy_stream = torch.cuda.Stream(device)
-    compute = torch.cuda.current_stream(device)
     trainer = SimpleNamespace(global_rank=rank)
     gatherer = LogitsGather(device) if gather else None
     rows = getattr(datamodule, "batch_size_per_device", 0)
-    it = iter(datamodule.predict_dataloader())
-    nxt = next(it, None)
-    staged = _to_device(nxt, device, copy_stream) if nxt is not None else None
     n_reads, batch_idx = 0, 0
     pending: _Deferred | None = None
     with torch.inference_mode():
-        while staged is not None:
-            compute.wait_stream(copy_stream)
-            cur = staged
-            nxt = next(it, None)                              # host collation of batch i+1 ...
-            staged = _to_device(nxt, device, copy_stream) if nxt is not None else None   # ... and its H2D overlap
+        for cur in _staged_batches(datamodule.predict_dataloader(), device):
             logits, labels = model.predict_step(cur, batch_idx)
             now = _Deferred(logits, labels, cur, batch_idx, gatherer, rows)
             if pending is not None:
@@ -133,6 +148,21 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
             _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch)
         elif pending is not None:
             pending.flush(writer, trainer, model, on_batch)
+    return n_reads
+
+
+def run_test(model, datamodule, device: torch.device) -> int:
+    """The test loop: every batch's forward and, behind it on the same stream, its metric update (`model.test_step`); no logits
+    leave the device and nothing waits per batch.  Returns the number of reads this rank ran; the sums stay in
+    `model.test_metrics` for the caller's one read."""
+    model.eval()
+    n_reads, batch_idx = 0, 0
+    with torch.inference_mode():
+        for cur in _staged_batches(datamodule.test_dataloader(), device, device_keys=("labels",)):
+            model.test_step(cur, batch_idx)
+            n_reads += cur["labels"].shape[0]
+            batch_idx += 1
+        _check_engine(model, device, batch_idx)
     return n_reads
 
 

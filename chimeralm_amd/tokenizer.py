@@ -1,8 +1,9 @@
-"""Token stream of the predict path, mirroring /root/reference/chimeralm/data/tokenizer.py.
+"""Token stream of the predict and test paths, mirroring /root/reference/chimeralm/data/tokenizer.py.
 
 * vocabulary                                           tokenizer.py:230-239
 * `load_tokenizer_from_hyena_model(model_name)`        tokenizer.py:36-55  (HF remote tokenizer in the reference:
   characters -> ids, ONE trailing [SEP], no [CLS], left padding, model_max_length 32770 -- SURVEY.md section 8(a))
+* `parse_target`, `tokenize_and_align_labels_and_quals`  tokenizer.py:25-33,58-82 (label = the integer after `|` in the id)
 * `tokenize_and_align_labels_and_quals_ids`            tokenizer.py:85-114 (id row = [len] + code points, 256 wide)
 * `DataCollator.torch_call`                            tokenizer.py:136-187 (pad to longest with [PAD]=4)
 
@@ -74,6 +75,25 @@ def load_tokenizer_from_hyena_model(model_name: str) -> CharTokenizer:
 def pack_read_name(name: str, max_id_length: int = MAX_ID_LENGTH) -> list[int]:
     row = [len(name)] + [ord(c) for c in name]
     return row[:max_id_length] if len(row) > max_id_length else row + [0] * (max_id_length - len(row))
+
+
+def parse_target(name: str) -> tuple[str, int]:
+    """`"read|1"` -> `("read", 1)`; an id without `|` has the target -1.  More than one `|` is a ValueError, as in the reference."""
+    content = name.split("|")
+    if len(content) < 2:
+        return content[0], -1
+    rid, target = content
+    return rid, int(target)
+
+
+def tokenize_and_align_labels_and_quals(data: dict, tokenizer: CharTokenizer, max_length: int, *, include_qual: bool = False,
+                                        seq_feature: str = SEQ_FEATURE, id_feature: str = ID_FEATURE) -> dict:
+    """Features of one labelled read (the test stage): token ids and the label parsed from the id."""
+    if include_qual:
+        raise NotImplementedError("include_qual: no net of this engine reads base qualities")
+    out = tokenizer(data[seq_feature], truncation=True, max_length=max_length, padding=True)
+    out[MODEL_LABEL_INPUT] = parse_target(data[id_feature])[1]
+    return out
 
 
 def tokenize_and_align_labels_and_quals_ids(data: dict, tokenizer: CharTokenizer, max_length: int, *,

@@ -1,9 +1,12 @@
 """`python eval.py ckpt_path=<ckpt|safetensors> +data.predict_data_path=<reads.bam> [data.batch_size=12] [hydra.run.dir=<out>]`
+`python eval.py ckpt_path=<ckpt|safetensors> data=fq model=mambasp data.test_data_path=<reads.parquet>`
 
-The Hydra entry route of the reference's predict path (/root/reference/eval.py:33-101, configs/eval.yaml): compose
+The Hydra entry route of the reference (/root/reference/eval.py:33-101, configs/eval.yaml): compose
 configs/eval.yaml, instantiate datamodule / model / callbacks / trainer from their `_target_`s and run
-`trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)`.
-Prediction files land in `${paths.output_dir}/predicts/{rank}_{batch}.txt` (configs/callbacks/write.yaml).
+`trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)` when the data node has
+a `predict_data_path`, `trainer.test(model=model, datamodule=datamodule, ckpt_path=cfg.ckpt_path)` otherwise (:74-80).
+Prediction files land in `${paths.output_dir}/predicts/{rank}_{batch}.txt` (configs/callbacks/write.yaml); the test stage
+leaves `test/loss`, `test/f1`, `test/precision`, `test/recall` in `trainer.callback_metrics` and logs them.
 The built-in composer (chimeralm_amd/config.py) reads the files -- whether or not hydra-core is installed: one behaviour everywhere.
 Multi-GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 eval.py trainer=ddp ...`.
 """
@@ -33,8 +36,9 @@ def evaluate(cfg):
     trainer = instantiate(cfg.trainer, callbacks=callbacks, logger=[])
     object_dict = {"cfg": cfg, "datamodule": datamodule, "model": model, "logger": [], "trainer": trainer}
     if getattr(datamodule, "predict_data_path", None) is None:
-        raise NotImplementedError("trainer.test: this build covers the predict stage only; pass +data.predict_data_path=<bam>")
-    trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)
+        trainer.test(model=model, datamodule=datamodule, ckpt_path=cfg.ckpt_path)
+    else:
+        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)
     return trainer.callback_metrics, object_dict
 
 

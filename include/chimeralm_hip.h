@@ -289,6 +289,41 @@ int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out,
 const char* clm_mamba_last_error(const clm_mamba_handle* h); /* h may be NULL: error of the last failed clm_mamba_create */
 int clm_mamba_destroy(clm_mamba_handle* h);
 
+/* ---- test-stage metrics (ABI 6, additive) -----------------------------------------------------------------------------
+ * What the reference's `test_step` feeds to torchmetrics on the host after a sync per batch (basic_module.py:153-175), summed on the
+ * device instead: the logits of a batch never leave it and the host waits once, in clm_eval_read.
+ *   create      n_classes must be 2 (binary F1 / precision / recall); `ignore_index` is the criterion's (torch's default -100).
+ *               device -1 makes a host-only handle that needs no GPU: it totals results (merge, read, reset); update is CLM_E_STATE.
+ *   update      logits fp32 [B, 2] contiguous and labels int64 [B], both device pointers; B >= 1.  One launch of one workgroup on
+ *               `stream`, no atomics, a fixed reduction order: the sums are bitwise the same from run to run.  It does not
+ *               synchronise.  Updates of one handle are ordered by the stream: use one stream per handle (the one the logits were
+ *               produced on needs no event).
+ *               Per row: label == ignore_index is skipped; otherwise a label outside {0, 1} counts in n_invalid_labels and a row
+ *               with a NaN / inf logit in n_nonfinite, and neither enters any sum (the reference raises inside the loss / computes
+ *               NaN).  A valid row adds loss = logsumexp(l0, l1) - l[label], in double from the fp32 logits with the maximum
+ *               subtracted first, and one of tp / fp / tn / fn with prediction = 1 only if l1 > l0 (a tie is 0, as torch.argmax).
+ *               A batch with at least one valid row adds its mean loss over its valid rows to sum_batch_mean_loss and 1 to
+ *               n_batches (the reference's MeanMetric weights batches alike), its ignored rows to n_ignored.  A batch with no valid
+ *               row adds 1 to n_empty_batches; of its rows only invalid labels and non-finite logits are still counted.
+ *   read        copies the sums to the host behind everything queued on `stream` and waits for that copy: the one sync of the
+ *               stage.  Sums merged in from other ranks are included.
+ *   merge       adds another handle's result (another rank's) to this handle's, on the host.  Ranks that want the same bits each
+ *               merge every rank's result, their own included, in rank order into a host-only handle.
+ *   reset       zeroes device and merged sums, behind what is queued on `stream`. */
+typedef struct clm_eval_handle clm_eval_handle;
+typedef struct clm_eval_result {
+    int64_t tp, fp, tn, fn;
+    int64_t n_valid, n_ignored, n_batches, n_empty_batches, n_invalid_labels, n_nonfinite;
+    double sum_batch_mean_loss, sum_loss;
+} clm_eval_result;
+int clm_eval_create(int device, int n_classes, int64_t ignore_index, clm_eval_handle** out);
+int clm_eval_update(clm_eval_handle* h, const float* logits, const int64_t* labels, int B, void* stream);
+int clm_eval_read(clm_eval_handle* h, clm_eval_result* out, void* stream);
+int clm_eval_merge(clm_eval_handle* h, const clm_eval_result* other);
+int clm_eval_reset(clm_eval_handle* h, void* stream);
+const char* clm_eval_last_error(const clm_eval_handle* h); /* h may be NULL: error of the last failed clm_eval_create */
+int clm_eval_destroy(clm_eval_handle* h);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:
