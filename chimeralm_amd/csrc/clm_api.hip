@@ -37,8 +37,6 @@ namespace {
 
 struct Tensor {
     DevBuf d;
-    std::vector<int64_t> shape;
-    size_t numel = 0;
     bool loaded = false;
 };
 
@@ -65,6 +63,32 @@ struct ProfRec {
     hipEvent_t e0, e1;
 };
 
+// Weights as the kernels take them: device pointers resolved ONCE, by clm_finalize (a key that is not there fails there, with
+// CLM_E_MISSING, instead of reaching a kernel as a null pointer).  The four products of a block are in_proj, out_proj, fc1, fc2,
+// [MAT_N][MAT_K] each: the order of BlockF32::w and of a Packing's slots
+constexpr int MAT_N[4] = {D3, D, DI, D}, MAT_K[4] = {D, D, D, DI};
+struct BlockF32 {                 // one block's tensors as loaded, fp32
+    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    const float* w[4];            // [out][in]: what the packers, the id table and the lone-token kernels read
+    const float *b_in, *b_out, *b_fc1, *b_fc2;
+    const float *short_w, *short_b;             // [768][3], [768]
+    const float* filt_bias;                     // [256]  (D skip term)
+    const float *pos_z, *pos_t, *f_w0, *f_b0, *f_freq, *f_w2, *f_b2, *f_w4, *f_b4, *f_w6, *deltas;   // the implicit filter (launch_filter)
+};
+struct NetF32 {                   // ... and what belongs to no block: embedding table, ln_f, the score layer, the classifier's matrices
+    const float *emb, *lnf_g, *lnf_b, *att_w1, *att_b1, *att_w2, *att_b2, *cls[5];
+};
+// One packing of the matrices the MFMA kernels read: the four of every block and the score layer (attention.0.weight)
+struct Packing {
+    DevBuf w[NLAYER][4], score;
+    DevBuf& slot(int i, int j) { return i < NLAYER ? w[i][j] : score; }   // i == NLAYER: the score layer
+};
+struct BlockW {                   // block i as one chunk's kernels read it (block_weights)
+    const BlockF32* f;
+    const void *w_in, *w_out, *w_fc1, *w_fc2;   // packed MFMA-fragment order, compute dtype: the GEMM kernels and the 16-bit tail
+    const void *t_in, *t_out, *t_fc1, *t_fc2;   // exact fp32 / fp16x3: the fused tail's packing (tail32.hip)
+};
+
 }  // namespace
 
 struct clm_handle {
@@ -73,29 +97,22 @@ struct clm_handle {
     std::string err;
     std::map<std::string, Tensor> w;
     bool finalized = false;
-    // packed / derived weights
-    DevBuf packed[NLAYER][4];
-    DevBuf packed_score;
-    // 16-bit handles: exact-fp32 packing of the same weights (fp16c's reads shorter than f16c_min_len, clm_selfcheck, clm_set_fallback)
-    DevBuf packed32[NLAYER][4];
-    DevBuf packed32t[NLAYER][4];       // exact fp32, the fused tail's packing (tail32.hip): in_proj, out_proj, fc1, fc2
+    // the weights resolved by clm_finalize (pointers into `w`) and their packings, one per kind (a chunk's choice: block_weights)
+    BlockF32 blk[NLAYER] = {};
+    NetF32 net = {};
+    Packing pk_mode;              // cfg.precision (fp16c: fc1 / fc2 plain fp16 -- tail16_kernel, MLP_PREC)
+    // 16-bit handles: exact-fp32 packing of the same weights for the GEMM kernels (fp16c's reads shorter than f16c_min_len,
+    // clm_selfcheck, clm_set_fallback)
+    Packing pk_f32;
+    // exact fp32 (the engine's own mode, or the referee / short-read / fall-back path of a 16-bit engine): the fused tail's packing
+    Packing pk_t32;               // (tail32.hip; its score layer: T32_SCORE)
     // the same weights as hi + lo halfs (launch_pack_x3; tail32.hip AR_X3): the arithmetic of a CLM_PREC_F16X3 handle AND, round 5,
-    // of every 16-bit handle's short reads and first fall-back level -- lwx = the handle's fp32-path LayerW with these
-    DevBuf packed32x[NLAYER][4];
-    LayerW lwx[NLAYER] = {};
-    bool referee = false;              // inside clm_selfcheck's second pass: exact fp32, whatever the handle's mode or fall-back level
-    DevBuf packed_score32;
-    DevBuf packed_score32t, packed_score32x;   // attention.0.weight in the fused tail's packings (tail32.hip T32_SCORE)
-    LayerW lw32[NLAYER]{};
-    // PREC_F16C: fc1 / fc2 packed as hi + lo as well (the mode's second level, clm_set_mlp_compensation; lw.w_fc1 / w_fc2 are plain fp16)
-    DevBuf packed_mlpc[NLAYER][2];
+    // of every 16-bit handle's short reads and first fall-back level
+    Packing pk_x3;
+    // PREC_F16C: fc1 / fc2 (slots 2, 3 alone) packed as hi + lo as well (the mode's second level, clm_set_mlp_compensation)
+    Packing pk_mlpc;
     bool mlp_lo = false;
     int f16c_min_len = 2048;
-    // clm_selfcheck / clm_set_fallback: the exact-fp32 kernels of the same handle as referee of, and replacement for, the 16-bit path
-    int force_prec = -1;          // >= 0 inside clm_selfcheck: the arithmetic forward_chunk runs in, whatever the length
-    // clm_set_fallback: 0 = the handle's own mode; 1 = the next arithmetic INSIDE the gate (a 16-bit handle: fp16x3 -- fp32-class
-    // results at about twice the exact rate; an fp16x3 handle: exact fp32); 2 = exact fp32 on every handle
-    int fallback = 0;
     DevBuf sc_logits;             // [2][B][2] fp32: logits of the two passes of a self-check
     // host batches: two device staging buffers fed by the handle's own copy stream
     struct Stage {
@@ -115,10 +132,8 @@ struct clm_handle {
     DevBuf edge_bnd, edge_read;   // float2
     bool raw_z = false;           // CLM_DEBUG=raw_z: the fused in_proj stage writes x0 | x1 | v as before round 3 (A/B runs, tests)
     DevBuf head_t[5];
-    LayerW lw[NLAYER]{};
     HeadW hw{};
     std::vector<FilterSet> filters;
-    uint64_t clock = 0;
     // workspace (one chunk of reads; ensure_workspace)
     size_t ws_es = 0;             // element size z / y were last written with
     DevBuf h;                     // fp32 residual stream
@@ -129,7 +144,7 @@ struct clm_handle {
     DevBuf ids8;                                    // clamped ids [B][Lp]
     // Round 5, the [PAD] prefix of left-padded batches (pad_prefix.hip): per read the 128-token tiles wholly inside its leading run
     // of [PAD], the list of tiles the tail kernels compute, and per arithmetic one table of what an all-[PAD] read leaves behind
-    DevBuf pad_p0;                                  // int [B]
+    DevBuf pad_p0;                                  // int [3][B]: p0 | pair order | pair partner (launch_pair_order)
     DevBuf tile_list;                               // int [1 + B * tiles_x]
     struct PadTable {
         int prec = -1;                              // the arithmetic it was computed in (effective precision, fp16c's level, fp32 path: x3?)
@@ -147,12 +162,22 @@ struct clm_handle {
         DevBuf dots[NLAYER];                        // fp32
     };
     std::vector<PadTable> pad_tables;
-    PadTable* capture = nullptr;                    // inside the forward that fills a table
     DevBuf pad_ids;                                 // all PAD_ID: the table read's ids
     DevBuf pad_logits;                              // fp32 [2]: that read's logits (unused)
     bool no_pad_skip = false;                       // CLM_DEBUG=no_pad_skip: every tile of every read is computed (A/B runs, tests)
     bool no_seg_skip = false;                       // CLM_DEBUG=no_seg_skip: ... but every segment of the long-read convolution is transformed
     int last_B = 0, last_L = 0, last_Lp = 0;
+    // How forwards run right now.  clm_selfcheck / clm_set_fallback: the exact-fp32 kernels of the same handle as referee of, and
+    // replacement for, the 16-bit path; clm_selfcheck and the build of a [PAD] table change it for a scope (ScopedRun)
+    struct RunMode {
+        int force_prec = -1;      // >= 0 inside clm_selfcheck / a table build: the arithmetic forward_chunk runs in, whatever the length
+        // clm_set_fallback: 0 = the handle's own mode; 1 = the next arithmetic INSIDE the gate (a 16-bit handle: fp16x3 -- fp32-class
+        // results at about twice the exact rate; an fp16x3 handle: exact fp32); 2 = exact fp32 on every handle
+        int fallback = 0;
+        bool referee = false;     // inside clm_selfcheck's second pass: exact fp32, whatever the handle's mode or fall-back level
+        bool prof = false;        // clm_profile_enable: StageTimer records its spans
+        PadTable* capture = nullptr;   // inside the forward that fills a table
+    } run;
     // debug / profiling
     int stop_layer = -1, stop_stage = -1;
     bool no_idconv = false;       // CLM_DEBUG=no_idconv: run block 0's in_proj instead of the id-table convolution (A/B runs)
@@ -161,7 +186,6 @@ struct clm_handle {
     bool x3 = false;              // CLM_PREC_F16X3: cfg.precision is PREC_F32 inside the engine, the fused tails run on hi + lo halfs (tail32.hip AR_X3)
     float x3_wmax = 0.f;          // largest |w| of the hi + lo packed weights (clm_finalize; NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32
     bool unfused_fp32 = false;    // CLM_DEBUG=unfused_fp32: exact fp32 through the separate GEMM kernels of rounds 1-3 (tests cross-check the fused tail)
-    bool prof = false;
     std::vector<ProfRec> recs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     double prof_ms[CLM_N_STAGES] = {};
@@ -171,73 +195,73 @@ struct clm_handle {
 namespace {
 
 size_t elem_size(int prec) { return prec == PREC_F32 ? 4 : 2; }
-// The arithmetic a chunk of L-token reads runs in.  fp16c keeps fp16 activation operands; their roundings are independent
-// from token to token and average out in the attention pooling like 1/sqrt(L) (measured max |dlogit| at 3x head scale:
-// 1.6e-4 at 8193 tokens, 5.6e-4 at 1000, 1.5e-3 at 100), so reads too short to average them take the exact-fp32 kernels --
-// they are cheap there -- and the mode stays within the reference's 1e-3 at every length.
-int effective_prec(const clm_handle* h, int L);
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
+int tiles_of(int L, int tile) { return (L + tile - 1) / tile; }
 // Row pitch (tokens) of the channel-major planes z / y and their lo-byte planes.  (A multiple of the 128-token tile, so that a
 // tile's piece of a BYTE row is one whole 128-byte line instead of straddling two on every other row, was measured in round 4:
 // tail kernel 21.7 vs 21.5 ms per step on one box, three alternations -- not kept.)
 constexpr int LP_ALIGN = 64;
 
-// ---- expected weights -------------------------------------------------------------------------------
+// ---- expected weights: key, shape, and where clm_finalize puts the device pointer ---------------------
 struct KeySpec {
     std::string key;
     std::vector<int64_t> shape;
+    const float** dst;
 };
 
-std::vector<KeySpec> expected_keys(const clm_config& c) {
+std::vector<KeySpec> expected_keys(clm_handle* h) {
     std::vector<KeySpec> k;
+    const clm_config& c = h->cfg;
     const int64_t d = c.d_model, di = c.d_inner, fo = c.filter_order, hh = c.head_hidden;
-    k.push_back({"bb.embeddings.word_embeddings.weight", {c.vocab_rows, d}});
+    NetF32& n = h->net;
+    k.push_back({"bb.embeddings.word_embeddings.weight", {c.vocab_rows, d}, &n.emb});
     for (int i = 0; i < c.n_layer; ++i) {
+        BlockF32& b = h->blk[i];
         std::string p = "bb.layers." + std::to_string(i) + ".";
-        for (const char* n : {"norm1", "norm2"}) {
-            k.push_back({p + n + ".weight", {d}});
-            k.push_back({p + n + ".bias", {d}});
-        }
-        k.push_back({p + "mixer.in_proj.weight", {3 * d, d}});
-        k.push_back({p + "mixer.in_proj.bias", {3 * d}});
-        k.push_back({p + "mixer.out_proj.weight", {d, d}});
-        k.push_back({p + "mixer.out_proj.bias", {d}});
-        k.push_back({p + "mixer.short_filter.weight", {3 * d, 1, 3}});
-        k.push_back({p + "mixer.short_filter.bias", {3 * d}});
+        k.push_back({p + "norm1.weight", {d}, &b.ln1_g});
+        k.push_back({p + "norm1.bias", {d}, &b.ln1_b});
+        k.push_back({p + "norm2.weight", {d}, &b.ln2_g});
+        k.push_back({p + "norm2.bias", {d}, &b.ln2_b});
+        k.push_back({p + "mixer.in_proj.weight", {3 * d, d}, &b.w[0]});
+        k.push_back({p + "mixer.in_proj.bias", {3 * d}, &b.b_in});
+        k.push_back({p + "mixer.out_proj.weight", {d, d}, &b.w[1]});
+        k.push_back({p + "mixer.out_proj.bias", {d}, &b.b_out});
+        k.push_back({p + "mixer.short_filter.weight", {3 * d, 1, 3}, &b.short_w});
+        k.push_back({p + "mixer.short_filter.bias", {3 * d}, &b.short_b});
         std::string f = p + "mixer.filter_fn.";
-        k.push_back({f + "bias", {d}});
-        k.push_back({f + "pos_emb.z", {1, c.max_seq_len, c.emb_dim}});
-        k.push_back({f + "pos_emb.t", {1, c.max_seq_len, 1}});
-        k.push_back({f + "implicit_filter.0.weight", {fo, c.emb_dim}});
-        k.push_back({f + "implicit_filter.0.bias", {fo}});
-        k.push_back({f + "implicit_filter.1.freq", {1, fo}});
-        k.push_back({f + "implicit_filter.2.weight", {fo, fo}});
-        k.push_back({f + "implicit_filter.2.bias", {fo}});
-        k.push_back({f + "implicit_filter.4.weight", {fo, fo}});
-        k.push_back({f + "implicit_filter.4.bias", {fo}});
-        k.push_back({f + "implicit_filter.6.weight", {d, fo}});
-        k.push_back({f + "modulation.deltas", {1, 1, d}});
-        k.push_back({p + "mlp.fc1.weight", {di, d}});
-        k.push_back({p + "mlp.fc1.bias", {di}});
-        k.push_back({p + "mlp.fc2.weight", {d, di}});
-        k.push_back({p + "mlp.fc2.bias", {d}});
+        k.push_back({f + "bias", {d}, &b.filt_bias});
+        k.push_back({f + "pos_emb.z", {1, c.max_seq_len, c.emb_dim}, &b.pos_z});
+        k.push_back({f + "pos_emb.t", {1, c.max_seq_len, 1}, &b.pos_t});
+        k.push_back({f + "implicit_filter.0.weight", {fo, c.emb_dim}, &b.f_w0});
+        k.push_back({f + "implicit_filter.0.bias", {fo}, &b.f_b0});
+        k.push_back({f + "implicit_filter.1.freq", {1, fo}, &b.f_freq});
+        k.push_back({f + "implicit_filter.2.weight", {fo, fo}, &b.f_w2});
+        k.push_back({f + "implicit_filter.2.bias", {fo}, &b.f_b2});
+        k.push_back({f + "implicit_filter.4.weight", {fo, fo}, &b.f_w4});
+        k.push_back({f + "implicit_filter.4.bias", {fo}, &b.f_b4});
+        k.push_back({f + "implicit_filter.6.weight", {d, fo}, &b.f_w6});
+        k.push_back({f + "modulation.deltas", {1, 1, d}, &b.deltas});
+        k.push_back({p + "mlp.fc1.weight", {di, d}, &b.w[2]});
+        k.push_back({p + "mlp.fc1.bias", {di}, &b.b_fc1});
+        k.push_back({p + "mlp.fc2.weight", {d, di}, &b.w[3]});
+        k.push_back({p + "mlp.fc2.bias", {d}, &b.b_fc2});
     }
-    k.push_back({"bb.ln_f.weight", {d}});
-    k.push_back({"bb.ln_f.bias", {d}});
-    k.push_back({"head.attention.0.weight", {hh / 2, d}});
-    k.push_back({"head.attention.0.bias", {hh / 2}});
-    k.push_back({"head.attention.2.weight", {1, hh / 2}});
-    k.push_back({"head.attention.2.bias", {1}});
-    k.push_back({"head.classifier.0.weight", {hh, d}});
-    k.push_back({"head.classifier.0.bias", {hh}});
-    k.push_back({"head.classifier.3.weight", {hh, hh}});
-    k.push_back({"head.classifier.3.bias", {hh}});
-    k.push_back({"head.classifier.6.layers.0.weight", {hh, hh}});
-    k.push_back({"head.classifier.6.layers.0.bias", {hh}});
-    k.push_back({"head.classifier.6.layers.3.weight", {hh, hh}});
-    k.push_back({"head.classifier.6.layers.3.bias", {hh}});
-    k.push_back({"head.output_layer.weight", {c.n_classes, hh}});
-    k.push_back({"head.output_layer.bias", {c.n_classes}});
+    k.push_back({"bb.ln_f.weight", {d}, &n.lnf_g});
+    k.push_back({"bb.ln_f.bias", {d}, &n.lnf_b});
+    k.push_back({"head.attention.0.weight", {hh / 2, d}, &n.att_w1});
+    k.push_back({"head.attention.0.bias", {hh / 2}, &n.att_b1});
+    k.push_back({"head.attention.2.weight", {1, hh / 2}, &n.att_w2});
+    k.push_back({"head.attention.2.bias", {1}, &n.att_b2});
+    k.push_back({"head.classifier.0.weight", {hh, d}, &n.cls[0]});
+    k.push_back({"head.classifier.0.bias", {hh}, &h->hw.b0});
+    k.push_back({"head.classifier.3.weight", {hh, hh}, &n.cls[1]});
+    k.push_back({"head.classifier.3.bias", {hh}, &h->hw.b3});
+    k.push_back({"head.classifier.6.layers.0.weight", {hh, hh}, &n.cls[2]});
+    k.push_back({"head.classifier.6.layers.0.bias", {hh}, &h->hw.b60});
+    k.push_back({"head.classifier.6.layers.3.weight", {hh, hh}, &n.cls[3]});
+    k.push_back({"head.classifier.6.layers.3.bias", {hh}, &h->hw.b63});
+    k.push_back({"head.output_layer.weight", {c.n_classes, hh}, &n.cls[4]});
+    k.push_back({"head.output_layer.bias", {c.n_classes}, &h->hw.bo});
     return k;
 }
 
@@ -271,36 +295,143 @@ __global__ void convert_to_f32_kernel(const void* in, float* out, size_t n, int 
         out[i] = to_float(reinterpret_cast<const f16_t*>(in)[i]);
 }
 
-const float* W(clm_handle* h, const std::string& key) { return h->w[key].d.get<float>(); }
+// W [n][k] fp32 -> MFMA fragment order of `prec` (the GEMM kernels, the 16-bit tail) / the fused exact tail's order, plain or hi + lo
+int pack_gemm(clm_handle* h, int prec, const float* w, int n, int k, DevBuf& out, hipStream_t st) {
+    HIPCHK(h, out.alloc(packed_weight_bytes(prec, n, k)));
+    HIPCHK(h, hipMemsetAsync(out.get(), 0, out.bytes(), st));
+    launch_pack_weight(prec, w, out.get(), n, k, st);
+    return CLM_OK;
+}
+int pack_tail(clm_handle* h, bool x3, const float* w, int n, int k, DevBuf& out, hipStream_t st) {
+    HIPCHK(h, out.alloc((size_t)n * k * 4));
+    (x3 ? launch_pack_x3 : launch_pack_f32t)(w, out.get(), n, k, st);
+    return CLM_OK;
+}
 
-// exact fp32 runs its block tails fused (tail32.hip) unless a debug stop wants an intermediate or CLM_DEBUG=unfused_fp32 asks
-bool fused_fp32(const clm_handle* h) { return !h->unfused_fp32 && h->stop_stage < 0; }
+// The arithmetic a chunk of L-token reads runs in.  fp16c keeps fp16 activation operands; their roundings are independent
+// from token to token and average out in the attention pooling like 1/sqrt(L) (measured max |dlogit| at 3x head scale:
+// 1.6e-4 at 8193 tokens, 5.6e-4 at 1000, 1.5e-3 at 100), so reads too short to average them take the exact-fp32 kernels --
+// they are cheap there -- and the mode stays within the reference's 1e-3 at every length.
+int mode_prec(const clm_handle* h, int L) { return (h->cfg.precision == PREC_F16C && L < h->f16c_min_len) ? (int)PREC_F32 : h->cfg.precision; }
+int effective_prec(const clm_handle* h, int L) {
+    if (h->run.force_prec >= 0) return h->run.force_prec;
+    return h->run.fallback > 0 ? (int)PREC_F32 : mode_prec(h, L);
+}
+// Does the fp32 path of this handle multiply hi + lo halfs (three fp16 MFMAs per product, tail32.hip AR_X3) right now?  An fp16x3
+// handle: unless told to fall back; a 16-bit handle (short reads of fp16c, fall-back level 1): unless told to fall back all the
+// way (level 2).  Never inside the referee pass of a self-check, never on an fp32 handle.
+bool fp32_path_is_x3(const clm_handle* h) {
+    if (h->run.referee || !(h->x3_wmax < X3_WEIGHT_LIMIT)) return false;   // (weights beyond the packing's range: exact fp32 instead)
+    if (h->x3) return h->run.fallback == 0;
+    return h->cfg.precision != PREC_F32 && h->run.fallback < 2;
+}
+bool is_exact(const clm_handle* h) { return h->cfg.precision == PREC_F32 && !h->x3; }   // the handle IS its own referee
+bool stop_here(const clm_handle* h, int layer, int stage) { return h->stop_layer == layer && h->stop_stage == stage; }
+
+// "Run forwards in this arithmetic, with profiling off / as referee / capturing into this table": what the scope changes in
+// h->run is put back as it stood on every way out of it.  Profiling is off inside: not part of anybody's timed region.
+struct ScopedRun {
+    clm_handle* const h;
+    const clm_handle::RunMode saved;
+    explicit ScopedRun(clm_handle* h_) : h(h_), saved(h_->run) { h->run.prof = false; }
+    ~ScopedRun() { h->run = saved; }
+};
+
+// Everything the engine decides about a chunk of Bc reads of L tokens, each decision once and under one name (plan_chunk says what
+// each means).  The stages read these fields; none looks at the precision, the CLM_DEBUG switches or the kind of a debug stop again.
+struct ChunkPlan {
+    int Bc, L, prec, Lp, Lmain, S, nt128, nt_pool;
+    size_t es;
+    bool tuned16, fused16, fused32, fused, unfused32, alt32, x3, mlpc, lo, keep_lo;
+    bool id_conv, id_resid, peel, zgated, pad_skip, seg_tables, seg_skip[NLAYER];
+};
+
+ChunkPlan plan_chunk(const clm_handle* h, int Bc, int L) {
+    ChunkPlan p{};
+    const bool stop = h->stop_stage >= 0;                     // a debug stop wants an intermediate: no fused tail
+    p.Bc = Bc; p.L = L;
+    p.prec = effective_prec(h, L);                            // (honours the self-check's referee pass and the fallback)
+    p.es = elem_size(p.prec);                                 // bytes per element of z / y
+    p.Lp = round_up(L, LP_ALIGN);
+    p.S = conv_segments_for(L);                               // segments of the long convolution (1: one shot)
+    p.alt32 = p.prec != h->cfg.precision;                     // fp16c engine, short reads: exact-fp32 kernels and packing
+    p.tuned16 = p.prec != PREC_F32;
+    // 16-bit modes, no debug stop: every block's tail kernel goes on, on the tile it has just produced, with LayerNorm-1 + in_proj
+    // of the next block (the last block: ln_f + attention scores + pooling partials): no separate in_proj / score launches
+    p.fused16 = p.tuned16 && !stop;
+    // exact fp32: one fused kernel per block tail, the next block's in_proj included (tail32.hip), unless a debug stop wants an
+    // intermediate or CLM_DEBUG=unfused_fp32 asks; then the separate GEMM kernels of rounds 1-3, with fc1's output in HBM
+    p.fused32 = !p.tuned16 && !h->unfused_fp32 && !stop;
+    p.unfused32 = !p.tuned16 && !p.fused32;
+    p.fused = p.fused16 || p.fused32;
+    p.x3 = p.fused32 && fp32_path_is_x3(h);                   // fp16x3: hi + lo halfs in the fused tails (the referee pass: exact)
+    // reads of 128 k + 1 tokens (every 8k-bp read: 8192 bases + [SEP]): the last token would be a tile of its own, a whole extra
+    // round of the tail kernel for one token per read; it is causally isolated, so a per-read matrix-vector kernel takes it
+    p.peel = p.fused16 && !h->no_lone_peel && L > 128 && L % 128 == 1;
+    p.Lmain = p.peel ? L - 1 : L;                             // tokens the 128-token tiles cover
+    // ... and hands z over in the form the convolution reads: x0f and g = x1f * vf, filtered and gated by the in_proj stage itself
+    // (two rows per channel instead of three; gemm16.hip inproj_blocks_gated)
+    p.zgated = p.fused16 && !h->raw_z;
+    // fp16c, round 4: y (every block) and the gated rows of z carry one lo byte per element next to the halfs; the workspace of an
+    // fp16c handle keeps y's lo plane whatever a chunk runs in; second level: fc1 / fc2 as hi + lo too
+    p.lo = p.prec == PREC_F16C;
+    p.keep_lo = h->cfg.precision == PREC_F16C;
+    p.mlpc = p.lo && h->mlp_lo;
+    // 16-bit modes: block 0's in_proj output is a function of the token id alone, the convolution looks it up (ztab), single-shot
+    // and segmented kernel alike, and no in_proj is launched -- unless a debug stop asks for z itself or CLM_DEBUG=no_idconv
+    // (id_conv).  Without a debug stop block 0 never touches the fp32 embedding rows in HBM either: its residual is gathered from
+    // the embedding table by its tail kernel (id_resid); the separate kernels a debug stop brings read the residual stream in HBM,
+    // which is the one case where the two differ.  Exact fp32 with the fused tail, single-shot convolution: the same table -- it
+    // is fp32 -- and h is first written by block 0's tail kernel, as in the 16-bit id path
+    p.id_conv = !h->no_idconv && ((p.tuned16 && !stop_here(h, 0, CLM_STAGE_INPROJ)) || (p.fused32 && p.S == 1));
+    p.id_resid = !h->no_idconv && (p.fused16 || (p.fused32 && p.S == 1));
+    // Round 5: tiles wholly inside a read's [PAD] prefix are not computed, their rows come from the all-[PAD] table (pad_prefix.hip).
+    // In the fused paths only (the debug / unfused paths keep computing everything), never inside the forward that fills a table,
+    // and only for reads long enough to hold a whole prefix tile next to a real token.
+    p.pad_skip = !h->no_pad_skip && !h->run.capture && L >= 256 && p.fused;
+    p.seg_tables = p.tuned16 && !h->no_seg_skip;              // (the 16-bit fused path's segmented convolution skips prefix segments)
+    // does block j's (segmented) convolution leave out the segments inside the [PAD] prefix of both reads of a pair (SegPrefix)?
+    // Block 0 looks z up by token id, the others read the gated hand-over (and the table must hold them: ChunkCtx::seg_skip)
+    for (int j = 0; j < NLAYER; ++j) p.seg_skip[j] = p.pad_skip && p.S > 1 && p.fused16 && (j == 0 ? p.id_resid : p.zgated);
+    // tiles of a read: 128 tokens in the 16-bit tail kernel; pooling partials: one per such tile, or per T32_TILE = 64 tokens (exact tail)
+    p.nt128 = tiles_of(L, 128);
+    p.nt_pool = p.tuned16 ? p.nt128 : tiles_of(L, T32_TILE);
+    return p;
+}
+
+// The weights of a chunk under its plan.  The GEMM kernels and the 16-bit tail: the mode's packing, or the exact-fp32 one a 16-bit
+// handle keeps next to it; the fused exact tail: plain fp32 or hi + lo halfs; the 16-bit tail's two MLP products: hi + lo when asked
+const Packing& gemm_packing(const clm_handle* h, const ChunkPlan& p) { return p.alt32 ? h->pk_f32 : h->pk_mode; }
+const Packing& tail_packing(const clm_handle* h, const ChunkPlan& p) { return p.x3 ? h->pk_x3 : h->pk_t32; }
+BlockW block_weights(const clm_handle* h, const ChunkPlan& p, int i) {
+    const Packing &g = gemm_packing(h, p), &m = p.mlpc ? h->pk_mlpc : g, &t = tail_packing(h, p);
+    return {&h->blk[i], g.w[i][0].get(), g.w[i][1].get(), m.w[i][2].get(), m.w[i][3].get(),
+            t.w[i][0].get(), t.w[i][1].get(), t.w[i][2].get(), t.w[i][3].get()};
+}
 
 // The per-chunk workspace: buffers grown each on its own -- a call needs Bc x (its own length) of each, and chunk_for() bounds that
 // product whatever the read length, so a handle that has seen 256 x 8k-token and 32 x 32k-token batches holds the larger of the two
 // needs per buffer, not 256 x 32k (the round-2 shape bookkeeping did).
-int ensure_workspace(clm_handle* h, int Bc, int L, hipStream_t st) {
-    const int prec = effective_prec(h, L);                   // (honours the self-check's referee pass and the fallback)
-    const size_t es = elem_size(prec), Lp = (size_t)round_up(L, LP_ALIGN), nb = (size_t)Bc, nl = (size_t)L;
-    const size_t S = conv_segments_for(L) > 1 ? (size_t)conv_segments_for(L) : 0;
+int ensure_workspace(clm_handle* h, const ChunkPlan& p, hipStream_t st) {
+    const size_t es = p.es, Lp = (size_t)p.Lp, nb = (size_t)p.Bc, nl = (size_t)p.L, S = p.S > 1 ? (size_t)p.S : 0;
     struct { DevBuf& buf; size_t need; bool zero; } ws[] = {   // zero: padding columns [L, Lp) must never hold NaN garbage
         {h->h, nb * nl * D * 4, false},
         {h->z, nb * D3 * Lp * es, true},
         {h->y, nb * D * Lp * es, true},
-        {h->u, (prec == PREC_F32 && !fused_fp32(h)) ? nb * DI * nl * es : 0, false},   // the 1024-wide fc1 output: unfused fp32 path only
+        {h->u, p.unfused32 ? nb * DI * nl * es : 0, false},   // the 1024-wide fc1 output: unfused fp32 path only
         {h->scores, nb * nl * 4, false},
         {h->stats, nb * 2 * 4, false},
         // pooling partials: [POOL_SPLIT][4][256] per read (unfused fp32 path) or one POOL_PSTRIDE row per tile -- 128 tokens in the
         // 16-bit tail kernel, T32_TILE = 64 in the exact / fp16x3 one
-        {h->partial, nb * std::max((size_t)POOL_SPLIT * 4 * D, (size_t)((nl + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE) * 4, false},
+        {h->partial, nb * std::max((size_t)POOL_SPLIT * 4 * D, (size_t)tiles_of(p.L, T32_TILE) * POOL_PSTRIDE) * 4, false},
         {h->pooled, nb * D * 4, false},
         {h->gscratch, ((nb + 1) / 2) * D * S * 16384 * sizeof(float2), false},
         {h->ids8, nb * Lp, false},
         {h->lone_ws, lone_token_ws_floats((int)nb) * 4, false},
         {h->edge_read, nb * D3 * sizeof(float2), false},
-        {h->ylo, h->cfg.precision == PREC_F16C ? nb * D * Lp : 0, true},
+        {h->ylo, p.keep_lo ? nb * D * Lp : 0, true},
         {h->pad_p0, 3 * nb * sizeof(int), false},                     // p0 | pair order | pair partner (pad_prefix.hip)
-        {h->tile_list, (1 + nb * ((nl + 127) / 128)) * sizeof(int), false},
+        {h->tile_list, (1 + nb * (size_t)p.nt128) * sizeof(int), false},
     };
     bool grow = false;
     for (auto& w : ws) grow |= w.need > w.buf.bytes();
@@ -343,14 +474,10 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
             HIPCHK(h, f.kf[i].alloc((size_t)D * f.KS * N * sizeof(float2)));
             float* const kt = f.ktime[i].get<float>();
             float2* const kf = f.kf[i].get<float2>();
-            std::string p = "bb.layers." + std::to_string(i) + ".mixer.filter_fn.";
-            launch_filter(W(h, p + "pos_emb.z"), W(h, p + "pos_emb.t"), W(h, p + "implicit_filter.0.weight"),
-                          W(h, p + "implicit_filter.0.bias"), W(h, p + "implicit_filter.1.freq"),
-                          W(h, p + "implicit_filter.2.weight"), W(h, p + "implicit_filter.2.bias"),
-                          W(h, p + "implicit_filter.4.weight"), W(h, p + "implicit_filter.4.bias"),
-                          W(h, p + "implicit_filter.6.weight"), W(h, p + "modulation.deltas"), kt, f.Lf, st);
+            const BlockF32& b = h->blk[i];
+            launch_filter(b.pos_z, b.pos_t, b.f_w0, b.f_b0, b.f_freq, b.f_w2, b.f_b2, b.f_w4, b.f_b4, b.f_w6, b.deltas, kt, f.Lf, st);
             if (S == 1) {
-                launch_filter_spectrum(kt, W(h, p + "bias"), kf, scratch.get<double2>(), f.Lf, logn, 0, f.Lf, -1, st);
+                launch_filter_spectrum(kt, b.filt_bias, kf, scratch.get<double2>(), f.Lf, logn, 0, f.Lf, -1, st);
                 if (logn == 14) {                            // (round 5: the exact / fp16x3 engine's fp32 rows take the persistent kernel too)
                     HIPCHK(h, f.kfp[i].alloc((size_t)D * N * sizeof(float2)));
                     launch_spectrum_lanepack(kf, f.kfp[i].get<float2>(), 1, 0, st);
@@ -359,7 +486,7 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
                 DevBuf tmp;
                 HIPCHK(h, tmp.alloc((size_t)D * N * sizeof(float2)));
                 for (int j = 0; j < f.KS; ++j) {
-                    launch_filter_spectrum(kt, W(h, p + "bias"), tmp.get<float2>(), scratch.get<double2>(), f.Lf, logn, j * SEG_LEN,
+                    launch_filter_spectrum(kt, b.filt_bias, tmp.get<float2>(), scratch.get<double2>(), f.Lf, logn, j * SEG_LEN,
                                            SEG_LEN, (j - 1) * SEG_LEN, st);
                     launch_spectrum_lanepack(tmp.get<float2>(), kf, f.KS, j, st);
                 }
@@ -379,9 +506,8 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
             r.L = L;
             r.stride = round_up(L, 8);
             for (int i = 0; i < NLAYER; ++i) {
-                std::string p = "bb.layers." + std::to_string(i) + ".mixer.filter_fn.";
                 HIPCHK(h, r.p[i].alloc((size_t)D * r.stride * 4));
-                launch_filter_reversed(fs->ktime[i].get<float>(), W(h, p + "bias"), r.p[i].get<float>(), L, r.stride, st);
+                launch_filter_reversed(fs->ktime[i].get<float>(), h->blk[i].filt_bias, r.p[i].get<float>(), L, r.stride, st);
             }
             fs->krev.push_back(std::move(r));
             *krev_out = &fs->krev.back();
@@ -397,7 +523,7 @@ struct StageTimer {
     int stage;
     bool on;
     hipEvent_t e0{}, e1{};
-    StageTimer(clm_handle* h_, hipStream_t st_, int stage_) : h(h_), st(st_), stage(stage_), on(h_->prof) {
+    StageTimer(clm_handle* h_, hipStream_t st_, int stage_) : h(h_), st(st_), stage(stage_), on(h_->run.prof) {
         if (!on) return;
         if (h->recs.size() > 200000) { on = false; return; }
         if (!h->free_events.empty()) {
@@ -417,20 +543,6 @@ struct StageTimer {
     }
 };
 
-int effective_prec(const clm_handle* h, int L) {
-    if (h->force_prec >= 0) return h->force_prec;
-    if (h->fallback > 0) return (int)PREC_F32;
-    return (h->cfg.precision == PREC_F16C && L < h->f16c_min_len) ? (int)PREC_F32 : h->cfg.precision;
-}
-// Does the fp32 path of this handle multiply hi + lo halfs (three fp16 MFMAs per product, tail32.hip AR_X3) right now?  An fp16x3
-// handle: unless told to fall back; a 16-bit handle (short reads of fp16c, fall-back level 1): unless told to fall back all the
-// way (level 2).  Never inside the referee pass of a self-check, never on an fp32 handle.
-bool fp32_path_is_x3(const clm_handle* h) {
-    if (h->referee || !(h->x3_wmax < X3_WEIGHT_LIMIT)) return false;   // (weights beyond the packing's range: exact fp32 instead)
-    if (h->x3) return h->fallback == 0;
-    return h->cfg.precision != PREC_F32 && h->fallback < 2;
-}
-
 // Asynchronous error of an EARLIER forward (the call itself returned before its kernels ran): reported once, by the next
 // forward / stage_wait / profile_read / clm_check call.  The reference raises IndexError inside nn.Embedding for such ids.
 int check_bad_ids(clm_handle* h) {
@@ -442,8 +554,6 @@ int check_bad_ids(clm_handle* h) {
     return CLM_OK;
 }
 
-bool stop_here(clm_handle* h, int layer, int stage) { return h->stop_layer == layer && h->stop_stage == stage; }
-
 // Reads pushed through all layers together: cfg.chunk_reads, capped by tokens so that a chunk's workspace stays bounded whatever
 // the read length -- 256 x 8,256 tokens in the 16-bit modes (z + y + h: 6.5 GB; measured round 3, same box: 7,976 / 8,047 / 8,164
 // reads/s at 64 / 128 / 256 reads per chunk: the ~26 small launches of a chunk, the persistent kernels' ramps and the head are paid
@@ -451,7 +561,7 @@ bool stop_here(clm_handle* h, int layer, int stage) { return h->stop_layer == la
 // proven size).  Even, so that a chunk boundary never splits a read pair of the packed transform.
 int chunk_for(const clm_handle* h, int L) {
     // (exact fp32 with the fused tail has no fc1 output in HBM either: the same cap as the 16-bit modes)
-    const long long cap_tokens = (effective_prec(h, L) == PREC_F32 && !fused_fp32(h)) ? 64LL * 8256 : 256LL * 8256;
+    const long long cap_tokens = plan_chunk(h, 1, L).unfused32 ? 64LL * 8256 : 256LL * 8256;
     long long c = cap_tokens / round_up(L, LP_ALIGN);
     if (c > h->cfg.chunk_reads) c = h->cfg.chunk_reads;
     if (c > TILE_LIST_MAX_READS) c = TILE_LIST_MAX_READS;     // (a tile-list entry holds its read in 12 bits)
@@ -459,41 +569,35 @@ int chunk_for(const clm_handle* h, int L) {
     return c < 1 ? 1 : (int)c;
 }
 
-int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits,
-                  hipStream_t st);
+int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st);
 
-// The all-[PAD] table of the arithmetic reads of this chunk run in (pad_prefix.hip), long enough for L tokens: built on first
-// use -- ONE forward of one all-[PAD] read through this very engine, with forward_chunk's capture hooks copying out what the
+// The all-[PAD] table of the arithmetic the reads of this chunk run in (pad_prefix.hip), long enough for its L tokens: built on
+// first use -- ONE forward of one all-[PAD] read through this very engine, with the stages' capture hooks copying out what the
 // later stages read of it -- and kept until the weights change.  Lengths come in classes (1,025 ... 32,769 tokens, then
 // max_seq_len) so that a file of ragged batches builds at most a handful.  The values at position t do not depend on the length of
 // the read they were computed in (causal backbone, taps independent of L) beyond the rounding of its transform size.
-int ensure_pad_table(clm_handle* h, int prec, bool x3, int L, hipStream_t st, clm_handle::PadTable** out) {
-    for (auto& t : h->pad_tables)
-        if (t.prec == prec && t.x3 == x3 && t.mlp_lo == (prec == PREC_F16C && h->mlp_lo) && t.L >= L) { *out = &t; return CLM_OK; }
+int ensure_pad_table(clm_handle* h, const ChunkPlan& p, hipStream_t st, clm_handle::PadTable** out) {
+    const auto same = [&p](const clm_handle::PadTable& t) { return t.prec == p.prec && t.x3 == p.x3 && t.mlp_lo == p.mlpc; };
+    size_t old = 0;                                          // the table of this arithmetic, if there is one
+    while (old < h->pad_tables.size() && !same(h->pad_tables[old])) ++old;
+    if (old < h->pad_tables.size() && h->pad_tables[old].L >= p.L) { *out = &h->pad_tables[old]; return CLM_OK; }
     int LT = 1025;
-    while (LT < L && LT < 32769) LT = 2 * (LT - 1) + 1;
-    if (LT < L) LT = h->cfg.max_seq_len;
+    while (LT < p.L && LT < 32769) LT = 2 * (LT - 1) + 1;
+    if (LT < p.L) LT = h->cfg.max_seq_len;
     if (LT > h->cfg.max_seq_len) LT = h->cfg.max_seq_len;
-    if (LT < L) return fail(h, CLM_E_INVALID, "ensure_pad_table: read longer than max_seq_len");
+    if (LT < p.L) return fail(h, CLM_E_INVALID, "ensure_pad_table: read longer than max_seq_len");
     HIPCHK(h, hipStreamSynchronize(st));
-    for (size_t k = 0; k < h->pad_tables.size(); ++k) {      // a shorter table of the same arithmetic is replaced
-        auto& t = h->pad_tables[k];
-        if (t.prec == prec && t.x3 == x3 && t.mlp_lo == (prec == PREC_F16C && h->mlp_lo)) {
-            h->pad_tables.erase(h->pad_tables.begin() + (long)k);
-            break;
-        }
-    }
+    if (old < h->pad_tables.size()) h->pad_tables.erase(h->pad_tables.begin() + (long)old);   // a shorter one is replaced
     clm_handle::PadTable t;
-    t.prec = prec; t.x3 = x3; t.mlp_lo = prec == PREC_F16C && h->mlp_lo;
+    t.prec = p.prec; t.x3 = p.x3; t.mlp_lo = p.mlpc;
     t.L = LT; t.Lp = round_up(LT, LP_ALIGN);
-    const size_t es = elem_size(prec);
-    for (int i = 1; i < NLAYER; ++i) HIPCHK(h, t.z[i].alloc((size_t)D3 * t.Lp * es));
+    for (int i = 1; i < NLAYER; ++i) HIPCHK(h, t.z[i].alloc((size_t)D3 * t.Lp * p.es));
     // (the exact path: partials per 64-token tile, and the final residual rows as well -- clm_debug_fetch("hidden") shows them)
-    if (prec == PREC_F32) HIPCHK(h, t.hfin.alloc((size_t)LT * D * 4));
+    if (!p.tuned16) HIPCHK(h, t.hfin.alloc((size_t)LT * D * 4));
     HIPCHK(h, t.scores.alloc((size_t)LT * 4));
-    HIPCHK(h, t.partial.alloc((size_t)((LT + T32_TILE - 1) / T32_TILE) * POOL_PSTRIDE * 4));
+    HIPCHK(h, t.partial.alloc((size_t)tiles_of(LT, T32_TILE) * POOL_PSTRIDE * 4));
     t.S = conv_segments_for(LT);
-    if (t.S > 1 && prec != PREC_F32 && !h->no_seg_skip)           // (the 16-bit fused path's segmented convolution skips prefix segments)
+    if (t.S > 1 && p.seg_tables)
         for (int i = 0; i < NLAYER; ++i) {
             HIPCHK(h, t.gspec[i].alloc((size_t)D * t.S * 16384 * sizeof(float2)));
             HIPCHK(h, t.dots[i].alloc((size_t)D * (t.S - 1) * SEG_DOT_THREADS * 4));
@@ -506,15 +610,13 @@ int ensure_pad_table(clm_handle* h, int prec, bool x3, int L, hipStream_t st, cl
     if (!h->pad_logits) HIPCHK(h, h->pad_logits.alloc(NCLS * 4));
     h->pad_tables.push_back(std::move(t));
     clm_handle::PadTable* tp = &h->pad_tables.back();
-    const int force = h->force_prec;
-    const bool prof = h->prof;
-    h->force_prec = prec;                                    // (fp16c: the class length may lie on the other side of the length switch)
-    h->prof = false;
-    h->capture = tp;
-    const int rc = forward_chunk(h, h->pad_ids.get(), CLM_DT_U8, tp->Lp, 1, LT, h->pad_logits.get<float>(), st);
-    h->capture = nullptr;
-    h->prof = prof;
-    h->force_prec = force;
+    int rc;
+    {
+        ScopedRun scope(h);
+        h->run.force_prec = p.prec;                          // (fp16c: the class length may lie on the other side of the length switch)
+        h->run.capture = tp;
+        rc = forward_chunk(h, h->pad_ids.get(), CLM_DT_U8, tp->Lp, 1, LT, h->pad_logits.get<float>(), st);
+    }
     if (rc) {
         h->pad_tables.pop_back();
         return rc;
@@ -523,286 +625,283 @@ int ensure_pad_table(clm_handle* h, int prec, bool x3, int L, hipStream_t st, cl
     return CLM_OK;
 }
 
-int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits,
-                  hipStream_t st) {
-    const int prec = effective_prec(h, L), Lp = round_up(L, LP_ALIGN);
-    const bool alt32 = prec != h->cfg.precision;              // fp16c engine, short reads: exact-fp32 kernels and packing
-    const float eps = h->cfg.ln_eps;
-    // the workspace sized for this chunk
-    auto size_workspace = [&]() -> int {
-        const int rc = ensure_workspace(h, Bc, L, st);
-        if (rc) return rc;
-        h->last_B = Bc; h->last_L = L; h->last_Lp = Lp;
-        if (h->ws_es != elem_size(prec)) {   // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
-            if (h->ws_es) {                  // columns may read as NaN in the other
-                HIPCHK(h, hipMemsetAsync(h->z.get(), 0, h->z.bytes(), st));
-                HIPCHK(h, hipMemsetAsync(h->y.get(), 0, h->y.bytes(), st));
-            }
-            h->ws_es = elem_size(prec);
-        }
-        return CLM_OK;
-    };
+// ---- the stages of a chunk's forward, free functions over ChunkCtx.  STOPPED: the debug stop (clm_debug_stop_after) sits right
+// behind the stage that returns it, and forward_chunk ends there with CLM_OK (the error codes are negative)
+constexpr int STOPPED = 1;
+
+struct ChunkCtx {
+    clm_handle* const h;
+    const ChunkPlan p;
+    const hipStream_t st;
     FilterSet* fs = nullptr;
-    const ReversedFilter* kr = nullptr;
-    int rc = ensure_filters(h, L, st, &fs, &kr);
-    const int S = conv_segments_for(L);
-    if (rc) return rc;
-    rc = size_workspace();
-    if (rc) return rc;
-    const bool tuned16 = prec != PREC_F32;
-    // 16-bit modes, no debug stop: block 0 never touches the fp32 embedding rows in HBM --
-    // its in_proj is a 16-row table looked up by the convolution and its residual is gathered from the embedding table
-    const bool idpath = tuned16 && !h->no_idconv && h->stop_stage < 0;
-    // ... and every block's tail kernel goes on, on the tile it has just produced, with LayerNorm-1 + in_proj of the next
-    // block (the last block: ln_f + attention scores + pooling partials): no separate in_proj / score launches
-    const bool fuse_next = tuned16 && h->stop_stage < 0;
-    // reads of 128 k + 1 tokens (every 8k-bp read: 8192 bases + [SEP]): the last token would be a tile of its own, a whole extra
-    // round of the tail kernel for one token per read; it is causally isolated, so a per-read matrix-vector kernel takes it
-    const bool peel = fuse_next && !h->no_lone_peel && L > 128 && L % 128 == 1;
-    // ... and hands z over in the form the convolution reads: x0f and g = x1f * vf, filtered and gated by the in_proj stage itself
-    // (two rows per channel instead of three; gemm16.hip inproj_blocks_gated)
-    const bool zgated = fuse_next && !h->raw_z;
-    // exact fp32: one fused kernel per block tail, the next block's in_proj included (tail32.hip)
-    const bool fused32 = prec == PREC_F32 && fused_fp32(h);
-    const bool x3 = fused32 && fp32_path_is_x3(h);              // fp16x3: hi + lo halfs in the fused tails (the referee pass: exact)
-    // Round 5: tiles wholly inside a read's [PAD] prefix are not computed, their rows come from the all-[PAD] table (pad_prefix.hip).
-    // In the fused paths only (the debug / unfused paths keep computing everything), never inside the forward that fills a table,
-    // and only for reads long enough to hold a whole prefix tile next to a real token.
-    const int Lmain = peel ? L - 1 : L;
-    const bool pad_skip = !h->no_pad_skip && !h->capture && L >= 256 && (fuse_next || fused32);
-    clm_handle::PadTable* ptab = nullptr;
-    if (pad_skip) {                                          // (before this chunk's ids land in the workspace: the build runs through it)
-        rc = ensure_pad_table(h, prec, x3, L, st, &ptab);
-        if (rc) return rc;
-        rc = size_workspace();                               // (the build may have regrown -- never shrunk -- the buffers; cheap when not)
-        if (rc) return rc;
-        rc = ensure_filters(h, L, st, &fs, &kr);             // (the build may have added a filter class: the vector behind fs moved)
-        if (rc) return rc;
+    const ReversedFilter* kr = nullptr;            // lone-tail lengths only
+    clm_handle::PadTable* ptab = nullptr;          // p.pad_skip only; (workspace pointers are taken where used: they may move until the table is there)
+    unsigned char* ylo() const { return p.lo ? h->ylo.get<unsigned char>() : nullptr; }
+    // (with segment skipping the pairs of the segmented convolutions are formed by descending prefix: perm / partner live behind p0)
+    int* pair_perm() const { return h->pad_p0.get<int>() + p.Bc; }
+    int* pair_partner() const { return h->pad_p0.get<int>() + 2 * p.Bc; }
+    // reads of S * 8192 + 1 tokens carry the last token's dot product through the segments: its table sums belong to ONE length
+    bool seg_skip(int j) const { return p.seg_skip[j] && ptab->gspec[j] && (!kr || p.L == ptab->L); }
+};
+
+// the workspace sized for this chunk
+int size_workspace(ChunkCtx& c) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    if (int rc = ensure_workspace(h, p, st)) return rc;
+    h->last_B = p.Bc; h->last_L = p.L; h->last_Lp = p.Lp;
+    if (h->ws_es != p.es) {                  // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
+        if (h->ws_es) {                      // columns may read as NaN in the other
+            HIPCHK(h, hipMemsetAsync(h->z.get(), 0, h->z.bytes(), st));
+            HIPCHK(h, hipMemsetAsync(h->y.get(), 0, h->y.bytes(), st));
+        }
+        h->ws_es = p.es;
     }
-    // fp16c, round 4: y (every block) and the gated rows of z carry one lo byte per element next to the halfs
-    unsigned char* const ylo = prec == PREC_F16C ? h->ylo.get<unsigned char>() : nullptr;
-    if (zgated && tail16_grid((Lmain + 127) / 128 * Bc) > 1024)
-        return fail(h, CLM_E_UNSUPPORTED, "more than 1024 compute units: edge_bnd is sized for 1024 workgroups");
-    const void* packed_score = alt32 ? h->packed_score32.get() : h->packed_score.get();
-    const ScorePoolArgs spa{h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
-                            W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                            W(h, "head.attention.2.bias"), h->scores.get<float>(), h->partial.get<float>(), Bc, L, (L + 127) / 128, eps};
+    return CLM_OK;
+}
+
+// short filter + gate + long convolution, one shot or segmented; idconv: z comes from the id table
+int stage_conv(ChunkCtx& c, int i, const BlockW& w, bool idconv) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    clm_handle::PadTable* const cap = h->run.capture;
+    StageTimer t(h, st, CLM_STAGE_CONV);
+    const unsigned char* ids8 = idconv ? h->ids8.get<unsigned char>() : nullptr;
+    const float* ztab = idconv ? h->ztab.get<float>() : nullptr;
+    const int flags = h->conv_flags | ((p.zgated && i > 0) ? CONV_GATED : 0);
+    if (p.S == 1) {
+        launch_hyena_conv(p.prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->tw.get<float2>(), fs->ktime[i].get<float>(), w.f->short_w, w.f->short_b,
+                          p.Bc, p.L, p.Lp, fs->logn, ids8, ztab, st, flags, fs->kfp[i].get<float2>(), c.ylo());
+        return CLM_OK;
+    }
+    // [PAD]-prefix reuse: segments inside the prefix of both reads of a pair come from the table (SegPrefix)
+    SegPrefix pfx;
+    if (cap && cap->gspec[i]) {
+        pfx.dots_out = kr ? cap->dots[i].get<float>() : nullptr;
+        pfx.dots_segs = cap->S - 1;
+    } else if (c.seg_skip(i)) {
+        pfx.p0 = h->pad_p0.get<int>();
+        pfx.perm = c.pair_perm();
+        pfx.tab = ptab->gspec[i].get<float2>();
+        pfx.tab_segs = ptab->S;
+        pfx.dots_in = ptab->dots[i].get<float>();
+        pfx.dots_segs = ptab->S - 1;
+    }
+    launch_hyena_conv_seg(p.prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->KS, fs->tw.get<float2>(), w.f->short_w, w.f->short_b, h->gscratch.get<float2>(),
+                          p.Bc, p.L, p.Lp, p.S, kr ? kr->p[i].get<float>() : nullptr, kr ? kr->stride : 0, ids8, ztab, st, flags, c.ylo(), pfx);
+    if (cap && cap->gspec[i]) {   // (one read = pair 0: [256][S][N] at the head of the scratch), then pair form
+        HIPCHK(h, hipMemcpyAsync(cap->gspec[i].get<float2>(), h->gscratch.get<float2>(), (size_t)D * p.S * 16384 * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        launch_spectra_pair_form(cap->gspec[i].get<float2>(), p.S, st);
+    }
+    return CLM_OK;
+}
+
+// The [PAD] prefix behind a fused tail: what block i leaves for the next stage -- z of nrow16 element rows + nlo byte rows, or the last
+// block's pooling scores and partials (exact path: its residual rows too) -- copied out of (capture) or in from (pad_skip) the table
+int prefix_hooks(ChunkCtx& c, int i, int nrow16, int nlo) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    clm_handle::PadTable* const cap = h->run.capture;
+    int* const p0 = h->pad_p0.get<int>();
+    float *const scores = h->scores.get<float>(), *const partial = h->partial.get<float>();
+    const bool last = i + 1 == NLAYER;
+    if (cap) {
+        if (!last) HIPCHK(h, hipMemcpyAsync(cap->z[i + 1].get(), h->z.get(), (size_t)D3 * p.Lp * p.es, hipMemcpyDeviceToDevice, st));
+        else {
+            if (!p.tuned16) HIPCHK(h, hipMemcpyAsync(cap->hfin.get<float>(), h->h.get<float>(), (size_t)p.L * D * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(cap->scores.get<float>(), scores, (size_t)p.L * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(cap->partial.get<float>(), partial, (size_t)p.nt_pool * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+        }
+    } else if (p.pad_skip) {
+        if (!last)                    // (rows of segments the next convolution will not read are not copied)
+            launch_prefix_fill_z(p0, h->z.get(), ptab->z[i + 1].get(), p.Bc, p.Lp, ptab->Lp, p.Lmain, (int)p.es, nrow16, nlo, st,
+                                 c.seg_skip(i + 1) ? p.S : 0, p.tuned16 ? c.pair_partner() : nullptr);
+        else {
+            if (!p.tuned16) launch_prefix_fill_h(p0, h->h.get<float>(), ptab->hfin.get<float>(), p.Bc, p.L, p.L, st);
+            launch_prefix_fill_pool(p0, scores, partial, ptab->scores.get<float>(), ptab->partial.get<float>(), p.Bc, p.L, p.nt_pool, p.Lmain, st,
+                                    p.tuned16 ? 1 : 128 / T32_TILE);   // (partials per 128 tokens)
+        }
+    }
+    return CLM_OK;
+}
+
+// 16-bit block tail: out_proj + LN2 + fc1 + GELU + fc2 + both residuals in one kernel (tail16_kernel), with the next block's
+// LN1 + in_proj or, after the last block, ln_f + scores + pooling partials when fused; then the gated patch, the lone token
+// (fp32 matrix-vector products on the fp32 originals, lone_token.hip) and the [PAD] prefix
+int tail16(ChunkCtx& c, int i, const BlockW& w) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const BlockF32& f = *w.f;
+    const NetF32& n = h->net;
+    const bool last = i + 1 == NLAYER;
+    StageTimer t(h, st, CLM_STAGE_TAIL);
+    const ScorePoolArgs spa{h->h.get<float>(), n.lnf_g, n.lnf_b, gemm_packing(h, p).score.get(), n.att_b1, n.att_w2, n.att_b2,
+                            h->scores.get<float>(), h->partial.get<float>(), p.Bc, p.L, p.nt128, h->cfg.ln_eps};
+    TailArgs ta{h->y.get(), h->h.get<float>(), w.w_out, w.w_fc1, w.w_fc2, f.b_out, f.ln2_g, f.ln2_b, f.b_fc1, f.b_fc2, p.Bc, p.L, p.Lp,
+                h->cfg.ln_eps, p.Lmain, (p.id_resid && i == 0) ? h->ids8.get<unsigned char>() : nullptr, n.emb,
+                nullptr, nullptr, nullptr, nullptr, nullptr, spa};
+    ta.ylo = c.ylo();
+    ta.mlp_lo = p.mlpc;
+    ta.tiles = h->tile_list.get<int>();
+    const BlockF32* nf = last ? nullptr : &h->blk[i + 1];
+    if (p.fused16 && !last) {
+        ta.n_w = block_weights(h, p, i + 1).w_in; ta.n_bias = nf->b_in; ta.n_g = nf->ln1_g; ta.n_b = nf->ln1_b; ta.n_z = h->z.get();
+        if (p.zgated) {
+            ta.zg = 1; ta.n_fir = h->fir[i + 1].get<float4>(); ta.edge_bnd = h->edge_bnd.get<float2>();
+            ta.edge_read = p.peel ? h->edge_read.get<float2>() : nullptr;
+            ta.zlo = p.lo;
+        }
+    }
+    launch_tail16(p.prec, ta, !p.fused16 ? NEXT_NONE : (last ? NEXT_SCORE : NEXT_INPROJ), st);
+    if (ta.zg) launch_gated_patch(p.prec, ta, st);          // tokens 0, 1 of the workgroup ranges that start inside a read
+    if (p.peel) {
+        LoneTokenArgs la{};
+        la.y = h->y.get(); la.h = h->h.get<float>(); la.ids8 = ta.ids8; la.emb = ta.emb;
+        la.w_out = f.w[1]; la.b_out = f.b_out; la.ln2_g = f.ln2_g; la.ln2_b = f.ln2_b;
+        la.w_fc1 = f.w[2]; la.b_fc1 = f.b_fc1; la.w_fc2 = f.w[3]; la.b_fc2 = f.b_fc2;
+        la.last = last;
+        if (last) {
+            la.n_g = n.lnf_g; la.n_b = n.lnf_b;
+            la.att_w1 = n.att_w1; la.att_b1 = n.att_b1; la.att_w2 = n.att_w2; la.att_b2 = n.att_b2;
+            la.scores = h->scores.get<float>(); la.partial = h->partial.get<float>();
+        } else {
+            la.n_g = nf->ln1_g; la.n_b = nf->ln1_b; la.n_w = nf->w[0]; la.n_bias = nf->b_in; la.n_z = h->z.get();
+            if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read.get<float2>(); }
+        }
+        la.ws = h->lone_ws.get<float>();
+        la.B = p.Bc; la.L = p.L; la.Lp = p.Lp; la.ntiles = p.nt128; la.eps = h->cfg.ln_eps;
+        la.ylo = c.ylo(); la.zlo = ta.zlo;
+        launch_lone_token(p.prec, la, st);
+    }
+    return p.fused16 ? prefix_hooks(c, i, ta.zg ? 2 * D : D3, ta.zlo ? 2 * D : 0) : CLM_OK;
+}
+
+// exact fp32 / fp16x3 block tail (tail32.hip), the next block's in_proj or -- the last block -- ln_f + pooling scores + per-tile
+// pooling partials on the tile still on chip (T32_SCORE); then the [PAD] prefix
+int tail32(ChunkCtx& c, int i, const BlockW& w) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const BlockF32& f = *w.f;
+    const NetF32& n = h->net;
+    StageTimer t(h, st, CLM_STAGE_TAIL);
+    const bool last = i + 1 == NLAYER;
+    const BlockF32* nf = last ? nullptr : &h->blk[i + 1];
+    const Tail32Score ts{tail_packing(h, p).score.get(), n.att_b1, n.att_w2, n.att_b2, n.lnf_g, n.lnf_b, h->scores.get<float>(), h->partial.get<float>()};
+    launch_tail32(h->y.get<float>(), h->h.get<float>(), w.t_out, w.t_fc1, w.t_fc2, last ? nullptr : block_weights(h, p, i + 1).t_in, f.b_out,
+                  f.b_fc1, f.b_fc2, last ? nullptr : nf->b_in, f.ln2_g, f.ln2_b, last ? nullptr : nf->ln1_g, last ? nullptr : nf->ln1_b,
+                  h->z.get<float>(), p.Bc, p.L, p.Lp, h->cfg.ln_eps, st, p.x3, p.pad_skip ? h->pad_p0.get<int>() : nullptr, last ? &ts : nullptr,
+                  (i == 0 && p.id_resid) ? h->ids8.get<unsigned char>() : nullptr, n.emb);
+    return prefix_hooks(c, i, D3, 0);
+}
+
+// the separate kernels: a debug stop after out_proj (16-bit modes), the unfused exact-fp32 path
+int tail_unfused(ChunkCtx& c, int i, const BlockW& w) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const BlockF32& f = *w.f;
     {
-        StageTimer t(h, st, CLM_STAGE_EMBED);
-        // (exact / fp16x3 engine, one-shot convolution: block 0 reads z from the id table and its tail gathers the residual rows from
-        //  the embedding table -- h is first written by that tail kernel, as in the 16-bit id path)
-        const bool id32 = fused32 && S == 1 && !h->no_idconv;
-        launch_embed(ids, ids_dtype, row_stride, W(h, "bb.embeddings.word_embeddings.weight"), (idpath || id32) ? nullptr : h->h.get<float>(),
-                     h->ids8.get<unsigned char>(), Bc, L, Lp, st, h->bad_ids);
+        StageTimer t(h, st, CLM_STAGE_OUTPROJ);
+        if (p.tuned16) launch_outproj16(p.prec, h->y.get(), w.w_out, f.b_out, h->h.get<float>(), p.Bc, p.L, p.Lp, st);
+        else launch_outproj(h->y.get(), w.w_out, f.b_out, h->h.get<float>(), p.Bc, p.L, p.Lp, st);
     }
-    if (stop_here(h, -1, CLM_STAGE_EMBED)) return CLM_OK;
-    if (tuned16 || pad_skip) launch_pad_tiles(h->ids8.get<unsigned char>(), Bc, Lp, Lmain, pad_skip ? 1 : 0, h->pad_p0.get<int>(), h->tile_list.get<int>(), st);
-    // does block j's (segmented) convolution leave out the segments inside the [PAD] prefix of both reads of a pair (SegPrefix)?  Block 0
-    // looks z up by token id, the others read the gated hand-over; reads of S * 8192 + 1 tokens need the table's dot-product sums, which
-    // belong to ONE length
-    // (with it the pairs of those convolutions are formed by descending prefix: perm / partner live behind p0)
-    int* const pair_perm = h->pad_p0.get<int>() + Bc;
-    int* const pair_partner = h->pad_p0.get<int>() + 2 * Bc;
-    if (pad_skip && S > 1) launch_pair_order(h->pad_p0.get<int>(), Bc, pair_perm, pair_partner, st);
-    auto seg_skip_layer = [&](int j) {
-        return pad_skip && S > 1 && fuse_next && !h->capture && (j == 0 ? idpath : zgated) && ptab->gspec[j] &&
-               (!kr || L == ptab->L);
-    };
-
-    // 16-bit block tail: out_proj + LN2 + fc1 + GELU + fc2 + both residuals in one kernel (tail16_kernel), with the next block's
-    // LN1 + in_proj or, after the last block, ln_f + scores + pooling partials when fuse_next; then the gated patch, the lone token
-    // and the [PAD] prefix
-    auto tail16 = [&](int i, const LayerW& lw) -> int {
-        StageTimer t(h, st, CLM_STAGE_TAIL);
-        const bool mlpc = prec == PREC_F16C && h->mlp_lo;
-        TailArgs ta{h->y.get(), h->h.get<float>(), lw.w_out, mlpc ? h->packed_mlpc[i][0].get() : lw.w_fc1, mlpc ? h->packed_mlpc[i][1].get() : lw.w_fc2, lw.b_out,
-                    lw.ln2_g, lw.ln2_b, lw.b_fc1, lw.b_fc2, Bc, L, Lp,
-                    eps, Lmain, (idpath && i == 0) ? h->ids8.get<unsigned char>() : nullptr, W(h, "bb.embeddings.word_embeddings.weight"),
-                    nullptr, nullptr, nullptr, nullptr, nullptr, spa};
-        ta.ylo = ylo;
-        ta.mlp_lo = mlpc;
-        ta.tiles = h->tile_list.get<int>();
-        int next = NEXT_NONE;
-        if (fuse_next && i + 1 < NLAYER) {
-            const LayerW& nx = h->lw[i + 1];
-            ta.n_w = nx.w_in; ta.n_bias = nx.b_in; ta.n_g = nx.ln1_g; ta.n_b = nx.ln1_b; ta.n_z = h->z.get();
-            next = NEXT_INPROJ;
-            if (zgated) {
-                ta.zg = 1; ta.n_fir = h->fir[i + 1].get<float4>(); ta.edge_bnd = h->edge_bnd.get<float2>();
-                ta.edge_read = peel ? h->edge_read.get<float2>() : nullptr;
-                ta.zlo = ylo != nullptr;
-            }
-        } else if (fuse_next) {
-            next = NEXT_SCORE;
-        }
-        launch_tail16(prec, ta, next, st);
-        if (ta.zg) launch_gated_patch(prec, ta, st);        // tokens 0, 1 of the workgroup ranges that start inside a read
-        if (peel) {
-            const std::string p = "bb.layers." + std::to_string(i) + ".", pn = "bb.layers." + std::to_string(i + 1) + ".";
-            const bool last = i + 1 == NLAYER;
-            LoneTokenArgs la{};
-            la.y = h->y.get(); la.h = h->h.get<float>(); la.ids8 = ta.ids8; la.emb = ta.emb;
-            la.w_out = W(h, p + "mixer.out_proj.weight"); la.b_out = lw.b_out; la.ln2_g = lw.ln2_g; la.ln2_b = lw.ln2_b;
-            la.w_fc1 = W(h, p + "mlp.fc1.weight"); la.b_fc1 = lw.b_fc1; la.w_fc2 = W(h, p + "mlp.fc2.weight"); la.b_fc2 = lw.b_fc2;
-            la.last = last;
-            if (last) {
-                la.n_g = W(h, "bb.ln_f.weight"); la.n_b = W(h, "bb.ln_f.bias");
-                la.att_w1 = W(h, "head.attention.0.weight"); la.att_b1 = W(h, "head.attention.0.bias");
-                la.att_w2 = W(h, "head.attention.2.weight"); la.att_b2 = W(h, "head.attention.2.bias");
-                la.scores = h->scores.get<float>(); la.partial = h->partial.get<float>();
-            } else {
-                const LayerW& nx = h->lw[i + 1];
-                la.n_g = nx.ln1_g; la.n_b = nx.ln1_b; la.n_w = W(h, pn + "mixer.in_proj.weight"); la.n_bias = nx.b_in; la.n_z = h->z.get();
-                if (ta.zg) { la.n_fir = ta.n_fir; la.edge_read = h->edge_read.get<float2>(); }
-            }
-            la.ws = h->lone_ws.get<float>();
-            la.B = Bc; la.L = L; la.Lp = Lp; la.ntiles = (L + 127) / 128; la.eps = eps;
-            la.ylo = ylo; la.zlo = ta.zlo;
-            launch_lone_token(prec, la, st);
-        }
-        // the [PAD] prefix: what this block leaves for the next stage, copied out of (capture) or in from (pad_skip) the table
-        const int nrow16 = ta.zg ? 2 * D : D3, nlo = ta.zlo ? 2 * D : 0;
-        if (h->capture && fuse_next) {
-            if (next == NEXT_INPROJ) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1].get(), h->z.get(), (size_t)D3 * Lp * elem_size(prec), hipMemcpyDeviceToDevice, st));
-            else {
-                HIPCHK(h, hipMemcpyAsync(h->capture->scores.get<float>(), h->scores.get<float>(), (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->partial.get<float>(), h->partial.get<float>(), (size_t)((L + 127) / 128) * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
-            }
-        } else if (pad_skip) {
-            if (next == NEXT_INPROJ)      // (rows of segments the next convolution will not read are not copied)
-                launch_prefix_fill_z(h->pad_p0.get<int>(), h->z.get(), ptab->z[i + 1].get(), Bc, Lp, ptab->Lp, Lmain, (int)elem_size(prec), nrow16, nlo, st,
-                                     seg_skip_layer(i + 1) ? S : 0, pair_partner);
-            else
-                launch_prefix_fill_pool(h->pad_p0.get<int>(), h->scores.get<float>(), h->partial.get<float>(), ptab->scores.get<float>(), ptab->partial.get<float>(), Bc, L, (L + 127) / 128, Lmain, st);
-        }
-        return CLM_OK;
-    };
-
-    // exact fp32 / fp16x3 block tail (tail32.hip), the next block's in_proj or -- the last block -- ln_f + pooling scores + per-tile
-    // pooling partials on the tile still on chip (T32_SCORE); then the [PAD] prefix
-    auto tail32 = [&](int i, const LayerW& lw, bool idconv) -> int {
-        StageTimer t(h, st, CLM_STAGE_TAIL);
-        const LayerW* nx = i + 1 < NLAYER ? &(x3 ? h->lwx[i + 1] : (alt32 ? h->lw32[i + 1] : h->lw[i + 1])) : nullptr;
-        const int nt32 = (L + T32_TILE - 1) / T32_TILE;
-        const Tail32Score ts{x3 ? h->packed_score32x.get() : h->packed_score32t.get(), W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                             W(h, "head.attention.2.bias"), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores.get<float>(), h->partial.get<float>()};
-        launch_tail32(h->y.get<float>(), h->h.get<float>(), lw.t_out, lw.t_fc1, lw.t_fc2, nx ? nx->t_in : nullptr, lw.b_out,
-                      lw.b_fc1, lw.b_fc2, nx ? nx->b_in : nullptr, lw.ln2_g, lw.ln2_b, nx ? nx->ln1_g : nullptr,
-                      nx ? nx->ln1_b : nullptr, h->z.get<float>(), Bc, L, Lp, eps, st, x3, pad_skip ? h->pad_p0.get<int>() : nullptr,
-                      nx ? nullptr : &ts, (i == 0 && idconv) ? h->ids8.get<unsigned char>() : nullptr, W(h, "bb.embeddings.word_embeddings.weight"));
-        if (h->capture) {
-            if (nx) HIPCHK(h, hipMemcpyAsync(h->capture->z[i + 1].get(), h->z.get(), (size_t)D3 * Lp * 4, hipMemcpyDeviceToDevice, st));
-            else {
-                HIPCHK(h, hipMemcpyAsync(h->capture->hfin.get<float>(), h->h.get<float>(), (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->scores.get<float>(), h->scores.get<float>(), (size_t)L * 4, hipMemcpyDeviceToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(h->capture->partial.get<float>(), h->partial.get<float>(), (size_t)nt32 * POOL_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
-            }
-        } else if (pad_skip) {
-            if (nx) launch_prefix_fill_z(h->pad_p0.get<int>(), h->z.get(), ptab->z[i + 1].get(), Bc, Lp, ptab->Lp, L, 4, D3, 0, st);
-            else {
-                launch_prefix_fill_h(h->pad_p0.get<int>(), h->h.get<float>(), ptab->hfin.get<float>(), Bc, L, L, st);
-                launch_prefix_fill_pool(h->pad_p0.get<int>(), h->scores.get<float>(), h->partial.get<float>(), ptab->scores.get<float>(), ptab->partial.get<float>(), Bc, L, nt32, L, st, 128 / T32_TILE);
-            }
-        }
-        return CLM_OK;
-    };
-
-    for (int i = 0; i < NLAYER; ++i) {
-        const LayerW& lw = x3 ? h->lwx[i] : (alt32 ? h->lw32[i] : h->lw[i]);
-        // block 0 in the 16-bit modes: its in_proj output is a function of the token id alone, the convolution looks it
-        // up (ztab), single-shot and segmented kernel alike -- unless a debug stop asks for z itself or CLM_DEBUG=no_idconv
-        // (exact fp32 with the fused tail, single-shot convolution: the same table -- it is fp32 -- so block 0 needs no in_proj launch)
-        const bool idconv = i == 0 && !h->no_idconv && ((tuned16 && !stop_here(h, 0, CLM_STAGE_INPROJ)) || (fused32 && S == 1));
-        if (!idconv && !(fuse_next && i > 0) && !(fused32 && i > 0)) {
-            StageTimer t(h, st, CLM_STAGE_INPROJ);
-            if (tuned16) launch_inproj16(prec, h->h.get<float>(), lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z.get(), Bc, L, Lp, eps, st);
-            else launch_inproj(h->h.get<float>(), lw.ln1_g, lw.ln1_b, lw.w_in, lw.b_in, h->z.get(), Bc, L, Lp, eps, st);
-        }
-        if (stop_here(h, i, CLM_STAGE_INPROJ)) return CLM_OK;
-        {
-            StageTimer t(h, st, CLM_STAGE_CONV);
-            if (S == 1)
-                launch_hyena_conv(prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->tw.get<float2>(), fs->ktime[i].get<float>(), lw.short_w, lw.short_b, Bc, L, Lp,
-                                  fs->logn, idconv ? h->ids8.get<unsigned char>() : nullptr, idconv ? h->ztab.get<float>() : nullptr, st,
-                                  h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), fs->kfp[i].get<float2>(), ylo);
-            else {
-                // [PAD]-prefix reuse: segments inside the prefix of both reads of a pair come from the table (SegPrefix).  Reads of
-                // S * 8192 + 1 tokens carry the last token's dot product through the segments: its table sums belong to ONE length
-                SegPrefix pfx;
-                if (h->capture && h->capture->gspec[i]) {
-                    pfx.dots_out = kr ? h->capture->dots[i].get<float>() : nullptr;
-                    pfx.dots_segs = h->capture->S - 1;
-                } else if (seg_skip_layer(i)) {
-                    pfx.p0 = h->pad_p0.get<int>();
-                    pfx.perm = pair_perm;
-                    pfx.tab = ptab->gspec[i].get<float2>();
-                    pfx.tab_segs = ptab->S;
-                    pfx.dots_in = ptab->dots[i].get<float>();
-                    pfx.dots_segs = ptab->S - 1;
-                }
-                launch_hyena_conv_seg(prec, h->z.get(), h->y.get(), fs->kf[i].get<float2>(), fs->KS, fs->tw.get<float2>(), lw.short_w, lw.short_b, h->gscratch.get<float2>(), Bc,
-                                      L, Lp, S, kr ? kr->p[i].get<float>() : nullptr, kr ? kr->stride : 0, idconv ? h->ids8.get<unsigned char>() : nullptr,
-                                      idconv ? h->ztab.get<float>() : nullptr, st, h->conv_flags | ((zgated && i > 0) ? CONV_GATED : 0), ylo, pfx);
-                if (h->capture && h->capture->gspec[i]) {   // (one read = pair 0: [256][S][N] at the head of the scratch), then pair form
-                    HIPCHK(h, hipMemcpyAsync(h->capture->gspec[i].get<float2>(), h->gscratch.get<float2>(), (size_t)D * S * 16384 * sizeof(float2), hipMemcpyDeviceToDevice, st));
-                    launch_spectra_pair_form(h->capture->gspec[i].get<float2>(), S, st);
-                }
-            }
-        }
-        if (stop_here(h, i, CLM_STAGE_CONV)) return CLM_OK;
-        const bool stop_mid = stop_here(h, i, CLM_STAGE_OUTPROJ);
-        if (tuned16 && !stop_mid) {
-            rc = tail16(i, lw);
-            if (rc) return rc;
-        } else if (fused32) {
-            rc = tail32(i, lw, idconv);
-            if (rc) return rc;
-        } else {   // the separate kernels: a debug stop after out_proj (16-bit modes), the unfused exact-fp32 path
-            {
-                StageTimer t(h, st, CLM_STAGE_OUTPROJ);
-                if (tuned16) launch_outproj16(prec, h->y.get(), lw.w_out, lw.b_out, h->h.get<float>(), Bc, L, Lp, st);
-                else launch_outproj(h->y.get(), lw.w_out, lw.b_out, h->h.get<float>(), Bc, L, Lp, st);
-            }
-            if (stop_mid) return CLM_OK;
-            {
-                StageTimer t(h, st, CLM_STAGE_FC1);
-                launch_fc1(h->h.get<float>(), lw.ln2_g, lw.ln2_b, lw.w_fc1, lw.b_fc1, h->u.get(), Bc, L, eps, st);
-            }
-            if (stop_here(h, i, CLM_STAGE_FC1)) return CLM_OK;
-            StageTimer t(h, st, CLM_STAGE_FC2);
-            launch_fc2(h->u.get(), lw.w_fc2, lw.b_fc2, h->h.get<float>(), Bc, L, st);
-        }
-        if (stop_here(h, i, CLM_STAGE_FC2) || (tuned16 && stop_here(h, i, CLM_STAGE_FC1))) return CLM_OK;
+    if (stop_here(h, i, CLM_STAGE_OUTPROJ)) return STOPPED;
+    {
+        StageTimer t(h, st, CLM_STAGE_FC1);
+        launch_fc1(h->h.get<float>(), f.ln2_g, f.ln2_b, w.w_fc1, f.b_fc1, h->u.get(), p.Bc, p.L, h->cfg.ln_eps, st);
     }
-    if (tuned16) {   // score + pooling partials in one pass over h, merged by the classifier kernel
-        if (!fuse_next) {
-            StageTimer t(h, st, CLM_STAGE_SCORE);
-            launch_score_pool16(prec, h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
-                                W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"),
-                                W(h, "head.attention.2.bias"), h->scores.get<float>(), h->partial.get<float>(), Bc, L, eps, st);
-        }
+    if (stop_here(h, i, CLM_STAGE_FC1)) return STOPPED;
+    StageTimer t(h, st, CLM_STAGE_FC2);
+    launch_fc2(h->u.get(), w.w_fc2, f.b_fc2, h->h.get<float>(), p.Bc, p.L, st);
+    return CLM_OK;
+}
+
+// One Hyena block: in_proj (when no tail kernel has done it and no table holds it), convolution, tail
+int run_block(ChunkCtx& c, int i) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const BlockW w = block_weights(h, p, i);
+    const bool idconv = i == 0 && p.id_conv;
+    if (!idconv && !(p.fused && i > 0)) {
+        StageTimer t(h, st, CLM_STAGE_INPROJ);
+        if (p.tuned16) launch_inproj16(p.prec, h->h.get<float>(), w.f->ln1_g, w.f->ln1_b, w.w_in, w.f->b_in, h->z.get(), p.Bc, p.L, p.Lp, h->cfg.ln_eps, st);
+        else launch_inproj(h->h.get<float>(), w.f->ln1_g, w.f->ln1_b, w.w_in, w.f->b_in, h->z.get(), p.Bc, p.L, p.Lp, h->cfg.ln_eps, st);
+    }
+    if (stop_here(h, i, CLM_STAGE_INPROJ)) return STOPPED;
+    if (int rc = stage_conv(c, i, w, idconv)) return rc;
+    if (stop_here(h, i, CLM_STAGE_CONV)) return STOPPED;
+    const int rc = (p.tuned16 && !stop_here(h, i, CLM_STAGE_OUTPROJ)) ? tail16(c, i, w) : (p.fused32 ? tail32(c, i, w) : tail_unfused(c, i, w));
+    if (rc) return rc;
+    return (stop_here(h, i, CLM_STAGE_FC2) || (p.tuned16 && stop_here(h, i, CLM_STAGE_FC1))) ? STOPPED : CLM_OK;
+}
+
+// ln_f + attention pooling + classifier
+int stage_head(ChunkCtx& c, float* logits) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const NetF32& n = h->net;
+    const void* const w1 = gemm_packing(h, p).score.get();
+    float *const hh = h->h.get<float>(), *const scores = h->scores.get<float>(), *const partial = h->partial.get<float>();
+    const float eps = h->cfg.ln_eps;
+    if (p.tuned16 && !p.fused16) {   // score + pooling partials in one pass over h, merged by the classifier kernel
+        StageTimer t(h, st, CLM_STAGE_SCORE);
+        launch_score_pool16(p.prec, hh, n.lnf_g, n.lnf_b, w1, n.att_b1, n.att_w2, n.att_b2, scores, partial, p.Bc, p.L, eps, st);
+    }
+    if (p.tuned16 || p.fused32) {    // (exact fused: scores and per-tile pooling partials came out of the last block's tail kernel)
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_tiles(h->partial.get<float>(), (L + 127) / 128, h->hw, h->pooled.get<float>(), logits, Bc, st);
-    } else if (fused32) {   // scores and per-tile pooling partials came out of the last block's tail kernel
-        StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_tiles(h->partial.get<float>(), (L + T32_TILE - 1) / T32_TILE, h->hw, h->pooled.get<float>(), logits, Bc, st);
+        launch_head_tiles(partial, p.nt_pool, h->hw, h->pooled.get<float>(), logits, p.Bc, st);
     } else {
         {
             StageTimer t(h, st, CLM_STAGE_SCORE);
-            launch_score(h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), packed_score,
-                         W(h, "head.attention.0.bias"), W(h, "head.attention.2.weight"), W(h, "head.attention.2.bias"),
-                         h->scores.get<float>(), Bc, L, eps, st);
+            launch_score(hh, n.lnf_g, n.lnf_b, w1, n.att_b1, n.att_w2, n.att_b2, scores, p.Bc, p.L, eps, st);
         }
         {
             StageTimer t(h, st, CLM_STAGE_POOL);
-            launch_softmax_stats(h->scores.get<float>(), h->stats.get<float>(), Bc, L, st);
-            launch_pool(h->h.get<float>(), W(h, "bb.ln_f.weight"), W(h, "bb.ln_f.bias"), h->scores.get<float>(), h->stats.get<float>(), h->partial.get<float>(), Bc, L, eps,
-                        st);
+            launch_softmax_stats(scores, h->stats.get<float>(), p.Bc, p.L, st);
+            launch_pool(hh, n.lnf_g, n.lnf_b, scores, h->stats.get<float>(), partial, p.Bc, p.L, eps, st);
         }
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
-        launch_head_mlp(h->partial.get<float>(), h->hw, h->pooled.get<float>(), logits, Bc, st);
+        launch_head_mlp(partial, h->hw, h->pooled.get<float>(), logits, p.Bc, st);
     }
     HIPCHK(h, hipGetLastError());
+    return CLM_OK;
+}
+
+int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st) {
+    ChunkCtx c{h, plan_chunk(h, Bc, L), st};
+    const ChunkPlan& p = c.p;
+    // filters of the length class, workspace, [PAD] table
+    if (int rc = ensure_filters(h, L, st, &c.fs, &c.kr)) return rc;
+    if (int rc = size_workspace(c)) return rc;
+    if (p.pad_skip) {                                        // (before this chunk's ids land in the workspace: the build runs through it)
+        if (int rc = ensure_pad_table(h, p, st, &c.ptab)) return rc;
+        if (int rc = size_workspace(c)) return rc;           // (the build may have regrown -- never shrunk -- the buffers; cheap when not)
+        if (int rc = ensure_filters(h, L, st, &c.fs, &c.kr)) return rc;   // (... or added a filter class: the vector behind fs moved)
+    }
+    if (p.zgated && tail16_grid(tiles_of(p.Lmain, 128) * Bc) > 1024)
+        return fail(h, CLM_E_UNSUPPORTED, "more than 1024 compute units: edge_bnd is sized for 1024 workgroups");
+    // embedding rows (unless block 0 gathers them itself) and clamped ids, then the [PAD] prefixes: tile list, pair order
+    unsigned char* const ids8 = h->ids8.get<unsigned char>();
+    {
+        StageTimer t(h, st, CLM_STAGE_EMBED);
+        launch_embed(ids, ids_dtype, row_stride, h->net.emb, p.id_resid ? nullptr : h->h.get<float>(), ids8, Bc, L, p.Lp, st, h->bad_ids);
+    }
+    if (stop_here(h, -1, CLM_STAGE_EMBED)) return CLM_OK;
+    if (p.tuned16 || p.pad_skip) launch_pad_tiles(ids8, Bc, p.Lp, p.Lmain, p.pad_skip ? 1 : 0, h->pad_p0.get<int>(), h->tile_list.get<int>(), st);
+    if (p.pad_skip && p.S > 1) launch_pair_order(h->pad_p0.get<int>(), Bc, c.pair_perm(), c.pair_partner(), st);
+    int rc = CLM_OK;
+    for (int i = 0; i < NLAYER && !rc; ++i) rc = run_block(c, i);
+    if (!rc) rc = stage_head(c, logits);
+    return rc == STOPPED ? CLM_OK : rc;
+}
+
+size_t ids_elem_size(int dtype) { return dtype == CLM_DT_I64 ? 8 : (dtype == CLM_DT_I32 ? 4 : 1); }
+// The ids argument of `who` (clm_forward, clm_stage_ids, clm_selfcheck); out: the pointer that call writes its result through
+int check_ids_arg(clm_handle* h, const char* who, const void* ids, const void* out, int ids_dtype, int64_t row_stride, int B, int L) {
+    if (!ids || !out || B < 1 || L < 1 || row_stride < L) return fail(h, CLM_E_INVALID, std::string(who) + ": bad argument");
+    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
+        return fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
+    return CLM_OK;
+}
+
+int forward_all(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int B, int L, float* logits, hipStream_t st) {
+    const int chunk = chunk_for(h, L);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int Bc = B - b0 < chunk ? B - b0 : chunk;
+        const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * row_stride * ids_elem_size(ids_dtype);
+        if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st)) return rc;
+    }
     return CLM_OK;
 }
 
@@ -868,7 +967,7 @@ int clm_load_weight(clm_handle* h, const char* key, const void* data, int dtype,
         return CLM_OK;  // aliases of the shared sine module's parameter (implicit_filter.1.freq)
     const KeySpec* spec = nullptr;
     static thread_local std::vector<KeySpec> specs;
-    specs = expected_keys(h->cfg);
+    specs = expected_keys(h);
     for (auto& s : specs)
         if (s.key == ck) spec = &s;
     if (!spec) return fail(h, CLM_E_INVALID, std::string("unknown weight key: ") + key);
@@ -884,8 +983,6 @@ int clm_load_weight(clm_handle* h, const char* key, const void* data, int dtype,
     HIPCHK(h, hipSetDevice(h->device));
     Tensor& t = h->w[ck];
     if (!t.d) HIPCHK(h, t.d.alloc(n * 4));
-    t.shape = shp;
-    t.numel = n;
     if (dtype == CLM_DT_F32) {
         HIPCHK(h, hipMemcpy(t.d.get(), data, n * 4, hipMemcpyDefault));
     } else if (dtype == CLM_DT_F64 || dtype == CLM_DT_BF16 || dtype == CLM_DT_F16) {
@@ -906,9 +1003,10 @@ int clm_load_weight(clm_handle* h, const char* key, const void* data, int dtype,
 int clm_finalize(clm_handle* h) {
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    for (auto& s : expected_keys(h->cfg)) {
-        auto it = h->w.find(s.key);
+    for (auto& s : expected_keys(h)) {                       // the pointers every later launch takes: blk / net / hw
+        const auto it = h->w.find(s.key);
         if (it == h->w.end() || !it->second.loaded) return fail(h, CLM_E_MISSING, "missing weight: " + s.key);
+        *s.dst = it->second.d.get<float>();
     }
     HIPCHK(h, hipDeviceSynchronize());
     h->filters.clear();                                      // (functions of the weights; each packing below replaces its own)
@@ -917,107 +1015,38 @@ int clm_finalize(clm_handle* h) {
     // hi + lo halfs of the tail weights: an fp16x3 handle's own arithmetic; a 16-bit handle's short reads and first fall-back level
     const bool pack_x3 = (h->x3 || prec != PREC_F32) && !h->unfused_fp32;
     h->x3_wmax = 0.f;
-    if (pack_x3) {                // what the hi + lo packing must hold: the four tail products of every block and the score layer
-        std::vector<std::string> keys{"head.attention.0.weight"};
-        for (int i = 0; i < NLAYER; ++i)
-            for (const char* k : {"mixer.in_proj.weight", "mixer.out_proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"})
-                keys.push_back("bb.layers." + std::to_string(i) + "." + k);
-        for (const auto& k : keys) {
-            float m = 0.f;
-            HIPCHK(h, device_max_abs(W(h, k), h->w[k].numel, m));
-            if (m != m || m > h->x3_wmax) h->x3_wmax = m;          // (NaN stays)
-        }
-    }
     hipStream_t st = 0;
-    auto pack_as = [&](int pr, const std::string& key, int n, int k, DevBuf& out) -> int {
-        HIPCHK(h, out.alloc(packed_weight_bytes(pr, n, k)));
-        HIPCHK(h, hipMemsetAsync(out.get(), 0, out.bytes(), st));
-        launch_pack_weight(pr, W(h, key), out.get(), n, k, st);
-        return CLM_OK;
-    };
-    auto pack = [&](const std::string& key, int n, int k, DevBuf& out) -> int { return pack_as(prec, key, n, k, out); };
-    for (int i = 0; i < NLAYER; ++i) {
-        std::string p = "bb.layers." + std::to_string(i) + ".";
-        int rc;
-        if ((rc = pack(p + "mixer.in_proj.weight", D3, D, h->packed[i][0]))) return rc;
-        if ((rc = pack(p + "mixer.out_proj.weight", D, D, h->packed[i][1]))) return rc;
-        // (fp16c: the two MLP products run on plain fp16 weights -- tail16_kernel, MLP_PREC)
-        const int mlp_prec = prec == PREC_F16C ? (int)PREC_F16 : prec;
-        if ((rc = pack_as(mlp_prec, p + "mlp.fc1.weight", DI, D, h->packed[i][2]))) return rc;
-        if ((rc = pack_as(mlp_prec, p + "mlp.fc2.weight", D, DI, h->packed[i][3]))) return rc;
-        if (prec == PREC_F16C) {
-            if ((rc = pack_as(PREC_F16C, p + "mlp.fc1.weight", DI, D, h->packed_mlpc[i][0]))) return rc;
-            if ((rc = pack_as(PREC_F16C, p + "mlp.fc2.weight", D, DI, h->packed_mlpc[i][1]))) return rc;
+    for (int i = 0; i <= NLAYER; ++i)              // the four tail products of every block, then (i == NLAYER) the score layer
+        for (int j = 0; j < (i < NLAYER ? 4 : 1); ++j) {
+            const float* src = i < NLAYER ? h->blk[i].w[j] : h->net.att_w1;
+            const int n = i < NLAYER ? MAT_N[j] : D, k = i < NLAYER ? MAT_K[j] : D;
+            // (fp16c: the two MLP products run on plain fp16 weights -- tail16_kernel, MLP_PREC -- or, second level, on hi + lo)
+            const bool mlp16c = prec == PREC_F16C && i < NLAYER && j >= 2;
+            int rc;
+            if ((rc = pack_gemm(h, mlp16c ? (int)PREC_F16 : prec, src, n, k, h->pk_mode.slot(i, j), st))) return rc;
+            if (mlp16c && (rc = pack_gemm(h, PREC_F16C, src, n, k, h->pk_mlpc.slot(i, j), st))) return rc;
+            if (prec != PREC_F32 && (rc = pack_gemm(h, PREC_F32, src, n, k, h->pk_f32.slot(i, j), st))) return rc;
+            if ((rc = pack_tail(h, false, src, n, k, h->pk_t32.slot(i, j), st))) return rc;
+            if (!pack_x3) continue;
+            if ((rc = pack_tail(h, true, src, n, k, h->pk_x3.slot(i, j), st))) return rc;
+            float m = 0.f;                                   // what the hi + lo packing must hold
+            HIPCHK(h, device_max_abs(src, (size_t)n * k, m));
+            if (m != m || m > h->x3_wmax) h->x3_wmax = m;            // (NaN stays)
         }
-        LayerW& lw = h->lw[i];
-        lw.ln1_g = W(h, p + "norm1.weight"); lw.ln1_b = W(h, p + "norm1.bias");
-        lw.ln2_g = W(h, p + "norm2.weight"); lw.ln2_b = W(h, p + "norm2.bias");
-        lw.w_in = h->packed[i][0].get(); lw.w_out = h->packed[i][1].get(); lw.w_fc1 = h->packed[i][2].get(); lw.w_fc2 = h->packed[i][3].get();
-        lw.b_in = W(h, p + "mixer.in_proj.bias"); lw.b_out = W(h, p + "mixer.out_proj.bias");
-        lw.b_fc1 = W(h, p + "mlp.fc1.bias"); lw.b_fc2 = W(h, p + "mlp.fc2.bias");
-        lw.short_w = W(h, p + "mixer.short_filter.weight"); lw.short_b = W(h, p + "mixer.short_filter.bias");
-        lw.filt_bias = W(h, p + "mixer.filter_fn.bias");
-        {   // exact fp32 (the engine's own mode, or the referee / short-read / fall-back path of a 16-bit engine): the fused tail's packing
-            struct { const char* key; int n, k; } tw[4] = {{"mixer.in_proj.weight", D3, D}, {"mixer.out_proj.weight", D, D},
-                                                           {"mlp.fc1.weight", DI, D}, {"mlp.fc2.weight", D, DI}};
-            for (int j = 0; j < 4; ++j) {
-                HIPCHK(h, h->packed32t[i][j].alloc((size_t)tw[j].n * tw[j].k * 4));
-                launch_pack_f32t(W(h, p + tw[j].key), h->packed32t[i][j].get(), tw[j].n, tw[j].k, st);
-                if (pack_x3) {
-                    HIPCHK(h, h->packed32x[i][j].alloc((size_t)tw[j].n * tw[j].k * 4));
-                    launch_pack_x3(W(h, p + tw[j].key), h->packed32x[i][j].get(), tw[j].n, tw[j].k, st);
-                }
-            }
-            lw.t_in = h->packed32t[i][0].get(); lw.t_out = h->packed32t[i][1].get(); lw.t_fc1 = h->packed32t[i][2].get(); lw.t_fc2 = h->packed32t[i][3].get();
-        }
-        if (prec != PREC_F32) {   // the exact-fp32 packing next to the 16-bit one: fp16c's short reads, clm_selfcheck, clm_set_fallback
-            if ((rc = pack_as(PREC_F32, p + "mixer.in_proj.weight", D3, D, h->packed32[i][0]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mixer.out_proj.weight", D, D, h->packed32[i][1]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mlp.fc1.weight", DI, D, h->packed32[i][2]))) return rc;
-            if ((rc = pack_as(PREC_F32, p + "mlp.fc2.weight", D, DI, h->packed32[i][3]))) return rc;
-            h->lw32[i] = lw;
-            h->lw32[i].w_in = h->packed32[i][0].get(); h->lw32[i].w_out = h->packed32[i][1].get();
-            h->lw32[i].w_fc1 = h->packed32[i][2].get(); h->lw32[i].w_fc2 = h->packed32[i][3].get();
-        }
-        if (pack_x3) {            // the fp32 path's LayerW with the fused tail's weights as hi + lo halfs
-            h->lwx[i] = prec != PREC_F32 ? h->lw32[i] : lw;
-            h->lwx[i].t_in = h->packed32x[i][0].get(); h->lwx[i].t_out = h->packed32x[i][1].get();
-            h->lwx[i].t_fc1 = h->packed32x[i][2].get(); h->lwx[i].t_fc2 = h->packed32x[i][3].get();
-        }
-    }
-    {
-        int rc;
-        if ((rc = pack("head.attention.0.weight", D, D, h->packed_score))) return rc;
-        if (prec != PREC_F32 && (rc = pack_as(PREC_F32, "head.attention.0.weight", D, D, h->packed_score32))) return rc;
-        HIPCHK(h, h->packed_score32t.alloc((size_t)D * D * 4));
-        launch_pack_f32t(W(h, "head.attention.0.weight"), h->packed_score32t.get(), D, D, st);
-        if (pack_x3) {
-            HIPCHK(h, h->packed_score32x.alloc((size_t)D * D * 4));
-            launch_pack_x3(W(h, "head.attention.0.weight"), h->packed_score32x.get(), D, D, st);
-        }
-    }
     if (prec != PREC_F32)
         for (int i = 0; i < NLAYER; ++i) {
             HIPCHK(h, h->fir[i].alloc((size_t)D * 3 * sizeof(float4)));
-            launch_fir_table(h->lw[i].short_w, h->lw[i].short_b, h->lw[i].b_in, h->fir[i].get<float4>(), st);
+            launch_fir_table(h->blk[i].short_w, h->blk[i].short_b, h->blk[i].b_in, h->fir[i].get<float4>(), st);
         }
     HIPCHK(h, h->ztab.alloc((size_t)VOCAB * D3 * 4));
-    launch_ztab(W(h, "bb.embeddings.word_embeddings.weight"), W(h, "bb.layers.0.norm1.weight"),
-                W(h, "bb.layers.0.norm1.bias"), W(h, "bb.layers.0.mixer.in_proj.weight"),
-                W(h, "bb.layers.0.mixer.in_proj.bias"), h->ztab.get<float>(), h->cfg.ln_eps, st);
-    struct { const char* key; int rows, cols; } tr[5] = {
-        {"head.classifier.0.weight", HH, D}, {"head.classifier.3.weight", HH, HH},
-        {"head.classifier.6.layers.0.weight", HH, HH}, {"head.classifier.6.layers.3.weight", HH, HH},
-        {"head.output_layer.weight", NCLS, HH}};
+    launch_ztab(h->net.emb, h->blk[0].ln1_g, h->blk[0].ln1_b, h->blk[0].w[0], h->blk[0].b_in, h->ztab.get<float>(), h->cfg.ln_eps, st);
+    const struct { int rows, cols; const float** t; } tr[5] = {   // the classifier's matrices, transposed [in][out]
+        {HH, D, &h->hw.w0t}, {HH, HH, &h->hw.w3t}, {HH, HH, &h->hw.w60t}, {HH, HH, &h->hw.w63t}, {NCLS, HH, &h->hw.wot}};
     for (int j = 0; j < 5; ++j) {
         HIPCHK(h, h->head_t[j].alloc((size_t)tr[j].rows * tr[j].cols * 4));
-        launch_transpose(W(h, tr[j].key), h->head_t[j].get<float>(), tr[j].rows, tr[j].cols, st);
+        launch_transpose(h->net.cls[j], h->head_t[j].get<float>(), tr[j].rows, tr[j].cols, st);
+        *tr[j].t = h->head_t[j].get<float>();
     }
-    h->hw.w0t = h->head_t[0].get<float>(); h->hw.b0 = W(h, "head.classifier.0.bias");
-    h->hw.w3t = h->head_t[1].get<float>(); h->hw.b3 = W(h, "head.classifier.3.bias");
-    h->hw.w60t = h->head_t[2].get<float>(); h->hw.b60 = W(h, "head.classifier.6.layers.0.bias");
-    h->hw.w63t = h->head_t[3].get<float>(); h->hw.b63 = W(h, "head.classifier.6.layers.3.bias");
-    h->hw.wot = h->head_t[4].get<float>(); h->hw.bo = W(h, "head.output_layer.bias");
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
@@ -1030,48 +1059,30 @@ int clm_reserve(clm_handle* h, int B, int L) {
     HIPCHK(h, hipSetDevice(h->device));
     FilterSet* fs = nullptr;
     const ReversedFilter* kr = nullptr;
-    int rc = ensure_filters(h, L, 0, &fs, &kr);
-    if (rc) return rc;
+    if (int rc = ensure_filters(h, L, 0, &fs, &kr)) return rc;
     const int chunk = chunk_for(h, L);
-    int Bc = B < chunk ? B : chunk;
-    return ensure_workspace(h, Bc, L, 0);
+    return ensure_workspace(h, plan_chunk(h, B < chunk ? B : chunk, L), 0);
 }
 
 int clm_forward(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
                 float* logits_out, void* stream) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_forward before clm_finalize");
-    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L)
-        return fail(h, CLM_E_INVALID, "clm_forward: bad argument");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, "clm_forward: ids dtype must be i64, i32 or u8");
+    if (int rc = check_ids_arg(h, "clm_forward", ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = check_bad_ids(h)) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const size_t ies = ids_dtype == CLM_DT_I64 ? 8 : (ids_dtype == CLM_DT_I32 ? 4 : 1);
-    const int chunk = chunk_for(h, L);
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        int Bc = B - b0 < chunk ? B - b0 : chunk;
-        const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * ids_row_stride * ies;
-        int rc = forward_chunk(h, p, ids_dtype, ids_row_stride, Bc, L, logits_out + (size_t)b0 * NCLS, st);
-        if (rc) return rc;
-    }
-    return CLM_OK;
+    return forward_all(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 int clm_stage_ids(clm_handle* h, const void* host_ids, int ids_dtype, int64_t ids_row_stride, int B, int L, int* staged) {
     if (!h) return CLM_E_INVALID;
-    if (!host_ids || !staged || B < 1 || L < 1 || ids_row_stride < L)
-        return fail(h, CLM_E_INVALID, "clm_stage_ids: bad argument");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, "clm_stage_ids: ids dtype must be i64, i32 or u8");
+    if (int rc = check_ids_arg(h, "clm_stage_ids", host_ids, staged, ids_dtype, ids_row_stride, B, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     const int k = h->next_stage;
     clm_handle::Stage& s = h->stage[k];
     if (s.pending) return fail(h, CLM_E_STATE, "clm_stage_ids: both staging buffers hold batches not yet run (clm_forward_staged)");
-    const size_t ies = ids_dtype == CLM_DT_I64 ? 8 : (ids_dtype == CLM_DT_I32 ? 4 : 1);
-    const size_t bytes = (size_t)B * (size_t)ids_row_stride * ies;
+    const size_t bytes = (size_t)B * (size_t)ids_row_stride * ids_elem_size(ids_dtype);
     if (!s.copied) {
         HIPCHK(h, hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
         HIPCHK(h, hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
@@ -1125,40 +1136,27 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
                   float* max_abs_diff, int* labels_differ) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_selfcheck before clm_finalize");
-    if (!ids || !max_abs_diff || B < 1 || L < 1 || ids_row_stride < L) return fail(h, CLM_E_INVALID, "clm_selfcheck: bad argument");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, "clm_selfcheck: ids dtype must be i64, i32 or u8");
+    if (int rc = check_ids_arg(h, "clm_selfcheck", ids, max_abs_diff, ids_dtype, ids_row_stride, B, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     *max_abs_diff = 0.f;
     if (labels_differ) *labels_differ = 0;
-    if (h->cfg.precision == PREC_F32 && !h->x3) return CLM_OK;   // the handle IS the referee
+    if (is_exact(h)) return CLM_OK;
     if ((size_t)2 * B * NCLS * 4 > h->sc_logits.bytes()) {
         HIPCHK(h, hipStreamSynchronize(st));
         HIPCHK(h, h->sc_logits.reserve((size_t)2 * B * NCLS * 4));
     }
-    // pass 0: the arithmetic the handle's mode runs reads of this length in (whatever clm_set_fallback says); pass 1: exact fp32
-    const int mode_prec = (h->cfg.precision == PREC_F16C && L < h->f16c_min_len) ? (int)PREC_F32 : h->cfg.precision;
-    const bool prof = h->prof;
-    const int fallback = h->fallback;
-    h->prof = false;                                            // not part of anybody's timed region
-    h->fallback = 0;                                            // the MODE is on trial (short reads of fp16c: its fp16x3 kernels)
-    const size_t ies = ids_dtype == CLM_DT_I64 ? 8 : (ids_dtype == CLM_DT_I32 ? 4 : 1);
     int rc = CLM_OK;
-    for (int pass = 0; pass < 2 && !rc; ++pass) {
-        h->force_prec = pass == 0 ? mode_prec : (int)PREC_F32;
-        h->referee = pass == 1;
-        const int chunk = chunk_for(h, L);
-        for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
-            const int Bc = B - b0 < chunk ? B - b0 : chunk;
-            const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * ids_row_stride * ies;
-            rc = forward_chunk(h, p, ids_dtype, ids_row_stride, Bc, L, h->sc_logits.get<float>() + ((size_t)pass * B + b0) * NCLS, st);
+    {
+        ScopedRun scope(h);
+        h->run.fallback = 0;                                    // the MODE is on trial (short reads of fp16c: its fp16x3 kernels)
+        // pass 0: the arithmetic the handle's mode runs reads of this length in (whatever clm_set_fallback says); pass 1: exact fp32
+        for (int pass = 0; pass < 2 && !rc; ++pass) {
+            h->run.force_prec = pass == 0 ? mode_prec(h, L) : (int)PREC_F32;
+            h->run.referee = pass == 1;
+            rc = forward_all(h, ids, ids_dtype, ids_row_stride, B, L, h->sc_logits.get<float>() + (size_t)pass * B * NCLS, st);
         }
     }
-    h->force_prec = -1;
-    h->referee = false;
-    h->prof = prof;
-    h->fallback = fallback;
     if (rc) return rc;
     std::vector<float> host((size_t)2 * B * NCLS);
     HIPCHK(h, hipMemcpyAsync(host.data(), h->sc_logits.get<float>(), host.size() * 4, hipMemcpyDeviceToHost, st));
@@ -1196,7 +1194,7 @@ int clm_set_fallback(clm_handle* h, int on) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_set_fallback before clm_finalize");
     if (on < 0 || on > 2) return fail(h, CLM_E_INVALID, "clm_set_fallback: level must be 0, 1 or 2");
-    h->fallback = (h->cfg.precision == PREC_F32 && !h->x3) ? 0 : on;   // (an exact-fp32 handle has nothing to fall back to)
+    h->run.fallback = is_exact(h) ? 0 : on;                    // (an exact-fp32 handle has nothing to fall back to)
     return CLM_OK;
 }
 
@@ -1216,8 +1214,8 @@ int clm_set_short_read_len(clm_handle* h, int min_len) {
 
 int clm_effective_precision(const clm_handle* h, int L) {
     if (!h || L < 1) return CLM_E_INVALID;
-    const int p = effective_prec(h, L);
-    return (p == PREC_F32 && fused_fp32(h) && fp32_path_is_x3(h)) ? CLM_PREC_F16X3 : p;
+    const ChunkPlan p = plan_chunk(h, 1, L);
+    return p.x3 ? CLM_PREC_F16X3 : p.prec;
 }
 
 int clm_debug_stop_after(clm_handle* h, int layer, int stage) {
@@ -1231,7 +1229,7 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
     if (!h || !name || !host_out) return fail(h, CLM_E_INVALID, "clm_debug_fetch: bad argument");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    const size_t es = elem_size(effective_prec(h, h->last_L));
+    const size_t es = plan_chunk(h, h->last_B, h->last_L).es;
     const size_t B = h->last_B, L = h->last_L, Lp = h->last_Lp;
     const void* src = nullptr;
     size_t have = 0;
@@ -1256,7 +1254,7 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
 
 int clm_profile_enable(clm_handle* h, int on) {
     if (!h) return CLM_E_INVALID;
-    h->prof = on != 0;
+    h->run.prof = on != 0;
     return CLM_OK;
 }
 

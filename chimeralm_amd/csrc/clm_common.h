@@ -290,15 +290,6 @@ inline hipError_t device_max_abs(const float* d, size_t n, float& out) {
 // (measured 1.2e-4 .. 9.6e-4 in the logits); clm_selfcheck measures it on the loaded weights.
 enum Prec { PREC_F32 = 0, PREC_BF16 = 1, PREC_F16 = 2, PREC_F16C = 3 };
 
-struct LayerW {            // device pointers, fp32 unless noted
-    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    const void *w_in, *w_out, *w_fc1, *w_fc2;   // packed MFMA-fragment order, compute dtype
-    const float *b_in, *b_out, *b_fc1, *b_fc2;
-    const float *short_w, *short_b;             // [768][3], [768]
-    const float *filt_bias;                     // [256]  (D skip term)
-    const void *t_in = nullptr, *t_out = nullptr, *t_fc1 = nullptr, *t_fc2 = nullptr;   // exact fp32: the fused tail's packing (tail32.hip)
-};
-
 // embedding gather: ids [B, L] (dtype code CLM_DT_*) -> h fp32 [B, L, 256]
 void launch_embed(const void* ids, int ids_dtype, int64_t row_stride, const float* table, float* h,
                   unsigned char* ids8 /*[B][Lp] clamped ids, may be null*/, int B, int L, int Lp, hipStream_t st,
