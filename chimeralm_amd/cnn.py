@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._reload import reload_signature
 
 PRODUCTION = dict(vocab_size=12, embedding_dim=256, num_filters=[256, 256, 256], kernel_sizes=[7, 7, 7], pool_sizes=[4, 4, 4],
                   hidden_dim=512, number_of_classes=2, padding_idx=4)
@@ -86,7 +87,7 @@ class DNAConvNet(nn.Module):
     def _prepare(self, device: torch.device):
         # (not `_engine`: predict.py's end-of-run device check reads `net._engine` as the Hyena engine object)
         lib = N.load()
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        sig = reload_signature(self)
         if self._h is not None and self._dev == device and sig == self._sig:
             return lib
         prec = self._arith()
@@ -106,6 +107,10 @@ class DNAConvNet(nn.Module):
         self._check(lib.clm_cnn_finalize(self._h))
         self._sig = sig
         return lib
+
+    def refresh_weights(self) -> None:
+        """The next forward reloads the engine from this module's tensors: for edits the signature cannot see (`p.data.mul_()`)."""
+        self._sig = None
 
     def forward(self, input_ids: torch.Tensor, input_quals: torch.Tensor | None = None) -> torch.Tensor:
         """`input_quals` is accepted and ignored, as in the reference."""

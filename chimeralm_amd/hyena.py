@@ -18,6 +18,7 @@ import math
 import torch
 from torch import nn
 
+from ._reload import reload_signature
 from .engine import Engine
 
 # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_finalize)
@@ -241,7 +242,11 @@ class HyenaDna(nn.Module):
 
     # -------------------------------------------------------------------------------- engine plumbing
     def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+        return reload_signature(self)
+
+    def refresh_weights(self) -> None:
+        """The next forward reloads the engine from this module's tensors: for edits the signature cannot see (`p.data.mul_()`)."""
+        self._engine_sig = None
 
     def engine(self, device: torch.device) -> Engine:
         """Engine for `device`, (re)loaded whenever a parameter tensor was replaced or modified in place."""

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._reload import reload_signature
 
 X3_WEIGHT_LIMIT = 64.0                     # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates
 HEADDIM, D_CONV, VOCAB, PAD = 64, 4, 12, 4
@@ -130,7 +131,7 @@ class _MambaNet(nn.Module):
     def _prepare(self, device: torch.device):
         # (not `_engine`: predict.py's end-of-run device check reads `net._engine` as the Hyena engine object)
         lib = N.load()
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        sig = reload_signature(self)
         if self._h is not None and self._dev == device and sig == self._sig:
             return lib
         prec = self._arith()
@@ -142,6 +143,10 @@ class _MambaNet(nn.Module):
             raise
         self._dev, self._hprec, self._sig = device, prec, sig
         return lib
+
+    def refresh_weights(self) -> None:
+        """The next forward rebuilds the handles from this module's tensors: for edits the signature cannot see (`p.data.mul_()`)."""
+        self._sig = None
 
     def _run(self, lib, h, ids, dt, mask, out):
         B, L = ids.shape

@@ -29,6 +29,7 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._reload import reload_signature
 
 # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_tf_finalize)
 X3_WEIGHT_LIMIT = 64.0
@@ -103,7 +104,7 @@ class SequenceCNNTransformer(nn.Module):
             if rc != 0:
                 raise TransformerEngineError(lib.clm_tf_last_error(None).decode())
             self._h, self._dev, self._sig = h, device, None
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        sig = reload_signature(self)
         if sig != self._sig:                                   # weights replaced or modified in place -> reload
             for k, t in self.state_dict().items():
                 t = t.detach().float().contiguous()
@@ -115,6 +116,10 @@ class SequenceCNNTransformer(nn.Module):
             self._recheck_next = False
             self._report_x3(lib)
         return lib
+
+    def refresh_weights(self) -> None:
+        """The next forward reloads the engine from this module's tensors: for edits the signature cannot see (`p.data.mul_()`)."""
+        self._sig = None
 
     def _arith(self, lib) -> str:
         """The arithmetic the engine runs a forward in right now (`clm_tf_effective_precision`)."""

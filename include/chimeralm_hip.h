@@ -102,7 +102,9 @@ int clm_create(const clm_config* cfg, int device, clm_handle** out);
 int clm_load_weight(clm_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
 
 /* Packs weights for the kernels (MFMA fragment order, compute dtype) and checks completeness.
- * May be called again after further clm_load_weight calls; the cached filter spectra are dropped. */
+ * May be called again after further clm_load_weight calls; everything derived from the weights (packings, filter spectra, [PAD]
+ * tables, the fp16x3 range verdict) is rebuilt.  The switches are handle state, not weight state: the clm_set_fallback level,
+ * clm_set_mlp_compensation and clm_set_short_read_len stay as they were set (chimeralm_amd/hyena.py resets them itself). */
 int clm_finalize(clm_handle* h);
 
 /* Grow the workspace for batches up to B reads of L tokens (optional; clm_forward does it on demand). */
