@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
 #include <atomic>
 #include <cstdio>
 #include <map>
@@ -245,15 +246,22 @@ int use_gfx950(int device, const char* who) {
     return CLM_OK;
 }
 
-// An fp32 tensor `k` of `expected` (key -> shape) into the handle's `w`: a device copy, replacing the one loaded before
+// ---- expected weights of the transformer, CNN and Mamba engines: a handle's `expected` table, built ONCE by its *_create --------
+// canonical key -> shape and where *_finalize puts the device pointer (a field of the handle; null: read by finalize alone).
+// Sorted by key: the first missing weight finalize names is the first in key order.
+struct WeightSpec {
+    std::vector<int64_t> shape;
+    const float** dst;
+};
+using WeightTable = std::map<std::string, WeightSpec>;
+
+inline std::string canonical_weight_key(const char* key) {       // a Lightning checkpoint's "net." prefix is optional
+    const std::string k(key);
+    return k.rfind("net.", 0) == 0 ? k.substr(4) : k;
+}
+// `n` fp32 values as tensor `k` of the handle's `w`: a device copy, replacing the one loaded before
 template <class H>
-int load_f32(H* h, const char* who, const std::map<std::string, std::vector<int64_t>>& expected, const std::string& k, const void* data,
-             const int64_t* shape, int ndim) {
-    const auto it = expected.find(k);
-    if (it == expected.end()) return fail(h, CLM_E_INVALID, std::string(who) + ": unknown key " + k);
-    if (it->second != std::vector<int64_t>(shape, shape + ndim)) return fail(h, CLM_E_INVALID, std::string(who) + ": wrong shape for " + k);
-    size_t n = 1;
-    for (int64_t s : it->second) n *= (size_t)s;
+int store_f32(H* h, const std::string& k, const void* data, size_t n) {
     HIPCHK(h, hipSetDevice(h->device));
     h->w.erase(k);
     DevBuf d;
@@ -261,6 +269,50 @@ int load_f32(H* h, const char* who, const std::map<std::string, std::vector<int6
     HIPCHK(h, hipMemcpy(d.get(), data, n * 4, hipMemcpyDefault));
     h->w.emplace(k, std::move(d));
     h->finalized = false;
+    return CLM_OK;
+}
+// *_load_weight: an fp32 tensor `k` of the handle's table, checked against it
+template <class H>
+int load_f32(H* h, const char* who, const std::string& k, const void* data, const int64_t* shape, int ndim) {
+    const auto it = h->expected.find(k);
+    if (it == h->expected.end()) return fail(h, CLM_E_INVALID, std::string(who) + ": unknown key " + k);
+    if (it->second.shape != std::vector<int64_t>(shape, shape + ndim)) return fail(h, CLM_E_INVALID, std::string(who) + ": wrong shape for " + k);
+    size_t n = 1;
+    for (int64_t s : it->second.shape) n *= (size_t)s;
+    return store_f32(h, k, data, n);
+}
+// *_finalize: every tensor of the table is loaded (else CLM_E_MISSING) and its device pointer stands where the forward reads it
+template <class H>
+int resolve_weights(H* h, const char* who) {
+    for (const auto& kv : h->expected) {
+        const auto it = h->w.find(kv.first);
+        if (it == h->w.end()) return fail(h, CLM_E_MISSING, std::string(who) + ": missing weight " + kv.first);
+        if (kv.second.dst) *kv.second.dst = it->second.template get<float>();
+    }
+    return CLM_OK;
+}
+// *_finalize: loaded tensor `k` back on the host (what finalize computes in fp64 or repacks there), and a product of it up again
+template <class H>
+int host_f32(H* h, const char* who, const std::string& k, std::vector<float>& out) {
+    const auto it = h->w.find(k);
+    if (it == h->w.end()) return fail(h, CLM_E_MISSING, std::string(who) + ": missing weight " + k);
+    out.resize(it->second.bytes() / 4);
+    HIPCHK(h, hipMemcpy(out.data(), it->second.get(), it->second.bytes(), hipMemcpyDeviceToHost));
+    return CLM_OK;
+}
+template <class H>
+int upload_f32(H* h, DevBuf& d, const std::vector<float>& src) {
+    HIPCHK(h, d.alloc(src.size() * 4));
+    HIPCHK(h, hipMemcpy(d.get(), src.data(), src.size() * 4, hipMemcpyHostToDevice));
+    return CLM_OK;
+}
+// A convolution's taps, split as [taps][co][ci] fp32 on the device, each packed by pack(tap, dst) into tap_bytes of `out`.
+// Synchronises before it returns: the caller reuses or frees `split` next.
+template <class H, class Pack>
+int pack_taps(H* h, const float* split, int taps, size_t tap_bytes, DevBuf& out, Pack pack) {
+    HIPCHK(h, out.alloc(taps * tap_bytes));
+    for (int dk = 0; dk < taps; ++dk) pack(split + (size_t)dk * D * D, out.get<char>() + dk * tap_bytes);
+    HIPCHK(h, hipDeviceSynchronize());
     return CLM_OK;
 }
 
@@ -327,6 +379,24 @@ void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const fl
 void launch_enc32(const float* att, float* h, const void* w_o, const void* w1, const void* w2, const void* w_qkv, const float* b_o,
                   const float* b1, const float* b2, const float* b_qkv, const float* ln1_g, const float* ln1_b, const float* ln2_g,
                   const float* ln2_b, float* qkv, size_t M, float eps, hipStream_t st, bool x3 = false);
+// SequenceCNNTransformer weights as the kernels take them: device pointers resolved ONCE, by clm_tf_finalize (tf_model.hip).  The
+// four products of a layer are in_proj, out_proj, linear1, linear2: the order of TfLayerF32::w and of a TfPacking's slots
+struct TfLayerF32 {               // one encoder layer's tensors as loaded, fp32
+    const float* w[4];            // [out][in]: what the packers and the unfused path read
+    const float *b_in, *b_out, *b_ff1, *b_ff2;
+    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+};
+struct TfNetF32 {                 // ... and what belongs to no layer: embedding, pe, norm, the stem convolutions, pooling, classifier
+    const float *emb, *pe, *norm_g, *norm_b, *conv_w[3], *conv_b[3], *pool_w, *pool_b, *cls0_w, *cls0_b, *cls3_w, *cls3_b;
+};
+struct TfPacking {                // one packing of the matrices the MFMA kernels read (16-bit mode, t32 or x3)
+    std::vector<std::array<DevBuf, 4>> mat;   // per layer
+    DevBuf conv[3];                           // stem convolutions: three taps [dk][co][ci], each tap packed
+};
+// tf_fp32.hip: the forward with exact-fp32 products (the reference's precision; x3: on hi + lo halfs), up to the encoder output h
+size_t tf32_workspace_floats(int B, int L);
+int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
+                 const TfLayerF32* lay, const TfPacking& pk /*t32, or x3's*/, hipStream_t st, bool unfused, bool x3);
 
 // GEMM family (gemm.hip): exact fp32, the unfused path (CLM_DEBUG=unfused_fp32, debug stops); activations fp32.
 // z  = in_proj(LN1(h))      -> channel-major [B, 768, Lp]

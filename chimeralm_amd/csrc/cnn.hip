@@ -125,13 +125,29 @@ __global__ __launch_bounds__(512) void cnn_head_kernel(const float* __restrict__
 // ================================================================================================ engine + C ABI
 using namespace clm;
 
+// Weights as the kernels take them: device pointers resolved ONCE, by clm_cnn_finalize, and what it computes from the rest
+struct CnnF32 {                   // tensors the forward reads as loaded, fp32
+    const float *conv_b[3], *fc0_b, *fc4_w, *fc4_b;
+};
+struct CnnBn {                    // BatchNorm1d in eval mode as y = x * scale + shift
+    DevBuf scale, shift;
+};
+struct CnnDev {                   // finalize products
+    DevBuf table;                 // block 0: T[dk][tok][co]
+    DevBuf conv1, conv2;          // blocks 1 and 2: seven taps [dk][co][ci], each tap packed (f32t, or x3 halfs: x3_active)
+    CnnBn bn[4];                  // blocks 0 .. 2, fc.1
+    DevBuf fc0t;                  // fc.0.weight transposed [256][512]
+};
+
 struct clm_cnn_handle {
     int device = 0;
     bool x3 = false;                              // CLM_PREC_F16X3 handle
     bool x3_active = false;                       // ... and its block 1 / 2 weights are inside the packing's range (finalize)
     std::string err;
     std::map<std::string, DevBuf> w;              // fp32 device copies by reference key
-    std::map<std::string, DevBuf> dev;            // finalize products: table, packed taps, BN scale / shift, fc.0 transposed
+    WeightTable expected;                         // (clm_cnn_create)
+    CnnF32 f = {};
+    CnnDev dev;
     bool finalized = false;
     DevBuf ids8, x1, x2, part, pooled;            // workspace (clm_cnn_forward)
     int last_B = 0, last_L = 0;
@@ -139,21 +155,18 @@ struct clm_cnn_handle {
 
 namespace {
 
-std::map<std::string, std::vector<int64_t>> cnn_expected() {
-    std::map<std::string, std::vector<int64_t>> e;
-    e["embedding.weight"] = {cnn::VOC, D};
+// clm_cnn_create: the state-dict keys, their shapes and the field of h->f the forward reads each from (none: finalize alone reads it)
+void cnn_expect(clm_cnn_handle* h) {
+    WeightTable& e = h->expected;
+    e["embedding.weight"] = {{cnn::VOC, D}, nullptr};
     for (int i = 0; i < 3; ++i) {
         const std::string p = "conv_blocks." + std::to_string(i) + ".";
-        e[p + "0.weight"] = {D, D, cnn::K};
-        e[p + "0.bias"] = {D};
-        for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[p + "1." + s] = {D};
+        e[p + "0.weight"] = {{D, D, cnn::K}, nullptr}; e[p + "0.bias"] = {{D}, &h->f.conv_b[i]};
+        for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[p + "1." + s] = {{D}, nullptr};
     }
-    e["fc.0.weight"] = {cnn::HID, D};
-    e["fc.0.bias"] = {cnn::HID};
-    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[std::string("fc.1.") + s] = {cnn::HID};
-    e["fc.4.weight"] = {NCLS, cnn::HID};
-    e["fc.4.bias"] = {NCLS};
-    return e;
+    e["fc.0.weight"] = {{cnn::HID, D}, nullptr}; e["fc.0.bias"] = {{cnn::HID}, &h->f.fc0_b};
+    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) e[std::string("fc.1.") + s] = {{cnn::HID}, nullptr};
+    e["fc.4.weight"] = {{NCLS, cnn::HID}, &h->f.fc4_w}; e["fc.4.bias"] = {{NCLS}, &h->f.fc4_b};
 }
 
 bool is_batches_tracked(const std::string& k) {
@@ -161,25 +174,10 @@ bool is_batches_tracked(const std::string& k) {
     return k.size() >= s.size() && k.compare(k.size() - s.size(), s.size(), s) == 0;
 }
 
-int cnn_host(clm_cnn_handle* h, const std::string& k, std::vector<float>& out) {
-    const std::vector<int64_t> shp = cnn_expected().at(k);     // (a copy: the map is a temporary)
-    size_t n = 1;
-    for (int64_t s : shp) n *= (size_t)s;
-    out.resize(n);
-    HIPCHK(h, hipMemcpy(out.data(), h->w.at(k).get(), n * 4, hipMemcpyDeviceToHost));
-    return CLM_OK;
-}
-
-int cnn_upload(clm_cnn_handle* h, const std::string& name, const void* src, size_t bytes) {
-    DevBuf d;
-    HIPCHK(h, d.alloc(bytes));
-    HIPCHK(h, hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
-    h->dev[name] = std::move(d);
-    return CLM_OK;
-}
+int cnn_host(clm_cnn_handle* h, const std::string& k, std::vector<float>& out) { return host_f32(h, "clm_cnn_finalize", k, out); }
 
 // BatchNorm1d in eval mode as scale / shift, computed in fp64 and rounded once
-int cnn_bn(clm_cnn_handle* h, const std::string& p, const std::string& name, int n) {
+int cnn_bn(clm_cnn_handle* h, const std::string& p, CnnBn& bn, int n) {
     std::vector<float> g, b, m, v;
     int rc;
     if ((rc = cnn_host(h, p + "weight", g)) || (rc = cnn_host(h, p + "bias", b)) || (rc = cnn_host(h, p + "running_mean", m)) ||
@@ -191,8 +189,8 @@ int cnn_bn(clm_cnn_handle* h, const std::string& p, const std::string& name, int
         sc[i] = (float)s;
         sh[i] = (float)((double)b[i] - (double)m[i] * s);
     }
-    if ((rc = cnn_upload(h, name + ".scale", sc.data(), (size_t)n * 4))) return rc;
-    return cnn_upload(h, name + ".shift", sh.data(), (size_t)n * 4);
+    if ((rc = upload_f32(h, bn.scale, sc))) return rc;
+    return upload_f32(h, bn.shift, sh);
 }
 
 }  // namespace
@@ -207,26 +205,25 @@ int clm_cnn_create(int device, int precision, clm_cnn_handle** out) {
     clm_cnn_handle* h = new clm_cnn_handle();
     h->device = device;
     h->x3 = precision == CLM_PREC_F16X3;
+    cnn_expect(h);
     *out = h;
     return CLM_OK;
 }
 
 int clm_cnn_load_weight(clm_cnn_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!h || !key || !data || !shape || ndim < 0) return fail(h, CLM_E_INVALID, "clm_cnn_load_weight: null argument");
-    std::string k(key);
-    if (k.rfind("net.", 0) == 0) k = k.substr(4);
+    const std::string k = canonical_weight_key(key);
     if (is_batches_tracked(k)) return CLM_OK;                  // BatchNorm's step counter: not used in eval mode
     if (dtype != CLM_DT_F32) return fail(h, CLM_E_INVALID, "clm_cnn_load_weight: fp32 tensors only");
-    return load_f32(h, "clm_cnn_load_weight", cnn_expected(), k, data, shape, ndim);
+    return load_f32(h, "clm_cnn_load_weight", k, data, shape, ndim);
 }
 
 int clm_cnn_finalize(clm_cnn_handle* h) {
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    for (const auto& kv : cnn_expected())
-        if (!h->w.count(kv.first)) return fail(h, CLM_E_MISSING, "clm_cnn_finalize: missing weight " + kv.first);
+    if (int rc = resolve_weights(h, "clm_cnn_finalize")) return rc;
     HIPCHK(h, hipDeviceSynchronize());
-    h->dev.clear();
+    h->dev = CnnDev{};
     h->finalized = false;
     int rc;
     // block 0's table T[dk][tok][co] = sum_ci W[co][ci][dk] E[tok][ci], in fp64
@@ -241,7 +238,7 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
                     for (int ci = 0; ci < D; ++ci) s += (double)W[((size_t)co * D + ci) * cnn::K + dk] * (double)E[(size_t)tok * D + ci];
                     T[((size_t)dk * cnn::VOC + tok) * D + co] = (float)s;
                 }
-        if ((rc = cnn_upload(h, "table", T.data(), T.size() * 4))) return rc;
+        if ((rc = upload_f32(h, h->dev.table, T))) return rc;
     }
     // blocks 1 and 2: [co][ci][dk] -> seven taps [co][ci], each packed for the MFMA.  fp16x3 packs w x 2^10 as fp16 hi + lo, which
     // saturates for |w| >= 64: such weights run in the exact-fp32 packing instead (chimeralm_amd/cnn.py reports it)
@@ -251,38 +248,33 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
         if ((rc = cnn_host(h, "conv_blocks." + std::to_string(i) + ".0.weight", Wb[i - 1]))) return rc;
         for (float v : Wb[i - 1]) wmax = std::fmax(wmax, std::fabs(v));
     }
-    h->x3_active = h->x3 && wmax < 64.f;
+    h->x3_active = h->x3 && wmax < X3_WEIGHT_LIMIT;
     {
         DevBuf split;
-        HIPCHK(h, split.alloc((size_t)cnn::K * D * D * 4));
         std::vector<float> hs((size_t)cnn::K * D * D);
         for (int i = 1; i <= 2; ++i) {
             const std::vector<float>& W = Wb[i - 1];
             for (int dk = 0; dk < cnn::K; ++dk)
                 for (int co = 0; co < D; ++co)
                     for (int ci = 0; ci < D; ++ci) hs[((size_t)dk * D + co) * D + ci] = W[((size_t)co * D + ci) * cnn::K + dk];
-            HIPCHK(h, hipMemcpy(split.get(), hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-            DevBuf q;
-            HIPCHK(h, q.alloc((size_t)cnn::K * D * D * 4));
-            for (int dk = 0; dk < cnn::K; ++dk) {
-                const float* tap = split.get<float>() + (size_t)dk * D * D;
-                if (h->x3_active) launch_pack_x3(tap, q.get<float>() + (size_t)dk * D * D, D, D, 0);
-                else launch_pack_f32t(tap, q.get<float>() + (size_t)dk * D * D, D, D, 0);
-            }
-            h->dev["conv" + std::to_string(i)] = std::move(q);
-            HIPCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next block, and freed after the last
+            if ((rc = upload_f32(h, split, hs))) return rc;
+            auto pack = [&](const float* tap, void* out) {
+                if (h->x3_active) launch_pack_x3(tap, out, D, D, 0);
+                else launch_pack_f32t(tap, out, D, D, 0);
+            };
+            if ((rc = pack_taps(h, split.get<float>(), cnn::K, (size_t)D * D * 4, i == 1 ? h->dev.conv1 : h->dev.conv2, pack))) return rc;   // (synchronised: `split` is reused)
         }
     }
     for (int i = 0; i < 3; ++i)
-        if ((rc = cnn_bn(h, "conv_blocks." + std::to_string(i) + ".1.", "bn" + std::to_string(i), D))) return rc;
-    if ((rc = cnn_bn(h, "fc.1.", "bnfc", cnn::HID))) return rc;
+        if ((rc = cnn_bn(h, "conv_blocks." + std::to_string(i) + ".1.", h->dev.bn[i], D))) return rc;
+    if ((rc = cnn_bn(h, "fc.1.", h->dev.bn[3], cnn::HID))) return rc;
     {
         std::vector<float> W0;
         if ((rc = cnn_host(h, "fc.0.weight", W0))) return rc;
         std::vector<float> W0t((size_t)D * cnn::HID);
         for (int j = 0; j < cnn::HID; ++j)
             for (int c = 0; c < D; ++c) W0t[(size_t)c * cnn::HID + j] = W0[(size_t)j * D + c];
-        if ((rc = cnn_upload(h, "fc0t", W0t.data(), W0t.size() * 4))) return rc;
+        if ((rc = upload_f32(h, h->dev.fc0t, W0t))) return rc;
     }
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
@@ -310,20 +302,22 @@ int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t i
             HIPCHK(h, hipDeviceSynchronize());
             HIPCHK(h, buf[i]->reserve(need[i]));
         }
-    auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
-    auto P = [&](const std::string& k) { return h->dev.at(k).get<float>(); };
+    const CnnF32& f = h->f;
+    const CnnDev& dv = h->dev;
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
     float *const x1 = h->x1.get<float>(), *const x2 = h->x2.get<float>(), *const part = h->part.get<float>();
     launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, ids8, B, L, Lp, st);   // ids of any dtype -> clamped bytes
     {
         const size_t lds = (size_t)cnn::K * cnn::TROWS * D * 4 + (size_t)(4 * cnn::PT0 + 2 * cnn::HALO) * 4;
         launch_lds<cnn::cnn_block0_kernel>(dim3((unsigned)((L4 + cnn::PT0 - 1) / cnn::PT0), (unsigned)B), dim3(512), lds, st, ids8, Lp,
-                                           P("table"), W("conv_blocks.0.0.bias"), P("bn0.scale"), P("bn0.shift"), x1, L);
+                                           dv.table.get<float>(), f.conv_b[0], dv.bn[0].scale.get<float>(), dv.bn[0].shift.get<float>(), x1, L);
     }
-    launch_cnn_gemm7(x1, P("conv1"), W("conv_blocks.1.0.bias"), P("bn1.scale"), P("bn1.shift"), x2, false, B, L4, st, h->x3_active);
-    launch_cnn_gemm7(x2, P("conv2"), W("conv_blocks.2.0.bias"), P("bn2.scale"), P("bn2.shift"), part, true, B, L16, st, h->x3_active);
-    hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, part, tiles2, L64, P("fc0t"), W("fc.0.bias"),
-                       P("bnfc.scale"), P("bnfc.shift"), W("fc.4.weight"), W("fc.4.bias"), h->pooled.get<float>(), logits_out);
+    launch_cnn_gemm7(x1, dv.conv1.get<float>(), f.conv_b[1], dv.bn[1].scale.get<float>(), dv.bn[1].shift.get<float>(), x2, false, B, L4, st,
+                     h->x3_active);
+    launch_cnn_gemm7(x2, dv.conv2.get<float>(), f.conv_b[2], dv.bn[2].scale.get<float>(), dv.bn[2].shift.get<float>(), part, true, B, L16, st,
+                     h->x3_active);
+    hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, part, tiles2, L64, dv.fc0t.get<float>(), f.fc0_b,
+                       dv.bn[3].scale.get<float>(), dv.bn[3].shift.get<float>(), f.fc4_w, f.fc4_b, h->pooled.get<float>(), logits_out);
     h->last_B = B; h->last_L = L;
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_cnn_forward: launch failed: ") + hipGetErrorString(e));

@@ -511,6 +511,15 @@ void launch_scan(const ScanArgs& m, int N, int reads, hipStream_t st) {
 // ================================================================================================ engine + C ABI
 using namespace clm;
 
+// Weights as the kernels take them: device pointers resolved ONCE, by clm_mamba_finalize, and the packings it makes
+struct MambaLayer {               // one Mamba2 layer
+    DevBuf in, out;               // in_proj (rows padded to n_in_pad), out_proj with norm.weight folded in: packed for the MFMA (f32t, or x3 halfs)
+    const float *dt_bias, *A_log, *D, *conv_w, *conv_b;   // as loaded, fp32
+};
+struct MambaNetF32 {              // ... and what belongs to no layer, as loaded: embedding, the front block (CLM_MAMBA_SEQ), head biases, classifier.3
+    const float *emb, *pos, *front_b, *front_ln_g, *front_ln_b, *pool_b, *cls0_b, *cls3_w, *cls3_b;
+};
+
 struct clm_mamba_handle {
     int device = 0;
     int variant = 0;                              // CLM_MAMBA_SEQ (mamba) or CLM_MAMBA_SP (mambasp)
@@ -519,7 +528,10 @@ struct clm_mamba_handle {
     bool x3 = false, x3_active = false;
     std::string err;
     std::map<std::string, DevBuf> w;              // fp32 device copies by reference key
-    std::map<std::string, DevBuf> dev;            // finalize products: packed projections, transposed head weights
+    WeightTable expected;                         // (clm_mamba_create)
+    std::vector<MambaLayer> layer;                // [n_layers], sized by clm_mamba_create: `expected` points into it
+    MambaNetF32 net = {};
+    DevBuf front, poolert, cls0t;                 // finalize products: input_block.0 packed; pooler.0 / classifier.0 weights transposed
     bool finalized = false;
     DevBuf ids8, h, zx, xc, g, ssq, part, pooled, dbg_front, dbg_layer0;   // workspace (clm_mamba_forward)
     int last_B = 0, last_L = 0;
@@ -535,66 +547,44 @@ std::string layer_prefix(const clm_mamba_handle* h, int i) {
     return "mamba_layers." + std::to_string(i) + (h->variant == CLM_MAMBA_SEQ ? ".mamba." : ".");
 }
 
-std::map<std::string, std::vector<int64_t>> mamba_expected(const clm_mamba_handle* h) {
-    std::map<std::string, std::vector<int64_t>> e;
+// clm_mamba_create: the state-dict keys, their shapes and the field of h->net / h->layer the forward reads each from (none: finalize's)
+void mamba_expect(clm_mamba_handle* h) {
+    WeightTable& e = h->expected;
+    MambaNetF32& n = h->net;
     const int64_t d = h->d;
-    e["embedding.weight"] = {mamba::VOC, d};
+    h->layer.resize(h->n_layers);
+    e["embedding.weight"] = {{mamba::VOC, d}, &n.emb};
     if (h->variant == CLM_MAMBA_SEQ) {
-        e["pos_embedding"] = {1, h->max_len, d};
-        e["input_block.0.weight"] = {d, d};
-        e["input_block.0.bias"] = {d};
-        e["input_block.1.weight"] = {d};
-        e["input_block.1.bias"] = {d};
+        e["pos_embedding"] = {{1, h->max_len, d}, &n.pos};
+        e["input_block.0.weight"] = {{d, d}, nullptr}; e["input_block.0.bias"] = {{d}, &n.front_b};
+        e["input_block.1.weight"] = {{d}, &n.front_ln_g}; e["input_block.1.bias"] = {{d}, &n.front_ln_b};
     }
     for (int i = 0; i < h->n_layers; ++i) {
         const std::string p = layer_prefix(h, i);
-        e[p + "in_proj.weight"] = {h->n_in, d};
-        e[p + "conv1d.weight"] = {h->conv_dim, 1, mamba::DCONV};
-        e[p + "conv1d.bias"] = {h->conv_dim};
-        e[p + "dt_bias"] = {h->H};
-        e[p + "A_log"] = {h->H};
-        e[p + "D"] = {h->H};
-        e[p + "norm.weight"] = {h->di};
-        e[p + "out_proj.weight"] = {d, h->di};
+        MambaLayer& l = h->layer[i];
+        e[p + "in_proj.weight"] = {{h->n_in, d}, nullptr};
+        e[p + "conv1d.weight"] = {{h->conv_dim, 1, mamba::DCONV}, &l.conv_w}; e[p + "conv1d.bias"] = {{h->conv_dim}, &l.conv_b};
+        e[p + "dt_bias"] = {{h->H}, &l.dt_bias}; e[p + "A_log"] = {{h->H}, &l.A_log}; e[p + "D"] = {{h->H}, &l.D};
+        e[p + "norm.weight"] = {{h->di}, nullptr}; e[p + "out_proj.weight"] = {{d, h->di}, nullptr};
     }
-    e["pooler.0.weight"] = {d, d};
-    e["pooler.0.bias"] = {d};
-    e["classifier.0.weight"] = {d / 2, d};
-    e["classifier.0.bias"] = {d / 2};
-    e["classifier.3.weight"] = {NCLS, d / 2};
-    e["classifier.3.bias"] = {NCLS};
-    return e;
+    e["pooler.0.weight"] = {{d, d}, nullptr}; e["pooler.0.bias"] = {{d}, &n.pool_b};
+    e["classifier.0.weight"] = {{d / 2, d}, nullptr}; e["classifier.0.bias"] = {{d / 2}, &n.cls0_b};
+    e["classifier.3.weight"] = {{NCLS, d / 2}, &n.cls3_w}; e["classifier.3.bias"] = {{NCLS}, &n.cls3_b};
 }
 
-int mamba_host(clm_mamba_handle* h, const std::string& k, std::vector<float>& out) {
-    const std::vector<int64_t> shp = mamba_expected(h).at(k);
-    size_t n = 1;
-    for (int64_t s : shp) n *= (size_t)s;
-    out.resize(n);
-    HIPCHK(h, hipMemcpy(out.data(), h->w.at(k).get(), n * 4, hipMemcpyDeviceToHost));
-    return CLM_OK;
-}
-
-int mamba_upload(clm_mamba_handle* h, const std::string& name, const void* src, size_t bytes) {
-    DevBuf d;
-    HIPCHK(h, d.alloc(bytes));
-    HIPCHK(h, hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
-    h->dev[name] = std::move(d);
-    return CLM_OK;
-}
+int mamba_host(clm_mamba_handle* h, const std::string& k, std::vector<float>& out) { return host_f32(h, "clm_mamba_finalize", k, out); }
 
 // W [rows][K] (rows <= rows_pad, zero rows appended) -> the MFMA packing of the handle's arithmetic
-int mamba_pack(clm_mamba_handle* h, const std::string& name, const std::vector<float>& W, int rows, int rows_pad, int K) {
+int mamba_pack(clm_mamba_handle* h, DevBuf& dst, const std::vector<float>& W, int rows, int rows_pad, int K) {
     std::vector<float> padded((size_t)rows_pad * K, 0.f);
     std::copy(W.begin(), W.begin() + (size_t)rows * K, padded.begin());
     DevBuf src, q;
-    HIPCHK(h, src.alloc(padded.size() * 4));
-    HIPCHK(h, hipMemcpy(src.get(), padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+    if (int rc = upload_f32(h, src, padded)) return rc;
     HIPCHK(h, q.alloc(padded.size() * 4));
     if (h->x3_active) launch_pack_x3(src.get<float>(), q.get(), rows_pad, K, 0);
     else launch_pack_f32t(src.get<float>(), q.get(), rows_pad, K, 0);
     HIPCHK(h, hipDeviceSynchronize());                 // (`src` is freed on return)
-    h->dev[name] = std::move(q);
+    dst = std::move(q);
     return CLM_OK;
 }
 
@@ -634,25 +624,25 @@ int clm_mamba_create(int device, int variant, int precision, int d_model, int n_
     h->conv_dim = h->di + 2 * d_state;
     h->n_in = 2 * h->di + 2 * d_state + h->H;
     h->n_in_pad = (h->n_in + 255) / 256 * 256;
+    mamba_expect(h);
     *out = h;
     return CLM_OK;
 }
 
 int clm_mamba_load_weight(clm_mamba_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!h || !key || !data || !shape || ndim < 0) return fail(h, CLM_E_INVALID, "clm_mamba_load_weight: null argument");
-    std::string k(key);
-    if (k.rfind("net.", 0) == 0) k = k.substr(4);
+    const std::string k = canonical_weight_key(key);
     if (dtype != CLM_DT_F32) return fail(h, CLM_E_INVALID, "clm_mamba_load_weight: fp32 tensors only");
-    return load_f32(h, "clm_mamba_load_weight", mamba_expected(h), k, data, shape, ndim);
+    return load_f32(h, "clm_mamba_load_weight", k, data, shape, ndim);
 }
 
 int clm_mamba_finalize(clm_mamba_handle* h) {
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    for (const auto& kv : mamba_expected(h))
-        if (!h->w.count(kv.first)) return fail(h, CLM_E_MISSING, "clm_mamba_finalize: missing weight " + kv.first);
+    if (int rc = resolve_weights(h, "clm_mamba_finalize")) return rc;
     HIPCHK(h, hipDeviceSynchronize());
-    h->dev.clear();
+    for (MambaLayer& l : h->layer) l.in.reset(), l.out.reset();
+    for (DevBuf* b : {&h->front, &h->poolert, &h->cls0t}) b->reset();
     h->finalized = false;
     int rc;
     const int d = h->d, di = h->di;
@@ -679,17 +669,16 @@ int clm_mamba_finalize(clm_mamba_handle* h) {
         if ((rc = mamba_host(h, "input_block.0.weight", wfront))) return rc;
         track(wfront);
     }
-    h->x3_active = h->x3 && wmax < 64.f;
+    h->x3_active = h->x3 && wmax < X3_WEIGHT_LIMIT;
     for (int i = 0; i < h->n_layers; ++i) {
-        if ((rc = mamba_pack(h, "in" + std::to_string(i), win[i], h->n_in, h->n_in_pad, d))) return rc;
-        if ((rc = mamba_pack(h, "out" + std::to_string(i), wout[i], d, d, di))) return rc;
+        if ((rc = mamba_pack(h, h->layer[i].in, win[i], h->n_in, h->n_in_pad, d))) return rc;
+        if ((rc = mamba_pack(h, h->layer[i].out, wout[i], d, d, di))) return rc;
     }
-    if (h->variant == CLM_MAMBA_SEQ && (rc = mamba_pack(h, "front", wfront, d, d, d))) return rc;
+    if (h->variant == CLM_MAMBA_SEQ && (rc = mamba_pack(h, h->front, wfront, d, d, d))) return rc;
     {
         std::vector<float> wp, w0;
         if ((rc = mamba_host(h, "pooler.0.weight", wp)) || (rc = mamba_host(h, "classifier.0.weight", w0))) return rc;
-        const std::vector<float> wpt = transposed(wp, d, d), w0t = transposed(w0, d / 2, d);
-        if ((rc = mamba_upload(h, "poolert", wpt.data(), wpt.size() * 4)) || (rc = mamba_upload(h, "cls0t", w0t.data(), w0t.size() * 4))) return rc;
+        if ((rc = upload_f32(h, h->poolert, transposed(wp, d, d))) || (rc = upload_f32(h, h->cls0t, transposed(w0, d / 2, d)))) return rc;
     }
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
@@ -724,8 +713,7 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
             HIPCHK(h, hipDeviceSynchronize());
             HIPCHK(h, buf[i]->reserve(need[i]));
         }
-    auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
-    auto Pk = [&](const std::string& k) { return h->dev.at(k).get<f32x4>(); };
+    const MambaNetF32& net = h->net;
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
     float *const hs = h->h.get<float>(), *const zx = h->zx.get<float>(), *const g = h->g.get<float>(), *const ssq = h->ssq.get<float>();
     launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, ids8, B, L, Lp, st);   // ids of any dtype -> clamped bytes
@@ -737,36 +725,36 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
         const unsigned row_blocks = (unsigned)(((size_t)rows + 3) / 4);
         if (h->variant == CLM_MAMBA_SEQ) {
             mamba::ProjArgs f{};
-            f.ids8 = id8, f.Lp = Lp, f.emb = W("embedding.weight"), f.pos = W("pos_embedding"), f.w = Pk("front"), f.K = d;
-            f.out = zx, f.ldo = d, f.bias = W("input_block.0.bias"), f.L = L, f.tiles_x = tiles_x, f.nblocks = d / 256, f.n_real = d;
+            f.ids8 = id8, f.Lp = Lp, f.emb = net.emb, f.pos = net.pos, f.w = h->front.get<f32x4>(), f.K = d;
+            f.out = zx, f.ldo = d, f.bias = net.front_b, f.L = L, f.tiles_x = tiles_x, f.nblocks = d / 256, f.n_real = d;
             mamba::launch_proj<mamba::EPI_FRONT>(f, n, x3, st);
             if (d == 256)
-                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<4>, dim3(row_blocks), dim3(256), 0, st, zx, W("input_block.1.weight"),
-                                   W("input_block.1.bias"), mk, mask_row_stride, hs, rows, L);
+                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<4>, dim3(row_blocks), dim3(256), 0, st, zx, net.front_ln_g,
+                                   net.front_ln_b, mk, mask_row_stride, hs, rows, L);
             else
-                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<8>, dim3(row_blocks), dim3(256), 0, st, zx, W("input_block.1.weight"),
-                                   W("input_block.1.bias"), mk, mask_row_stride, hs, rows, L);
+                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<8>, dim3(row_blocks), dim3(256), 0, st, zx, net.front_ln_g,
+                                   net.front_ln_b, mk, mask_row_stride, hs, rows, L);
         } else {
-            hipLaunchKernelGGL(mamba::mamba_embed_kernel, dim3(row_blocks), dim3(256), 0, st, id8, Lp, W("embedding.weight"), hs, rows, L, d);
+            hipLaunchKernelGGL(mamba::mamba_embed_kernel, dim3(row_blocks), dim3(256), 0, st, id8, Lp, net.emb, hs, rows, L, d);
         }
         if (dbg)
             HIPCHK(h, hipMemcpyAsync(h->dbg_front.get<float>() + (size_t)r0 * L * d, hs, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, st));
         for (int l = 0; l < h->n_layers; ++l) {
-            const std::string p = layer_prefix(h, l);
+            const MambaLayer& ly = h->layer[l];
             const bool last = l + 1 == h->n_layers;
             mamba::ProjArgs a{};
-            a.a = hs, a.lda = d, a.w = Pk("in" + std::to_string(l)), a.K = d, a.out = zx, a.ldo = NP, a.bias = W(p + "dt_bias");
+            a.a = hs, a.lda = d, a.w = ly.in.get<f32x4>(), a.K = d, a.out = zx, a.ldo = NP, a.bias = ly.dt_bias;
             a.dt0 = 2 * di + 2 * N, a.H = H, a.L = L, a.tiles_x = tiles_x, a.nblocks = NP / 256, a.n_real = h->n_in;
             mamba::launch_proj<mamba::EPI_INPROJ>(a, n, x3, st);
             {
                 const size_t quads = (size_t)rows * h->conv_dim / 4;
                 hipLaunchKernelGGL(mamba::mamba_conv_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, zx, NP, di,
-                                   W(p + "conv1d.weight"), W(p + "conv1d.bias"), h->xc.get<float>(), h->conv_dim, rows, L);
+                                   ly.conv_w, ly.conv_b, h->xc.get<float>(), h->conv_dim, rows, L);
             }
-            mamba::ScanArgs s{h->xc.get<float>(), h->conv_dim, zx, NP, 2 * di + 2 * N, W(p + "A_log"), W(p + "D"), g, ssq, L, di, H};
+            mamba::ScanArgs s{h->xc.get<float>(), h->conv_dim, zx, NP, 2 * di + 2 * N, ly.A_log, ly.D, g, ssq, L, di, H};
             mamba::launch_scan(s, N, n, st);
             mamba::ProjArgs o{};
-            o.a = g, o.lda = di, o.w = Pk("out" + std::to_string(l)), o.K = di, o.out = hs, o.ldo = d, o.H = H, o.ssq = ssq;
+            o.a = g, o.lda = di, o.w = ly.out.get<f32x4>(), o.K = di, o.out = hs, o.ldo = d, o.H = H, o.ssq = ssq;
             o.inv_di = 1.0f / (float)di, o.mask = mk, o.mask_stride = mask_row_stride, o.part = h->part.get<float>();
             o.store = dbg && l == 0, o.L = L, o.tiles_x = tiles_x, o.nblocks = d / 256, o.n_real = d;
             if (last) mamba::launch_proj<mamba::EPI_OUTPOOL>(o, n, x3, st);
@@ -775,9 +763,8 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
                 HIPCHK(h, hipMemcpyAsync(h->dbg_layer0.get<float>() + (size_t)r0 * L * d, hs, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, st));
         }
         hipLaunchKernelGGL(mamba::mamba_head_kernel, dim3((unsigned)n), dim3(512), 0, st, h->part.get<float>(), tiles_x, L, d,
-                           h->dev.at("poolert").get<float>(), W("pooler.0.bias"), h->dev.at("cls0t").get<float>(), W("classifier.0.bias"),
-                           W("classifier.3.weight"), W("classifier.3.bias"), h->pooled.get<float>() + (size_t)r0 * d,
-                           logits_out + (size_t)r0 * NCLS);
+                           h->poolert.get<float>(), net.pool_b, h->cls0t.get<float>(), net.cls0_b, net.cls3_w, net.cls3_b,
+                           h->pooled.get<float>() + (size_t)r0 * d, logits_out + (size_t)r0 * NCLS);
     }
     h->last_B = B, h->last_L = L, h->last_dbg = dbg;
     const hipError_t e = hipGetLastError();

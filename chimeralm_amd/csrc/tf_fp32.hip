@@ -9,7 +9,6 @@
 //     fp32 throughout (8 heads of 32; scores scaled by 1/sqrt(32) like nn.MultiheadAttention);
 //   * LayerNorm (post-norm: LN(x + sublayer(x))), positional encoding, ReLU / MaxPool1d(2) as plain fp32 kernels.
 // It is a correctness reference on the GPU, not tuned: stages are separate kernels and activations live in HBM as fp32.
-#include <string>
 #include <utility>
 
 #include "clm_common.h"
@@ -477,10 +476,10 @@ size_t tf32_workspace_floats(int B, int L) {
     return (size_t)2 * B * L * D + M * (768 + 256 + 1024 + 256);
 }
 
-// `get(key)`: fp32 device pointer of a reference state-dict tensor.  h [M][256] receives the encoder output (the residual stream
-// the pooling head reads), exactly where the 16-bit path leaves it.
-int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h,
-                 const float* (*get)(void*, const std::string&), void* ctx, hipStream_t st, bool unfused, bool x3) {
+// net / lay / pk: the weights as clm_tf_finalize resolved them (pk: the packing the caller chose, t32 or x3).  h [M][256] receives the
+// encoder output (the residual stream the pooling head reads), exactly where the 16-bit path leaves it.
+int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
+                 const TfLayerF32* lay, const TfPacking& pk, hipStream_t st, bool unfused, bool x3) {
     using namespace tf32;
     const int L1 = L / 2, L2 = L1 / 2, L3 = L2 / 2;
     const size_t M = (size_t)B * L3;
@@ -490,55 +489,45 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
     float* att = qkv + M * 768;
     float* u = att + M * D;
     float* t = u + M * 1024;
-    auto Wt = [&](const std::string& k) { return get(ctx, k); };
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)(((size_t)B * L + 3) / 4)), dim3(256), 0, st, ids8, ids_stride, Wt("embedding.weight"),
-                       x, B, L);
+    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)(((size_t)B * L + 3) / 4)), dim3(256), 0, st, ids8, ids_stride, net.emb, x, B, L);
     // 3 x [Conv1d(k = 3, padding = 1) -> ReLU -> MaxPool1d(2)]; a trailing odd position is dropped by the pooling, as in torch
     int Lin = L;
-    for (int i : {0, 3, 6}) {
-        const std::string n = "cnn." + std::to_string(i);
+    for (int c = 0; c < 3; ++c) {
         const int Lout = Lin / 2;
         if (!unfused) {      // round 4: convolution + ReLU + pooling in one kernel on the fp32 MFMA (tail32.hip conv32_kernel)
-            launch_conv32(x, get(ctx, "t32." + n), Wt(n + ".bias"), y, B, Lin, st, x3);
+            launch_conv32(x, pk.conv[c].get(), net.conv_b[c], y, B, Lin, st, x3);
             std::swap(x, y);
         } else {
-            gemm<true, true>(x, D, Wt(n + ".weight"), Wt(n + ".bias"), nullptr, y, D, (size_t)B * Lin, D, 3 * D, Lin, st);
+            gemm<true, true>(x, D, net.conv_w[c], net.conv_b[c], nullptr, y, D, (size_t)B * Lin, D, 3 * D, Lin, st);
             hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)(((size_t)B * Lout * (D / 4) + 255) / 256)), dim3(256), 0, st, y, x, B, Lin, Lout);
         }
         Lin = Lout;
     }
     // + positional encoding, LayerNorm -> residual stream
-    hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, Wt("pos_encoder.pe"), Wt("norm.weight"),
-                       Wt("norm.bias"), h, M, L3, 1e-5f);
+    hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, net.pe, net.norm_g, net.norm_b, h, M, L3, 1e-5f);
     // Round 4: the dense layers of an encoder layer run fused on the fp32 MFMA (tail32.hip enc32_kernel: out_proj + LN1 + FFN + LN2 +
-    // the next layer's in_proj on 64-token tiles; weights in its packing under "t32.<layer>.<in|out|ff1|ff2>").  CLM_DEBUG=unfused_fp32:
-    // the seven separate launches per layer of round 2 (the tests cross-check the two).
-    auto T32 = [&](int i, const char* what) { return get(ctx, "t32." + std::to_string(i) + "." + what); };
-    auto LP = [&](int i) { return "transformer_encoder.layers." + std::to_string(i) + "."; };
+    // the next layer's in_proj on 64-token tiles; weights in its packing, pk.mat[layer]).  CLM_DEBUG=unfused_fp32: the seven separate
+    // launches per layer of round 2 (the tests cross-check the two).
     if (!unfused && n_layers > 0)
-        launch_enc32(nullptr, h, nullptr, nullptr, nullptr, T32(0, "in"), nullptr, nullptr, nullptr, Wt(LP(0) + "self_attn.in_proj_bias"),
-                     nullptr, nullptr, nullptr, nullptr, qkv, M, 1e-5f, st, x3);
+        launch_enc32(nullptr, h, nullptr, nullptr, nullptr, pk.mat[0][0].get(), nullptr, nullptr, nullptr, lay[0].b_in, nullptr, nullptr,
+                     nullptr, nullptr, qkv, M, 1e-5f, st, x3);
     for (int i = 0; i < n_layers; ++i) {
-        const std::string p = LP(i);
+        const TfLayerF32& l = lay[i];
         if (!unfused) {
             if (x3) hipLaunchKernelGGL(attention_x3_kernel, dim3((unsigned)(((L3 + AX_QT - 1) / AX_QT) * 8 * B)), dim3(256), 0, st, qkv, att, L3);
             else hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)(((L3 + A32_QT - 1) / A32_QT) * 8 * B)), dim3(256), 0, st, qkv, att, L3);
             const bool more = i + 1 < n_layers;
-            launch_enc32(att, h, T32(i, "out"), T32(i, "ff1"), T32(i, "ff2"), more ? T32(i + 1, "in") : nullptr,
-                         Wt(p + "self_attn.out_proj.bias"), Wt(p + "linear1.bias"), Wt(p + "linear2.bias"),
-                         more ? Wt(LP(i + 1) + "self_attn.in_proj_bias") : nullptr, Wt(p + "norm1.weight"), Wt(p + "norm1.bias"),
-                         Wt(p + "norm2.weight"), Wt(p + "norm2.bias"), qkv, M, 1e-5f, st, x3);
+            launch_enc32(att, h, pk.mat[i][1].get(), pk.mat[i][2].get(), pk.mat[i][3].get(), more ? pk.mat[i + 1][0].get() : nullptr, l.b_out,
+                         l.b_ff1, l.b_ff2, more ? lay[i + 1].b_in : nullptr, l.ln1_g, l.ln1_b, l.ln2_g, l.ln2_b, qkv, M, 1e-5f, st, x3);
             continue;
         }
-        gemm<false, false>(h, D, Wt(p + "self_attn.in_proj_weight"), Wt(p + "self_attn.in_proj_bias"), nullptr, qkv, 768, M, 768, D, 0, st);
+        gemm<false, false>(h, D, l.w[0], l.b_in, nullptr, qkv, 768, M, 768, D, 0, st);
         hipLaunchKernelGGL(attention_kernel, dim3((unsigned)((L3 + 255) / 256), 8, (unsigned)B), dim3(256), 0, st, qkv, att, L3);
-        gemm<false, false>(att, D, Wt(p + "self_attn.out_proj.weight"), Wt(p + "self_attn.out_proj.bias"), h, t, D, M, D, D, 0, st);
-        hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, t, (const float*)nullptr, Wt(p + "norm1.weight"),
-                           Wt(p + "norm1.bias"), h, M, 1, 1e-5f);
-        gemm<true, false>(h, D, Wt(p + "linear1.weight"), Wt(p + "linear1.bias"), nullptr, u, 1024, M, 1024, D, 0, st);
-        gemm<false, false>(u, 1024, Wt(p + "linear2.weight"), Wt(p + "linear2.bias"), h, t, D, M, D, 1024, 0, st);
-        hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, t, (const float*)nullptr, Wt(p + "norm2.weight"),
-                           Wt(p + "norm2.bias"), h, M, 1, 1e-5f);
+        gemm<false, false>(att, D, l.w[1], l.b_out, h, t, D, M, D, D, 0, st);
+        hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, t, (const float*)nullptr, l.ln1_g, l.ln1_b, h, M, 1, 1e-5f);
+        gemm<true, false>(h, D, l.w[2], l.b_ff1, nullptr, u, 1024, M, 1024, D, 0, st);
+        gemm<false, false>(u, 1024, l.w[3], l.b_ff2, h, t, D, M, D, 1024, 0, st);
+        hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, t, (const float*)nullptr, l.ln2_g, l.ln2_b, h, M, 1, 1e-5f);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -446,10 +446,6 @@ __global__ __launch_bounds__(256) void pool_head_kernel(const float* __restrict_
 }  // namespace tf
 
 void launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hipStream_t st, bool hilo);   // attention.hip
-// tf_fp32.hip: the same forward with exact-fp32 products (the reference's precision), up to the encoder output h
-size_t tf32_workspace_floats(int B, int L);
-int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h,
-                 const float* (*get)(void*, const std::string&), void* ctx, hipStream_t st, bool unfused, bool x3);
 
 }  // namespace clm
 
@@ -460,8 +456,14 @@ struct clm_tf_handle {
     int device = 0, prec = PREC_F16, n_layers = 12;
     std::string err;
     std::map<std::string, DevBuf> w;              // fp32 device copies by reference key
-    std::map<std::string, std::vector<int64_t>> shape;
-    std::map<std::string, DevBuf> packed;
+    WeightTable expected;                         // (clm_tf_create) every key but pos_encoder.pe, whose length is the tensor's own
+    int max_len = 0;                              // positions of the loaded pos_encoder.pe [1, max_len, 256]
+    // the weights resolved by clm_tf_finalize (pointers into `w`) and their packings, one per kind (a forward's choice: tf_run)
+    std::vector<TfLayerF32> lay;                  // [n_layers], sized by clm_tf_create: `expected` points into it
+    TfNetF32 net = {};
+    TfPacking pk_mode;                            // the handle's 16-bit mode (none on an fp32 / fp16x3 handle)
+    TfPacking pk_t32;                             // exact fp32: the fused kernels' packing (tail32.hip); a 16-bit handle's referee / fall-back
+    TfPacking pk_x3;                              // the same weights as hi + lo halfs (have_x3)
     bool finalized = false;
     // workspace (tf_run)
     DevBuf ids8;
@@ -475,7 +477,7 @@ struct clm_tf_handle {
     // clm_tf_set_fallback (as clm_set_fallback): 0 = the handle's mode; 1 = the next arithmetic inside the gate (16-bit handle: the
     // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
     int fallback = 0;
-    bool have_x3 = false;                         // the "x3.*" packings exist (fp16x3 and 16-bit handles, fused kernels only)
+    bool have_x3 = false;                         // pk_x3 is filled (fp16x3 and 16-bit handles, fused kernels only)
     float x3_wmax = 0.f;                          // largest |w| they hold (NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32 instead
     DevBuf sc_logits;                             // clm_tf_selfcheck: [2][B][2] fp32 logits of the two forwards
     // profiling taps (clm_tf_profile_*): HIP events on the launch stream around each stage, stages: 0 conv stack + pe/LN,
@@ -506,32 +508,37 @@ struct TfTimer {                                   // RAII: one event pair per s
     }
 };
 
-std::string tf_canon(const char* key) {
-    std::string k(key);
-    if (k.rfind("net.", 0) == 0) k = k.substr(4);
-    return k;
+// clm_tf_create: the state-dict keys of an n_layers-deep net, their shapes and the field of h->net / h->lay each resolves into
+void tf_expect(clm_tf_handle* h) {
+    WeightTable& e = h->expected;
+    TfNetF32& n = h->net;
+    h->lay.assign(h->n_layers, TfLayerF32{});
+    e["embedding.weight"] = {{tf::TVOC, D}, &n.emb};
+    for (int c = 0; c < 3; ++c) {
+        e["cnn." + std::to_string(3 * c) + ".weight"] = {{D, D, 3}, &n.conv_w[c]};
+        e["cnn." + std::to_string(3 * c) + ".bias"] = {{D}, &n.conv_b[c]};
+    }
+    e["norm.weight"] = {{D}, &n.norm_g}; e["norm.bias"] = {{D}, &n.norm_b};
+    for (int i = 0; i < h->n_layers; ++i) {
+        const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
+        TfLayerF32& l = h->lay[i];
+        e[p + "self_attn.in_proj_weight"] = {{tf::TQKV, D}, &l.w[0]}; e[p + "self_attn.in_proj_bias"] = {{tf::TQKV}, &l.b_in};
+        e[p + "self_attn.out_proj.weight"] = {{D, D}, &l.w[1]}; e[p + "self_attn.out_proj.bias"] = {{D}, &l.b_out};
+        e[p + "linear1.weight"] = {{tf::TFF, D}, &l.w[2]}; e[p + "linear1.bias"] = {{tf::TFF}, &l.b_ff1};
+        e[p + "linear2.weight"] = {{D, tf::TFF}, &l.w[3]}; e[p + "linear2.bias"] = {{D}, &l.b_ff2};
+        e[p + "norm1.weight"] = {{D}, &l.ln1_g}; e[p + "norm1.bias"] = {{D}, &l.ln1_b};
+        e[p + "norm2.weight"] = {{D}, &l.ln2_g}; e[p + "norm2.bias"] = {{D}, &l.ln2_b};
+    }
+    e["attn_pool.weight"] = {{1, D}, &n.pool_w}; e["attn_pool.bias"] = {{1}, &n.pool_b};
+    e["classifier.0.weight"] = {{tf::TCH, D}, &n.cls0_w}; e["classifier.0.bias"] = {{tf::TCH}, &n.cls0_b};
+    e["classifier.3.weight"] = {{NCLS, tf::TCH}, &n.cls3_w}; e["classifier.3.bias"] = {{NCLS}, &n.cls3_b};
 }
 
-std::map<std::string, std::vector<int64_t>> tf_expected(int n_layers) {
-    std::map<std::string, std::vector<int64_t>> e;
-    e["embedding.weight"] = {tf::TVOC, D};
-    for (int i : {0, 3, 6}) {
-        e["cnn." + std::to_string(i) + ".weight"] = {D, D, 3};
-        e["cnn." + std::to_string(i) + ".bias"] = {D};
-    }
-    e["norm.weight"] = {D}; e["norm.bias"] = {D};
-    for (int i = 0; i < n_layers; ++i) {
-        const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
-        e[p + "self_attn.in_proj_weight"] = {tf::TQKV, D}; e[p + "self_attn.in_proj_bias"] = {tf::TQKV};
-        e[p + "self_attn.out_proj.weight"] = {D, D}; e[p + "self_attn.out_proj.bias"] = {D};
-        e[p + "linear1.weight"] = {tf::TFF, D}; e[p + "linear1.bias"] = {tf::TFF};
-        e[p + "linear2.weight"] = {D, tf::TFF}; e[p + "linear2.bias"] = {D};
-        e[p + "norm1.weight"] = {D}; e[p + "norm1.bias"] = {D}; e[p + "norm2.weight"] = {D}; e[p + "norm2.bias"] = {D};
-    }
-    e["attn_pool.weight"] = {1, D}; e["attn_pool.bias"] = {1};
-    e["classifier.0.weight"] = {tf::TCH, D}; e["classifier.0.bias"] = {tf::TCH};
-    e["classifier.3.weight"] = {NCLS, tf::TCH}; e["classifier.3.bias"] = {NCLS};
-    return e;
+void tf_pool_head(clm_tf_handle* h, int B, int L3, float* logits, hipStream_t st) {   // stage 3 of either path, on the residual stream h->h
+    const TfNetF32& n = h->net;
+    hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), n.pool_w, n.pool_b, n.cls0_w, n.cls0_b, n.cls3_w,
+                       n.cls3_b, h->scores.get<float>(), h->pooled.get<float>(), logits, L3);
+    h->last_B = B; h->last_L3 = L3;
 }
 
 template <int PREC>
@@ -539,29 +546,29 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
     using elem = typename CT<PREC>::elem;
     const int L1 = L / 2, L2 = L1 / 2, L3 = L2 / 2, Lp = (L + 63) / 64 * 64;
     const size_t M = (size_t)B * L3;
-    auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
-    auto P = [&](const std::string& k) { return h->packed.at(k).get(); };
-    TfTimer* tconv = new TfTimer(h, st, 0);
-    launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);   // ids of any dtype -> clamped uint8
-    constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
+    const TfNetF32& n = h->net;
+    const TfPacking& pk = h->pk_mode;
     {
+        TfTimer t(h, st, 0);
+        launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);   // ids of any dtype -> clamped uint8
+        constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
         constexpr auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
         constexpr auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
-        launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8.get<unsigned char>(), Lp, W("embedding.weight"),
-                       (const elem*)nullptr, P("cnn.0"), W("cnn.0.bias"), h->x1.get<elem>(), L, L1);
+        launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8.get<unsigned char>(), Lp, n.emb,
+                       (const elem*)nullptr, pk.conv[0].get(), n.conv_b[0], h->x1.get<elem>(), L, L1);
         launch_lds<k2>(dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                       (const float*)nullptr, h->x1.get<const elem>(), P("cnn.3"), W("cnn.3.bias"), h->x2.get<elem>(), L1, L2);
+                       (const float*)nullptr, h->x1.get<const elem>(), pk.conv[1].get(), n.conv_b[1], h->x2.get<elem>(), L1, L2);
         launch_lds<k2>(dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
-                       (const float*)nullptr, h->x2.get<const elem>(), P("cnn.6"), W("cnn.6.bias"), h->x3.get<elem>(), L2, L3);
+                       (const float*)nullptr, h->x2.get<const elem>(), pk.conv[2].get(), n.conv_b[2], h->x3.get<elem>(), L2, L3);
+        hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, h->x3.get<const elem>(), n.pe, n.norm_g,
+                           n.norm_b, h->h.get<float>(), h->hx.get<elem>(), M, L3, 1e-5f);
     }
-    hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, h->x3.get<const elem>(),
-                       W("pos_encoder.pe"), W("norm.weight"), W("norm.bias"), h->h.get<float>(), h->hx.get<elem>(), M, L3, 1e-5f);
-    delete tconv;
     for (int i = 0; i < h->n_layers; ++i) {
-        const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
+        const TfLayerF32& l = h->lay[i];
+        const std::array<DevBuf, 4>& m = pk.mat[i];
         if (i == 0) {   // later layers: computed at the end of the previous layer's feed-forward kernel
             TfTimer t(h, st, 2);
-            const tf::LinArgs a{h->hx.get(), P(p + "in"), W(p + "self_attn.in_proj_bias"), h->qkv.get(), M, 0};
+            const tf::LinArgs a{h->hx.get(), m[0].get(), l.b_in, h->qkv.get(), M, 0};
             constexpr size_t lds = (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2;
             launch_lds<tf::linear16_kernel<PREC, tf::E_ACT, D, tf::TQKV>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, a);
         }
@@ -572,21 +579,16 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
         TfTimer tl(h, st, 2);
         // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel
         const bool more = i + 1 < h->n_layers;
-        const std::string pn = "transformer_encoder.layers." + std::to_string(i + 1) + ".";
-        const tf::FfnArgs f{h->hx.get(), P(p + "ff1"), P(p + "ff2"), W(p + "linear1.bias"), W(p + "linear2.bias"),
-                            W(p + "norm2.weight"), W(p + "norm2.bias"), h->h.get<float>(), h->hx.get(), M, 1e-5f,
-                            more ? P(pn + "in") : nullptr, more ? W(pn + "self_attn.in_proj_bias") : nullptr, h->qkv.get(),
-                            h->att.get(), P(p + "out"), W(p + "self_attn.out_proj.bias"), W(p + "norm1.weight"), W(p + "norm1.bias")};
+        const tf::FfnArgs f{h->hx.get(), m[2].get(), m[3].get(), l.b_ff1, l.b_ff2, l.ln2_g, l.ln2_b, h->h.get<float>(), h->hx.get(), M, 1e-5f,
+                            more ? pk.mat[i + 1][0].get() : nullptr, more ? h->lay[i + 1].b_in : nullptr, h->qkv.get(),
+                            h->att.get(), m[1].get(), l.b_out, l.ln1_g, l.ln1_b};
         constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
         launch_lds<tf::enc_ffn16_kernel<PREC>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
     }
     {
         TfTimer t(h, st, 3);
-        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), W("attn_pool.weight"), W("attn_pool.bias"),
-                           W("classifier.0.weight"), W("classifier.0.bias"), W("classifier.3.weight"), W("classifier.3.bias"),
-                           h->scores.get<float>(), h->pooled.get<float>(), logits, L3);
+        tf_pool_head(h, B, L3, logits, st);
     }
-    h->last_B = B; h->last_L3 = L3;
     return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
 }
 
@@ -613,6 +615,7 @@ int clm_tf_create(int device, int precision, int n_layers, clm_tf_handle** out) 
     h->prec = precision == CLM_PREC_BF16 ? PREC_BF16 : (precision == CLM_PREC_F32 || h->arith_x3) ? PREC_F32 : precision == CLM_PREC_F16C ? PREC_F16C
                                                                                                                                    : PREC_F16;
     h->n_layers = n_layers;
+    tf_expect(h);
     *out = h;
     return CLM_OK;
 }
@@ -620,109 +623,63 @@ int clm_tf_create(int device, int precision, int n_layers, clm_tf_handle** out) 
 int clm_tf_load_weight(clm_tf_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!h || !key || !data || !shape) return fail(h, CLM_E_INVALID, "clm_tf_load_weight: null argument");
     if (dtype != CLM_DT_F32) return fail(h, CLM_E_INVALID, "clm_tf_load_weight: fp32 tensors only");
-    const std::string k = tf_canon(key);
-    std::vector<int64_t> shp(shape, shape + ndim);
-    auto exp = tf_expected(h->n_layers);
-    if (k == "pos_encoder.pe") {                               // buffer [1, max_len, 256]
-        if (ndim != 3 || shp[0] != 1 || shp[2] != D) return fail(h, CLM_E_INVALID, "pos_encoder.pe: expected [1, max_len, 256]");
-        exp[k] = shp;
-    }
-    if (int rc = load_f32(h, "clm_tf_load_weight", exp, k, data, shape, ndim)) return rc;
-    h->shape[k] = shp;
+    const std::string k = canonical_weight_key(key);
+    if (k != "pos_encoder.pe") return load_f32(h, "clm_tf_load_weight", k, data, shape, ndim);
+    if (ndim != 3 || shape[0] != 1 || shape[2] != D) return fail(h, CLM_E_INVALID, "pos_encoder.pe: expected [1, max_len, 256]");   // a buffer
+    if (int rc = store_f32(h, k, data, (size_t)shape[1] * D)) return rc;
+    h->max_len = (int)shape[1];
     return CLM_OK;
 }
 
 int clm_tf_finalize(clm_tf_handle* h) {
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
-    for (const auto& kv : tf_expected(h->n_layers))
-        if (!h->w.count(kv.first)) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing weight " + kv.first);
-    if (!h->w.count("pos_encoder.pe")) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing buffer pos_encoder.pe");
-    h->packed.clear();
+    if (int rc = resolve_weights(h, "clm_tf_finalize")) return rc;
+    const auto pe = h->w.find("pos_encoder.pe");
+    if (pe == h->w.end()) return fail(h, CLM_E_MISSING, "clm_tf_finalize: missing buffer pos_encoder.pe");
+    h->net.pe = pe->second.get<float>();
+    constexpr int MAT_N[4] = {tf::TQKV, D, tf::TFF, D}, MAT_K[4] = {D, D, D, tf::TFF};
     h->have_x3 = (h->arith_x3 || h->prec != PREC_F32) && !h->unfused_fp32;
     h->x3_wmax = 0.f;
     if (h->have_x3) {             // what the hi + lo packing must hold: the CNN stem and the four dense products of every layer
-        std::vector<std::string> keys{"cnn.0.weight", "cnn.3.weight", "cnn.6.weight"};
-        for (int i = 0; i < h->n_layers; ++i)
-            for (const char* k : {"self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight"})
-                keys.push_back("transformer_encoder.layers." + std::to_string(i) + "." + k);
-        for (const auto& k : keys) {
+        auto track = [&](const float* w, size_t n) {
             float m = 0.f;
-            HIPCHK(h, device_max_abs(h->w.at(k).get<float>(), h->w.at(k).bytes() / 4, m));
+            const hipError_t e = device_max_abs(w, n, m);
             if (m != m || m > h->x3_wmax) h->x3_wmax = m;          // (NaN stays)
-        }
+            return e;
+        };
+        for (const float* w : h->net.conv_w) HIPCHK(h, track(w, (size_t)3 * D * D));
+        for (const TfLayerF32& l : h->lay)
+            for (int j = 0; j < 4; ++j) HIPCHK(h, track(l.w[j], (size_t)MAT_N[j] * MAT_K[j]));
     }
-    // exact fp32 (the handle's own mode, or the referee / fall-back of a 16-bit handle): the dense layers of the encoder in the fused
-    // kernel's packing (tail32.hip enc32_kernel); everything else of tf_fp32.hip reads the fp32 tensors as they are
-    for (int i = 0; i < h->n_layers; ++i) {
-        const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".", t = "t32." + std::to_string(i) + ".";
-        struct { const char* name; const char* key; int n, k; } tw[4] = {{"in", "self_attn.in_proj_weight", tf::TQKV, D}, {"out", "self_attn.out_proj.weight", D, D},
-                                                                         {"ff1", "linear1.weight", tf::TFF, D}, {"ff2", "linear2.weight", D, tf::TFF}};
-        for (auto& e : tw) {
-            DevBuf q;
-            HIPCHK(h, q.alloc((size_t)e.n * e.k * 4));
-            launch_pack_f32t(h->w.at(p + e.key).get<float>(), q.get(), e.n, e.k, 0);
-            h->packed[t + e.name] = std::move(q);
-            if (h->have_x3) {                                 // fp16x3 (a handle's mode, or a 16-bit handle's first fall-back level): the same weights as hi + lo halfs ("x3." keys); "t32." = the referee
-                DevBuf qx;
-                HIPCHK(h, qx.alloc((size_t)e.n * e.k * 4));
-                launch_pack_x3(h->w.at(p + e.key).get<float>(), qx.get(), e.n, e.k, 0);
-                h->packed["x3." + std::to_string(i) + "." + e.name] = std::move(qx);
-            }
-        }
-    }
-    {   // ... and the three taps of each CNN-stem convolution ([co][ci][3] -> [3][co][ci], each tap packed)
-        DevBuf split;
-        HIPCHK(h, split.alloc((size_t)3 * D * D * 4));
-        float* const split32 = split.get<float>();
-        for (int i : {0, 3, 6}) {
-            const std::string name = "cnn." + std::to_string(i);
-            hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight").get<float>(), split32);
-            DevBuf q;
-            HIPCHK(h, q.alloc((size_t)3 * D * D * 4));
-            for (int dk = 0; dk < 3; ++dk) launch_pack_f32t(split32 + (size_t)dk * D * D, q.get<float>() + (size_t)dk * D * D, D, D, 0);
-            h->packed["t32." + name] = std::move(q);
-            if (h->have_x3) {
-                DevBuf qx;
-                HIPCHK(h, qx.alloc((size_t)3 * D * D * 4));
-                for (int dk = 0; dk < 3; ++dk) launch_pack_x3(split32 + (size_t)dk * D * D, qx.get<float>() + (size_t)dk * D * D, D, D, 0);
-                h->packed["x3." + name] = std::move(qx);
-            }
-            HIPCHK(h, hipDeviceSynchronize());                 // `split` is reused by the next layer, and freed after the last
-        }
-    }
-    if (h->prec == PREC_F32) {
-        HIPCHK(h, hipDeviceSynchronize());
-        h->finalized = true;
-        return CLM_OK;
-    }
-    auto pack = [&](const std::string& name, const std::string& key, int n, int k) -> int {
-        DevBuf p;
-        HIPCHK(h, p.alloc(packed_weight_bytes(h->prec, n, k)));
-        launch_pack_weight(h->prec, h->w.at(key).get<float>(), p.get(), n, k, 0);
-        h->packed[name] = std::move(p);
-        return CLM_OK;
+    // Three kinds of packing.  t32: exact fp32 (the handle's own mode, or the referee / fall-back of a 16-bit handle), the dense layers
+    // and the stem in the fused kernels' packing (tail32.hip); everything else of tf_fp32.hip reads the fp32 tensors as they are.
+    // x3: the same as hi + lo halfs (an fp16x3 handle's mode, or a 16-bit handle's first fall-back level).  mode: a 16-bit handle's own.
+    TfPacking* const pks[3] = {&h->pk_t32, &h->pk_x3, &h->pk_mode};
+    const bool on[3] = {true, h->have_x3, h->prec != PREC_F32};
+    auto bytes = [&](int q, int n, int k) { return q < 2 ? (size_t)n * k * 4 : packed_weight_bytes(h->prec, n, k); };
+    auto pack = [&](int q, const float* src, void* out, int n, int k) {
+        if (q == 0) launch_pack_f32t(src, out, n, k, 0);
+        else if (q == 1) launch_pack_x3(src, out, n, k, 0);
+        else launch_pack_weight(h->prec, src, out, n, k, 0);
     };
-    DevBuf split;
+    for (TfPacking* pk : pks) *pk = TfPacking{};                   // (a reload leaves nothing of the packings before it)
+    h->finalized = false;
+    DevBuf split;                 // a stem convolution's three taps: [co][ci][3] -> [3][co][ci]
     HIPCHK(h, split.alloc((size_t)3 * D * D * 4));
-    for (int i : {0, 3, 6}) {
-        const std::string name = "cnn." + std::to_string(i);
-        hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->w.at(name + ".weight").get<float>(), split.get<float>());
-        DevBuf p;
-        HIPCHK(h, p.alloc(3 * packed_weight_bytes(h->prec, D, D)));
-        for (int dk = 0; dk < 3; ++dk)
-            launch_pack_weight(h->prec, split.get<float>() + (size_t)dk * D * D, p.get<char>() + dk * packed_weight_bytes(h->prec, D, D), D, D, 0);
-        HIPCHK(h, hipDeviceSynchronize());                     // `split` is reused by the next layer, and freed after the last
-        h->packed[name] = std::move(p);
-    }
-    split.reset();
-    for (int i = 0; i < h->n_layers; ++i) {
-        const std::string p = "transformer_encoder.layers." + std::to_string(i) + ".";
-        int rc;
-        if ((rc = pack(p + "in", p + "self_attn.in_proj_weight", tf::TQKV, D))) return rc;
-        if ((rc = pack(p + "out", p + "self_attn.out_proj.weight", D, D))) return rc;
-        if ((rc = pack(p + "ff1", p + "linear1.weight", tf::TFF, D))) return rc;
-        if ((rc = pack(p + "ff2", p + "linear2.weight", D, tf::TFF))) return rc;
+    for (int q = 0; q < 3; ++q) {
+        if (!on[q]) continue;
+        pks[q]->mat.resize(h->n_layers);
+        for (int i = 0; i < h->n_layers; ++i)
+            for (int j = 0; j < 4; ++j) {
+                HIPCHK(h, pks[q]->mat[i][j].alloc(bytes(q, MAT_N[j], MAT_K[j])));
+                pack(q, h->lay[i].w[j], pks[q]->mat[i][j].get(), MAT_N[j], MAT_K[j]);
+            }
+        for (int c = 0; c < 3; ++c) {   // (pack_taps synchronises: `split` is reused by the next convolution, and freed after the last)
+            hipLaunchKernelGGL(tf::conv_w_split_kernel, dim3((3 * D * D + 255) / 256), dim3(256), 0, 0, h->net.conv_w[c], split.get<float>());
+            auto tap = [&](const float* src, void* out) { pack(q, src, out, D, D); };
+            if (int rc = pack_taps(h, split.get<float>(), 3, bytes(q, D, D), pks[q]->conv[c], tap)) return rc;
+        }
     }
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;
@@ -762,18 +719,10 @@ static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype,
         launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);
         // hi + lo halfs on the fp32 path: an fp16x3 handle unless told to fall back; a 16-bit handle at fall-back level 1
         const bool use_x3 = tf_fp32_path_is_x3(h);
-        auto get = [](void* ctx, const std::string& k) -> const float* {     // "t32.*": the fused kernels' packed weights ("x3.*" in fp16x3)
-            auto* hh = static_cast<clm_tf_handle*>(ctx);
-            if (k.rfind("t32.", 0) != 0) return hh->w.at(k).get<float>();
-            return hh->packed.at(tf_fp32_path_is_x3(hh) ? "x3." + k.substr(4) : k).get<const float>();
-        };
-        if (tf32_forward(h->ids8.get<unsigned char>(), Lp, B, L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), get, h, st, h->unfused_fp32, use_x3))
+        if (tf32_forward(h->ids8.get<unsigned char>(), Lp, B, L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), h->net, h->lay.data(),
+                         use_x3 ? h->pk_x3 : h->pk_t32, st, h->unfused_fp32, use_x3))
             return fail(h, CLM_E_HIP, std::string("clm_tf_forward (fp32): ") + hipGetErrorString(hipGetLastError()));
-        auto W = [&](const std::string& k) { return h->w.at(k).get<float>(); };
-        hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), W("attn_pool.weight"), W("attn_pool.bias"),
-                           W("classifier.0.weight"), W("classifier.0.bias"), W("classifier.3.weight"), W("classifier.3.bias"),
-                           h->scores.get<float>(), h->pooled.get<float>(), logits_out, L3);
-        h->last_B = B; h->last_L3 = L3;
+        tf_pool_head(h, B, L3, logits_out, st);
         return hipGetLastError() == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
     }
     {   // the 16-bit activations, each buffer grown on its own (x1 / x2 scale with B * (L / 2), B * (L / 4), not with M)
@@ -799,7 +748,7 @@ static int tf_check_args(clm_tf_handle* h, const char* who, const void* ids, int
     if (!ids || B < 1 || L < 8 || ids_row_stride < L) return fail(h, CLM_E_INVALID, std::string(who) + ": bad argument (L >= 8)");
     if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
         return fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
-    if ((int64_t)(L / 8) > h->shape.at("pos_encoder.pe")[1])
+    if (L / 8 > h->max_len)
         return fail(h, CLM_E_INVALID, std::string(who) + ": Sequence too long (" + std::to_string(L / 8) + " > max_len of pos_encoder.pe)");
     return CLM_OK;
 }
