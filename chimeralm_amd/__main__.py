@@ -43,11 +43,20 @@ def predict(
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
     gather_logits: bool = typer.Option(False, "--gather-logits", help="multi-GPU: all-gather every batch's logits (RCCL, side "
                                        "stream) and let rank 0 also write them to logits.tsv (batch, rank, row, logit0, logit1)"),
+    save_attention: bool = typer.Option(False, "--save-attention", help="also write {rank}_{batch}.attn.tsv per batch: per read its "
+                                        "label, number of bases and pads, the pooling weight on pads and on [SEP], and the bases "
+                                        "of largest pooling weight as pos:weight (where in the read the model looked)"),
+    attention_top_k: int = typer.Option(10, "--attention-top-k", help="bases listed per read by --save-attention (1 ... 32)"),
+    attention_weights: bool = typer.Option(False, "--attention-weights", help="with --save-attention (implied): also write "
+                                           "{rank}_{batch}.attn.npz with the pooling weight of every base of every read"),
 ):
     """Predict the given dataset using ChimeraLM."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
     if gpus < 1:
         raise typer.BadParameter("this engine runs on MI355X GPUs only; use --gpus >= 1 (no CPU path exists)")
+    save_attention = save_attention or attention_weights
+    if save_attention and not 1 <= attention_top_k <= 32:
+        raise typer.BadParameter("--attention-top-k must be 1 ... 32")
     if output_path is None:                       # README-documented default (the reference crashes here)
         output_path = data_path.with_suffix(".predictions")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -76,28 +85,30 @@ def predict(
         raise RuntimeError(f"Batch size ({batch_size}) is not divisible by the number of devices ({world}).")
     if ckpt_path is not None:
         log.info(f"Loading model from {ckpt_path}")
-        model = lm.ChimeraLM.new(precision=precision, selfcheck=None if selfcheck_tol > 0 else False,
-                                 selfcheck_tol=selfcheck_tol).load_reference_checkpoint(ckpt_path)
+        model = lm.ChimeraLM.new(precision=precision, selfcheck=None if selfcheck_tol > 0 else False, selfcheck_tol=selfcheck_tol,
+                                 attention_top_k=attention_top_k if save_attention else None).load_reference_checkpoint(ckpt_path)
     else:
         log.info(f"Loading model weights {weights}")
         model = lm.ChimeraLM.from_pretrained(weights, precision=precision, selfcheck=None if selfcheck_tol > 0 else False,
-                                             selfcheck_tol=selfcheck_tol)
+                                             selfcheck_tol=selfcheck_tol, attention_top_k=attention_top_k if save_attention else None)
     output_path.mkdir(parents=True, exist_ok=True)
     writer = callbacks.PredictionWriter(output_dir=output_path, write_interval="batch")
+    attn_writer = callbacks.AttentionWriter(output_dir=output_path, weights=attention_weights) if save_attention else None
     if feeder == "native":
         from .feeder import BamFeeder
 
         with BamFeeder(data_path, batch_size=batch_size // world, max_tokens=tok.max_len_single_sentence, rank=rank,
                        world=world, pad_left=tok.padding_side == "left") as fd:
             n = loop.run_predict_native(model, fd, writer, device, rank=rank, gather=world > 1 and gather_logits,
-                                        on_batch=_gathered_sink(output_path, rank) if gather_logits else None)
+                                        on_batch=_gathered_sink(output_path, rank) if gather_logits else None,
+                                        attention_writer=attn_writer)
             log.info(f"[rank {rank}] feeder: {fd.stats()}")
     else:
         dm = bam.BamDataModule(tokenizer=tok, train_data_path=Path("dummy.bam"), predict_data_path=data_path,
                                batch_size=batch_size, num_workers=num_workers)
         dm.setup("predict", world_size=world, rank=rank)
         n = loop.run_predict(model, dm, writer, device, rank=rank, gather=world > 1 and gather_logits,
-                             on_batch=_gathered_sink(output_path, rank) if gather_logits else None)
+                             on_batch=_gathered_sink(output_path, rank) if gather_logits else None, attention_writer=attn_writer)
     distributed.barrier()
     rep = getattr(model.net, "selfcheck_report", None)
     if rep:

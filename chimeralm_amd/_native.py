@@ -23,6 +23,7 @@ STAGES = ["embed", "ln1_in_proj", "short_long_conv", "out_proj", "ln2_fc1_gelu",
           "softmax_pool", "head_mlp", "filter", "out_proj_ln2_mlp", "ln2_mlp"]
 N_STAGES = len(STAGES)
 ABI_VERSION = 6
+ATTN_MAX_TOP_K = 32                   # clm_attn_out.top_k: 1 ... 32
 MAMBA_SEQ, MAMBA_SP = 0, 1            # clm_mamba_create variants (CLM_MAMBA_SEQ, CLM_MAMBA_SP)
 
 
@@ -52,6 +53,16 @@ class ClmEvalResult(C.Structure):             # include/chimeralm_hip.h: struct 
                                                                                 ("sum_loss", C.c_double)]
 
 
+class ClmAttnSummary(C.Structure):            # include/chimeralm_hip.h: struct clm_attn_summary (one record per read)
+    _fields_ = [("n_pad", C.c_int32), ("n_bases", C.c_int32), ("has_sep", C.c_int32), ("n_peaks", C.c_int32),
+                ("pad_weight", C.c_float), ("sep_weight", C.c_float), ("base_weight", C.c_float), ("reserved", C.c_int32)]
+
+
+class ClmAttnOut(C.Structure):                # include/chimeralm_hip.h: struct clm_attn_out
+    _fields_ = [("struct_size", C.c_int32), ("top_k", C.c_int32), ("weights", C.c_void_p), ("weights_row_stride", C.c_int64),
+                ("summary", C.c_void_p), ("peak_pos", C.c_void_p), ("peak_weight", C.c_void_p)]
+
+
 # every symbol include/chimeralm_hip.h and include/chimeralm_feed.h declare: name -> (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -62,6 +73,9 @@ SYMBOLS = {
     "clm_finalize": (C.c_int, [_H]),
     "clm_reserve": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "clm_forward_attn": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut),
+                                   C.c_void_p]),
+    "clm_forward_staged_attn": (C.c_int, [_H, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut), C.c_void_p]),
     "clm_stage_ids": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "clm_forward_staged": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
     "clm_stage_wait": (C.c_int, [_H, C.c_int]),

@@ -6,13 +6,20 @@
 Difference kept on purpose: the id row is decoded with its length byte read as UNSIGNED, so read names of
 128..255 characters work; the reference's collator raises on them (torch.tensor(..., dtype=int8) overflow,
 tokenizer.py:168), so no input the reference accepts is treated differently.
+
+`AttentionWriter` has no counterpart there: the reference keeps `attention_weights` of ONE forward on the module (hyena.py:129-130)
+and notebooks/attention.ipynb works from that; here the engine's per-read summary and peaks (csrc/attn_weights.hip) are written
+per batch next to the predictions, under names `filter` does not glob (`*.txt`, filter.py).
 """
 from __future__ import annotations
 
+import io
 import logging
+import zipfile
 from pathlib import Path
 from typing import Any
 
+import numpy as np
 import torch
 
 log = logging.getLogger(__name__)
@@ -64,3 +71,78 @@ class PredictionWriter:
         rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
         with (self.output_dir / f"{rank}_{batch_idx}.txt").open("w") as f:
             f.writelines(lines)
+
+
+def _read_names(ids) -> list[str]:
+    """Names of a batch's id rows, with `PredictionWriter`'s fall-backs."""
+    names = []
+    for i, row in enumerate(ids):
+        try:
+            names.append(resume_read_name(row) or f"unknown_read_{i}")
+        except ValueError:
+            names.append(f"error_read_{i}")
+    return names
+
+
+def _npz_bytes(arrays: dict[str, np.ndarray]) -> bytes:
+    """An uncompressed `.npz` (np.load reads it) whose bytes depend on the arrays alone: np.savez stamps its members with the time."""
+    buf = io.BytesIO()
+    with zipfile.ZipFile(buf, "w", zipfile.ZIP_STORED) as zf:
+        for name, arr in arrays.items():
+            member = io.BytesIO()
+            np.lib.format.write_array(member, np.ascontiguousarray(arr), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), member.getvalue())
+    return buf.getvalue()
+
+
+class AttentionWriter:
+    """Where in each read the model looked: one `{rank}_{batch_idx}.attn.tsv` per batch, one line per read,
+
+        name<TAB>label<TAB>n_bases<TAB>n_pad<TAB>pad_weight<TAB>sep_weight<TAB>pos:weight;pos:weight;...
+
+    with the read's largest-weight bases in descending weight (`pos` 0-based among the read's bases, weights as %.6g; an empty
+    field for a read without bases), and with `weights=True` one `{rank}_{batch_idx}.attn.npz` holding `names`, `n_bases` int32
+    [B], `offsets` int64 [B + 1] and `weights` fp32: the per-base weights of all reads concatenated, [PAD] and [SEP] stripped
+    (read i: weights[offsets[i]:offsets[i + 1]]).  `attention` is an `engine.AttentionOutput` of HOST tensors."""
+
+    def __init__(self, output_dir: str | Path, weights: bool = False) -> None:
+        self.output_dir = Path(output_dir)
+        self.weights = bool(weights)
+
+    def write_on_batch_end(self, trainer: Any, pl_module: Any, prediction: Any, attention: Any, batch: dict[str, Any],
+                           batch_idx: int) -> None:
+        if prediction is None or attention is None or attention.summary is None or "id" not in batch:
+            log.error("batch %d: missing prediction, attention summary or 'id'", batch_idx)
+            return
+        pred = prediction[0] if isinstance(prediction, (list, tuple)) else prediction
+        labels = pred.argmax(dim=1).tolist()
+        ids = batch["id"].cpu() if isinstance(batch["id"], torch.Tensor) else batch["id"]
+        f = {k: v.tolist() for k, v in attention.fields().items()}
+        if not len(labels) == len(ids) == len(f["n_bases"]):
+            log.error("Size mismatch: predictions=%d, batch_ids=%d, attention=%d for batch %d", len(labels), len(ids),
+                      len(f["n_bases"]), batch_idx)
+            return
+        names = _read_names(ids)
+        pos, wgt = attention.peak_pos.tolist(), attention.peak_weight.tolist()
+        lines = []
+        for i, name in enumerate(names):
+            n = f["n_peaks"][i]
+            peaks = ";".join(f"{p}:{w:.6g}" for p, w in zip(pos[i][:n], wgt[i][:n]))
+            lines.append(f"{name}\t{labels[i]}\t{f['n_bases'][i]}\t{f['n_pad'][i]}\t{f['pad_weight'][i]:.6g}\t"
+                         f"{f['sep_weight'][i]:.6g}\t{peaks}\n")
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
+        with (self.output_dir / f"{rank}_{batch_idx}.attn.tsv").open("w") as fh:
+            fh.writelines(lines)
+        if not self.weights:
+            return
+        if attention.weights is None:
+            log.error("batch %d: per-base weights were asked for but the forward left none", batch_idx)
+            return
+        w = attention.weights.numpy()
+        n_bases = np.asarray(f["n_bases"], dtype=np.int32)
+        offsets = np.zeros(len(names) + 1, dtype=np.int64)
+        np.cumsum(n_bases, out=offsets[1:])
+        flat = np.concatenate([w[i, p: p + n] for i, (p, n) in enumerate(zip(f["n_pad"], f["n_bases"]))] or [np.zeros(0, np.float32)])
+        (self.output_dir / f"{rank}_{batch_idx}.attn.npz").write_bytes(_npz_bytes(
+            {"names": np.asarray(names, dtype=np.str_), "n_bases": n_bases, "offsets": offsets, "weights": flat.astype(np.float32)}))

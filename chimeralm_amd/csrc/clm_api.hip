@@ -569,7 +569,8 @@ int chunk_for(const clm_handle* h, int L) {
     return c < 1 ? 1 : (int)c;
 }
 
-int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st);
+int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st,
+                  const clm_attn_out* attn = nullptr, int b0 = 0);
 
 // The all-[PAD] table of the arithmetic the reads of this chunk run in (pad_prefix.hip), long enough for its L tokens: built on
 // first use -- ONE forward of one all-[PAD] read through this very engine, with the stages' capture hooks copying out what the
@@ -858,7 +859,21 @@ int stage_head(ChunkCtx& c, float* logits) {
     return CLM_OK;
 }
 
-int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st) {
+// The chunk's attention outputs (clm_forward_attn), at the rows of its reads [b0, b0 + Bc) in the caller's buffers: one kernel behind
+// the head, on the scores every path has completed by then (fused tails, separate kernels, the lone token, rows from the [PAD] table)
+int stage_attn(ChunkCtx& c, const clm_attn_out& a, int b0) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const size_t r = (size_t)b0;
+    launch_attn_weights(h->scores.get<float>(), h->ids8.get<unsigned char>(), p.Bc, p.L, p.Lp,
+                        a.weights ? a.weights + r * (size_t)a.weights_row_stride : nullptr, a.weights_row_stride,
+                        a.summary ? a.summary + r : nullptr, a.summary ? a.peak_pos + r * a.top_k : nullptr,
+                        a.summary ? a.peak_weight + r * a.top_k : nullptr, a.top_k, st);
+    HIPCHK(h, hipGetLastError());
+    return CLM_OK;
+}
+
+int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st,
+                  const clm_attn_out* attn, int b0) {
     ChunkCtx c{h, plan_chunk(h, Bc, L), st};
     const ChunkPlan& p = c.p;
     // filters of the length class, workspace, [PAD] table
@@ -883,7 +898,26 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     int rc = CLM_OK;
     for (int i = 0; i < NLAYER && !rc; ++i) rc = run_block(c, i);
     if (!rc) rc = stage_head(c, logits);
+    if (!rc && attn) rc = stage_attn(c, *attn, b0);
     return rc == STOPPED ? CLM_OK : rc;
+}
+
+// The attention request of clm_forward_attn / clm_forward_staged_attn for reads of L tokens (null: none, nothing to check)
+int check_attn_arg(clm_handle* h, const char* who, const clm_attn_out* a, int L) {
+    if (!a) return CLM_OK;
+    const std::string w(who);
+    if (a->struct_size != (int32_t)sizeof(clm_attn_out)) return fail(h, CLM_E_INVALID, w + ": clm_attn_out size mismatch");
+    const int n_peak_args = (a->summary != nullptr) + (a->peak_pos != nullptr) + (a->peak_weight != nullptr);
+    if (n_peak_args != 0 && n_peak_args != 3)
+        return fail(h, CLM_E_INVALID, w + ": summary, peak_pos and peak_weight go together (all three or none)");
+    if (!a->weights && !a->summary) return fail(h, CLM_E_INVALID, w + ": the attention request asks for nothing (weights and summary are NULL)");
+    if (a->summary && (a->top_k < 1 || a->top_k > ATTN_MAX_TOP_K))
+        return fail(h, CLM_E_INVALID, w + ": top_k must be 1 ... " + std::to_string(ATTN_MAX_TOP_K));
+    if (a->weights && a->weights_row_stride < L) return fail(h, CLM_E_INVALID, w + ": weights_row_stride is shorter than a read");
+    if (L > ATTN_MAX_L)
+        return fail(h, CLM_E_UNSUPPORTED, w + ": attention outputs exist for reads of up to " + std::to_string(ATTN_MAX_L) + " tokens");
+    if (h->stop_stage >= 0) return fail(h, CLM_E_STATE, w + ": a debug stop is set (clm_debug_stop_after): the forward ends before the head");
+    return CLM_OK;
 }
 
 size_t ids_elem_size(int dtype) { return dtype == CLM_DT_I64 ? 8 : (dtype == CLM_DT_I32 ? 4 : 1); }
@@ -895,12 +929,15 @@ int check_ids_arg(clm_handle* h, const char* who, const void* ids, const void* o
     return CLM_OK;
 }
 
-int forward_all(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int B, int L, float* logits, hipStream_t st) {
+// `attn`: the caller's attention outputs for all B reads, or null -- the self-check, the [PAD]-table build and every other forward the
+// engine runs for itself pass none
+int forward_all(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int B, int L, float* logits, hipStream_t st,
+                const clm_attn_out* attn = nullptr) {
     const int chunk = chunk_for(h, L);
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = B - b0 < chunk ? B - b0 : chunk;
         const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * row_stride * ids_elem_size(ids_dtype);
-        if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st)) return rc;
+        if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st, attn, b0)) return rc;
     }
     return CLM_OK;
 }
@@ -1064,14 +1101,21 @@ int clm_reserve(clm_handle* h, int B, int L) {
     return ensure_workspace(h, plan_chunk(h, B < chunk ? B : chunk, L), 0);
 }
 
-int clm_forward(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
-                float* logits_out, void* stream) {
+int clm_forward_attn(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                     const clm_attn_out* attn, void* stream) {
     if (!h) return CLM_E_INVALID;
-    if (!h->finalized) return fail(h, CLM_E_STATE, "clm_forward before clm_finalize");
-    if (int rc = check_ids_arg(h, "clm_forward", ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
+    const char* const who = attn ? "clm_forward_attn" : "clm_forward";
+    if (!h->finalized) return fail(h, CLM_E_STATE, std::string(who) + " before clm_finalize");
+    if (int rc = check_ids_arg(h, who, ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
+    if (int rc = check_attn_arg(h, who, attn, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = check_bad_ids(h)) return rc;
-    return forward_all(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, reinterpret_cast<hipStream_t>(stream));
+    return forward_all(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, reinterpret_cast<hipStream_t>(stream), attn);
+}
+
+int clm_forward(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
+                float* logits_out, void* stream) {
+    return clm_forward_attn(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, nullptr, stream);
 }
 
 int clm_stage_ids(clm_handle* h, const void* host_ids, int ids_dtype, int64_t ids_row_stride, int B, int L, int* staged) {
@@ -1102,6 +1146,10 @@ int clm_stage_ids(clm_handle* h, const void* host_ids, int ids_dtype, int64_t id
 }
 
 int clm_forward_staged(clm_handle* h, int staged, float* logits_out, void* stream) {
+    return clm_forward_staged_attn(h, staged, logits_out, nullptr, stream);
+}
+
+int clm_forward_staged_attn(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, void* stream) {
     if (!h) return CLM_E_INVALID;
     if (staged < 0 || staged > 1 || !h->stage[staged].pending)
         return fail(h, CLM_E_STATE, "clm_forward_staged: no batch staged in that buffer");
@@ -1109,7 +1157,7 @@ int clm_forward_staged(clm_handle* h, int staged, float* logits_out, void* strea
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(h, hipStreamWaitEvent(st, s.copied, 0));
-    const int rc = clm_forward(h, s.buf.get(), s.dtype, s.stride, s.B, s.L, logits_out, stream);
+    const int rc = clm_forward_attn(h, s.buf.get(), s.dtype, s.stride, s.B, s.L, logits_out, attn, stream);
     // whatever happened, the buffer is no longer "staged and waiting": a failed forward must not wedge it for good
     s.pending = false;
     s.used = true;

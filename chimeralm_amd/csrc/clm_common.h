@@ -612,4 +612,11 @@ void launch_head_tiles(const float* partial, int ntiles, const HeadW& hw, float*
                        hipStream_t st);
 void launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t st);
 
+// attention as an output (attn_weights.hip): softmax of the chunk's pooling scores [Bc][L] to weights (rows w_stride floats apart; null:
+// not wanted), and per read the summary record with its top_k peaks among the bases (null together: not wanted).  ids8 [Bc][Lp].
+constexpr int ATTN_MAX_L = 32832;   // tokens whose scores fit one workgroup's LDS (128.25 KiB of the CU's 160)
+constexpr int ATTN_MAX_TOP_K = 32;
+void launch_attn_weights(const float* scores, const unsigned char* ids8, int Bc, int L, int Lp, float* weights, int64_t w_stride,
+                         clm_attn_summary* summary, int* peak_pos, float* peak_w, int top_k, hipStream_t st);
+
 }  // namespace clm

@@ -3,6 +3,7 @@ and the current HIP stream; all arithmetic happens behind the C ABI (include/chi
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -17,6 +18,54 @@ class EngineError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"chimeralm_hip error {code}: {msg}")
         self.code = code
+
+
+@dataclass(frozen=True)
+class AttentionRequest:
+    """What a forward should also leave on the device (`clm_forward_attn`): per read the summary record and the `top_k` (1 ... 32)
+    largest-weight bases -- `top_k=None`: not wanted -- and / or the softmax weights of every position."""
+    top_k: int | None = 10
+    weights: bool = False
+
+    def __post_init__(self):
+        if self.top_k is None and not self.weights:
+            raise ValueError("an attention request asks for peaks (top_k), weights, or both")
+        if self.top_k is not None and not 1 <= int(self.top_k) <= N.ATTN_MAX_TOP_K:
+            raise ValueError(f"top_k must be 1 ... {N.ATTN_MAX_TOP_K}")
+
+
+@dataclass
+class AttentionOutput:
+    """Device tensors of one batch, complete when the forward's stream reaches them (nothing here synchronises).
+    `summary` int32 [B, 8] is the batch's `clm_attn_summary` records (`fields()` names the columns), `peak_pos` int32 [B, top_k]
+    0-based positions among a read's bases (token index = position + n_pad; -1 beyond n_peaks), `peak_weight` fp32 [B, top_k],
+    `weights` fp32 [B, L] the softmax over all positions, [PAD] and [SEP] included.  Parts not asked for are None."""
+    top_k: int | None
+    summary: torch.Tensor | None
+    peak_pos: torch.Tensor | None
+    peak_weight: torch.Tensor | None
+    weights: torch.Tensor | None
+
+    def tensors(self) -> dict[str, torch.Tensor]:
+        return {k: v for k, v in (("summary", self.summary), ("peak_pos", self.peak_pos), ("peak_weight", self.peak_weight),
+                                  ("weights", self.weights)) if v is not None}
+
+    def to_host(self, non_blocking: bool = True) -> "AttentionOutput":
+        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
+        host = {}
+        for k, v in self.tensors().items():
+            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
+            host[k].copy_(v, non_blocking=non_blocking)
+        return AttentionOutput(self.top_k, host.get("summary"), host.get("peak_pos"), host.get("peak_weight"), host.get("weights"))
+
+    def fields(self) -> dict[str, torch.Tensor]:
+        """The summary's columns by name (views): n_pad, n_bases, has_sep, n_peaks int32; pad_weight, sep_weight, base_weight fp32."""
+        if self.summary is None:
+            return {}
+        f = self.summary.view(torch.float32)
+        out = {n: self.summary[:, i] for i, n in enumerate(("n_pad", "n_bases", "has_sep", "n_peaks"))}
+        out.update({n: f[:, 4 + i] for i, n in enumerate(("pad_weight", "sep_weight", "base_weight"))})
+        return out
 
 
 class Engine:
@@ -86,8 +135,24 @@ class Engine:
         self._check(self._lib.clm_reserve(self._h, int(batch), int(length)))
 
     # ------------------------------------------------------------------ forward
-    def forward(self, input_ids: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """input_ids [B, L] (int64 / int32 / uint8) on this engine's device -> logits fp32 [B, 2].
+    def _attn_out(self, req: AttentionRequest, B: int, L: int) -> tuple[AttentionOutput, N.ClmAttnOut]:
+        """Device tensors for a request (torch's allocator, like the logits) and the `clm_attn_out` that points at them."""
+        a = AttentionOutput(None if req.top_k is None else int(req.top_k), None, None, None, None)
+        c = N.ClmAttnOut()
+        c.struct_size = C.sizeof(N.ClmAttnOut)
+        if req.weights:
+            a.weights = torch.empty((B, L), dtype=torch.float32, device=self.device)
+            c.weights, c.weights_row_stride = a.weights.data_ptr(), L
+        if a.top_k is not None:
+            a.summary = torch.empty((B, 8), dtype=torch.int32, device=self.device)
+            a.peak_pos = torch.empty((B, a.top_k), dtype=torch.int32, device=self.device)
+            a.peak_weight = torch.empty((B, a.top_k), dtype=torch.float32, device=self.device)
+            c.top_k, c.summary, c.peak_pos, c.peak_weight = a.top_k, a.summary.data_ptr(), a.peak_pos.data_ptr(), a.peak_weight.data_ptr()
+        return a, c
+
+    def forward(self, input_ids: torch.Tensor, out: torch.Tensor | None = None, attention: AttentionRequest | None = None):
+        """input_ids [B, L] (int64 / int32 / uint8) on this engine's device -> logits fp32 [B, 2]; with an `attention` request
+        -> (logits, AttentionOutput), written by the same call for every chunk of the batch (`clm_forward_attn`).
         Asynchronous on torch's current stream."""
         if input_ids.dim() != 2:
             raise ValueError("input_ids must be [batch, length]")
@@ -102,9 +167,14 @@ class Engine:
         if out is None:
             out = torch.empty((B, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self._lib.clm_forward(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
-                                          input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-        return out
+        if attention is None:
+            self._check(self._lib.clm_forward(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
+                                              input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            return out
+        att, c = self._attn_out(attention, B, L)
+        self._check(self._lib.clm_forward_attn(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
+                                               input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
+        return out, att
 
     __call__ = forward
 
@@ -117,12 +187,21 @@ class Engine:
                                             int(length), C.byref(k)))
         return k.value
 
-    def forward_staged(self, staged: int, batch: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    def forward_staged(self, staged: int, batch: int, out: torch.Tensor | None = None,
+                       attention: AttentionRequest | None = None, length: int | None = None):
+        """The forward of a staged batch of `batch` reads; with an `attention` request (then `length`, the batch's tokens per read,
+        is needed to size the weights) -> (logits, AttentionOutput), as `forward`."""
         if out is None:
             out = torch.empty((batch, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self._lib.clm_forward_staged(self._h, int(staged), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-        return out
+        if attention is None:
+            self._check(self._lib.clm_forward_staged(self._h, int(staged), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+            return out
+        if length is None:
+            raise ValueError("forward_staged with an attention request needs the batch's `length`")
+        att, c = self._attn_out(attention, int(batch), int(length))
+        self._check(self._lib.clm_forward_staged_attn(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
+        return out, att
 
     def check(self):
         """Wait for the current stream and raise for errors only the device can see (token ids outside the embedding table:

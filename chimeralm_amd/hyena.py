@@ -209,7 +209,8 @@ class HyenaDna(nn.Module):
 
     def __init__(self, number_of_classes: int, head: nn.Module, backbone_name: str = "hyenadna-small-32k-seqlen", *,
                  freeze_backbone: bool = False, precision: str = "fp16c", chunk_reads: int = 256,
-                 selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16):
+                 selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
+                 attention_top_k: int | None = None):
         super().__init__()
         if number_of_classes != 2:
             raise NotImplementedError("the engine implements the binary (2-class) head only")
@@ -227,6 +228,12 @@ class HyenaDna(nn.Module):
         self.selfcheck_every = int(selfcheck_every)
         self.selfcheck_report: dict = {}
         self.precision_report: dict = {}
+        # attention as an output (an engine knob, csrc/attn_weights.hip): with `attention_top_k` set every forward also leaves
+        # `last_attention`, an engine.AttentionOutput of DEVICE tensors -- per read the summary and its top-k bases, and the weights
+        # of every position too when `attention_device_weights` is set (the predict loops set it for --attention-weights)
+        self.attention_top_k = None if attention_top_k is None else int(attention_top_k)
+        self.attention_device_weights = False
+        self.last_attention = None
         if freeze_backbone:
             for p in self.backbone.parameters():
                 p.requires_grad = False
@@ -452,10 +459,24 @@ class HyenaDna(nn.Module):
                                "there is no CPU forward")
         eng = self.engine(input_ids.device)
         self.guard(eng, input_ids)
-        logits = eng.forward(input_ids)
+        req = self.attention_request()
+        if req is None:
+            return eng.forward(input_ids)
+        logits, att = eng.forward(input_ids, attention=req)
+        if self.attention_top_k is not None:
+            self.last_attention = att                       # device tensors; nothing waits for them here
         if getattr(self.head, "save_attention", False):
-            B, L = input_ids.shape
-            torch.cuda.current_stream(input_ids.device).synchronize()
-            scores = torch.from_numpy(eng.debug_fetch("scores", (B, L)))
-            self.head.attention_weights = torch.softmax(scores, dim=1).unsqueeze(-1)
+            # the reference's contract (hyena.py:129-130, a CPU tensor [B, L, 1]): the kernel's weights of every chunk of the batch,
+            # in the arithmetic the forward ran in, brought over by one D2H copy
+            self.head.attention_weights = att.weights.cpu().unsqueeze(-1)
         return logits
+
+    def attention_request(self):
+        """The `engine.AttentionRequest` this module's forwards make (None: none): peaks for `attention_top_k`, weights for
+        `head.save_attention` or `attention_device_weights`.  Loops that drive the engine directly pass it on themselves."""
+        from .engine import AttentionRequest
+
+        weights = bool(getattr(self.head, "save_attention", False)) or (self.attention_top_k is not None and self.attention_device_weights)
+        if self.attention_top_k is None and not weights:
+            return None
+        return AttentionRequest(top_k=self.attention_top_k, weights=weights)

@@ -10,6 +10,10 @@ Results leave the device one batch behind: the logits of batch i are copied to p
 forward, the forward of batch i+1 is enqueued, and only then does the host wait for copy i and write its file -- the GPU never
 idles while Python formats read names (the reference syncs on every batch, callbacks.py:107).
 
+With an `attention_writer` (callbacks.AttentionWriter; `predict --save-attention`) every batch's attention summary, peaks and --
+if asked for -- per-position weights (csrc/attn_weights.hip) take the same road: device -> page-locked host memory behind the forward,
+read one batch behind, after the same event as the logits.  No wait is added per batch.
+
 `run_test` is the loop of `lightning.Trainer.test` over the same double buffer: `model.test_step(batch)` queues the batch's metric
 update (csrc/eval_metrics.hip) behind its forward, so neither logits nor labels come back and the host waits for nothing per batch.
 
@@ -66,15 +70,19 @@ class _Deferred:
     behind this forward only; the gathered `[world * rows, 3]` tensor follows to page-locked host memory on that stream."""
 
     def __init__(self, logits: torch.Tensor | None, labels, batch: dict | None, batch_idx: int,
-                 gather: LogitsGather | None = None, rows: int = 0, device: torch.device | None = None):
+                 gather: LogitsGather | None = None, rows: int = 0, device: torch.device | None = None, attention=None):
         self.host, self.event = None, None
+        self.attention = None                                  # engine.AttentionOutput of host tensors, behind the same event
         if logits is not None and logits.is_cuda:
             self.host = torch.empty(logits.shape, dtype=logits.dtype, pin_memory=True)   # caching host allocator: cheap after the first
             self.host.copy_(logits, non_blocking=True)
+            if attention is not None:
+                self.attention = attention.to_host()
             self.event = torch.cuda.Event()
             self.event.record()
         elif logits is not None:                               # host tensors: the CPU rehearsal of the multi-rank protocol (tests)
             self.host = logits
+            self.attention = attention
         self.gathered, self.gathered_done = None, None
         if gather is not None:
             mine = torch.zeros((rows, 3), dtype=torch.float32, device=device if logits is None else logits.device)
@@ -93,7 +101,7 @@ class _Deferred:
                 self.gathered = full.cpu()
         self.labels, self.batch, self.batch_idx = labels, batch, batch_idx
 
-    def flush(self, writer, trainer, model, on_batch) -> bool:
+    def flush(self, writer, trainer, model, on_batch, attention_writer=None) -> bool:
         """Write this batch's file; hand the gathered round to `on_batch`.  Returns whether ANY rank had reads in this round."""
         alive = self.host is not None
         if self.gathered is not None:
@@ -106,25 +114,39 @@ class _Deferred:
             if self.event is not None:
                 self.event.synchronize()
             writer.write_on_batch_end(trainer, model, (self.host, self.labels), None, self.batch, self.batch_idx, 0)
+            if attention_writer is not None and self.attention is not None:
+                attention_writer.write_on_batch_end(trainer, model, (self.host, self.labels), self.attention, self.batch, self.batch_idx)
         return alive
 
 
-def _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch):
+def _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch, attention_writer=None):
     """Ranks run out of reads at different times, but a collective needs every rank: a rank that is done keeps contributing
     empty rounds until one round has come back with no valid row from anybody.  All ranks see the same gathered tensors one
     round behind, so all of them leave this loop after the same number of rounds."""
     while True:
         now = _Deferred(None, None, None, batch_idx, gatherer, rows, device)
-        alive = pending.flush(writer, trainer, model, on_batch) if pending is not None else True
+        alive = pending.flush(writer, trainer, model, on_batch, attention_writer) if pending is not None else True
         pending = now
         batch_idx += 1
         if not alive:
             break
-    pending.flush(writer, trainer, model, on_batch)
+    pending.flush(writer, trainer, model, on_batch, attention_writer)
+
+
+def _attention_setup(model, attention_writer):
+    """The net's attention request for a loop that writes attention files (None without a writer): the writer decides whether the
+    per-position weights come along (`attention_writer.weights`)."""
+    if attention_writer is None:
+        return None
+    net = model.net
+    if getattr(net, "attention_top_k", None) is None:
+        raise ValueError("an attention writer needs a net built with attention_top_k (HyenaDna(attention_top_k=...))")
+    net.attention_device_weights = bool(getattr(attention_writer, "weights", False))
+    return net.attention_request()
 
 
 def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                on_batch=None) -> int:
+                on_batch=None, attention_writer=None) -> int:
     """Returns the number of reads this rank classified.  `gather`: every batch's logits are also all-gathered over the process
     group (RCCL over xGMI when the backend is "nccl"), off the compute stream, and handed to `on_batch(batch_idx, tensor)` one
     batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows)."""
@@ -134,20 +156,22 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
     rows = getattr(datamodule, "batch_size_per_device", 0)
     n_reads, batch_idx = 0, 0
     pending: _Deferred | None = None
+    want_attention = _attention_setup(model, attention_writer) is not None
     with torch.inference_mode():
         for cur in _staged_batches(datamodule.predict_dataloader(), device):
             logits, labels = model.predict_step(cur, batch_idx)
-            now = _Deferred(logits, labels, cur, batch_idx, gatherer, rows)
+            now = _Deferred(logits, labels, cur, batch_idx, gatherer, rows,
+                            attention=model.net.last_attention if want_attention else None)   # (left by this batch's forward)
             if pending is not None:
-                pending.flush(writer, trainer, model, on_batch)   # batch i-1: its copy finished while batch i was enqueued
+                pending.flush(writer, trainer, model, on_batch, attention_writer)   # batch i-1: its copy finished while batch i was enqueued
             pending = now
             n_reads += logits.shape[0]
             batch_idx += 1
         _check_engine(model, device, batch_idx)
         if gatherer is not None:
-            _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch)
+            _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch, attention_writer)
         elif pending is not None:
-            pending.flush(writer, trainer, model, on_batch)
+            pending.flush(writer, trainer, model, on_batch, attention_writer)
     return n_reads
 
 
@@ -183,7 +207,7 @@ def _check_engine(model, device: torch.device, batch_idx: int) -> None:
 
 
 def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                       on_batch=None) -> int:
+                       on_batch=None, attention_writer=None) -> int:
     """Predict loop over a `chimeralm_amd.feeder.BamFeeder`; same files as `run_predict` over `BamDataModule`."""
     from ._native import DT_U8
 
@@ -194,6 +218,7 @@ def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int
     rows = feeder.batch_size
     n_reads, batch_idx = 0, 0
     pending: _Deferred | None = None
+    request = _attention_setup(model, attention_writer)
     cur = feeder.next()
     staged = eng.stage_host_ids(cur.ids_ptr, DT_U8, cur.row_stride, cur.n_reads, cur.n_tokens) if cur is not None else -1
     with torch.inference_mode():
@@ -205,21 +230,25 @@ def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int
             # (a callable: the host copy + H2D of the sampled rows happens only on the few batches a check is due for)
             model.net.guard(eng, lambda c=cur: torch.from_numpy(c.ids[: c.n_reads, : c.n_tokens][
                 model.net._sample_rows(c.n_reads, model.net._BATCH_ROWS)].copy()).to(device), n_tokens=cur.n_tokens, n_reads=cur.n_reads)
-            logits = eng.forward_staged(staged, cur.n_reads)
+            attention = None
+            if request is None:
+                logits = eng.forward_staged(staged, cur.n_reads)
+            else:
+                logits, attention = eng.forward_staged(staged, cur.n_reads, attention=request, length=cur.n_tokens)
             eng.stage_wait(staged)                            # the copy has left the slot ...
             feeder.release(cur)                               # ... which goes back to the decoder
             labels = torch.full((cur.n_reads,), -1, dtype=torch.int64)   # tokenizer.py:113: predict labels are all -1
             batch = {"id": torch.from_numpy(cur.names), "labels": labels}
-            now = _Deferred(logits, labels, batch, batch_idx, gatherer, rows)
+            now = _Deferred(logits, labels, batch, batch_idx, gatherer, rows, attention=attention)
             if pending is not None:
-                pending.flush(writer, trainer, model, on_batch)
+                pending.flush(writer, trainer, model, on_batch, attention_writer)
             pending = now
             n_reads += cur.n_reads
             batch_idx += 1
             cur, staged = nxt, nxt_staged
         _check_engine(model, device, batch_idx)
         if gatherer is not None:
-            _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch)
+            _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch, attention_writer)
         elif pending is not None:
-            pending.flush(writer, trainer, model, on_batch)
+            pending.flush(writer, trainer, model, on_batch, attention_writer)
     return n_reads

@@ -130,6 +130,44 @@ int clm_stage_ids(clm_handle* h, const void* host_ids, int ids_dtype, int64_t id
 int clm_forward_staged(clm_handle* h, int staged, float* logits_out, void* stream);
 int clm_stage_wait(clm_handle* h, int staged);
 
+/* ---- attention as an output -------------------------------------------------------------------------------------------
+ * Replaces `save_attention` of the reference (chimeralm/models/lm.py:14,40; BinarySequenceClassifier keeps
+ * `attention_weights = softmax(self.attention(x), dim=1)`, hyena.py:52,119,129-130) and what notebooks/attention.ipynb does with it
+ * on the host (find_attention_peaks: np.argsort(weights)[-top_k:][::-1]; the mass of a window), for whole batches and without a
+ * host synchronisation.  Per read b of L tokens with pooling scores s[b, t]:
+ *   weights     w[b, t] = exp(s[b, t] - max_t s) / sum_t exp(s[b, t] - max_t s) over ALL L positions, [PAD] and [SEP] included (the
+ *               reference's mask is always None, hyena.py:256): fp32, row b at weights + b * weights_row_stride.  The scores are
+ *               those of the arithmetic the forward ran in (precision, fall-back level, short-read switch).
+ *   summary     n_pad = length of the leading run of token id 4 ([PAD]); has_sep = the last token is id 1 ([SEP]); the BASES are the
+ *               n_bases positions in between.  pad_weight / sep_weight / base_weight: the weight on each of the three.
+ *   peaks       the n_peaks = min(top_k, n_bases) bases of largest weight, in descending weight, equal weights by lower position:
+ *               peak_pos[b * top_k + k] is 0-based among the read's bases (token index = position + n_pad), peak_weight its
+ *               weight; slots k >= n_peaks hold -1 / 0.  top_k is 1 ... 32.
+ * A read whose scores hold a NaN or +-inf reports n_peaks = 0 and NaN masses (never a position outside the read).
+ * `weights` may be NULL (summary and peaks only); `summary`, `peak_pos` and `peak_weight` may be NULL together (weights only); all
+ * NULL is CLM_E_INVALID, as are a top_k outside 1 ... 32 with a summary and a weights_row_stride < L.  All are device pointers for
+ * the B reads of the call: a batch larger than a chunk is written chunk by chunk at its rows.  One kernel per chunk behind the
+ * head on `stream` (csrc/attn_weights.hip: one workgroup per read, the scores cross HBM once, no atomics -- bitwise the same from
+ * run to run); L above 32,832 tokens is CLM_E_UNSUPPORTED.  Nothing else writes these buffers: not clm_selfcheck, not the
+ * forwards the engine runs for itself.  With `attn` NULL the two calls ARE clm_forward / clm_forward_staged. */
+typedef struct clm_attn_summary {
+    int32_t n_pad, n_bases, has_sep, n_peaks;
+    float pad_weight, sep_weight, base_weight;
+    int32_t reserved;
+} clm_attn_summary;
+typedef struct clm_attn_out {
+    int32_t struct_size;          /* = sizeof(clm_attn_out), ABI guard */
+    int32_t top_k;
+    float* weights;               /* fp32 [B][weights_row_stride] or NULL */
+    int64_t weights_row_stride;   /* floats between rows, >= L */
+    clm_attn_summary* summary;    /* [B] or NULL */
+    int32_t* peak_pos;            /* [B][top_k] */
+    float* peak_weight;           /* [B][top_k] */
+} clm_attn_out;
+int clm_forward_attn(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                     const clm_attn_out* attn, void* stream);
+int clm_forward_staged_attn(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, void* stream);
+
 /* Errors a forward can only detect on the device after the call has returned: a token id outside [0, vocab_rows), for
  * which the reference's nn.Embedding raises IndexError inside HyenaDna.forward (hyena.py:249).  The id kernels clamp such an
  * id (no wild read) and flag the handle; the flag is reported ONCE, as CLM_E_INVALID with the message in clm_last_error,
