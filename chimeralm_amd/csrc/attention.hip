@@ -17,7 +17,7 @@
 //     O^T = V^T P^T up to a fixed permutation of the key index inside each group of 16 -- which, being the reduction index, may
 //     be permuted freely as long as V's rows are permuted the same way: V rows are simply stored in that order when the tile
 //     is staged into LDS (bits 2 and 3 of the key index swapped);
-//   * V^T fragments come from the [key][d] tile with transposing LDS reads (ds_read_b64_tr_b16), K fragments with plain
+//   * V^T fragments come from the [key][d] tile with transposing LDS reads (ds_read_tr16_b64), K fragments with plain
 //     16-byte reads; K rows are padded to 80 bytes and V rows kept at 64 bytes so that both patterns are bank-conflict free
 //     (MI355X_MICROARCH.md "LDS": 4 x 16-lane groups for b128, 2 x 32 for the transposing read);
 //   * 256-thread workgroups (4 waves x 32 queries), 64-key tiles double-buffered in 18 KiB of LDS, < 128 VGPRs: several
@@ -184,16 +184,33 @@ __global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT
     if (q < L) {
         elem* op = out + ((size_t)b * L + q) * D + h * HD + 4 * hf;
         const float sc = HILO ? inv * ATT_HILO_SCALE : inv;
+        if constexpr (HILO) {
+            // One fp32 product x, one hi = fp16(x), and lo the rounding of their exact difference.  x is made opaque to the compiler:
+            // under -ffp-contract=fast it rounded o * sc to fp16 twice, once through fp32 for the stored hi (v_cvt_pk_f16_f32) and
+            // once directly from the exact product for the hi that lo is measured against (v_fma_mixlo_f16).  Where the two
+            // roundings fell on different sides of an fp16 midpoint the pair (hi, lo) was a whole ulp(hi) off: 131.0 - 0.0625
+            // stored for 131.0625 (tests/test_gpu_attention16.py).
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const elem e0 = from_float<elem>(o[4 * g + 0] * sc), e1 = from_float<elem>(o[4 * g + 1] * sc),
-                       e2 = from_float<elem>(o[4 * g + 2] * sc), e3 = from_float<elem>(o[4 * g + 3] * sc);
-            u16x4 pk = {e0.bits, e1.bits, e2.bits, e3.bits};
-            *reinterpret_cast<u16x4*>(op + 8 * g) = pk;
-            if constexpr (HILO) {
-                u16x4 pl = {from_float<elem>(o[4 * g + 0] * sc - to_float(e0)).bits, from_float<elem>(o[4 * g + 1] * sc - to_float(e1)).bits,
-                            from_float<elem>(o[4 * g + 2] * sc - to_float(e2)).bits, from_float<elem>(o[4 * g + 3] * sc - to_float(e3)).bits};
+            for (int g = 0; g < 4; ++g) {
+                u16x4 pk, pl;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float x = o[4 * g + e] * sc;
+                    asm("" : "+v"(x));
+                    const elem hi = from_float<elem>(x);
+                    pk[e] = hi.bits;
+                    pl[e] = from_float<elem>(x - to_float(hi)).bits;
+                }
+                *reinterpret_cast<u16x4*>(op + 8 * g) = pk;
                 *reinterpret_cast<u16x4*>(op + plane + 8 * g) = pl;
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const elem e0 = from_float<elem>(o[4 * g + 0] * sc), e1 = from_float<elem>(o[4 * g + 1] * sc),
+                           e2 = from_float<elem>(o[4 * g + 2] * sc), e3 = from_float<elem>(o[4 * g + 3] * sc);
+                u16x4 pk = {e0.bits, e1.bits, e2.bits, e3.bits};
+                *reinterpret_cast<u16x4*>(op + 8 * g) = pk;
             }
         }
     }
@@ -215,8 +232,12 @@ void launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hi
 
 // ---- C ABI (include/chimeralm_hip.h): stand-alone entry for tests and for the encoder path under construction
 extern "C" int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, void* stream) {
-    if (!qkv || !out || B < 1 || L < 1 || (precision != CLM_PREC_F16 && precision != CLM_PREC_BF16)) return CLM_E_INVALID;
+    if (!qkv || !out || B < 1 || L < 1) return CLM_E_INVALID;
+    if (precision != CLM_PREC_F16 && precision != CLM_PREC_BF16 && precision != CLM_PREC_F16C) return CLM_E_INVALID;
+    // the kernel reads qkv in 16-byte pieces and writes out in 8-byte ones: refuse what it cannot address, before any launch
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7)) return CLM_E_INVALID;
+    // CLM_PREC_F16C: the transformer's fp16c attention, fp16 operands and the two-plane HILO output (as tf_model.hip launches it)
     clm::launch_attention_fwd(precision == CLM_PREC_BF16 ? clm::PREC_BF16 : clm::PREC_F16, qkv, out, B, L,
-                              reinterpret_cast<hipStream_t>(stream), false);
+                              reinterpret_cast<hipStream_t>(stream), precision == CLM_PREC_F16C);
     return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
 }

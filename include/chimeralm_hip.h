@@ -220,7 +220,11 @@ int clm_set_mlp_compensation(clm_handle* h, int on);
  * Multi-head self-attention of nn.TransformerEncoderLayer as the reference builds it
  * (/root/reference/chimeralm/models/components/transformer.py:64-68,98: d_model 256, 8 heads of 32, no masks):
  *   qkv  device, [B, L, 768] 16-bit, the in_proj output q | k | v per token;  out  device, [B, L, 256] 16-bit, heads concatenated
- *   precision CLM_PREC_F16 or CLM_PREC_BF16 (element type of qkv / out; statistics and accumulation are fp32). */
+ *   precision CLM_PREC_F16 or CLM_PREC_BF16 (element type of qkv / out; statistics and accumulation are fp32), or CLM_PREC_F16C:
+ *   the attention of the transformer's fp16c mode -- qkv fp16, out 2 * B * L * 256 fp16 values, the plane hi = fp16(64 a) and then
+ *   the plane lo = fp16(64 a - hi), so that a = (hi + lo) / 64 to ~2^-21.  CLM_PREC_F32 and CLM_PREC_F16X3 are CLM_E_INVALID here
+ *   (clm_attention_exact_fwd).  qkv must be 16-byte aligned and out 8-byte aligned (the kernel's load and store widths), else
+ *   CLM_E_INVALID and nothing is launched.  Asynchronous on `stream`; writes nothing beyond out[B * L * 256] (F16C: twice that). */
 int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, void* stream);
 /* The same attention in the arithmetic of the exact path (csrc/tf_fp32.hip; the kernels clm_tf_forward runs there): qkv device fp32
  * [B, L, 768], out device fp32 [B, L, 256]; precision CLM_PREC_F32 (fp32 products) or CLM_PREC_F16X3 (every operand as fp16 hi + lo,

@@ -290,6 +290,34 @@ def test_long_context_matches_oracle(built_lib, prec, seed, B, L):
     net.close()
 
 
+_LONG_FP32: dict = {}
+
+
+@pytest.mark.parametrize("prec", ["fp16c", "fp16", "bf16"])
+def test_16bit_modes_at_long_context(built_lib, prec):
+    """The 16-bit modes at the net's long-context shape, 2 x 32,768 bp = 4,096 attention positions (32 query tiles, 64 key tiles of
+    attention_fwd_kernel; elsewhere they stop at 512 positions): logits and the `hidden` tap against an fp32 handle on the same
+    weights and ids -- the very handle `test_long_context_matches_oracle[7-2-32768-fp32]` ties to the oracle at this shape -- within
+    the file's own TOL and TOL_HIDDEN."""
+    B, L = 2, 32768
+    sd = to.make_state_dict(7, to.PRODUCTION, scale=3.0)                          # weights and ids of `_long_case(7, 2, 32768)`
+    t = torch.from_numpy(to.synthetic_ids(207, B, L)).cuda()
+    if not _LONG_FP32:
+        exact = _model(sd, "fp32")
+        _LONG_FP32["logits"] = exact(t).cpu().numpy()
+        _LONG_FP32["hidden"] = exact.debug_fetch("hidden", (B, L // 8, 256)).copy()
+        exact.close()
+    net = _model(sd, prec)
+    got = net(t).cpu().numpy()
+    assert np.isfinite(got).all()
+    err = np.abs(got - _LONG_FP32["logits"]).max()
+    err_h = np.abs(net.debug_fetch("hidden", (B, L // 8, 256)) - _LONG_FP32["hidden"]).max()
+    net.close()
+    msg = f"{prec} B={B} L={L} (4,096 positions): |logits - fp32 handle| = {err:.2e}, |hidden - fp32 handle| = {err_h:.2e}"
+    print(msg)
+    assert err < TOL[prec] and err_h < TOL_HIDDEN[prec], msg
+
+
 def test_fp16x3_bench_line_rows_are_independent(built_lib):
     """The benched transformer line, 32 x 32,768 in fp16x3 (4,096 positions through attention_x3_kernel): bit-identical on a second
     run, rows run alone equal their batch rows bit for bit (no operation mixes reads), and exact fp32 agrees on all 32 rows."""
