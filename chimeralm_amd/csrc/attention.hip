@@ -1,4 +1,6 @@
-// attention.hip -- multi-head self-attention forward for the SequenceCNNTransformer encoder.
+// attention.hip -- multi-head self-attention forward for the SequenceCNNTransformer encoder: ONE
+// tiled online-softmax skeleton (attention_tiles) and the three MFMA arithmetics that run on it -- 16 bit (fp16 / bf16, and fp16c's
+// two-plane output), exact fp32, and fp16x3.
 //
 // Reference arithmetic: nn.TransformerEncoderLayer's self-attention as the reference constructs it
 //   /root/reference/chimeralm/models/components/transformer.py:64-68,98   (d_model 256, nhead 8 -> head dim 32, batch_first,
@@ -7,23 +9,28 @@
 // with q | k | v the three 256-wide thirds of the in_proj output (in_proj_weight [768, 256] is laid out q, k, v).
 //
 // Shape of the problem on MI355X: head dim 32 makes the softmax, not the matrix products, the bound -- per 32 x 32 block of
-// scores a wave issues 4 MFMAs (128 cycles of pipe) and ~450 cycles of VALU (exp2 at quarter rate).  So the kernel is built
-// around a cheap softmax:
+// scores a wave issues 4 16-bit MFMAs (128 cycles of pipe) and ~450 cycles of VALU (exp2 at quarter rate).  So the skeleton is
+// built around a cheap softmax:
 //   * scores are computed TRANSPOSED, S^T = K Q^T (rows = keys, columns = queries): in the 32x32 accumulator layout a lane then
 //     owns ONE query (column l & 31) and 16 of its 32 keys in registers, so the row maximum / row sum of the softmax are
 //     register reductions plus one exchange between the two half-waves (lane ^ 32) -- no 32-lane shuffle trees;
-//   * exp2(s*c - m*c) with c = log2(e)/sqrt(32): one FMA + one v_exp_f32 per score;
-//   * P^T never leaves the registers: the accumulator registers of S^T, converted to 16 bit, ARE the B operand of
-//     O^T = V^T P^T up to a fixed permutation of the key index inside each group of 16 -- which, being the reduction index, may
-//     be permuted freely as long as V's rows are permuted the same way: V rows are simply stored in that order when the tile
-//     is staged into LDS (bits 2 and 3 of the key index swapped);
-//   * V^T fragments come from the [key][d] tile with transposing LDS reads (ds_read_tr16_b64), K fragments with plain
-//     16-byte reads; K rows are padded to 80 bytes and V rows kept at 64 bytes so that both patterns are bank-conflict free
-//     (MI355X_MICROARCH.md "LDS": 4 x 16-lane groups for b128, 2 x 32 for the transposing read);
-//   * 256-thread workgroups (4 waves x 32 queries), 64-key tiles double-buffered in 18 KiB of LDS, < 128 VGPRs: several
-//     workgroups per CU hide the exp latency of each other.
+//   * exp2(s*c - m*c) with c = log2(e)/sqrt(32): one FMA + one v_exp_f32 per score, in place in the score accumulators;
+//   * P^T never leaves the registers: the accumulator registers of S^T ARE (converted, split, or as they are) the B operand of
+//     O^T = V^T P^T, because the key index, being the reduction index, may be paired freely as long as V's rows are paired the
+//     same way -- each arithmetic's pv() says how it pairs them;
+//   * 256-thread workgroups (4 waves x 32 queries), 64-key tiles double-buffered in LDS, the next tile's global loads in flight
+//     under the current tile's arithmetic: several workgroups per CU hide the exp latency of each other.
 // Online softmax (running maximum m, running sum l, accumulator rescaled when m grows) over the key tiles; keys beyond L are
-// masked to -inf in the last tile; fp32 statistics and accumulation, 16-bit MFMA inputs.
+// masked to -inf in the last tile; fp32 statistics and accumulation in every arithmetic.
+//
+// An arithmetic A is a plain struct of registers and LDS pointers:
+//   in_t                                element type of qkv
+//   load_q(row, hf)                     Q^T fragments of this lane's query (row = its q, this head) into registers
+//   load_tile(base, k0, L, tid)         keys k0 .. k0 + 63 (clamped to L - 1) of K and V from global memory into registers
+//   store_tile(buf, tid)                ... from there into LDS buffer buf
+//   scores(buf, blk, n, hf) -> f32x16   S^T of the 32-key block blk
+//   pv(buf, p, o, lane, n, hf)          o += V^T P^T, p = the two blocks' fp32 probabilities in accumulator layout: register r of
+//                                       block blk is key blk * 32 + (r & 3) + 8 (r >> 2) + 4 hf of the tile
 #include "chimeralm_hip.h"
 #include "gemm_common.h"
 
@@ -31,39 +38,47 @@ namespace clm {
 
 namespace {
 
+using f32x4 = float __attribute__((ext_vector_type(4)));
+using s16x8 = short __attribute__((ext_vector_type(8)));
 using v4i16 = short __attribute__((ext_vector_type(4)));
 typedef v4i16 __attribute__((address_space(3))) * lds_v4i16_ptr;
+template <int N>
+using fvec = float __attribute__((ext_vector_type(N)));
+template <int N>
+using hvec = _Float16 __attribute__((ext_vector_type(N)));
 
 constexpr int HD = 32;            // head dim
 constexpr int NH = D / HD;        // 8 heads
 constexpr int QT = 128;           // queries per workgroup (4 waves x 32)
 constexpr int KT = 64;            // keys per staged tile
-constexpr int KRS = 40;           // K tile row stride in elements: 80 bytes
-constexpr int VRS = 32;           // V tile row stride in elements: 64 bytes
+// Tile row strides.  16-bit elements (A16, AX3): K rows padded to 80 bytes and V rows kept at 64 bytes so that the plain 16-byte
+// reads of K and the transposing reads of V are both bank-conflict free (MI355X_MICROARCH.md "LDS": 4 x 16-lane groups for b128,
+// 2 x 32 for the transposing read).  Floats (A32): the 16 rows of a ds_read_b128 group on 16 bank groups (K); rows 4 apart on
+// banks + 32 (V, ds_read_b32).
+constexpr int KRS = 40, VRS = 32;
+constexpr int KRS32 = 36, VRS32 = 40;
 
 // exchange between the two half-waves (lane ^ 32): one ds_bpermute per 64-key tile
 __device__ __forceinline__ float half_max(float x) { return fmaxf(x, __shfl_xor(x, 32, 64)); }
 __device__ __forceinline__ float half_sum(float x) { return x + __shfl_xor(x, 32, 64); }
 
-// row of the V tile that holds key `k` (k < KT): bits 2 and 3 swapped inside each group of 16
+// A16 / AX3: the accumulator registers 8 s .. 8 s + 7 of a block are, as B operand of a K = 16 MFMA step, its 16 keys with bits 2 and
+// 3 of the key index swapped.  V rows are simply stored in that order when the tile is staged: v_row(k) holds key k (k < KT) ...
 __device__ __forceinline__ int v_row(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
+// ... and the V^T fragment of a step comes from the [key row][d] tile with two transposing reads (ds_read_tr16_b64), rows 4 apart
+template <class F, class T>
+__device__ __forceinline__ F vt_frag(const T* p0) {
+    const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16_ptr)(p0));
+    const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16_ptr)(p0 + 4 * VRS));
+    const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(F, both);
+}
 
-}  // namespace
-
-// HILO (round 3, the transformer's fp16c mode): the output leaves as TWO 16-bit planes, out[0] = fp16(64 a) and out[1] =
-// fp16(64 a - out[0]), `plane` elements apart.  The attention output is close to the same vector at every position of a read
-// (an average of v over all keys), so its rounding to 16 bits is the one activation rounding of this net that does NOT average
-// out in the pooling: measured on the CPU (tests/tf_error_probe.py) it alone moves the logits by 2-4e-3 where every other
-// operand's rounding stays below 1e-3.  The factor 64 (exact) keeps the lo plane out of fp16's subnormal range; out_proj
-// multiplies both planes by the same weights and scales its accumulators by 1/64 (tf_model.hip, enc_ffn16_kernel).
-constexpr float ATT_HILO_SCALE = 64.0f;
-
-template <int PREC, bool HILO = false>
-__global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT<PREC>::elem* __restrict__ qkv,
-                                                            typename CT<PREC>::elem* __restrict__ out, int L, size_t plane) {
-    using elem = typename CT<PREC>::elem;
-    __shared__ __attribute__((aligned(16))) elem Ks[2][KT * KRS];
-    __shared__ __attribute__((aligned(16))) elem Vs[2][KT * VRS];
+// The one text of the tile loop.  On return o = this lane's unnormalised O^T column (rows d = (r & 3) + 8 (r >> 2) + 4 hf), inv =
+// 1 / its softmax denominator, and (b, h, q) = read, head and query of the lane; q >= L in the ragged last query tile.
+template <class A>
+__device__ __forceinline__ void attention_tiles(A& a, const typename A::in_t* __restrict__ qkv, int L, f32x16& o, float& inv, int& b,
+                                                int& h, int& q) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hf = lane >> 5;
     // Workgroup -> (query tile, head, read).  The hardware deals consecutive workgroup ids round-robin to the 8 XCDs, each with
     // its own L2: the query tiles of one (read, head) -- which all stream the same K / V -- are given ids that are congruent
@@ -72,57 +87,29 @@ __global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT
     const int ntq = (L + QT - 1) / QT;
     const int g = blockIdx.x, xcd = g & 7, slot = g >> 3;
     const int bh = (slot / ntq) * 8 + xcd;                          // B * 8 (read, head) pairs: always a multiple of 8
-    const int q0 = (slot % ntq) * QT, h = bh & 7, b = bh >> 3;
-    const elem* base = qkv + (size_t)b * L * D3 + h * HD;            // row t: base + t * 768 ; q at +0, k at +256, v at +512
+    const int q0 = (slot % ntq) * QT;
+    h = bh & 7, b = bh >> 3;
+    const typename A::in_t* base = qkv + (size_t)b * L * D3 + h * HD;   // row t: base + t * 768 ; q at +0, k at +256, v at +512
     const float c = 1.4426950408889634f * 0.17677669529663687f;      // log2(e) / sqrt(32)
+    q = q0 + wave * 32 + n;
+    a.load_q(base + (size_t)(q < L ? q : L - 1) * D3, hf);
 
-    // Q^T as B operand, both k-steps: lane (query n, half hf) holds q[d = 16 s + 8 hf + 0..7]
-    u16x8 qf[2];
-    {
-        const int q = q0 + wave * 32 + n;
-        const elem* qp = base + (size_t)(q < L ? q : L - 1) * D3;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) qf[s] = *reinterpret_cast<const u16x8*>(qp + 16 * s + 8 * hf);
-    }
-    // staging map: thread -> (key row, 16-byte piece) of the K and of the V tile: 64 keys x 4 pieces = 256 threads
-    const int sk = tid >> 2, sp = tid & 3;
-    auto load_tile = [&](int k0, uint4& kreg, uint4& vreg) {
-        const int key = k0 + sk < L ? k0 + sk : L - 1;                // clamped; the score mask removes the clones
-        const elem* p = base + (size_t)key * D3 + 8 * sp;
-        kreg = *reinterpret_cast<const uint4*>(p + D);
-        vreg = *reinterpret_cast<const uint4*>(p + 2 * D);
-    };
-    auto store_tile = [&](int buf, const uint4& kreg, const uint4& vreg) {
-        *reinterpret_cast<uint4*>(&Ks[buf][sk * KRS + 8 * sp]) = kreg;
-        *reinterpret_cast<uint4*>(&Vs[buf][v_row(sk) * VRS + 8 * sp]) = vreg;
-    };
-
-    f32x16 o;                      // O^T: rows d, column = this lane's query
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = 0.f;
     float m = -INFINITY, l = 0.f;  // running maximum (shared by both halves) and this half's share of the running sum
 
     const int ntiles = (L + KT - 1) / KT;
-    uint4 kreg, vreg;
-    load_tile(0, kreg, vreg);
-    store_tile(0, kreg, vreg);
+    a.load_tile(base, 0, L, tid);
+    a.store_tile(0, tid);
     __syncthreads();
 #pragma unroll 1
     for (int t = 0; t < ntiles; ++t) {
         const int buf = t & 1, k0 = t * KT;
-        if (t + 1 < ntiles) load_tile(k0 + KT, kreg, vreg);           // in flight under the block below
+        if (t + 1 < ntiles) a.load_tile(base, k0 + KT, L, tid);       // in flight under the block below
         // ---- S^T = K Q^T for the 64 keys of the tile: two 32-key blocks
         f32x16 s[2];
 #pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[blk][r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const u16x8 kf = *reinterpret_cast<const u16x8*>(&Ks[buf][(blk * 32 + n) * KRS + 16 * ks + 8 * hf]);
-                s[blk] = mfma<PREC>(kf, qf[ks], s[blk]);
-            }
-        }
+        for (int blk = 0; blk < 2; ++blk) s[blk] = a.scores(buf, blk, n, hf);
         if (k0 + KT > L) {                                             // last tile: keys beyond the read
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk)
@@ -141,46 +128,249 @@ __global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT
         const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c);   // 0 on the first tile (m = -inf)
         const float mc = m_new * c;
         float psum = 0.f;
-        u16x8 pf[2][2];                                                // P^T as B operand: [block][k-step of 16 keys]
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                float p[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    p[j] = __builtin_amdgcn_exp2f(fmaf(s[blk][8 * ks + j], c, -mc));
-                    psum += p[j];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pf[blk][ks][j] = from_float<elem>(p[j]).bits;
+            for (int r = 0; r < 16; ++r) {
+                s[blk][r] = __builtin_amdgcn_exp2f(fmaf(s[blk][r], c, -mc));
+                psum += s[blk][r];
             }
         l = l * alpha + psum;
         m = m_new;
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        // ---- O^T += V^T P^T: V^T fragments by transposing reads of the [key row][d] tile
-        {
-            const int li = lane & 15, g1 = (lane >> 4) & 1, q4 = li >> 2, p4 = li & 3;
-            const elem* vb = &Vs[buf][(8 * hf + q4) * VRS + 16 * g1 + 4 * p4];
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const elem* p0 = vb + (blk * 32 + ks * 16) * VRS;
-                    const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16_ptr)(p0));
-                    const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16_ptr)(p0 + 4 * VRS));
-                    const u16x8 vf = {(unsigned short)lo[0], (unsigned short)lo[1], (unsigned short)lo[2], (unsigned short)lo[3],
-                                      (unsigned short)hi[0], (unsigned short)hi[1], (unsigned short)hi[2], (unsigned short)hi[3]};
-                    o = mfma<PREC>(vf, pf[blk][ks], o);
-                }
-        }
-        if (t + 1 < ntiles) store_tile(buf ^ 1, kreg, vreg);           // the other buffer was last read in trip t - 1
+        a.pv(buf, s, o, lane, n, hf);                                  // ---- O^T += V^T P^T
+        if (t + 1 < ntiles) a.store_tile(buf ^ 1, tid);                // the other buffer was last read in trip t - 1
         __syncthreads();
     }
+    inv = 1.0f / half_sum(l);
+}
+
+// ---- 16 bit: fp16 / bf16 operands, v_mfma_f32_32x32x16; 4 MFMAs per 32-key block for the scores and 4 for P V.  18 KiB of LDS.
+template <int PREC>
+struct A16 {
+    using in_t = typename CT<PREC>::elem;
+    in_t *Ks, *Vs;                 // [2][KT * KRS], [2][KT * VRS]
+    u16x8 qf[2];                   // Q^T as B operand, both k-steps: lane (query n, half hf) holds q[d = 16 s + 8 hf + 0..7]
+    uint4 kreg, vreg;              // staging: thread -> (key row tid >> 2, 16-byte piece tid & 3) of the K and of the V tile
+
+    __device__ __forceinline__ void load_q(const in_t* row, int hf) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) qf[s] = *reinterpret_cast<const u16x8*>(row + 16 * s + 8 * hf);
+    }
+    __device__ __forceinline__ void load_tile(const in_t* base, int k0, int L, int tid) {
+        const int sk = tid >> 2, sp = tid & 3;
+        const int key = k0 + sk < L ? k0 + sk : L - 1;                // clamped; the score mask removes the clones
+        const in_t* p = base + (size_t)key * D3 + 8 * sp;
+        kreg = *reinterpret_cast<const uint4*>(p + D);
+        vreg = *reinterpret_cast<const uint4*>(p + 2 * D);
+    }
+    __device__ __forceinline__ void store_tile(int buf, int tid) {
+        const int sk = tid >> 2, sp = tid & 3;
+        *reinterpret_cast<uint4*>(&Ks[buf * KT * KRS + sk * KRS + 8 * sp]) = kreg;
+        *reinterpret_cast<uint4*>(&Vs[buf * KT * VRS + v_row(sk) * VRS + 8 * sp]) = vreg;
+    }
+    __device__ __forceinline__ f32x16 scores(int buf, int blk, int n, int hf) const {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const u16x8 kf = *reinterpret_cast<const u16x8*>(&Ks[buf * KT * KRS + (blk * 32 + n) * KRS + 16 * ks + 8 * hf]);
+            s = mfma<PREC>(kf, qf[ks], s);
+        }
+        return s;
+    }
+    __device__ __forceinline__ void pv(int buf, const f32x16 (&p)[2], f32x16& o, int lane, int n, int hf) const {
+        const int li = lane & 15, g1 = (lane >> 4) & 1, q4 = li >> 2, p4 = li & 3;
+        const in_t* vb = &Vs[buf * KT * VRS + (8 * hf + q4) * VRS + 16 * g1 + 4 * p4];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                u16x8 pf;                                              // P^T as B operand of this 16-key step
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pf[j] = from_float<in_t>(p[blk][8 * ks + j]).bits;
+                o = mfma<PREC>(vt_frag<u16x8>(vb + (blk * 32 + ks * 16) * VRS), pf, o);
+            }
+    }
+};
+
+// ---- fp32 staging shared by the two exact arithmetics: thread -> (key row, 4-float piece) x 2 of the K and of the V tile
+struct StageF32 {
+    using in_t = float;
+    f32x4 kreg[2], vreg[2];
+    __device__ __forceinline__ void load_tile(const float* base, int k0, int L, int tid) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
+            const int key = k0 + j < L ? k0 + j : L - 1;                // clamped; the score mask removes the clones
+            const float* p = base + (size_t)key * D3 + 4 * d4;
+            kreg[i] = *reinterpret_cast<const f32x4*>(p + D);
+            vreg[i] = *reinterpret_cast<const f32x4*>(p + 2 * D);
+        }
+    }
+};
+
+// ---- exact fp32: v_mfma_f32_32x32x2_f32, 16 MFMAs per 32-key block for the scores and 16 for P V: per 64-key tile 64 MFMAs of 64
+// cycles next to ~900 cycles of softmax VALU -- MFMA-bound.  Accumulator register t of a block IS the B operand of step t of
+// O^T = V^T P^T, with the A operand read from the V row of the key that register holds (lanes 0-31 feed key (t & 3) + 8 (t >> 2),
+// lanes 32-63 that key + 4): V rows are stored in key order.  38 KiB of LDS.
+struct A32 : StageF32 {
+    float *Ks, *Vs;                // [2][KT * KRS32], [2][KT * VRS32]
+    f32x4 qf[4];                   // Q^T as B operand: d = 8 s + 4 hf + 0..3
+
+    __device__ __forceinline__ void load_q(const float* row, int hf) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const f32x4*>(row + 4 * hf + 8 * s);
+    }
+    __device__ __forceinline__ void store_tile(int buf, int tid) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
+            *reinterpret_cast<f32x4*>(&Ks[buf * KT * KRS32 + j * KRS32 + 4 * d4]) = kreg[i];
+            *reinterpret_cast<f32x4*>(&Vs[buf * KT * VRS32 + j * VRS32 + 4 * d4]) = vreg[i];
+        }
+    }
+    __device__ __forceinline__ f32x16 scores(int buf, int blk, int n, int hf) const {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        const float* kp = &Ks[buf * KT * KRS32 + (blk * 32 + n) * KRS32 + 4 * hf];
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + 8 * st);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j], qf[st][j], s, 0, 0, 0);
+        }
+        return s;
+    }
+    __device__ __forceinline__ void pv(int buf, const f32x16 (&p)[2], f32x16& o, int lane, int n, int hf) const {
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const float* vp = &Vs[buf * KT * VRS32 + (blk * 32 + 4 * hf) * VRS32 + n];
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+                o = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[((t & 3) + 8 * (t >> 2)) * VRS32], p[blk][t], o, 0, 0, 0);
+        }
+    }
+};
+
+// ---- fp16x3: every operand as two halfs (hi = fp16(x), lo = fp16(x - hi)) and three fp16 MFMAs per product (hi hi, lo hi, hi lo):
+// 12 MFMAs per 32-key block for the scores and 12 for P V.  q / k / v arrive as fp32 and are split on their way into registers / LDS,
+// the probabilities per 16-key step, immediately before that step's MFMAs.  Operand layouts, strides, the V-row permutation and the
+// transposing V reads are A16's, with a hi and a lo plane of every tile: 36 KiB of LDS.
+struct AX3 : StageF32 {
+    _Float16 *Ks, *Vs;             // [2][2][KT * KRS], [2][2][KT * VRS]: [buffer][hi | lo]
+    hvec<8> qh[2], ql[2];          // Q^T as B operand: d = 16 s + 8 hf + 0..7
+
+    template <int N>
+    static __device__ __forceinline__ fvec<N> clamp(fvec<N> v) {      // (beyond fp16's range: saturate, never inf -- tail32.hip split4)
+        fvec<N> r;
+#pragma unroll
+        for (int e = 0; e < N; ++e) r[e] = __builtin_amdgcn_fmed3f(v[e], -65504.f, 65504.f);
+        return r;
+    }
+    template <int N>
+    static __device__ __forceinline__ void split(fvec<N> v, hvec<N>& hi, hvec<N>& lo) {
+        hi = __builtin_convertvector(clamp<N>(v), hvec<N>);
+        lo = __builtin_convertvector(clamp<N>(v - __builtin_convertvector(hi, fvec<N>)), hvec<N>);
+    }
+    static __device__ __forceinline__ f32x16 mm(hvec<8> a, hvec<8> b, f32x16 acc) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+    }
+
+    __device__ __forceinline__ void load_q(const float* row, int hf) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(row + 8 * hf + 16 * s), y = *reinterpret_cast<const f32x4*>(row + 8 * hf + 16 * s + 4);
+            split<8>(fvec<8>{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]}, qh[s], ql[s]);
+        }
+    }
+    __device__ __forceinline__ void store_tile(int buf, int tid) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
+            hvec<4> kh, kl, vh, vl;
+            split<4>(kreg[i], kh, kl);
+            split<4>(vreg[i], vh, vl);
+            _Float16* kp = &Ks[buf * 2 * KT * KRS + j * KRS + 4 * d4];
+            _Float16* vp = &Vs[buf * 2 * KT * VRS + v_row(j) * VRS + 4 * d4];
+            *reinterpret_cast<hvec<4>*>(kp) = kh;
+            *reinterpret_cast<hvec<4>*>(kp + KT * KRS) = kl;
+            *reinterpret_cast<hvec<4>*>(vp) = vh;
+            *reinterpret_cast<hvec<4>*>(vp + KT * VRS) = vl;
+        }
+    }
+    __device__ __forceinline__ f32x16 scores(int buf, int blk, int n, int hf) const {
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const _Float16* kp = &Ks[buf * 2 * KT * KRS + (blk * 32 + n) * KRS + 16 * ks + 8 * hf];
+            const hvec<8> kh = *reinterpret_cast<const hvec<8>*>(kp), kl = *reinterpret_cast<const hvec<8>*>(kp + KT * KRS);
+            s = mm(kh, qh[ks], s);
+            s = mm(kl, qh[ks], s);
+            s = mm(kh, ql[ks], s);
+        }
+        return s;
+    }
+    __device__ __forceinline__ void pv(int buf, const f32x16 (&p)[2], f32x16& o, int lane, int n, int hf) const {
+        const int li = lane & 15, g1 = (lane >> 4) & 1, q4 = li >> 2, p4 = li & 3;
+        const _Float16* vb = &Vs[buf * 2 * KT * VRS + (8 * hf + q4) * VRS + 16 * g1 + 4 * p4];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                fvec<8> pp;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) pp[j] = p[blk][8 * ks + j];
+                hvec<8> ph, pl;                                        // P^T as B operand of this 16-key step, hi and lo halfs
+                split<8>(pp, ph, pl);
+                const _Float16* p0 = vb + (blk * 32 + ks * 16) * VRS;
+                const hvec<8> vh = vt_frag<hvec<8>>(p0), vl = vt_frag<hvec<8>>(p0 + KT * VRS);
+                o = mm(vh, ph, o);
+                o = mm(vl, ph, o);
+                o = mm(vh, pl, o);
+            }
+    }
+};
+
+// output of the two exact kernels: lane (query n, half hf) holds d = (r & 3) + 8 (r >> 2) + 4 hf
+__device__ __forceinline__ void store_f32(float* __restrict__ out, int L, const f32x16& o, float inv, int b, int h, int q) {
+    if (q >= L) return;
+    const int hf = (threadIdx.x >> 5) & 1;
+    float* op = out + ((size_t)b * L + q) * D + h * HD + 4 * hf;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+        *reinterpret_cast<float4*>(op + 8 * gq) = make_float4(o[4 * gq + 0] * inv, o[4 * gq + 1] * inv, o[4 * gq + 2] * inv, o[4 * gq + 3] * inv);
+}
+
+}  // namespace
+
+// HILO (round 3, the transformer's fp16c mode): the output leaves as TWO 16-bit planes, out[0] = fp16(64 a) and out[1] =
+// fp16(64 a - out[0]), `plane` elements apart.  The attention output is close to the same vector at every position of a read
+// (an average of v over all keys), so its rounding to 16 bits is the one activation rounding of this net that does NOT average
+// out in the pooling: measured on the CPU (tests/tf_error_probe.py) it alone moves the logits by 2-4e-3 where every other
+// operand's rounding stays below 1e-3.  The factor 64 (exact) keeps the lo plane out of fp16's subnormal range; out_proj
+// multiplies both planes by the same weights and scales its accumulators by 1/64 (tf_model.hip, enc_ffn16_kernel).
+constexpr float ATT_HILO_SCALE = 64.0f;
+
+template <int PREC, bool HILO = false>
+__global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT<PREC>::elem* __restrict__ qkv,
+                                                            typename CT<PREC>::elem* __restrict__ out, int L, size_t plane) {
+    using elem = typename CT<PREC>::elem;
+    __shared__ __attribute__((aligned(16))) elem Ks[2][KT * KRS];
+    __shared__ __attribute__((aligned(16))) elem Vs[2][KT * VRS];
+    A16<PREC> a;
+    a.Ks = &Ks[0][0], a.Vs = &Vs[0][0];
+    f32x16 o;                      // O^T: rows d, column = this lane's query
+    float inv;
+    int b, h, q;
+    attention_tiles(a, qkv, L, o, inv, b, h, q);
     // ---- normalise and store: lane (query n, half hf) holds d = (r & 3) + 8 (r >> 2) + 4 hf
-    const float inv = 1.0f / half_sum(l);
-    const int q = q0 + wave * 32 + n;
+    const int hf = (threadIdx.x >> 5) & 1;
     if (q < L) {
         elem* op = out + ((size_t)b * L + q) * D + h * HD + 4 * hf;
         const float sc = HILO ? inv * ATT_HILO_SCALE : inv;
@@ -216,9 +406,42 @@ __global__ __launch_bounds__(256, 4) void attention_fwd_kernel(const typename CT
     }
 }
 
-void launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hipStream_t st, bool hilo) {
+__global__ __launch_bounds__(256, 4) void attention32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L) {
+    __shared__ __attribute__((aligned(16))) float Ks[2][KT * KRS32];
+    __shared__ __attribute__((aligned(16))) float Vs[2][KT * VRS32];
+    A32 a;
+    a.Ks = &Ks[0][0], a.Vs = &Vs[0][0];
+    f32x16 o;
+    float inv;
+    int b, h, q;
+    attention_tiles(a, qkv, L, o, inv, b, h, q);
+    store_f32(out, L, o, inv, b, h, q);
+}
+
+__global__ __launch_bounds__(256, 3) void attention_x3_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L) {
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[2][2][KT * KRS];
+    __shared__ __attribute__((aligned(16))) _Float16 Vs[2][2][KT * VRS];
+    AX3 a;
+    a.Ks = &Ks[0][0][0], a.Vs = &Vs[0][0][0];
+    f32x16 o;
+    float inv;
+    int b, h, q;
+    attention_tiles(a, qkv, L, o, inv, b, h, q);
+    store_f32(out, L, o, inv, b, h, q);
+}
+
+// grid of every launch here: ceil(L / QT) query tiles x 8 heads x B reads; false where that is more than a launch takes
+static bool attention_grid(int B, int L, dim3& grid) {
     static_assert(NH == 8, "the workgroup -> XCD mapping assumes 8 heads");
-    dim3 grid((unsigned)(((L + QT - 1) / QT) * NH * B)), block(256);
+    const size_t n = (size_t)((L + QT - 1) / QT) * NH * B;
+    if (n > 0x7fffffff) return false;
+    grid = dim3((unsigned)n);
+    return true;
+}
+
+bool launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hipStream_t st, bool hilo) {
+    dim3 grid, block(256);
+    if (!attention_grid(B, L, grid)) return false;
     const size_t plane = (size_t)B * L * D;
     if (prec == PREC_BF16)
         hipLaunchKernelGGL(attention_fwd_kernel<PREC_BF16>, grid, block, 0, st, (const bf16_t*)qkv, (bf16_t*)out, L, plane);
@@ -226,18 +449,37 @@ void launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hi
         hipLaunchKernelGGL((attention_fwd_kernel<PREC_F16, true>), grid, block, 0, st, (const f16_t*)qkv, (f16_t*)out, L, plane);
     else
         hipLaunchKernelGGL(attention_fwd_kernel<PREC_F16>, grid, block, 0, st, (const f16_t*)qkv, (f16_t*)out, L, plane);
+    return true;
+}
+
+bool launch_attention_exact(bool x3, const float* qkv, float* out, int B, int L, hipStream_t st) {
+    dim3 grid, block(256);
+    if (!attention_grid(B, L, grid)) return false;
+    if (x3) hipLaunchKernelGGL(attention_x3_kernel, grid, block, 0, st, qkv, out, L);
+    else hipLaunchKernelGGL(attention32_kernel, grid, block, 0, st, qkv, out, L);
+    return true;
 }
 
 }  // namespace clm
 
-// ---- C ABI (include/chimeralm_hip.h): stand-alone entry for tests and for the encoder path under construction
+// ---- C ABI (include/chimeralm_hip.h): the attention launches on their own, for the tests that hold the kernels to an fp64
+// softmax(q k^T / sqrt(32)) v at shapes and score patterns a whole-model bound cannot resolve
 extern "C" int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, void* stream) {
     if (!qkv || !out || B < 1 || L < 1) return CLM_E_INVALID;
     if (precision != CLM_PREC_F16 && precision != CLM_PREC_BF16 && precision != CLM_PREC_F16C) return CLM_E_INVALID;
     // the kernel reads qkv in 16-byte pieces and writes out in 8-byte ones: refuse what it cannot address, before any launch
     if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 7)) return CLM_E_INVALID;
     // CLM_PREC_F16C: the transformer's fp16c attention, fp16 operands and the two-plane HILO output (as tf_model.hip launches it)
-    clm::launch_attention_fwd(precision == CLM_PREC_BF16 ? clm::PREC_BF16 : clm::PREC_F16, qkv, out, B, L,
-                              reinterpret_cast<hipStream_t>(stream), precision == CLM_PREC_F16C);
+    if (!clm::launch_attention_fwd(precision == CLM_PREC_BF16 ? clm::PREC_BF16 : clm::PREC_F16, qkv, out, B, L,
+                                   reinterpret_cast<hipStream_t>(stream), precision == CLM_PREC_F16C))
+        return CLM_E_INVALID;
+    return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
+}
+
+extern "C" int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream) {
+    if (!qkv || !out || B < 1 || L < 1 || (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)) return CLM_E_INVALID;
+    // the kernels read qkv and write out as float4
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return CLM_E_INVALID;
+    if (!clm::launch_attention_exact(precision == CLM_PREC_F16X3, qkv, out, B, L, reinterpret_cast<hipStream_t>(stream))) return CLM_E_INVALID;
     return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
 }

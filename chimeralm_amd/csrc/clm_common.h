@@ -379,6 +379,10 @@ void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const fl
 void launch_enc32(const float* att, float* h, const void* w_o, const void* w1, const void* w2, const void* w_qkv, const float* b_o,
                   const float* b1, const float* b2, const float* b_qkv, const float* ln1_g, const float* ln1_b, const float* ln2_g,
                   const float* ln2_b, float* qkv, size_t M, float eps, hipStream_t st, bool x3 = false);
+// SequenceCNNTransformer self-attention (attention.hip), qkv [B, L, 768] -> out [B, L, 256]: 16 bit (hilo: fp16c's two output planes)
+// and exact (fp32 products, or x3).  false, and nothing launched, where ceil(L / 128) * 8 * B workgroups are more than a grid takes
+bool launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hipStream_t st, bool hilo);
+bool launch_attention_exact(bool x3, const float* qkv, float* out, int B, int L, hipStream_t st);
 // SequenceCNNTransformer weights as the kernels take them: device pointers resolved ONCE, by clm_tf_finalize (tf_model.hip).  The
 // four products of a layer are in_proj, out_proj, linear1, linear2: the order of TfLayerF32::w and of a TfPacking's slots
 struct TfLayerF32 {               // one encoder layer's tensors as loaded, fp32

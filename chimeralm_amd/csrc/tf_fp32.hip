@@ -8,7 +8,10 @@
 //   * attention: one thread per query row, K / V tiles of 64 keys staged in LDS (read as broadcasts), online softmax,
 //     fp32 throughout (8 heads of 32; scores scaled by 1/sqrt(32) like nn.MultiheadAttention);
 //   * LayerNorm (post-norm: LN(x + sublayer(x))), positional encoding, ReLU / MaxPool1d(2) as plain fp32 kernels.
-// It is a correctness reference on the GPU, not tuned: stages are separate kernels and activations live in HBM as fp32.
+// This file holds two things.  The kernels listed above, one launch per stage with activations in HBM as fp32, are the untuned form that
+// CLM_DEBUG=unfused_fp32 runs: the independent referee the tests cross-check the fused path against, sharing no code with it.
+// tf32_forward is the host side of both forms; by default it runs the fused kernels of the exact path, which live elsewhere --
+// conv32_kernel and enc32_kernel in tail32.hip, the MFMA attention (attention32_kernel, attention_x3_kernel) in attention.hip.
 #include <utility>
 
 #include "clm_common.h"
@@ -173,294 +176,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     }
 }
 
-// Round 4: the same attention on the fp32 MFMA (v_mfma_f32_32x32x2_f32), built like the 16-bit kernel (attention.hip): scores
-// TRANSPOSED, S^T = K Q^T (rows = keys, column = the lane's query), so the softmax statistics are register reductions plus one
-// exchange between the half-waves; P^T never leaves the registers -- accumulator register t of a 32-key block IS the B operand of
-// MFMA step t of O^T = V^T P^T, with the A operand read from the V row of the key that register holds (the reduction index may be
-// paired freely: lanes 0-31 feed key (t & 3) + 8 (t >> 2), lanes 32-63 that key + 4).  Per 64-key tile a wave issues 64 MFMAs of 64
-// cycles next to ~900 cycles of softmax VALU: MFMA-bound, where the scalar kernel above spends 2 x 32 FMAs per (query, key).
-// 128 queries per workgroup (4 waves), K / V tiles of 64 keys double-buffered: 38 KiB of LDS, four workgroups per CU.
-constexpr int A32_QT = 128, A32_KT = 64, A32_KRS = 36, A32_VRS = 40;   // row strides (floats): 16 rows of a ds_read_b128 group on 16 bank
-                                                                      // groups (K); rows 4 apart on banks + 32 (V, ds_read_b32)
-__global__ __launch_bounds__(256, 4) void attention32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L) {
-    using f32x4 = float __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) float Ks[2][A32_KT * A32_KRS];
-    __shared__ __attribute__((aligned(16))) float Vs[2][A32_KT * A32_VRS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hf = lane >> 5;
-    // workgroup -> (query tile, head, read): the query tiles of one (read, head) share an XCD's L2 (as attention.hip)
-    const int ntq = (L + A32_QT - 1) / A32_QT;
-    const int g = blockIdx.x, xcd = g & 7, slot = g >> 3;
-    const int bh = (slot / ntq) * 8 + xcd, q0 = (slot % ntq) * A32_QT, h = bh & 7, b = bh >> 3;
-    const float* base = qkv + (size_t)b * L * 768 + h * 32;            // row t: q at +0, k at +256, v at +512
-    const float c = 1.4426950408889634f * 0.17677669529663687f;        // log2(e) / sqrt(32)
-    f32x4 qf[4];                                                       // Q^T as B operand: d = 8 s + 4 hf + 0..3
-    {
-        const int q = q0 + wave * 32 + n;
-        const float* qp = base + (size_t)(q < L ? q : L - 1) * 768 + 4 * hf;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const f32x4*>(qp + 8 * s);
-    }
-    f32x4 kreg[2], vreg[2];
-    auto load_tile = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
-            const int key = k0 + j < L ? k0 + j : L - 1;                // clamped; the score mask removes the clones
-            const float* p = base + (size_t)key * 768 + 4 * d4;
-            kreg[i] = *reinterpret_cast<const f32x4*>(p + 256);
-            vreg[i] = *reinterpret_cast<const f32x4*>(p + 512);
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
-            *reinterpret_cast<f32x4*>(&Ks[buf][j * A32_KRS + 4 * d4]) = kreg[i];
-            *reinterpret_cast<f32x4*>(&Vs[buf][j * A32_VRS + 4 * d4]) = vreg[i];
-        }
-    };
-    f32x16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int ntiles = (L + A32_KT - 1) / A32_KT;
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-#pragma unroll 1
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1, k0 = t * A32_KT;
-        if (t + 1 < ntiles) load_tile(k0 + A32_KT);
-        f32x16 s[2];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[blk][r] = 0.f;
-            const float* kp = &Ks[buf][(blk * 32 + n) * A32_KRS + 4 * hf];
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + 8 * st);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) s[blk] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[j], qf[st][j], s[blk], 0, 0, 0);
-            }
-        }
-        if (k0 + A32_KT > L) {
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (k0 + blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf >= L) s[blk][r] = -INFINITY;
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[blk][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx);                              // finite: key k0 is always valid
-        const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c);   // 0 on the first tile
-        const float mc = m_new * c;
-        float psum = 0.f;
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                s[blk][r] = __builtin_amdgcn_exp2f(fmaf(s[blk][r], c, -mc));
-                psum += s[blk][r];
-            }
-        l = l * alpha + psum;
-        m = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        // O^T += V^T P^T: step t2 of a block pairs register t2 of P^T with the V row of the key it holds
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-            const float* vp = &Vs[buf][(blk * 32 + 4 * hf) * A32_VRS + n];
-#pragma unroll
-            for (int t2 = 0; t2 < 16; ++t2)
-                o = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[((t2 & 3) + 8 * (t2 >> 2)) * A32_VRS], s[blk][t2], o, 0, 0, 0);
-        }
-        if (t + 1 < ntiles) store_tile(buf ^ 1);                       // the other buffer was last read in trip t - 1
-        __syncthreads();
-    }
-    const float inv = 1.0f / (l + __shfl_xor(l, 32, 64));
-    const int q = q0 + wave * 32 + n;
-    if (q < L) {
-        float* op = out + ((size_t)b * L + q) * D + h * 32 + 4 * hf;    // lane (query n, half hf) holds d = (r & 3) + 8 (r >> 2) + 4 hf
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            *reinterpret_cast<float4*>(op + 8 * gq) = make_float4(o[4 * gq + 0] * inv, o[4 * gq + 1] * inv, o[4 * gq + 2] * inv, o[4 * gq + 3] * inv);
-    }
-}
-
-// fp16x3: the same attention with every operand as two halfs (hi = fp16(x), lo = fp16(x - hi)) and three fp16 MFMAs per product,
-// built like the 16-bit kernel (attention.hip): S^T = K Q^T with a lane owning one query; P^T stays in registers and, split into
-// halfs, is the B operand of O^T = V^T P^T up to the fixed permutation of the key index that is applied to V's rows when the tile
-// is staged; V^T fragments by transposing LDS reads.  q / k / v arrive as fp32 and are split on their way into registers / LDS.
-constexpr int AX_QT = 128, AX_KT = 64, AX_KRS = 40, AX_VRS = 32;       // halfs: K rows 80 B, V rows 64 B (attention.hip's strides)
-__device__ __forceinline__ int ax_v_row(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
-__global__ __launch_bounds__(256, 3) void attention_x3_kernel(const float* __restrict__ qkv, float* __restrict__ out, int L) {
-    using f32x4 = float __attribute__((ext_vector_type(4)));
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    typedef float f8 __attribute__((ext_vector_type(8)));
-    using v4i16 = short __attribute__((ext_vector_type(4)));
-    typedef v4i16 __attribute__((address_space(3))) * lds_v4;
-    __shared__ __attribute__((aligned(16))) _Float16 Ks[2][2][AX_KT * AX_KRS];       // [buffer][hi | lo]
-    __shared__ __attribute__((aligned(16))) _Float16 Vs[2][2][AX_KT * AX_VRS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hf = lane >> 5;
-    const int ntq = (L + AX_QT - 1) / AX_QT;
-    const int g = blockIdx.x, xcd = g & 7, slot = g >> 3;
-    const int bh = (slot / ntq) * 8 + xcd, q0 = (slot % ntq) * AX_QT, h = bh & 7, b = bh >> 3;
-    const float* base = qkv + (size_t)b * L * 768 + h * 32;
-    const float c = 1.4426950408889634f * 0.17677669529663687f;        // log2(e) / sqrt(32)
-    auto clamp8 = [](f8 v) {                                           // (beyond fp16's range: saturate, never inf -- tail32.hip split4)
-        f8 r;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] = __builtin_amdgcn_fmed3f(v[e], -65504.f, 65504.f);
-        return r;
-    };
-    auto split8 = [&](f8 v, h8& hi, h8& lo) {
-        hi = __builtin_convertvector(clamp8(v), h8);
-        lo = __builtin_convertvector(clamp8(v - __builtin_convertvector(hi, f8)), h8);
-    };
-    h8 qh[2], ql[2];                                                   // Q^T as B operand: d = 16 s + 8 hf + 0..7
-    {
-        const int q = q0 + wave * 32 + n;
-        const float* qp = base + (size_t)(q < L ? q : L - 1) * 768 + 8 * hf;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * s2), bq = *reinterpret_cast<const f32x4*>(qp + 16 * s2 + 4);
-            split8(f8{a[0], a[1], a[2], a[3], bq[0], bq[1], bq[2], bq[3]}, qh[s2], ql[s2]);
-        }
-    }
-    // staging: thread -> (key row, 4-float piece) x 2 of the K and of the V tile
-    f32x4 kreg[2], vreg[2];
-    auto load_tile = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
-            const int key = k0 + j < L ? k0 + j : L - 1;
-            const float* p = base + (size_t)key * 768 + 4 * d4;
-            kreg[i] = *reinterpret_cast<const f32x4*>(p + 256);
-            vreg[i] = *reinterpret_cast<const f32x4*>(p + 512);
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = tid + i * 256, j = e >> 3, d4 = e & 7;
-            auto clamp4 = [](f32x4 v) {
-                f32x4 r;
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) r[e2] = __builtin_amdgcn_fmed3f(v[e2], -65504.f, 65504.f);
-                return r;
-            };
-            const h4 kh = __builtin_convertvector(clamp4(kreg[i]), h4), vh = __builtin_convertvector(clamp4(vreg[i]), h4);
-            const h4 kl = __builtin_convertvector(clamp4(kreg[i] - __builtin_convertvector(kh, f32x4)), h4);
-            const h4 vl = __builtin_convertvector(clamp4(vreg[i] - __builtin_convertvector(vh, f32x4)), h4);
-            *reinterpret_cast<h4*>(&Ks[buf][0][j * AX_KRS + 4 * d4]) = kh;
-            *reinterpret_cast<h4*>(&Ks[buf][1][j * AX_KRS + 4 * d4]) = kl;
-            *reinterpret_cast<h4*>(&Vs[buf][0][ax_v_row(j) * AX_VRS + 4 * d4]) = vh;
-            *reinterpret_cast<h4*>(&Vs[buf][1][ax_v_row(j) * AX_VRS + 4 * d4]) = vl;
-        }
-    };
-    auto mm = [](h8 a, h8 bq, f32x16 acc) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bq, acc, 0, 0, 0); };
-    f32x16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int ntiles = (L + AX_KT - 1) / AX_KT;
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-#pragma unroll 1
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1, k0 = t * AX_KT;
-        if (t + 1 < ntiles) load_tile(k0 + AX_KT);
-        f32x16 s[2];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[blk][r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const h8 kh = *reinterpret_cast<const h8*>(&Ks[buf][0][(blk * 32 + n) * AX_KRS + 16 * ks + 8 * hf]);
-                const h8 kl = *reinterpret_cast<const h8*>(&Ks[buf][1][(blk * 32 + n) * AX_KRS + 16 * ks + 8 * hf]);
-                s[blk] = mm(kh, qh[ks], s[blk]);
-                s[blk] = mm(kl, qh[ks], s[blk]);
-                s[blk] = mm(kh, ql[ks], s[blk]);
-            }
-        }
-        if (k0 + AX_KT > L) {
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    if (k0 + blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf >= L) s[blk][r] = -INFINITY;
-        }
-        float mx = s[0][0];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[blk][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m - m_new) * c);
-        const float mc = m_new * c;
-        float psum = 0.f;
-        h8 ph[2][2], pl[2][2];                                         // P^T as B operand: [block][k-step of 16 keys], hi and lo halfs
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                f8 p;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    p[j] = __builtin_amdgcn_exp2f(fmaf(s[blk][8 * ks + j], c, -mc));
-                    psum += p[j];
-                }
-                split8(p, ph[blk][ks], pl[blk][ks]);
-            }
-        l = l * alpha + psum;
-        m = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        {
-            const int li = lane & 15, g1 = (lane >> 4) & 1, q4 = li >> 2, p4 = li & 3;
-            const int voff = (8 * hf + q4) * AX_VRS + 16 * g1 + 4 * p4;
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    h8 vf[2];
-#pragma unroll
-                    for (int pln = 0; pln < 2; ++pln) {
-                        const _Float16* p0 = &Vs[buf][pln][voff + (blk * 32 + ks * 16) * AX_VRS];
-                        const v4i16 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(p0));
-                        const v4i16 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(p0 + 4 * AX_VRS));
-                        typedef short s8 __attribute__((ext_vector_type(8)));
-                        const s8 both = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-                        vf[pln] = __builtin_bit_cast(h8, both);
-                    }
-                    o = mm(vf[0], ph[blk][ks], o);
-                    o = mm(vf[1], ph[blk][ks], o);
-                    o = mm(vf[0], pl[blk][ks], o);
-                }
-        }
-        if (t + 1 < ntiles) store_tile(buf ^ 1);
-        __syncthreads();
-    }
-    const float inv = 1.0f / (l + __shfl_xor(l, 32, 64));
-    const int q = q0 + wave * 32 + n;
-    if (q < L) {
-        float* op = out + ((size_t)b * L + q) * D + h * 32 + 4 * hf;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-            *reinterpret_cast<float4*>(op + 8 * gq) = make_float4(o[4 * gq + 0] * inv, o[4 * gq + 1] * inv, o[4 * gq + 2] * inv, o[4 * gq + 3] * inv);
-    }
-}
-
 template <bool RELU, bool CONV3>
 static void gemm(const float* A, int lda, const float* W, const float* bias, const float* R, float* C, int ldc, size_t M, int N,
                  int K, int Lrow, hipStream_t st) {
@@ -514,8 +229,7 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
     for (int i = 0; i < n_layers; ++i) {
         const TfLayerF32& l = lay[i];
         if (!unfused) {
-            if (x3) hipLaunchKernelGGL(attention_x3_kernel, dim3((unsigned)(((L3 + AX_QT - 1) / AX_QT) * 8 * B)), dim3(256), 0, st, qkv, att, L3);
-            else hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)(((L3 + A32_QT - 1) / A32_QT) * 8 * B)), dim3(256), 0, st, qkv, att, L3);
+            if (!launch_attention_exact(x3, qkv, att, B, L3, st)) return -1;                  // attention.hip, on the MFMA
             const bool more = i + 1 < n_layers;
             launch_enc32(att, h, pk.mat[i][1].get(), pk.mat[i][2].get(), pk.mat[i][3].get(), more ? pk.mat[i + 1][0].get() : nullptr, l.b_out,
                          l.b_ff1, l.b_ff2, more ? lay[i + 1].b_in : nullptr, l.ln1_g, l.ln1_b, l.ln2_g, l.ln2_b, qkv, M, 1e-5f, st, x3);
@@ -533,17 +247,3 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
 }
 
 }  // namespace clm
-
-// The exact attention kernels on their own (chimeralm_hip.h): the launches of tf32_forward, for the tests that hold them to an fp64
-// softmax(q k^T / sqrt(32)) v at shapes and score patterns a whole-model bound cannot resolve.
-extern "C" int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream) {
-    using namespace clm::tf32;
-    if (!qkv || !out || B < 1 || L < 1 || (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)) return CLM_E_INVALID;
-    const int qt = precision == CLM_PREC_F32 ? A32_QT : AX_QT;
-    const size_t grid = (size_t)((L + qt - 1) / qt) * 8 * B;
-    if (grid > 0x7fffffff) return CLM_E_INVALID;
-    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (precision == CLM_PREC_F32) hipLaunchKernelGGL(attention32_kernel, dim3((unsigned)grid), dim3(256), 0, st, qkv, out, L);
-    else hipLaunchKernelGGL(attention_x3_kernel, dim3((unsigned)grid), dim3(256), 0, st, qkv, out, L);
-    return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
-}

@@ -445,8 +445,6 @@ __global__ __launch_bounds__(256) void pool_head_kernel(const float* __restrict_
 
 }  // namespace tf
 
-void launch_attention_fwd(int prec, const void* qkv, void* out, int B, int L, hipStream_t st, bool hilo);   // attention.hip
-
 }  // namespace clm
 
 // ================================================================================================ engine + C ABI
@@ -574,7 +572,8 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
         }
         {
             TfTimer t(h, st, 1);
-            launch_attention_fwd(PREC, h->qkv.get(), h->att.get(), B, L3, st, PREC == PREC_F16C);   // fp16c: hi and lo planes (attention.hip)
+            if (!launch_attention_fwd(PREC, h->qkv.get(), h->att.get(), B, L3, st, PREC == PREC_F16C))   // fp16c: hi and lo planes (attention.hip)
+                return CLM_E_INVALID;
         }
         TfTimer tl(h, st, 2);
         // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel

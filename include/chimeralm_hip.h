@@ -224,11 +224,13 @@ int clm_set_mlp_compensation(clm_handle* h, int on);
  *   the attention of the transformer's fp16c mode -- qkv fp16, out 2 * B * L * 256 fp16 values, the plane hi = fp16(64 a) and then
  *   the plane lo = fp16(64 a - hi), so that a = (hi + lo) / 64 to ~2^-21.  CLM_PREC_F32 and CLM_PREC_F16X3 are CLM_E_INVALID here
  *   (clm_attention_exact_fwd).  qkv must be 16-byte aligned and out 8-byte aligned (the kernel's load and store widths), else
- *   CLM_E_INVALID and nothing is launched.  Asynchronous on `stream`; writes nothing beyond out[B * L * 256] (F16C: twice that). */
+ *   CLM_E_INVALID and nothing is launched; likewise a shape whose ceil(L / 128) * 8 * B workgroups exceed 2^31 - 1, the most one
+ *   launch takes.  Asynchronous on `stream`; writes nothing beyond out[B * L * 256] (F16C: twice that). */
 int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, void* stream);
-/* The same attention in the arithmetic of the exact path (csrc/tf_fp32.hip; the kernels clm_tf_forward runs there): qkv device fp32
+/* The same attention in the arithmetic of the exact path (csrc/attention.hip; the kernels clm_tf_forward runs there): qkv device fp32
  * [B, L, 768], out device fp32 [B, L, 256]; precision CLM_PREC_F32 (fp32 products) or CLM_PREC_F16X3 (every operand as fp16 hi + lo,
- * three fp16 MFMAs per product).  Asynchronous on `stream`; writes nothing beyond out[B * L * 256]. */
+ * three fp16 MFMAs per product).  qkv and out must be 16-byte aligned (the kernels read and write float4) and ceil(L / 128) * 8 * B
+ * at most 2^31 - 1, else CLM_E_INVALID and nothing is launched.  Asynchronous on `stream`; writes nothing beyond out[B * L * 256]. */
 int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream);
 
 /* The whole SequenceCNNTransformer forward (transformer.py:88-104; configuration of configs/model/transformer.yaml:3-12:

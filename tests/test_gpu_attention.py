@@ -58,9 +58,16 @@ def test_attention_bf16_and_arguments(built_lib):
     lib = N.load()
     assert lib.clm_attention_fwd(None, None, 1, 1, N.PREC_F16, None) == N.E_INVALID
     assert lib.clm_attention_fwd(C.c_void_p(1), C.c_void_p(1), 1, 1, N.PREC_F32, None) == N.E_INVALID   # 16-bit only
+    # ceil(L / 128) * 8 * B = 2^36 workgroups are more than a grid takes: refused by both entries before any launch (the pointers are
+    # non-null and aligned, and never read)
+    big = 1 << 20
+    for prec in (N.PREC_F16, N.PREC_BF16, N.PREC_F16C):
+        assert lib.clm_attention_fwd(C.c_void_p(16), C.c_void_p(16), big, big, prec, None) == N.E_INVALID
+    for prec in (N.PREC_F32, N.PREC_F16X3):
+        assert lib.clm_attention_exact_fwd(C.c_void_p(16), C.c_void_p(16), big, big, prec, None) == N.E_INVALID
 
 
-# ---- the exact path's attention kernels (csrc/tf_fp32.hip attention32_kernel, attention_x3_kernel) through clm_attention_exact_fwd ---
+# ---- the exact path's attention kernels (csrc/attention.hip attention32_kernel, attention_x3_kernel) through clm_attention_exact_fwd ---
 # 128-query tiles, 64-key tiles: one key too many or too few at 4,096 positions moves an output by ~|v| / L = 2.4e-4, which the
 # whole-model bounds (1e-4 on logits after 12 layers) cannot resolve -- here each kernel is held to an fp64 softmax(q k^T / sqrt(32)) v.
 ATT32_TOL = {"fp32": 1e-5, "fp16x3": 2e-5}                  # absolute, unit-scale v: >= 10x below one miscounted key at 4,096
@@ -155,3 +162,6 @@ def test_exact_attention_arguments(built_lib):
         assert lib.clm_attention_exact_fwd(C.c_void_p(1), C.c_void_p(1), 1, 1, prec, None) == N.E_INVALID
     assert lib.clm_attention_exact_fwd(C.c_void_p(1), C.c_void_p(1), 0, 1, N.PREC_F32, None) == N.E_INVALID
     assert lib.clm_attention_exact_fwd(C.c_void_p(1), C.c_void_p(1), 1, 0, N.PREC_F16X3, None) == N.E_INVALID
+    for prec in (N.PREC_F32, N.PREC_F16X3):                                     # the kernels read and write float4: 16-byte alignment
+        assert lib.clm_attention_exact_fwd(C.c_void_p(8), C.c_void_p(16), 1, 1, prec, None) == N.E_INVALID
+        assert lib.clm_attention_exact_fwd(C.c_void_p(16), C.c_void_p(8), 1, 1, prec, None) == N.E_INVALID

@@ -13,7 +13,12 @@ the number formats (no safety factor; tests/test_attention16_host.py proves it o
   and the entry's argument checks: CLM_PREC_F16C accepted, the fp32 arithmetics and misaligned pointers refused before any launch.
 
 Each of these five source mutations of attention.hip (memory-safe: the loads stay clamped), applied alone on a scratch copy,
-against this file and against the older tests/test_gpu_attention.py::test_attention_matches_oracle_fp16:
+against this file and against the older tests/test_gpu_attention.py::test_attention_matches_oracle_fp16.  The table is of the
+kernel as it was when it had a tile loop of its own.  Mutations 1, 3 and 4 now sit in `attention_tiles`, the one loop under all
+three MFMA attention kernels (the mask line, the `o[r] *= alpha` line, `ntiles`), so they would break attention32_kernel and
+attention_x3_kernel too; 2 is `v_row`, shared by `A16::store_tile` and `AX3::store_tile`; 5 is the HILO branch of
+attention_fwd_kernel's own output stage.  They were not run again: the kernels' outputs are bit-identical to before
+(profiles/attention_tiles_ab.txt).
 
   mutation                               fails here (of 75)                                   worst err / tol        the older fp16 test
   1 mask `>= L` becomes `> L`            44: (a) 33, (b) 2, (c) all 9                         1,159 (L = 2, hilo)    notices: 4 of 9, 0.17 .. 0.51
