@@ -5,6 +5,12 @@
 plus engine-only options `--weights` (directory/file with the released `model.safetensors`; the reference downloads
 `yangliz5/chimeralm` from the Hub) and `--precision`.  `--gpus 0` (the reference's CPU mode) is refused: this engine
 has no CPU path.  `filter` (reference :320-331) is the host-only step after predict; `web` is not built.
+
+    python -m chimeralm_amd explain DATA_PATH [-o OUTPUT] [--max-reads N] [--window W --stride S --substitute N|all --score prob|gap
+                                              --top-k K --values] [--weights DIR | --ckpt FILE] [--precision P]
+
+has no command in the reference: it is `Mamba2Analyzer.get_position_importance` (chimeralm/explain/motif.py:64-82) as an engine
+capability, for the released Hyena model (`python explain.py model=...` at the repository's root serves every net).
 """
 from __future__ import annotations
 
@@ -131,6 +137,66 @@ def _gathered_sink(output_path: Path, rank: int):
                 f.write(f"{batch_idx}\t{i // rows}\t{i % rows}\t{row[0]:.7g}\t{row[1]:.7g}\n")
         f.flush()
     return sink
+
+
+@app.command()
+def explain(
+    data_path: Path = typer.Argument(..., help="Path to the dataset (BAM)"),
+    output_path: Path | None = typer.Option(None, "--output", "-o", help="Output directory (default: DATA_PATH with suffix .explain)"),
+    max_reads: int | None = typer.Option(None, "--max-reads", help="scan only the first N reads"),
+    window: int = typer.Option(1, "--window", help="bases replaced together (>= 1)"),
+    stride: int = typer.Option(1, "--stride", help="distance between window starts (1 ... window)"),
+    substitute: str = typer.Option("N", "--substitute", help="N: the window's bases become N | all: saturation mutagenesis, every "
+                                   "base becomes each of the other three (needs --window 1 --stride 1)"),
+    score: str = typer.Option("prob", "--score", help="prob: |change of p1| (the reference's number; vanishes on confident reads) | "
+                              "gap: |change of logit1 - logit0|"),
+    top_k: int = typer.Option(10, "--top-k", help="bases listed per read (1 ... 32)"),
+    values: bool = typer.Option(False, "--values", help="also write {rank}_{index}.explain.npz per read with logits, dp1, dgap, "
+                                "importance and peaks"),
+    batch_size: int = typer.Option(256, "--batch-size", "-b", help="mutants per forward"),
+    ckpt_path: Path | None = typer.Option(None, "--ckpt", "-c", help="Path to the checkpoint file"),
+    weights: str = typer.Option("yangliz5/chimeralm", "--weights", help="Directory/file with model.safetensors"),
+    precision: str = typer.Option("fp16x3", "--precision", help="arithmetic of the dense projections: fp16x3 (default) | fp32 | fp16c | "
+                                  "fp16 | bf16.  The default is NOT predict's fp16c: fp16c may be up to 5e-4 off in a logit, and a "
+                                  "scan reports DIFFERENCES of logits between a read and its mutants -- that error is a noise floor "
+                                  "under the signal; fp16x3 stays within ~1e-5"),
+    verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
+):
+    """In-silico mutagenesis: which bases of each read the prediction rests on (writes {rank}_explain.tsv)."""
+    logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
+    from . import explain as ex
+
+    try:
+        opts = ex.Options(window=window, stride=stride, substitute=substitute, score=score, top_k=top_k)
+    except ValueError as e:
+        raise typer.BadParameter(str(e)) from None
+    if max_reads is not None and max_reads < 1:
+        raise typer.BadParameter("--max-reads must be >= 1")
+    if not 1 <= batch_size <= 65535:
+        raise typer.BadParameter("--batch-size must be 1 ... 65535")
+    if output_path is None:
+        output_path = data_path.with_suffix(".explain")
+
+    from . import bam, callbacks, lm, predict as loop, tokenizer
+
+    torch.manual_seed(42)
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    tok = tokenizer.load_tokenizer_from_hyena_model("hyenadna-small-32k-seqlen")
+    kw = dict(precision=precision, selfcheck=None)
+    if ckpt_path is not None:
+        log.info(f"Loading model from {ckpt_path}")
+        model = lm.ChimeraLM.new(**kw).load_reference_checkpoint(ckpt_path)
+    else:
+        log.info(f"Loading model weights {weights}")
+        model = lm.ChimeraLM.from_pretrained(weights, **kw)
+    dm = bam.BamDataModule(tokenizer=tok, train_data_path=Path("dummy.bam"), predict_data_path=data_path, batch_size=12, num_workers=0,
+                           max_predict_samples=max_reads)
+    dm.setup("predict", world_size=1, rank=0)
+    writer = callbacks.ExplainWriter(output_dir=output_path, values=values)
+    n = loop.run_explain(model, dm, writer, device, max_reads=max_reads, batch_size=batch_size, window=opts.window, stride=opts.stride,
+                         substitute=opts.substitute, score=opts.score, top_k=opts.top_k)
+    log.info(f"{n} reads scanned; results saved to {output_path}")
 
 
 @app.command()

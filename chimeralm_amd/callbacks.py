@@ -10,6 +10,9 @@ tokenizer.py:168), so no input the reference accepts is treated differently.
 `AttentionWriter` has no counterpart there: the reference keeps `attention_weights` of ONE forward on the module (hyena.py:129-130)
 and notebooks/attention.ipynb works from that; here the engine's per-read summary and peaks (csrc/attn_weights.hip) are written
 per batch next to the predictions, under names `filter` does not glob (`*.txt`, filter.py).
+
+`ExplainWriter` writes what the mutagenesis scan (explain.py, csrc/explain.hip) found per read; the reference's counterpart
+(chimeralm/explain/motif.py) plots one read's scores and writes no file.
 """
 from __future__ import annotations
 
@@ -146,3 +149,47 @@ class AttentionWriter:
         flat = np.concatenate([w[i, p: p + n] for i, (p, n) in enumerate(zip(f["n_pad"], f["n_bases"]))] or [np.zeros(0, np.float32)])
         (self.output_dir / f"{rank}_{batch_idx}.attn.npz").write_bytes(_npz_bytes(
             {"names": np.asarray(names, dtype=np.str_), "n_bases": n_bases, "offsets": offsets, "weights": flat.astype(np.float32)}))
+
+
+class ExplainWriter:
+    """Which bases a read's prediction rests on (explain.position_importance): one `{rank}_explain.tsv` per rank, one line per read,
+
+        name<TAB>label<TAB>p1<TAB>logit0<TAB>logit1<TAB>n_bases<TAB>window<TAB>stride<TAB>substitute<TAB>score<TAB>pos:value;...<TAB>n_nonfinite
+
+    with label, p1 = softmax(logits)[1] (in double) and the logits of the unmodified read, the scan's options, and the read's bases
+    of largest importance in descending order (`pos` 0-based among the read's bases, numbers as %.6g; an empty field for a read that
+    reports no peaks).  With `values=True` also one `{rank}_{index}.explain.npz` per read (`index` counts this rank's reads) holding
+    `name` [1], `logits`, `dp1`, `dgap`, `importance`, `peak_pos`, `peak_val` and `n_nonfinite`.  `importance` is an `explain.Importance`
+    of HOST tensors.  The file of a rank starts empty with the writer's first read.  `filter`'s `*.txt` glob sees neither name."""
+
+    def __init__(self, output_dir: str | Path, values: bool = False) -> None:
+        self.output_dir = Path(output_dir)
+        self.values = bool(values)
+        self._started: set = set()
+
+    @staticmethod
+    def line(name: str, importance: Any) -> str:
+        lg = importance.logits[0].tolist()
+        l0, l1 = float(lg[0]), float(lg[1])
+        label = int(l1 > l0)                                    # a tie is class 0, as torch.argmax
+        p1 = float("nan")
+        if np.isfinite(l0) and np.isfinite(l1):
+            e0, e1 = np.exp(np.float64(l0) - max(l0, l1)), np.exp(np.float64(l1) - max(l0, l1))
+            p1 = float(e1 / (e0 + e1))
+        o = importance.options
+        pos, val = importance.peak_pos.tolist(), importance.peak_val.tolist()
+        peaks = ";".join(f"{p}:{v:.6g}" for p, v in zip(pos, val) if p >= 0)
+        return (f"{name}\t{label}\t{p1:.6g}\t{l0:.7g}\t{l1:.7g}\t{importance.n_bases}\t{o.window}\t{o.stride}\t{o.substitute}\t"
+                f"{o.score}\t{peaks}\t{int(importance.n_nonfinite[0])}\n")
+
+    def write_read(self, trainer: Any, name: str, index: int, importance: Any) -> None:
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
+        path = self.output_dir / f"{rank}_explain.tsv"
+        with path.open("a" if path in self._started else "w") as fh:
+            fh.write(self.line(name, importance))
+        self._started.add(path)
+        if self.values:
+            arrays = {"name": np.asarray([name], dtype=np.str_)}
+            arrays.update({k: v.numpy() for k, v in importance.tensors().items()})
+            (self.output_dir / f"{rank}_{index}.explain.npz").write_bytes(_npz_bytes(arrays))

@@ -17,6 +17,9 @@ read one batch behind, after the same event as the logits.  No wait is added per
 `run_test` is the loop of `lightning.Trainer.test` over the same double buffer: `model.test_step(batch)` queues the batch's metric
 update (csrc/eval_metrics.hip) behind its forward, so neither logits nor labels come back and the host waits for nothing per batch.
 
+`run_explain` scans every read of every batch for the bases its prediction rests on (explain.position_importance: mutants built on
+the device, the net's own forward, csrc/explain.hip) and hands the results to a `callbacks.ExplainWriter` one read behind.
+
 `run_predict_native` is the same loop fed by the native BAM feeder (csrc/bam_feeder.cpp): a C++ thread decodes, selects,
 tokenises and collates into a ring of page-locked slots; each batch crosses PCIe as uint8 on the engine's copy stream
 (`clm_stage_ids`) while the previous batch is computing, and the slot goes back to the ring once its copy has landed.
@@ -188,6 +191,58 @@ def run_test(model, datamodule, device: torch.device) -> int:
             batch_idx += 1
         _check_engine(model, device, batch_idx)
     return n_reads
+
+
+def run_explain(model, datamodule, writer, device: torch.device, *, rank: int = 0, max_reads: int | None = None,
+                batch_size: int = 256, **options) -> int:
+    """Every read of every predict batch, stripped of the collator's left pads, through `explain.position_importance` (`options`:
+    window, stride, substitute, score, top_k); `batch_size` is the number of mutants per forward.  A read's result follows to
+    page-locked host memory behind its last kernel and is written while the next read's scan is queued.  A read the scan does not
+    take (no base, or a token that is not A, C, G, T or N) is logged and left out.  Returns the number of reads written."""
+    import logging
+
+    from .callbacks import _read_names
+    from .explain import Options, position_importance
+    from .tokenizer import PAD_ID
+
+    Options(**options)                                        # a bad option fails before the first read
+    log = logging.getLogger(__name__)
+    model.eval()
+    trainer = SimpleNamespace(global_rank=rank)
+    n_written, index = 0, 0
+    pending = None                                            # (name, index, host Importance, event)
+
+    def flush(p):
+        p[3].synchronize()
+        writer.write_read(trainer, p[0], p[1], p[2])
+
+    with torch.cuda.device(device), torch.inference_mode():
+        for batch in datamodule.predict_dataloader():
+            if max_reads is not None and index >= max_reads:
+                break
+            names = _read_names(batch["id"])
+            for row, name in zip(batch["input_ids"], names):
+                if max_reads is not None and index >= max_reads:
+                    break
+                keep = (row != PAD_ID).nonzero()
+                ids = row[int(keep[0]):] if keep.numel() else row[:0]
+                try:
+                    imp = position_importance(model, ids, batch_size=batch_size, device=device, **options)
+                except ValueError as e:
+                    log.warning("read %s is not scanned: %s", name, e)
+                    index += 1
+                    continue
+                host = imp.to_host()
+                done = torch.cuda.Event()
+                done.record()
+                if pending is not None:
+                    flush(pending)
+                pending = (name, index, host, done)
+                index += 1
+                n_written += 1
+        if pending is not None:
+            flush(pending)
+    return n_written
 
 
 def _check_engine(model, device: torch.device, batch_idx: int) -> None:

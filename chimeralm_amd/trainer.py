@@ -6,6 +6,7 @@ one process per GPU (torchrun environment), the datamodule set up for this rank,
 ckpt_path=cfg.ckpt_path)` of the same file: the test loop (`run_test`) with the metric sums kept on the device, one read of them at
 the end, one all-gather of that small struct across ranks, and the reference's metric names in `callback_metrics`.  Training keywords
 (`min_epochs`, `max_epochs`, `check_val_every_n_epoch`, ...) are accepted and ignored: this engine has no training path.
+`explain` has no Lightning counterpart: the predict datamodule's reads through the mutagenesis scan (`run_explain`), for any net.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from pathlib import Path
 import torch
 
 from . import distributed
-from .predict import run_predict, run_test
+from .predict import run_explain, run_predict, run_test
 
 log = logging.getLogger(__name__)
 
@@ -64,6 +65,26 @@ class Trainer:
         distributed.barrier()
         log.info("[rank %d] %d reads predicted", rank, n)
         return None
+
+    def explain(self, model, datamodule=None, dataloaders=None, ckpt_path: str | Path | None = None, *, writer=None,
+                max_reads: int | None = None, batch_size: int = 256, **options) -> int:
+        """Per-base importance of the predict datamodule's reads under `model` (any net), written by `writer` (a
+        callbacks.ExplainWriter); `options` are explain.position_importance's.  Each rank scans the reads of its shard.  Returns the
+        number of reads this rank wrote."""
+        dm = datamodule if datamodule is not None else dataloaders
+        if dm is None or not hasattr(dm, "predict_dataloader"):
+            raise ValueError("Trainer.explain needs a datamodule with predict_dataloader()")
+        if writer is None or not hasattr(writer, "write_read"):
+            raise ValueError("Trainer.explain needs a writer with write_read() (callbacks.ExplainWriter)")
+        rank, world, device = self._start()
+        if ckpt_path is not None:
+            log.info("Loading checkpoint %s", ckpt_path)
+            model.load_reference_checkpoint(ckpt_path)
+        dm.setup("predict", world_size=world, rank=rank)
+        n = run_explain(model, dm, writer, device, rank=rank, max_reads=max_reads, batch_size=batch_size, **options)
+        distributed.barrier()
+        log.info("[rank %d] %d reads scanned", rank, n)
+        return n
 
     def test(self, model, datamodule=None, dataloaders=None, ckpt_path: str | Path | None = None) -> list[dict]:
         """Loss, F1, precision and recall of `model` over the datamodule's labelled test set, as `lightning.Trainer.test` reports

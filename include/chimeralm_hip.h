@@ -370,6 +370,68 @@ int clm_eval_reset(clm_eval_handle* h, void* stream);
 const char* clm_eval_last_error(const clm_eval_handle* h); /* h may be NULL: error of the last failed clm_eval_create */
 int clm_eval_destroy(clm_eval_handle* h);
 
+/* ---- in-silico mutagenesis: per-base importance for every net (ABI 6, additive) ------------------------------------------
+ * Replaces Mamba2Analyzer.get_position_importance of the reference (chimeralm/explain/motif.py:64-82): replace one base by N, run
+ * the model again, report |p1(read) - p1(mutant)| per position -- one forward and one host wait per position there.  Here the
+ * mutants of a read are built on the device in batches, the forward between "rows" and "scores" is the net's own on the uint8
+ * rows (any of the clm_*_forward calls), and nothing waits on the host.  The calls are tied to no net.
+ *
+ * The read     n_bases base ids (A, C, G, T, N = 7 ... 11) followed by [SEP] (id 1), as `predict` tokenises it, no pads:
+ *              L = n_bases + 1, 1 <= n_bases <= 32768.  (The reference feeds ord(c) and no [SEP] to a model trained on this
+ *              tokenisation; that is a bug there and is not reproduced.)
+ * Windows      window w >= 1, stride s with 1 <= s <= w: window k starts at base k * s and covers the bases
+ *              [k * s, min(k * s + w, n_bases)); n_windows = ceil(n_bases / s).  [SEP] is never replaced.
+ * Substitute   CLM_EXPLAIN_SUB_N: every base of the window becomes N; S = 1 column per window.
+ *              CLM_EXPLAIN_SUB_ALL: saturation mutagenesis, needs w = s = 1; S = 4 columns A, C, G, T.  The column of the read's
+ *              own base is exactly 0.0 and has no mutant (no forward is spent on it); a base that is N has all four.
+ * A mutant     clm_explain_mutant: the first base of its window, the substitute id, and its slot k * S + column in dp1 / dgap.
+ * Outputs      logits [M + 1, 2] fp32: row 0 the unmodified read, rows 1 ... M the mutants in plan order, as the net returned them.
+ *              dp1, dgap [n_windows, S] fp32, signed, mutant minus read: p1 = softmax(logits)[1] in double from the fp32 logits with
+ *              the maximum taken out first (as clm_eval_update), gap = l1 - l0 in double.  A mutant with a NaN / inf logit has NaN
+ *              in both and counts in n_nonfinite.
+ *              importance [n_bases] fp32: the maximum of |d| over the windows that cover the base and over the S columns, d being
+ *              dp1 (the reference's number for w = s = 1 and N) or dgap (which does not vanish on confident reads); NaN if one of
+ *              them is NaN.
+ *              peak_pos int32 / peak_val fp32 [top_k], 1 <= top_k <= 32: the min(top_k, n_bases) bases of largest importance in
+ *              descending order, equal values by the lower position (a total order, as for the attention peaks: the result does
+ *              not depend on the shape of the reduction); positions 0-based among the bases; slots beyond hold -1 and 0.  A read
+ *              with any NaN importance reports no peaks.
+ *   plan       host only, needs no GPU and no handle: enumerates the mutants of `ids` [L] (host memory) in window order, columns
+ *              ascending.  Writes at most `capacity` entries to `plan` (NULL: count only) and always the counts; more mutants than
+ *              capacity, a token that is not a base, a missing [SEP] and bad options are CLM_E_INVALID (clm_explain_last_error of
+ *              NULL has the text).  The caller uploads the plan once per read.
+ *   rows       device: writes mutants m0 ... m0 + rows - 1 of the plan as uint8 rows of L ids to `out`, row r at out + r *
+ *              row_stride.  16-byte stores: `ids` and `out` 16-byte aligned, row_stride a multiple of 16 and >= L; the bytes of a
+ *              row between L and the next multiple of 16 are written as 0.  rows <= 65535.  ids [L], plan: device pointers.
+ *   scores     device, one workgroup behind the forward of a batch: batch_logits [rows, 2] fp32 as the net wrote them.  With
+ *              has_base = 1 (the read's first batch, m0 = 0) row 0 is the unmodified read and rows 1 ... the mutants 0 ...: its
+ *              logits are kept in the handle for the read's later batches (ordered by the stream), all n_slots = n_windows * S
+ *              entries of dp1 / dgap are zeroed and *n_nonfinite starts at 0.  With has_base = 0 the rows are mutants m0 ...  Fills
+ *              logits_out rows, dp1 / dgap at the mutants' slots, and adds to *n_nonfinite (int32, device).
+ *   reduce     device, one workgroup: importance and peaks from d = dp1 or dgap [n_windows, n_sub] (n_sub = S).
+ * All three launches go to `stream` and do not synchronise; no atomics and fixed reduction orders, so results are bitwise the same
+ * from run to run.  One read at a time per handle (the handle holds the read's base logits); use one stream per handle. */
+#define CLM_EXPLAIN_SUB_N 0
+#define CLM_EXPLAIN_SUB_ALL 1
+typedef struct clm_explain_handle clm_explain_handle;
+typedef struct clm_explain_mutant {
+    int32_t start;    /* first base of the window                   */
+    int32_t sub;      /* the id its bases are replaced by (7 ... 11) */
+    int32_t slot;     /* index into dp1 / dgap: window * S + column  */
+    int32_t reserved; /* 0                                          */
+} clm_explain_mutant;
+int clm_explain_plan(const unsigned char* ids, int L, int window, int stride, int substitute, clm_explain_mutant* plan, int capacity,
+                     int* n_mutants, int* n_windows);
+int clm_explain_create(int device, clm_explain_handle** out);
+int clm_explain_rows(clm_explain_handle* h, const unsigned char* ids, int L, int window, const clm_explain_mutant* plan, int n_mutants,
+                     int m0, int rows, unsigned char* out, int64_t row_stride, void* stream);
+int clm_explain_scores(clm_explain_handle* h, const float* batch_logits, int rows, int has_base, const clm_explain_mutant* plan,
+                       int n_mutants, int m0, int n_slots, float* logits_out, float* dp1, float* dgap, int* n_nonfinite, void* stream);
+int clm_explain_reduce(clm_explain_handle* h, const float* d, int n_bases, int window, int stride, int n_sub, int top_k,
+                       float* importance, int* peak_pos, float* peak_val, void* stream);
+const char* clm_explain_last_error(const clm_explain_handle* h); /* h may be NULL: error of the last failed clm_explain_create / _plan */
+int clm_explain_destroy(clm_explain_handle* h);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:
