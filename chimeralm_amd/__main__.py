@@ -1,6 +1,7 @@
 """`chimeralm predict` for the MI355X engine -- same options as /root/reference/chimeralm/__main__.py:248-259:
 
     python -m chimeralm_amd predict DATA_PATH [-g GPUS] [-o OUTPUT] [-b BATCH] [-w WORKERS] [-c CKPT] [-r] [-v]
+                                              [--long-reads truncate|tile --long-overlap 4096 --long-max-bases 262144]
 
 plus engine-only options `--weights` (directory/file with the released `model.safetensors`; the reference downloads
 `yangliz5/chimeralm` from the Hub) and `--precision`.  `--gpus 0` (the reference's CPU mode) is refused: this engine
@@ -55,6 +56,17 @@ def predict(
     attention_top_k: int = typer.Option(10, "--attention-top-k", help="bases listed per read by --save-attention (1 ... 32)"),
     attention_weights: bool = typer.Option(False, "--attention-weights", help="with --save-attention (implied): also write "
                                            "{rank}_{batch}.attn.npz with the pooling weight of every base of every read"),
+    long_reads: str = typer.Option("truncate", "--long-reads", help="reads longer than the model's context (32,768 bases): truncate "
+                                   "(the reference's: only the first 32,768 bases are seen) | tile: cut them into overlapping "
+                                   "context-sized windows, judge every window, call the read an artifact if any window is one and "
+                                   "write {rank}_{batch}.windows.tsv with every window's logits.  How well the model judges a window "
+                                   "cut from the middle of a read has not been measured: it was trained on read starts"),
+    long_overlap: int = typer.Option(4096, "--long-overlap", help="--long-reads tile: bases two consecutive windows share (0 ... half "
+                                     "the window; a choice, not a tuned value)"),
+    long_max_bases: int = typer.Option(262144, "--long-max-bases", help="--long-reads tile: bases of a read that are looked at; the "
+                                       "rest is cut off and counted by the feeder (truncated_bases)"),
+    long_window: int | None = typer.Option(None, "--long-window", hidden=True, help="--long-reads tile: bases per window (default: "
+                                           "the tokenizer's length; for tests and checkpoints of a shorter context)"),
 ):
     """Predict the given dataset using ChimeraLM."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
@@ -63,6 +75,19 @@ def predict(
     save_attention = save_attention or attention_weights
     if save_attention and not 1 <= attention_top_k <= 32:
         raise typer.BadParameter("--attention-top-k must be 1 ... 32")
+    if long_reads not in ("truncate", "tile"):
+        raise typer.BadParameter("--long-reads must be truncate or tile")
+    tile = None
+    if long_reads == "tile":
+        if save_attention:
+            raise typer.BadParameter("--long-reads tile and --save-attention exclude each other: the pooling weights of a read "
+                                     "reduced from several windows are not defined")
+        from .longread import Options as LongReadOptions
+
+        try:
+            tile = LongReadOptions(mode="tile", window=long_window, overlap=long_overlap, max_bases=long_max_bases)
+        except ValueError as e:
+            raise typer.BadParameter(f"--long-reads tile: {e}") from None
     if output_path is None:                       # README-documented default (the reference crashes here)
         output_path = data_path.with_suffix(".predictions")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -103,18 +128,26 @@ def predict(
     if feeder == "native":
         from .feeder import BamFeeder
 
-        with BamFeeder(data_path, batch_size=batch_size // world, max_tokens=tok.max_len_single_sentence, rank=rank,
+        max_tokens, slots = tok.max_len_single_sentence if tile is None else tile.max_tokens, 4
+        if tile is not None:
+            if tok.padding_side != "left":
+                raise typer.BadParameter("--long-reads tile takes batches padded on the left only")
+            log.info(f"[rank {rank}] long reads: windows of {tile.window_bases:,} bases, overlap {tile.overlap:,}, up to {tile.max_bases:,} "
+                     f"bases per read; feeder ring {slots} x {batch_size // world} x {max_tokens:,} = "
+                     f"{slots * (batch_size // world) * max_tokens / 1e6:,.0f} MB page-locked")
+        with BamFeeder(data_path, batch_size=batch_size // world, max_tokens=max_tokens, slots=slots, rank=rank,
                        world=world, pad_left=tok.padding_side == "left") as fd:
             n = loop.run_predict_native(model, fd, writer, device, rank=rank, gather=world > 1 and gather_logits,
                                         on_batch=_gathered_sink(output_path, rank) if gather_logits else None,
-                                        attention_writer=attn_writer)
+                                        attention_writer=attn_writer, long_reads=tile)
             log.info(f"[rank {rank}] feeder: {fd.stats()}")
     else:
         dm = bam.BamDataModule(tokenizer=tok, train_data_path=Path("dummy.bam"), predict_data_path=data_path,
-                               batch_size=batch_size, num_workers=num_workers)
+                               batch_size=batch_size, num_workers=num_workers, max_length=None if tile is None else tile.max_tokens)
         dm.setup("predict", world_size=world, rank=rank)
         n = loop.run_predict(model, dm, writer, device, rank=rank, gather=world > 1 and gather_logits,
-                             on_batch=_gathered_sink(output_path, rank) if gather_logits else None, attention_writer=attn_writer)
+                             on_batch=_gathered_sink(output_path, rank) if gather_logits else None, attention_writer=attn_writer,
+                             long_reads=tile)
     distributed.barrier()
     rep = getattr(model.net, "selfcheck_report", None)
     if rep:

@@ -26,6 +26,7 @@ ABI_VERSION = 6
 ATTN_MAX_TOP_K = 32                   # clm_attn_out.top_k: 1 ... 32
 EXPLAIN_SUB_N, EXPLAIN_SUB_ALL = 0, 1   # clm_explain_plan substitutes (CLM_EXPLAIN_SUB_*)
 EXPLAIN_MAX_BASES = 32768             # bases of one read the explain calls take
+LONGREAD_SEP = 1                      # clm_longread_span.flags bit 0 (CLM_LONGREAD_SEP)
 MAMBA_SEQ, MAMBA_SP = 0, 1            # clm_mamba_create variants (CLM_MAMBA_SEQ, CLM_MAMBA_SP)
 
 
@@ -63,6 +64,10 @@ class ClmAttnSummary(C.Structure):            # include/chimeralm_hip.h: struct 
 class ClmAttnOut(C.Structure):                # include/chimeralm_hip.h: struct clm_attn_out
     _fields_ = [("struct_size", C.c_int32), ("top_k", C.c_int32), ("weights", C.c_void_p), ("weights_row_stride", C.c_int64),
                 ("summary", C.c_void_p), ("peak_pos", C.c_void_p), ("peak_weight", C.c_void_p)]
+
+
+class ClmLongreadSpan(C.Structure):           # include/chimeralm_hip.h: struct clm_longread_span
+    _fields_ = [("read", C.c_int32), ("src_col", C.c_int32), ("n_copy", C.c_int32), ("flags", C.c_int32)]
 
 
 class ClmExplainMutant(C.Structure):          # include/chimeralm_hip.h: struct clm_explain_mutant
@@ -142,6 +147,15 @@ SYMBOLS = {
                                      C.c_void_p]),
     "clm_explain_last_error": (C.c_char_p, [_H]),
     "clm_explain_destroy": (C.c_int, [_H]),
+    "clm_longread_lengths": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "clm_longread_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "clm_longread_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
+    "clm_longread_rows": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_int64, C.c_int, C.c_void_p]),
+    "clm_longread_reduce": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clm_longread_last_error": (C.c_char_p, [_H]),
+    "clm_longread_destroy": (C.c_int, [_H]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

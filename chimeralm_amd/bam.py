@@ -83,10 +83,14 @@ class BamDataModule:
 
     def __init__(self, tokenizer, train_data_path=None, batch_size: int = 12, val_data_path=None, test_data_path=None,
                  predict_data_path=None, num_workers: int = 0, max_train_samples=None, max_val_samples=None,
-                 max_test_samples=None, max_predict_samples: int | None = None, *, pin_memory: bool = False):
+                 max_test_samples=None, max_predict_samples: int | None = None, *, pin_memory: bool = False,
+                 max_length: int | None = None):
         self.tokenizer, self.batch_size, self.predict_data_path = tokenizer, batch_size, predict_data_path
         self.max_predict_samples, self.pin_memory, self.num_workers = max_predict_samples, pin_memory, num_workers
         self.batch_size_per_device = batch_size
+        # tokens a read is truncated to (None: the tokenizer's `max_len_single_sentence`, as the reference); the long-read mode of
+        # `predict` asks for its cap instead (longread.Options.max_tokens) and cuts the windows on the device
+        self.max_length = max_length
         self.data_collator = DataCollator(tokenizer)
         self.data_predict = False
         self.world_size, self.rank = 1, 0
@@ -116,7 +120,7 @@ class BamDataModule:
         so memory holds one batch whatever the size of the BAM (the native feeder, the default of `predict`, does the same
         in C++)."""
         assert self.data_predict, "call setup('predict') first"
-        max_length = self.tokenizer.max_len_single_sentence
+        max_length = self.max_length if self.max_length is not None else self.tokenizer.max_len_single_sentence
         batch: list[dict] = []
         for i, rec in enumerate(parse_bam_file(self.predict_data_path)):
             if self.max_predict_samples is not None and i >= self.max_predict_samples:

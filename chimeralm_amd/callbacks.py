@@ -13,6 +13,9 @@ per batch next to the predictions, under names `filter` does not glob (`*.txt`, 
 
 `ExplainWriter` writes what the mutagenesis scan (explain.py, csrc/explain.hip) found per read; the reference's counterpart
 (chimeralm/explain/motif.py) plots one read's scores and writes no file.
+
+`WindowWriter` writes the per-window table of `predict --long-reads tile` (longread.py, csrc/longread.hip); the reference truncates
+a long read and has nothing to write.
 """
 from __future__ import annotations
 
@@ -193,3 +196,44 @@ class ExplainWriter:
             arrays = {"name": np.asarray([name], dtype=np.str_)}
             arrays.update({k: v.numpy() for k, v in importance.tensors().items()})
             (self.output_dir / f"{rank}_{index}.explain.npz").write_bytes(_npz_bytes(arrays))
+
+
+class WindowWriter:
+    """Which window of a long read decided its label (longread.tiled_forward): one `{rank}_{batch_idx}.windows.tsv` per batch that
+    holds a read of more than one window, one line per such read,
+
+        name<TAB>n_bases<TAB>n_windows<TAB>chosen<TAB>start:end:logit0:logit1;...<TAB>n_nonfinite
+
+    with the bases looked at (after the cap), the chosen window's index, every window's bases [start, end) among the read's and its
+    logits (%.7g) in window order, and the number of windows with a non-finite logit.  The read's line in `{rank}_{batch_idx}.txt`
+    carries the chosen window's label.  `tiled` is a `longread.TiledLogits` of HOST tensors.  A batch without a long read writes no
+    file; `filter`'s `*.txt` glob does not see the name."""
+
+    def __init__(self, output_dir: str | Path) -> None:
+        self.output_dir = Path(output_dir)
+
+    def write_on_batch_end(self, trainer: Any, tiled: Any, batch: dict[str, Any], batch_idx: int) -> None:
+        if tiled is None or tiled.plan.n_extra == 0:
+            return
+        if tiled.chosen is None or "id" not in batch:
+            log.error("batch %d: missing window table or 'id'", batch_idx)
+            return
+        plan = tiled.plan
+        ids = batch["id"].cpu() if isinstance(batch["id"], torch.Tensor) else batch["id"]
+        if len(ids) != plan.B:
+            log.error("Size mismatch: windows of %d reads, batch_ids=%d for batch %d", plan.B, len(ids), batch_idx)
+            return
+        names = _read_names(ids)
+        wl, chosen, bad = tiled.window_logits.tolist(), tiled.chosen.tolist(), tiled.nonfinite.tolist()
+        wb = plan.C - 1
+        lines = []
+        for r in range(plan.B):
+            win = plan.windows_of(r)
+            if len(win) < 2:
+                continue
+            table = ";".join(f"{s}:{s + wb}:{wl[i][0]:.7g}:{wl[i][1]:.7g}" for i, s in win)
+            lines.append(f"{names[r]}\t{int(plan.n_bases[r])}\t{len(win)}\t{chosen[r]}\t{table}\t{bad[r]}\n")
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
+        with (self.output_dir / f"{rank}_{batch_idx}.windows.tsv").open("w") as fh:
+            fh.writelines(lines)

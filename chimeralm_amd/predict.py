@@ -23,6 +23,12 @@ the device, the net's own forward, csrc/explain.hip) and hands the results to a 
 `run_predict_native` is the same loop fed by the native BAM feeder (csrc/bam_feeder.cpp): a C++ thread decodes, selects,
 tokenises and collates into a ring of page-locked slots; each batch crosses PCIe as uint8 on the engine's copy stream
 (`clm_stage_ids`) while the previous batch is computing, and the slot goes back to the ring once its copy has landed.
+
+With `long_reads` (a `longread.Options` of mode "tile"; `predict --long-reads tile`) both predict loops take UNTRUNCATED batches --
+the data path is opened with `long_reads.max_tokens` -- which cross PCIe as uint8 on the copy stream and go through
+`longread.tiled_forward`: the head batch is the batch the truncating path delivers, the extra windows of the long reads follow
+through the same forward (and the same fp16c guard), and the reduced logits take the `_Deferred` road like any batch's.  A
+`callbacks.WindowWriter` writes the per-window table behind the same event.  Without `long_reads` the loops run exactly as before.
 """
 from __future__ import annotations
 
@@ -33,11 +39,24 @@ import torch
 from .distributed import LogitsGather
 
 
-def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, device_keys: tuple = ()) -> dict:
+def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, device_keys: tuple = (), lengths=None) -> dict:
+    """`lengths` (the long-read loop's `longread.Options`): the batch also carries its rows' token counts (host, found before the
+    copy), and one that holds a long read lands in rows whose stride is a multiple of 16, as the window kernel reads them."""
     out = {}
     with torch.cuda.stream(stream):
         for k, v in batch.items():
-            if k == "input_ids":
+            if k == "input_ids" and lengths:
+                from .longread import needs_windows, row_lengths
+
+                u8 = v.to(torch.uint8)
+                out["lengths"] = row_lengths(u8.numpy())
+                if needs_windows(out["lengths"], u8.shape[1], lengths):
+                    host = torch.empty((u8.shape[0], (u8.shape[1] + 15) // 16 * 16), dtype=torch.uint8, pin_memory=True)
+                    host[:, : u8.shape[1]] = u8
+                    v = host.to(device, non_blocking=True)[:, : u8.shape[1]]
+                else:                                             # forwarded as it is: the truncating path's copy
+                    v = u8.pin_memory().to(device, non_blocking=True)
+            elif k == "input_ids":
                 # ids fit a byte (vocabulary 12): 8x less PCIe traffic than the reference's int64 batch
                 v = v.to(torch.uint8).pin_memory().to(device, non_blocking=True)
             elif k in device_keys:
@@ -46,19 +65,19 @@ def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, dev
     return out
 
 
-def _staged_batches(loader, device: torch.device, device_keys: tuple = ()):
+def _staged_batches(loader, device: torch.device, device_keys: tuple = (), lengths=None):
     """The double buffer of the predict and test loops: yields batch i on the device once the compute stream waits for its copy,
     with batch i+1 already collated on the host and its H2D copy queued on a side stream -- under the forward the caller runs next."""
     copy_stream = torch.cuda.Stream(device)
     compute = torch.cuda.current_stream(device)
     it = iter(loader)
     nxt = next(it, None)
-    staged = _to_device(nxt, device, copy_stream, device_keys) if nxt is not None else None
+    staged = _to_device(nxt, device, copy_stream, device_keys, lengths) if nxt is not None else None
     while staged is not None:
         compute.wait_stream(copy_stream)
         cur = staged
         nxt = next(it, None)                              # host collation of batch i+1 ...
-        staged = _to_device(nxt, device, copy_stream, device_keys) if nxt is not None else None   # ... and its H2D overlap
+        staged = _to_device(nxt, device, copy_stream, device_keys, lengths) if nxt is not None else None   # ... and its H2D overlap
         for k, v in cur.items():
             if k == "input_ids" or k in device_keys:
                 v.record_stream(compute)                  # allocated on the copy stream, read by the caller's kernels
@@ -73,14 +92,18 @@ class _Deferred:
     behind this forward only; the gathered `[world * rows, 3]` tensor follows to page-locked host memory on that stream."""
 
     def __init__(self, logits: torch.Tensor | None, labels, batch: dict | None, batch_idx: int,
-                 gather: LogitsGather | None = None, rows: int = 0, device: torch.device | None = None, attention=None):
+                 gather: LogitsGather | None = None, rows: int = 0, device: torch.device | None = None, attention=None,
+                 windows=None, window_writer=None):
         self.host, self.event = None, None
         self.attention = None                                  # engine.AttentionOutput of host tensors, behind the same event
+        self.windows, self.window_writer = None, window_writer  # longread.TiledLogits of host tensors, behind the same event
         if logits is not None and logits.is_cuda:
             self.host = torch.empty(logits.shape, dtype=logits.dtype, pin_memory=True)   # caching host allocator: cheap after the first
             self.host.copy_(logits, non_blocking=True)
             if attention is not None:
                 self.attention = attention.to_host()
+            if windows is not None and window_writer is not None and windows.plan.n_extra:
+                self.windows = windows.to_host()
             self.event = torch.cuda.Event()
             self.event.record()
         elif logits is not None:                               # host tensors: the CPU rehearsal of the multi-rank protocol (tests)
@@ -119,6 +142,8 @@ class _Deferred:
             writer.write_on_batch_end(trainer, model, (self.host, self.labels), None, self.batch, self.batch_idx, 0)
             if attention_writer is not None and self.attention is not None:
                 attention_writer.write_on_batch_end(trainer, model, (self.host, self.labels), self.attention, self.batch, self.batch_idx)
+            if self.windows is not None:
+                self.window_writer.write_on_batch_end(trainer, self.windows, self.batch, self.batch_idx)
         return alive
 
 
@@ -148,11 +173,29 @@ def _attention_setup(model, attention_writer):
     return net.attention_request()
 
 
+def _long_read_setup(long_reads, writer, attention_writer):
+    """The options of a loop that tiles long reads (None: it does not) and the writer of its window tables, next to the predictions."""
+    if long_reads is None or long_reads.mode != "tile":
+        return None, None
+    if attention_writer is not None:
+        raise ValueError("the pooling weights of a read reduced from several windows are not defined: no attention writer with long_reads")
+    from .callbacks import WindowWriter
+
+    return long_reads, WindowWriter(writer.output_dir)
+
+
 def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                on_batch=None, attention_writer=None) -> int:
+                on_batch=None, attention_writer=None, long_reads=None) -> int:
     """Returns the number of reads this rank classified.  `gather`: every batch's logits are also all-gathered over the process
     group (RCCL over xGMI when the backend is "nccl"), off the compute stream, and handed to `on_batch(batch_idx, tensor)` one
-    batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows)."""
+    batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows).
+    `long_reads`: see the module docstring; the datamodule must deliver untruncated reads (`max_length=long_reads.max_tokens`)."""
+    long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
+    if long_reads is not None:
+        from .longread import tiled_forward
+
+        if getattr(datamodule, "max_length", None) != long_reads.max_tokens:
+            raise ValueError(f"long_reads needs a datamodule with max_length={long_reads.max_tokens} (max_bases and [SEP])")
     model.eval()
     trainer = SimpleNamespace(global_rank=rank)
     gatherer = LogitsGather(device) if gather else None
@@ -161,10 +204,17 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
     pending: _Deferred | None = None
     want_attention = _attention_setup(model, attention_writer) is not None
     with torch.inference_mode():
-        for cur in _staged_batches(datamodule.predict_dataloader(), device):
-            logits, labels = model.predict_step(cur, batch_idx)
+        for cur in _staged_batches(datamodule.predict_dataloader(), device, lengths=long_reads):
+            tiled = None
+            if long_reads is None:
+                logits, labels = model.predict_step(cur, batch_idx)
+            else:
+                tiled = tiled_forward(model, cur["input_ids"], options=long_reads, batch_size=max(1, rows or cur["input_ids"].shape[0]),
+                                      lengths=cur["lengths"])
+                logits, labels = tiled.logits, cur["labels"]
             now = _Deferred(logits, labels, cur, batch_idx, gatherer, rows,
-                            attention=model.net.last_attention if want_attention else None)   # (left by this batch's forward)
+                            attention=model.net.last_attention if want_attention else None,   # (left by this batch's forward)
+                            windows=tiled, window_writer=window_writer)
             if pending is not None:
                 pending.flush(writer, trainer, model, on_batch, attention_writer)   # batch i-1: its copy finished while batch i was enqueued
             pending = now
@@ -261,10 +311,76 @@ def _check_engine(model, device: torch.device, batch_idx: int) -> None:
         raise EngineError(e.code, f"{e} [detected after batch {batch_idx - 1}, the last of this rank]") from None
 
 
+def _run_predict_native_tiled(model, feeder, writer, window_writer, long_reads, device: torch.device, *, rank: int, gather: bool,
+                              on_batch) -> int:
+    """`run_predict_native` with `long_reads`: the untruncated slot crosses PCIe as uint8 on a copy stream, into rows whose stride
+    is a multiple of 16, under the previous batch's forwards; the slot goes back to the ring after the copy's event; the batch goes
+    through `longread.tiled_forward` (the module's own forward, so the 16-bit guard hears the head batch and the extra windows)."""
+    import numpy as np
+
+    from .longread import needs_windows, row_lengths, tiled_forward
+
+    model.eval()
+    trainer = SimpleNamespace(global_rank=rank)
+    gatherer = LogitsGather(device) if gather else None
+    rows = feeder.batch_size
+    copy_stream = torch.cuda.Stream(device)
+    compute = torch.cuda.current_stream(device)
+
+    def stage(fb):
+        host = np.lib.stride_tricks.as_strided(fb.ids, shape=(fb.n_reads, fb.n_tokens), strides=(fb.row_stride, 1))
+        lengths = row_lengths(host)
+        # a batch that is forwarded as it is crosses as one contiguous copy, as on the truncating path; one with a long read lands
+        # in rows the window kernel can read (torch copies it across and re-strides it on the device)
+        stride = (fb.n_tokens + 15) // 16 * 16 if needs_windows(lengths, fb.n_tokens, long_reads) else fb.n_tokens
+        with torch.cuda.stream(copy_stream):
+            dev = torch.empty((fb.n_reads, stride), dtype=torch.uint8, device=device)
+            dev[:, : fb.n_tokens].copy_(torch.from_numpy(host), non_blocking=True)     # (the slot is page-locked: no host wait)
+            done = torch.cuda.Event()
+            done.record(copy_stream)
+        return dev, lengths, done
+
+    n_reads, batch_idx = 0, 0
+    pending: _Deferred | None = None
+    cur = feeder.next()
+    staged = stage(cur) if cur is not None else None
+    with torch.inference_mode():
+        while cur is not None:
+            nxt = feeder.next()
+            nxt_staged = stage(nxt) if nxt is not None else None      # H2D of batch i+1 overlaps the forwards of batch i
+            dev, lengths, done = staged
+            compute.wait_event(done)
+            dev.record_stream(compute)                                # allocated on the copy stream, read by this stream's kernels
+            tiled = tiled_forward(model, dev[:, : cur.n_tokens], options=long_reads, batch_size=rows, lengths=lengths)
+            done.synchronize()                                        # the copy has left the slot ...
+            feeder.release(cur)                                       # ... which goes back to the decoder
+            labels = torch.full((cur.n_reads,), -1, dtype=torch.int64)
+            batch = {"id": torch.from_numpy(cur.names), "labels": labels}
+            now = _Deferred(tiled.logits, labels, batch, batch_idx, gatherer, rows, windows=tiled, window_writer=window_writer)
+            if pending is not None:
+                pending.flush(writer, trainer, model, on_batch)
+            pending = now
+            n_reads += cur.n_reads
+            batch_idx += 1
+            cur, staged = nxt, nxt_staged
+        _check_engine(model, device, batch_idx)
+        if gatherer is not None:
+            _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, model, on_batch)
+        elif pending is not None:
+            pending.flush(writer, trainer, model, on_batch)
+    return n_reads
+
+
 def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                       on_batch=None, attention_writer=None) -> int:
-    """Predict loop over a `chimeralm_amd.feeder.BamFeeder`; same files as `run_predict` over `BamDataModule`."""
+                       on_batch=None, attention_writer=None, long_reads=None) -> int:
+    """Predict loop over a `chimeralm_amd.feeder.BamFeeder`; same files as `run_predict` over `BamDataModule`.  `long_reads`: see the
+    module docstring; the feeder must be opened with `max_tokens=long_reads.max_tokens`."""
     from ._native import DT_U8
+
+    long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
+    if long_reads is not None:
+        return _run_predict_native_tiled(model, feeder, writer, window_writer, long_reads, device, rank=rank, gather=gather,
+                                         on_batch=on_batch)
 
     model.eval()
     eng = model.net.engine(device)

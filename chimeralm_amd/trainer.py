@@ -49,7 +49,9 @@ class Trainer:
         return rank, world, device
 
     def predict(self, model, dataloaders=None, datamodule=None, ckpt_path: str | Path | None = None,
-                return_predictions: bool = False):
+                return_predictions: bool = False, *, long_reads=None):
+        """`long_reads` (a `longread.Options` of mode "tile"): reads longer than the window are judged in overlapping windows, for
+        any net; the datamodule must deliver them untruncated (`max_length=long_reads.max_tokens`)."""
         dm = datamodule if datamodule is not None else dataloaders
         if dm is None or not hasattr(dm, "predict_dataloader"):
             raise ValueError("Trainer.predict needs a datamodule with predict_dataloader()")
@@ -61,7 +63,7 @@ class Trainer:
         writers = [cb for cb in self.callbacks if hasattr(cb, "write_on_batch_end")]
         if not writers:
             raise ValueError("no prediction-writer callback configured (configs/callbacks/write.yaml)")
-        n = run_predict(model, dm, writers[0], device, rank=rank)
+        n = run_predict(model, dm, writers[0], device, rank=rank, long_reads=long_reads)
         distributed.barrier()
         log.info("[rank %d] %d reads predicted", rank, n)
         return None

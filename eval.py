@@ -8,6 +8,9 @@ a `predict_data_path`, `trainer.test(model=model, datamodule=datamodule, ckpt_pa
 Prediction files land in `${paths.output_dir}/predicts/{rank}_{batch}.txt` (configs/callbacks/write.yaml); the test stage
 leaves `test/loss`, `test/f1`, `test/precision`, `test/recall` in `trainer.callback_metrics` and logs them.
 The built-in composer (chimeralm_amd/config.py) reads the files -- whether or not hydra-core is installed: one behaviour everywhere.
+`+long_reads.mode=tile [+long_reads.overlap=4096] [+long_reads.max_bases=262144] [+long_reads.window=N]` on the predict route cuts reads
+longer than the model's context into overlapping windows for whichever net `model=` names (chimeralm_amd/longread.py) and writes
+`{rank}_{batch}.windows.tsv` next to the predictions; unknown keys are refused.
 Multi-GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 eval.py trainer=ddp ...`.
 """
 from __future__ import annotations
@@ -22,10 +25,28 @@ sys.path.insert(0, str(ROOT))
 log = logging.getLogger("eval")
 
 
+LONG_READ_KEYS = ("mode", "window", "overlap", "max_bases")
+
+
+def long_read_options(cfg):
+    """The `longread.Options` of `+long_reads.*` (None: no such node, or mode=truncate); unknown keys and bad values are a ValueError."""
+    from chimeralm_amd.longread import Options
+
+    node = dict(cfg.get("long_reads") or {})
+    unknown = sorted(set(node) - set(LONG_READ_KEYS))
+    if unknown:
+        raise ValueError(f"unknown long_reads option(s) {unknown}; known: {list(LONG_READ_KEYS)}")
+    if not node:
+        return None
+    options = Options(**{k: (str(v) if k == "mode" else v) for k, v in node.items()})     # a bad option fails before anything is loaded
+    return options if options.mode == "tile" else None
+
+
 def evaluate(cfg):
     from chimeralm_amd.config import instantiate, instantiate_callbacks
 
     assert cfg.ckpt_path
+    long_reads = long_read_options(cfg)
     log.info(f"Instantiating datamodule <{cfg.data._target_}>")
     datamodule = instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model._target_}>")
@@ -36,7 +57,14 @@ def evaluate(cfg):
     trainer = instantiate(cfg.trainer, callbacks=callbacks, logger=[])
     object_dict = {"cfg": cfg, "datamodule": datamodule, "model": model, "logger": [], "trainer": trainer}
     if getattr(datamodule, "predict_data_path", None) is None:
+        if long_reads is not None:
+            raise ValueError("+long_reads.mode=tile belongs to the predict route (+data.predict_data_path=<reads.bam>)")
         trainer.test(model=model, datamodule=datamodule, ckpt_path=cfg.ckpt_path)
+    elif long_reads is not None:
+        if not hasattr(datamodule, "max_length"):
+            raise ValueError(f"+long_reads.mode=tile needs a datamodule that can deliver untruncated reads, not {cfg.data._target_}")
+        datamodule.max_length = long_reads.max_tokens
+        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, long_reads=long_reads)
     else:
         trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)
     return trainer.callback_metrics, object_dict

@@ -432,6 +432,64 @@ int clm_explain_reduce(clm_explain_handle* h, const float* d, int n_bases, int w
 const char* clm_explain_last_error(const clm_explain_handle* h); /* h may be NULL: error of the last failed clm_explain_create / _plan */
 int clm_explain_destroy(clm_explain_handle* h);
 
+/* ---- reads longer than the model's context, in overlapping windows (ABI 6, additive) ------------------------------------------
+ * The reference truncates a read to the tokenizer's 32,768 bases (chimeralm/data/bam.py:166-170); the rest reaches no net.  These
+ * calls cut a long read into overlapping context-sized windows around the net's own forward (any of the clm_*_forward calls on the
+ * uint8 rows) and reduce the windows' logits to one pair per read.  They are tied to no net; nothing waits on the host.
+ *
+ * Window       Wb >= 1 bases, C = Wb + 1 tokens (the product: Wb = 32768).  Overlap O, 0 <= O <= Wb / 2; step = Wb - O.
+ * Cap          max_bases >= Wb: a longer read is cut to its first max_bases bases before anything else.
+ * Windows of a read of n bases (after the cap): n <= Wb: one window, the read itself.  Otherwise K = 1 + ceil((n - Wb) / step)
+ *              windows of exactly Wb bases; window k < K - 1 starts at base k * step, the last at n - Wb (it ends on the read's
+ *              last base).  A window row is its Wb bases followed by [SEP] (id 1), no pads.
+ * The batch    ids uint8 [B, L] with row stride row_stride: each row [PAD] (id 4) x (L - n_tokens), then the read's n_tokens tokens
+ *              (its bases and one [SEP]), untruncated.  [PAD] never occurs inside a read.
+ * Head batch   the first forward: L_out = min(L, C) tokens wide; a read that fits is right-aligned with [PAD] on its left, a long
+ *              read appears as its window 0 -- byte for byte the batch the truncating path delivers.
+ * Extra rows   the windows k >= 1 of the batch's long reads, C tokens wide, in read order, then window order.
+ * A span       clm_longread_span, one per output row, the B head rows first, then the extra rows: the output row is
+ *              [PAD] x (width - n_copy - sep), then n_copy bytes of source row `read` from column src_col, then [SEP] if sep
+ *              (bit 0 of flags).  A short read's head row copies its tokens, its own [SEP] included, with sep = 0.
+ * Reduction    gap_k = (double)logit1_k - (double)logit0_k from the fp32 logits.  The chosen window has the largest gap, equal gaps
+ *              go to the lowest k; if a window has a non-finite logit the chosen window is the lowest such k.  The read's logits
+ *              are the chosen window's two floats, bit for bit.  With no non-finite window: label = OR of the windows' labels.
+ *   lengths    host only: n_tokens [B] of a left-padded batch in host memory, by a search per row (not a pass over the bytes);
+ *              the boundary is verified.  A row that ends in [PAD] (all pads, or padded on the right) or whose boundary is not
+ *              [PAD] followed by a token is CLM_E_INVALID.
+ *   plan       host only, needs no GPU and no handle.  Writes L_out, first [B + 1] (may be NULL; read r's extra windows are extra
+ *              rows first[r] ... first[r + 1] - 1, so K_r = 1 + first[r + 1] - first[r]), n_spans = B + first[B], and at most
+ *              `capacity` spans with each span's first base in `starts` (may be NULL).  spans = NULL: count only.  More spans than
+ *              capacity, 1 > n_tokens[r] or n_tokens[r] > L and bad options are CLM_E_INVALID (clm_longread_last_error of NULL has
+ *              the text).
+ *   rows       device: writes spans s0 ... s0 + rows - 1 as rows of `width` bytes (L_out for head rows, C for extra rows), row r at
+ *              out + r * out_stride; the bytes between width and the next multiple of 16 are written as 0.  16-byte stores: `out`
+ *              16-byte aligned, out_stride a multiple of 16 that holds width rounded up to 16.  The source of a row starts at an
+ *              arbitrary byte; it is read with aligned 16-byte loads, all inside the batch: `ids` 16-byte aligned, row_stride a
+ *              multiple of 16 and >= L, the buffer holds B * row_stride bytes.  Anything else is CLM_E_INVALID and launches
+ *              nothing.  1 <= rows <= 65535.  ids, spans, out: device pointers.
+ *   reduce     device, one thread per read: logits [B + n_extra, 2] fp32 (head rows, then extra rows), first [B + 1] int32 ->
+ *              logits_out [B, 2], chosen int32 [B], gap fp32 [B + n_extra], nonfinite int32 [B] (windows of the read with a
+ *              non-finite logit).
+ * Both launches go to `stream` and do not synchronise; no atomics and no sums across threads: bitwise the same from run to run. */
+#define CLM_LONGREAD_SEP 1
+typedef struct clm_longread_handle clm_longread_handle;
+typedef struct clm_longread_span {
+    int32_t read;    /* source row in the batch                     */
+    int32_t src_col; /* first source column                         */
+    int32_t n_copy;  /* bytes copied                                */
+    int32_t flags;   /* bit 0 (CLM_LONGREAD_SEP): [SEP] follows them */
+} clm_longread_span;
+int clm_longread_lengths(const unsigned char* ids, int64_t row_stride, int B, int L, int32_t* n_tokens);
+int clm_longread_plan(const int32_t* n_tokens, int B, int L, int window, int overlap, int max_bases, int* L_out, int32_t* first,
+                      clm_longread_span* spans, int32_t* starts, int capacity, int* n_spans);
+int clm_longread_create(int device, clm_longread_handle** out);
+int clm_longread_rows(clm_longread_handle* h, const unsigned char* ids, int64_t row_stride, int B, int L, const clm_longread_span* spans,
+                      int n_spans, int s0, int rows, unsigned char* out, int64_t out_stride, int width, void* stream);
+int clm_longread_reduce(clm_longread_handle* h, const float* logits, const int32_t* first, int B, float* logits_out, int32_t* chosen,
+                        float* gap, int32_t* nonfinite, void* stream);
+const char* clm_longread_last_error(const clm_longread_handle* h); /* h may be NULL: the last failed _lengths / _plan / _create */
+int clm_longread_destroy(clm_longread_handle* h);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:

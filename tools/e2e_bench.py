@@ -2,6 +2,7 @@
 
     python tools/e2e_bench.py [--reads 6000] [--bases 8192] [--batch 256] [--precision fp16c]
     python tools/e2e_bench.py --bam tests/golden/test_chimric_reads.bam --batch 12 --repeat 5     (a real, ragged file: the reference's)
+    python tools/e2e_bench.py ... --long-reads tile      (reads beyond the context in overlapping windows: predict --long-reads tile)
 
 Same loop as `python -m chimeralm_amd predict` (chimeralm_amd.predict.run_predict_native) with seeded random weights; the
 clock starts after the first batch (filters / workspace for the length are built on it) and stops when the last prediction
@@ -29,14 +30,19 @@ def main():
     ap.add_argument("--min-bases", type=int, default=None, help="ragged file: read lengths uniform in [min-bases, bases]")
     ap.add_argument("--bam", type=Path, default=None, help="a real BAM instead of the synthetic one (batches padded on the left to their longest read)")
     ap.add_argument("--repeat", type=int, default=3, help="--bam: timed passes over the file after one warm-up pass")
+    ap.add_argument("--long-reads", choices=("truncate", "tile"), default="truncate", help="as predict --long-reads (tile: the defaults)")
     a = ap.parse_args()
     from feeder_bench import write_bam
 
     from chimeralm_amd import lm
     from chimeralm_amd.callbacks import PredictionWriter
     from chimeralm_amd.feeder import BamFeeder
+    from chimeralm_amd.longread import Options
     from chimeralm_amd.predict import run_predict_native
 
+    tile = Options() if a.long_reads == "tile" else None
+    tag = (lambda label: label) if tile is None else (lambda label: f"{label} (long reads tiled)")
+    feed = {} if tile is None else {"max_tokens": tile.max_tokens}         # untruncated rows: the windows are cut on the device
     device = torch.device("cuda", 0)
     torch.manual_seed(0)
     model = lm.ChimeraLM.new(precision=a.precision)
@@ -66,10 +72,10 @@ def main():
             for label, reps in (("warm-up", 1), ("timed", a.repeat)):
                 t0, done = time.perf_counter(), 0
                 for r in range(reps):
-                    with BamFeeder(a.bam, batch_size=a.batch) as f:
-                        done += run_predict_native(model, f, PredictionWriter(Path(td) / f"pred_{label}_{r}"), device)
+                    with BamFeeder(a.bam, batch_size=a.batch, **feed) as f:
+                        done += run_predict_native(model, f, PredictionWriter(Path(td) / f"pred_{label}_{r}"), device, long_reads=tile)
                 dt = time.perf_counter() - t0
-                print(f"{label}: {done} reads in {reps} pass(es), {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
+                print(f"{tag(label)}: {done} reads in {reps} pass(es), {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
             print("guard:", {k: v for k, v in model.net.selfcheck_report.items() if k != "samples"})
         return
     with tempfile.TemporaryDirectory() as td:
@@ -78,11 +84,11 @@ def main():
         for label, n in (("warm-up", 2 * a.batch), ("timed", None)):
             out = Path(td) / f"pred_{label}"
             t0 = time.perf_counter()
-            with BamFeeder(path, batch_size=a.batch, max_reads=n) as f:
-                done = run_predict_native(model, f, PredictionWriter(out), device)
+            with BamFeeder(path, batch_size=a.batch, max_reads=n, **feed) as f:
+                done = run_predict_native(model, f, PredictionWriter(out), device, long_reads=tile)
             dt = time.perf_counter() - t0
             files = len(list(out.glob("*.txt")))
-            print(f"{label}: {done} reads, {files} prediction files, {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
+            print(f"{tag(label)}: {done} reads, {files} prediction files, {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
 
 
 if __name__ == "__main__":
