@@ -2,6 +2,7 @@
 
     python -m chimeralm_amd predict DATA_PATH [-g GPUS] [-o OUTPUT] [-b BATCH] [-w WORKERS] [-c CKPT] [-r] [-v]
                                               [--long-reads truncate|tile --long-overlap 4096 --long-max-bases 262144]
+                                              [--batching file|bucket --bucket-steps 3]
 
 plus engine-only options `--weights` (directory/file with the released `model.safetensors`; the reference downloads
 `yangliz5/chimeralm` from the Hub) and `--precision`.  `--gpus 0` (the reference's CPU mode) is refused: this engine
@@ -67,11 +68,35 @@ def predict(
                                        "rest is cut off and counted by the feeder (truncated_bases)"),
     long_window: int | None = typer.Option(None, "--long-window", hidden=True, help="--long-reads tile: bases per window (default: "
                                            "the tokenizer's length; for tests and checkpoints of a shorter context)"),
+    batching: str = typer.Option("file", "--batching", help="how batches are formed: file (the reference's: reads in file order, "
+                                 "every batch padded to its longest read, so a read's logits depend on its batch-mates) | bucket: "
+                                 "every read is padded to a canonical length of its own and reads of one such length are forwarded "
+                                 "together -- the verdict on a read does not depend on -b, -g or the reads around it, and a ragged "
+                                 "file pays for few pads.  The pads differ from the reference's: not reference parity.  File "
+                                 "{rank}_{k}.txt is then the rank's k-th emitted batch"),
+    bucket_steps: int = typer.Option(3, "--bucket-steps", help="--batching bucket: log2 of the canonical lengths per octave above "
+                                     "1,024 bases (0 ... 5; 3: at most an eighth of a row is pads)"),
 ):
     """Predict the given dataset using ChimeraLM."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
     if gpus < 1:
         raise typer.BadParameter("this engine runs on MI355X GPUs only; use --gpus >= 1 (no CPU path exists)")
+    if batching not in ("file", "bucket"):
+        raise typer.BadParameter("--batching must be file or bucket")
+    bucket = None
+    if batching == "bucket":
+        if long_reads == "tile":
+            raise typer.BadParameter("--batching bucket and --long-reads tile exclude each other: a window plan is made per "
+                                     "file-order batch")
+        if gather_logits:
+            raise typer.BadParameter("--batching bucket and --gather-logits exclude each other: logits.tsv identifies a read by its "
+                                     "position in a file-order batch, which a regrouped batch does not have")
+        from .bucket import Options as BucketOptions
+
+        try:
+            bucket = BucketOptions(mode="bucket", steps_log2=bucket_steps)
+        except ValueError as e:
+            raise typer.BadParameter(f"--bucket-steps: {e}") from None
     save_attention = save_attention or attention_weights
     if save_attention and not 1 <= attention_top_k <= 32:
         raise typer.BadParameter("--attention-top-k must be 1 ... 32")
@@ -129,6 +154,8 @@ def predict(
         from .feeder import BamFeeder
 
         max_tokens, slots = tok.max_len_single_sentence if tile is None else tile.max_tokens, 4
+        if bucket is not None and tok.padding_side != "left":
+            raise typer.BadParameter("--batching bucket takes batches padded on the left only")
         if tile is not None:
             if tok.padding_side != "left":
                 raise typer.BadParameter("--long-reads tile takes batches padded on the left only")
@@ -139,7 +166,7 @@ def predict(
                        world=world, pad_left=tok.padding_side == "left") as fd:
             n = loop.run_predict_native(model, fd, writer, device, rank=rank, gather=world > 1 and gather_logits,
                                         on_batch=_gathered_sink(output_path, rank) if gather_logits else None,
-                                        attention_writer=attn_writer, long_reads=tile)
+                                        attention_writer=attn_writer, long_reads=tile, batching=bucket)
             log.info(f"[rank {rank}] feeder: {fd.stats()}")
     else:
         dm = bam.BamDataModule(tokenizer=tok, train_data_path=Path("dummy.bam"), predict_data_path=data_path,
@@ -147,7 +174,7 @@ def predict(
         dm.setup("predict", world_size=world, rank=rank)
         n = loop.run_predict(model, dm, writer, device, rank=rank, gather=world > 1 and gather_logits,
                              on_batch=_gathered_sink(output_path, rank) if gather_logits else None, attention_writer=attn_writer,
-                             long_reads=tile)
+                             long_reads=tile, batching=bucket)
     distributed.barrier()
     rep = getattr(model.net, "selfcheck_report", None)
     if rep:

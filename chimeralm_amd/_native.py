@@ -27,6 +27,8 @@ ATTN_MAX_TOP_K = 32                   # clm_attn_out.top_k: 1 ... 32
 EXPLAIN_SUB_N, EXPLAIN_SUB_ALL = 0, 1   # clm_explain_plan substitutes (CLM_EXPLAIN_SUB_*)
 EXPLAIN_MAX_BASES = 32768             # bases of one read the explain calls take
 LONGREAD_SEP = 1                      # clm_longread_span.flags bit 0 (CLM_LONGREAD_SEP)
+BUCKET_SCATTER, BUCKET_EMIT = 0, 1     # clm_bucket_step.kind (CLM_BUCKET_*)
+BUCKET_MAX_TOKENS = 32769             # tokens of the longest row the bucket calls take (CLM_BUCKET_MAX_TOKENS)
 MAMBA_SEQ, MAMBA_SP = 0, 1            # clm_mamba_create variants (CLM_MAMBA_SEQ, CLM_MAMBA_SP)
 
 
@@ -68,6 +70,16 @@ class ClmAttnOut(C.Structure):                # include/chimeralm_hip.h: struct 
 
 class ClmLongreadSpan(C.Structure):           # include/chimeralm_hip.h: struct clm_longread_span
     _fields_ = [("read", C.c_int32), ("src_col", C.c_int32), ("n_copy", C.c_int32), ("flags", C.c_int32)]
+
+
+class ClmBucketSpan(C.Structure):             # include/chimeralm_hip.h: struct clm_bucket_span
+    _fields_ = [("src_row", C.c_int32), ("src_col", C.c_int32), ("n_copy", C.c_int32), ("dst_width", C.c_int32),
+                ("dst_offset", C.c_int64)]
+
+
+class ClmBucketStep(C.Structure):             # include/chimeralm_hip.h: struct clm_bucket_step
+    _fields_ = [("kind", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("length", C.c_int32), ("offset", C.c_int64),
+                ("stride", C.c_int64)]
 
 
 class ClmExplainMutant(C.Structure):          # include/chimeralm_hip.h: struct clm_explain_mutant
@@ -156,6 +168,20 @@ SYMBOLS = {
     "clm_longread_reduce": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "clm_longread_last_error": (C.c_char_p, [_H]),
     "clm_longread_destroy": (C.c_int, [_H]),
+    "clm_bucket_length": (C.c_int, [C.c_int, C.c_int]),
+    "clm_bucket_pool_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "clm_bucket_plan_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_H)]),
+    "clm_bucket_plan_push": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int]),
+    "clm_bucket_plan_finish": (C.c_int, [_H]),
+    "clm_bucket_plan_steps": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "clm_bucket_plan_last_error": (C.c_char_p, [_H]),
+    "clm_bucket_plan_destroy": (C.c_int, [_H]),
+    "clm_bucket_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
+    "clm_bucket_scatter": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_int64, C.c_void_p]),
+    "clm_bucket_last_error": (C.c_char_p, [_H]),
+    "clm_bucket_destroy": (C.c_int, [_H]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

@@ -48,7 +48,7 @@ class BamFeeder:
         if rc != 0:
             self._h = None
             raise FeederError(self._lib.clm_feeder_last_error(None).decode())
-        self.batch_size = batch_size
+        self.batch_size, self.pad_left = batch_size, bool(pad_left)
 
     def next(self) -> FeedBatch | None:
         b = N.ClmFeedBatch()

@@ -29,6 +29,11 @@ the data path is opened with `long_reads.max_tokens` -- which cross PCIe as uint
 `longread.tiled_forward`: the head batch is the batch the truncating path delivers, the extra windows of the long reads follow
 through the same forward (and the same fp16c guard), and the reduced logits take the `_Deferred` road like any batch's.  A
 `callbacks.WindowWriter` writes the per-window table behind the same event.  Without `long_reads` the loops run exactly as before.
+
+With `batching` (a `bucket.Options` of mode "bucket"; `predict --batching bucket`) the staged device batches of either loop go through
+`bucket.regroup` before `predict_step`: every read is padded to a canonical length of its own and reads of one such length are
+forwarded together, so a read's logits no longer depend on its batch-mates; file `{rank}_{k}.txt` is the rank's k-th emitted batch.
+Without `batching` the loops run exactly as before.
 """
 from __future__ import annotations
 
@@ -41,7 +46,8 @@ from .distributed import LogitsGather
 
 def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, device_keys: tuple = (), lengths=None) -> dict:
     """`lengths` (the long-read loop's `longread.Options`): the batch also carries its rows' token counts (host, found before the
-    copy), and one that holds a long read lands in rows whose stride is a multiple of 16, as the window kernel reads them."""
+    copy), and one that holds a long read lands in rows whose stride is a multiple of 16, as the window kernel reads them.  With
+    the bucketed loop's `bucket.Options` every batch does: the scatter kernel reads them all."""
     out = {}
     with torch.cuda.stream(stream):
         for k, v in batch.items():
@@ -50,7 +56,7 @@ def _to_device(batch: dict, device: torch.device, stream: torch.cuda.Stream, dev
 
                 u8 = v.to(torch.uint8)
                 out["lengths"] = row_lengths(u8.numpy())
-                if needs_windows(out["lengths"], u8.shape[1], lengths):
+                if getattr(lengths, "mode", None) == "bucket" or needs_windows(out["lengths"], u8.shape[1], lengths):
                     host = torch.empty((u8.shape[0], (u8.shape[1] + 15) // 16 * 16), dtype=torch.uint8, pin_memory=True)
                     host[:, : u8.shape[1]] = u8
                     v = host.to(device, non_blocking=True)[:, : u8.shape[1]]
@@ -184,12 +190,68 @@ def _long_read_setup(long_reads, writer, attention_writer):
     return long_reads, WindowWriter(writer.output_dir)
 
 
+def _batching_setup(batching, long_reads, gather: bool, on_batch, pad_left: bool):
+    """The options of a loop that regroups its reads by canonical length (None: it does not), after the refusals."""
+    if batching is None or batching.mode != "bucket":
+        return None
+    if long_reads is not None and long_reads.mode == "tile":
+        raise ValueError("batching 'bucket' and long_reads 'tile' exclude each other: a window plan is made per file-order batch")
+    if gather or on_batch is not None:
+        raise ValueError("batching 'bucket' and gathered logits exclude each other: logits.tsv identifies a read by its position in a "
+                         "file-order batch, which a regrouped batch does not have")
+    if not pad_left:
+        raise ValueError("batching 'bucket' takes batches padded on the left only")
+    return batching
+
+
+def _run_predict_bucket(model, staged, writer, device: torch.device, rows: int, batching, *, rank: int, attention_writer) -> int:
+    """The predict loop over `bucket.regroup(staged)`: each emitted batch through `predict_step` (the module's own forward, so the
+    16-bit guard hears every batch), its logits on the `_Deferred` road like any batch's."""
+    import logging
+
+    from .bucket import Regrouper, regroup
+
+    model.eval()
+    trainer = SimpleNamespace(global_rank=rank)
+    n_reads, batch_idx = 0, 0
+    pending: _Deferred | None = None
+    want_attention = _attention_setup(model, attention_writer) is not None
+    regrouper = Regrouper(device, rows, batching)
+    try:
+        with torch.inference_mode():
+            for cur in regroup(staged, regrouper):
+                logits, labels = model.predict_step(cur, batch_idx)
+                now = _Deferred(logits, labels, cur, batch_idx, attention=model.net.last_attention if want_attention else None)
+                if pending is not None:
+                    pending.flush(writer, trainer, model, None, attention_writer)
+                pending = now
+                n_reads += logits.shape[0]
+                batch_idx += 1
+            _check_engine(model, device, batch_idx)
+            if pending is not None:
+                pending.flush(writer, trainer, model, None, attention_writer)
+    finally:
+        regrouper.close()
+    logging.getLogger(__name__).info("[rank %d] bucketed predict: %d reads in %d batches, %s tokens forwarded", rank, n_reads, batch_idx,
+                                     f"{regrouper.n_tokens:,}")
+    return n_reads
+
+
 def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                on_batch=None, attention_writer=None, long_reads=None) -> int:
+                on_batch=None, attention_writer=None, long_reads=None, batching=None) -> int:
     """Returns the number of reads this rank classified.  `gather`: every batch's logits are also all-gathered over the process
     group (RCCL over xGMI when the backend is "nccl"), off the compute stream, and handed to `on_batch(batch_idx, tensor)` one
     batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows).
-    `long_reads`: see the module docstring; the datamodule must deliver untruncated reads (`max_length=long_reads.max_tokens`)."""
+    `long_reads`: see the module docstring; the datamodule must deliver untruncated reads (`max_length=long_reads.max_tokens`).
+    `batching`: see the module docstring; the reads of this rank's shard are regrouped at the datamodule's per-device batch size."""
+    batching = _batching_setup(batching, long_reads, gather, on_batch,
+                               getattr(getattr(datamodule, "tokenizer", None), "padding_side", "left") == "left")
+    if batching is not None:
+        rows = getattr(datamodule, "batch_size_per_device", 0) or getattr(datamodule, "batch_size", 0)
+        if not rows:
+            raise ValueError("batching 'bucket' needs a datamodule that knows its batch size (batch_size_per_device)")
+        return _run_predict_bucket(model, _staged_batches(datamodule.predict_dataloader(), device, lengths=batching), writer, device,
+                                   int(rows), batching, rank=rank, attention_writer=attention_writer)
     long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
     if long_reads is not None:
         from .longread import tiled_forward
@@ -371,12 +433,53 @@ def _run_predict_native_tiled(model, feeder, writer, window_writer, long_reads, 
     return n_reads
 
 
+def _native_staged(feeder, device: torch.device):
+    """The feeder's batches as staged device batches for `bucket.regroup`: each slot crosses PCIe as uint8 on a copy stream, into
+    rows whose stride is a multiple of 16, under the forwards of the batches before it, with its rows' token counts found on the host
+    first; the slot goes back to the ring once its copy has landed and the batches it filled are queued."""
+    import numpy as np
+
+    from .longread import row_lengths
+
+    copy_stream = torch.cuda.Stream(device)
+    compute = torch.cuda.current_stream(device)
+
+    def stage(fb):
+        host = np.lib.stride_tricks.as_strided(fb.ids, shape=(fb.n_reads, fb.n_tokens), strides=(fb.row_stride, 1))
+        lengths = row_lengths(host)
+        with torch.cuda.stream(copy_stream):
+            dev = torch.empty((fb.n_reads, (fb.n_tokens + 15) // 16 * 16), dtype=torch.uint8, device=device)
+            dev[:, : fb.n_tokens].copy_(torch.from_numpy(host), non_blocking=True)     # (the slot is page-locked: no host wait)
+            done = torch.cuda.Event()
+            done.record(copy_stream)
+        return dev, lengths, done
+
+    cur = feeder.next()
+    staged = stage(cur) if cur is not None else None
+    while cur is not None:
+        nxt = feeder.next()
+        nxt_staged = stage(nxt) if nxt is not None else None          # H2D of batch i+1 overlaps the forwards batch i fills
+        dev, lengths, done = staged
+        compute.wait_event(done)
+        dev.record_stream(compute)                                    # allocated on the copy stream, read by this stream's kernels
+        yield {"input_ids": dev[:, : cur.n_tokens], "id": torch.from_numpy(cur.names), "lengths": lengths,
+               "labels": torch.full((cur.n_reads,), -1, dtype=torch.int64)}   # tokenizer.py:113: predict labels are all -1
+        done.synchronize()                                            # the copy has left the slot ...
+        feeder.release(cur)                                           # ... which goes back to the decoder
+        cur, staged = nxt, nxt_staged
+
+
 def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                       on_batch=None, attention_writer=None, long_reads=None) -> int:
+                       on_batch=None, attention_writer=None, long_reads=None, batching=None) -> int:
     """Predict loop over a `chimeralm_amd.feeder.BamFeeder`; same files as `run_predict` over `BamDataModule`.  `long_reads`: see the
-    module docstring; the feeder must be opened with `max_tokens=long_reads.max_tokens`."""
+    module docstring; the feeder must be opened with `max_tokens=long_reads.max_tokens`.  `batching`: see the module docstring; the
+    reads are regrouped at the feeder's batch size."""
     from ._native import DT_U8
 
+    batching = _batching_setup(batching, long_reads, gather, on_batch, getattr(feeder, "pad_left", True))
+    if batching is not None:
+        return _run_predict_bucket(model, _native_staged(feeder, device), writer, device, feeder.batch_size, batching, rank=rank,
+                                   attention_writer=attention_writer)
     long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
     if long_reads is not None:
         return _run_predict_native_tiled(model, feeder, writer, window_writer, long_reads, device, rank=rank, gather=gather,

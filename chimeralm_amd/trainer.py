@@ -49,9 +49,11 @@ class Trainer:
         return rank, world, device
 
     def predict(self, model, dataloaders=None, datamodule=None, ckpt_path: str | Path | None = None,
-                return_predictions: bool = False, *, long_reads=None):
+                return_predictions: bool = False, *, long_reads=None, batching=None):
         """`long_reads` (a `longread.Options` of mode "tile"): reads longer than the window are judged in overlapping windows, for
-        any net; the datamodule must deliver them untruncated (`max_length=long_reads.max_tokens`)."""
+        any net; the datamodule must deliver them untruncated (`max_length=long_reads.max_tokens`).  `batching` (a `bucket.Options`
+        of mode "bucket"): every read is padded to a canonical length of its own and reads of one such length are forwarded
+        together, for any net; each rank regroups its own shard."""
         dm = datamodule if datamodule is not None else dataloaders
         if dm is None or not hasattr(dm, "predict_dataloader"):
             raise ValueError("Trainer.predict needs a datamodule with predict_dataloader()")
@@ -63,7 +65,7 @@ class Trainer:
         writers = [cb for cb in self.callbacks if hasattr(cb, "write_on_batch_end")]
         if not writers:
             raise ValueError("no prediction-writer callback configured (configs/callbacks/write.yaml)")
-        n = run_predict(model, dm, writers[0], device, rank=rank, long_reads=long_reads)
+        n = run_predict(model, dm, writers[0], device, rank=rank, long_reads=long_reads, batching=batching)
         distributed.barrier()
         log.info("[rank %d] %d reads predicted", rank, n)
         return None

@@ -11,6 +11,8 @@ The built-in composer (chimeralm_amd/config.py) reads the files -- whether or no
 `+long_reads.mode=tile [+long_reads.overlap=4096] [+long_reads.max_bases=262144] [+long_reads.window=N]` on the predict route cuts reads
 longer than the model's context into overlapping windows for whichever net `model=` names (chimeralm_amd/longread.py) and writes
 `{rank}_{batch}.windows.tsv` next to the predictions; unknown keys are refused.
+`+batching.mode=bucket [+batching.steps_log2=3]` on the predict route pads every read to a canonical length of its own and forwards reads
+of one such length together (chimeralm_amd/bucket.py): a read's logits do not depend on its batch-mates; unknown keys are refused.
 Multi-GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 eval.py trainer=ddp ...`.
 """
 from __future__ import annotations
@@ -42,11 +44,31 @@ def long_read_options(cfg):
     return options if options.mode == "tile" else None
 
 
+BATCHING_KEYS = ("mode", "steps_log2")
+
+
+def batching_options(cfg):
+    """The `bucket.Options` of `+batching.*` (None: no such node, or mode=file); unknown keys and bad values are a ValueError."""
+    from chimeralm_amd.bucket import Options
+
+    node = dict(cfg.get("batching") or {})
+    unknown = sorted(set(node) - set(BATCHING_KEYS))
+    if unknown:
+        raise ValueError(f"unknown batching option(s) {unknown}; known: {list(BATCHING_KEYS)}")
+    if not node:
+        return None
+    options = Options(**{k: (str(v) if k == "mode" else v) for k, v in node.items()})     # a bad option fails before anything is loaded
+    return options if options.mode == "bucket" else None
+
+
 def evaluate(cfg):
     from chimeralm_amd.config import instantiate, instantiate_callbacks
 
     assert cfg.ckpt_path
     long_reads = long_read_options(cfg)
+    batching = batching_options(cfg)
+    if batching is not None and long_reads is not None:
+        raise ValueError("+batching.mode=bucket and +long_reads.mode=tile exclude each other")
     log.info(f"Instantiating datamodule <{cfg.data._target_}>")
     datamodule = instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model._target_}>")
@@ -59,12 +81,16 @@ def evaluate(cfg):
     if getattr(datamodule, "predict_data_path", None) is None:
         if long_reads is not None:
             raise ValueError("+long_reads.mode=tile belongs to the predict route (+data.predict_data_path=<reads.bam>)")
+        if batching is not None:
+            raise ValueError("+batching.mode=bucket belongs to the predict route (+data.predict_data_path=<reads.bam>)")
         trainer.test(model=model, datamodule=datamodule, ckpt_path=cfg.ckpt_path)
     elif long_reads is not None:
         if not hasattr(datamodule, "max_length"):
             raise ValueError(f"+long_reads.mode=tile needs a datamodule that can deliver untruncated reads, not {cfg.data._target_}")
         datamodule.max_length = long_reads.max_tokens
         trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, long_reads=long_reads)
+    elif batching is not None:
+        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, batching=batching)
     else:
         trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)
     return trainer.callback_metrics, object_dict

@@ -490,6 +490,79 @@ int clm_longread_reduce(clm_longread_handle* h, const float* logits, const int32
 const char* clm_longread_last_error(const clm_longread_handle* h); /* h may be NULL: the last failed _lengths / _plan / _create */
 int clm_longread_destroy(clm_longread_handle* h);
 
+/* ---- length-bucketed predict: a read's row depends on the read alone (ABI 6, additive) -----------------------------------------
+ * The reference pads a batch on the left to its longest read (chimeralm/data/tokenizer.py:152-159) and masks nothing: a read's
+ * logits depend on its batch-mates, and a ragged file pays for the pads.  These calls regroup the reads of the incoming batches
+ * into batches of one canonical length each, around the net's own forward.  They are tied to no net; the left pads differ from
+ * the reference's, so this mode is not reference parity.
+ *
+ * Row          a read of n tokens is b = n - 1 bases and one trailing [SEP] (id 1), truncated as today: 1 <= n <= 32769.
+ * Canonical    with m = steps_log2 (0 ... 5, the product: 3): e = max(6, floor(log2(max(b, 1))) - m), q = 2^e and
+ * length         Lc(n) = min(32769, 1 + q * max(1, ceil(b / q))).
+ *              Quantum 64 up to 1,024 bases, then 2^m steps per octave; the ladder is laid on bases, so 1025, 2049, ..., 32769
+ *              tokens are class tops with no pad.  Lc >= max(n, 65), Lc is monotone in n and Lc - n <= max(64, b / 2^m).
+ * Bucket row   [PAD] (id 4) x (Lc - n), then the read's n tokens: a function of the read alone.
+ * Regrouping   reads are taken in the order they arrive and each goes to the staging slab of its class (its Lc).  A class that
+ *              reaches batch_size rows is emitted as one batch, rows in arrival order; at the end of the input (`finish`) the
+ *              classes that hold rows are emitted in ascending Lc.  No class is merged into another.
+ * Pool         one slab of batch_size rows of round16(Lc) bytes per class, laid behind one another in the order the classes first
+ *              appear.  clm_bucket_pool_bytes is the size with every class of the ladder present (m = 3: 56 classes, 406,400
+ *              bytes x batch_size).
+ * Steps        what a push or finish asks of the caller, in order.  CLM_BUCKET_SCATTER: spans first ... first + count - 1 are
+ *              written (clm_bucket_scatter).  CLM_BUCKET_EMIT: the class `length` holds `count` rows at pool + offset, `stride`
+ *              bytes apart, ready to forward; they are the reads reads[first ... first + count - 1] (indices counted over all
+ *              pushes since create, from 0).  A scatter group closes at every emit: the emitted rows go through the forward
+ *              before a later group refills their slab (one stream orders both).
+ * A span       clm_bucket_span: n_copy bytes of source row src_row from column src_col become the last n_copy bytes of a row of
+ *              dst_width bytes at pool + dst_offset; [PAD] before them, zeroes up to the next multiple of 16 behind them.
+ *   length     Lc(n_tokens), or CLM_E_INVALID for n_tokens outside 1 ... 32769 or steps_log2 outside 0 ... 5.
+ *   plan       host only, needs no GPU.  push takes the token counts n_tokens [B] of a left-padded batch L columns wide (every one
+ *              in 1 ... min(L, 32769); clm_longread_lengths finds them) and leaves steps, spans and reads in the planner, where
+ *              clm_bucket_plan_steps finds them until the next push, finish or destroy.  A refused push changes nothing.
+ *   scatter    device: writes spans[s0 ... s0 + rows - 1] (HOST memory: they are checked, then copied to the device behind the
+ *              stream's earlier work).  A thread owns 16 destination bytes and stores them once; the source is read with aligned
+ *              16-byte loads, each issued only inside [0, B * row_stride), each store only inside [0, pool_bytes).  `ids` and
+ *              `pool` 16-byte aligned, row_stride a multiple of 16 and >= L, every span inside its source row and, rounded up to
+ *              16 bytes, inside the pool at a 16-byte offset, n_copy <= dst_width <= 32769, 1 <= rows <= 65535: anything else is
+ *              CLM_E_INVALID and launches nothing.  ids, pool: device pointers.  Up to 4,096 spans go out per launch, through a ring
+ *              of eight page-locked buffers that clm_bucket_create allocates; the launches go to `stream` and do not synchronise,
+ *              the call waits only for the launch eight launches back, whose buffer it reuses.  No atomics: bitwise the same from
+ *              run to run. */
+#define CLM_BUCKET_SCATTER 0
+#define CLM_BUCKET_EMIT 1
+#define CLM_BUCKET_MAX_TOKENS 32769
+typedef struct clm_bucket_handle clm_bucket_handle;
+typedef struct clm_bucket_plan clm_bucket_plan;
+typedef struct clm_bucket_span {
+    int32_t src_row;    /* source row in the batch                       */
+    int32_t src_col;    /* first source column                           */
+    int32_t n_copy;     /* bytes copied: the read's tokens               */
+    int32_t dst_width;  /* the class's Lc                                */
+    int64_t dst_offset; /* bytes into the pool, a multiple of 16         */
+} clm_bucket_span;
+typedef struct clm_bucket_step {
+    int32_t kind;   /* CLM_BUCKET_SCATTER | CLM_BUCKET_EMIT                              */
+    int32_t first;  /* scatter: the first span; emit: the first entry of reads           */
+    int32_t count;  /* scatter: spans; emit: rows                                        */
+    int32_t length; /* emit: the class's Lc (scatter: 0)                                 */
+    int64_t offset; /* emit: the slab's offset in the pool (scatter: 0)                  */
+    int64_t stride; /* emit: bytes from row to row, round16(Lc) (scatter: 0)             */
+} clm_bucket_step;
+int clm_bucket_length(int n_tokens, int steps_log2);
+int64_t clm_bucket_pool_bytes(int batch_size, int steps_log2); /* < 0: CLM_E_INVALID */
+int clm_bucket_plan_create(int batch_size, int steps_log2, clm_bucket_plan** out);
+int clm_bucket_plan_push(clm_bucket_plan* p, const int32_t* n_tokens, int B, int L);
+int clm_bucket_plan_finish(clm_bucket_plan* p);
+int clm_bucket_plan_steps(const clm_bucket_plan* p, const clm_bucket_step** steps, int* n_steps, const clm_bucket_span** spans,
+                          int* n_spans, const int64_t** reads, int* n_reads);
+const char* clm_bucket_plan_last_error(const clm_bucket_plan* p); /* p may be NULL: the last failed _length / _pool_bytes / _create */
+int clm_bucket_plan_destroy(clm_bucket_plan* p);
+int clm_bucket_create(int device, clm_bucket_handle** out);
+int clm_bucket_scatter(clm_bucket_handle* h, const unsigned char* ids, int64_t row_stride, int B, int L, const clm_bucket_span* spans,
+                       int n_spans, int s0, int rows, unsigned char* pool, int64_t pool_bytes, void* stream);
+const char* clm_bucket_last_error(const clm_bucket_handle* h); /* h may be NULL: the last failed clm_bucket_create */
+int clm_bucket_destroy(clm_bucket_handle* h);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:

@@ -3,6 +3,8 @@
     python tools/e2e_bench.py [--reads 6000] [--bases 8192] [--batch 256] [--precision fp16c]
     python tools/e2e_bench.py --bam tests/golden/test_chimric_reads.bam --batch 12 --repeat 5     (a real, ragged file: the reference's)
     python tools/e2e_bench.py ... --long-reads tile      (reads beyond the context in overlapping windows: predict --long-reads tile)
+    python tools/e2e_bench.py ... --batching bucket      (reads regrouped by canonical length: predict --batching bucket)
+    python tools/e2e_bench.py --ragged --reads 3000      (synthetic file, seeded log-uniform lengths of 500 ... 32,768 bases)
 
 Same loop as `python -m chimeralm_amd predict` (chimeralm_amd.predict.run_predict_native) with seeded random weights; the
 clock starts after the first batch (filters / workspace for the length are built on it) and stops when the last prediction
@@ -31,6 +33,10 @@ def main():
     ap.add_argument("--bam", type=Path, default=None, help="a real BAM instead of the synthetic one (batches padded on the left to their longest read)")
     ap.add_argument("--repeat", type=int, default=3, help="--bam: timed passes over the file after one warm-up pass")
     ap.add_argument("--long-reads", choices=("truncate", "tile"), default="truncate", help="as predict --long-reads (tile: the defaults)")
+    ap.add_argument("--batching", choices=("file", "bucket"), default="file", help="as predict --batching (bucket: the defaults)")
+    ap.add_argument("--ragged", action="store_true", help="synthetic file: seeded log-uniform read lengths of 500 ... 32,768 bases")
+    ap.add_argument("--net", choices=("hyena", "mambasp"), default="hyena", help="the net: the Hyena model (--precision applies) or "
+                    "configs/model/mambasp.yaml's (synthetic files only, through the Python data path), both with seeded random weights")
     a = ap.parse_args()
     from feeder_bench import write_bam
 
@@ -41,11 +47,28 @@ def main():
     from chimeralm_amd.predict import run_predict_native
 
     tile = Options() if a.long_reads == "tile" else None
+    bucket = None
+    if a.batching == "bucket":
+        from chimeralm_amd.bucket import Options as BucketOptions
+
+        import logging
+
+        bucket = BucketOptions()
+        logging.basicConfig(level=logging.INFO, format="%(message)s")      # the loop's line with the tokens it forwarded
     tag = (lambda label: label) if tile is None else (lambda label: f"{label} (long reads tiled)")
+    if bucket is not None:
+        tag = lambda label: f"{label} (bucketed)"                          # noqa: E731
     feed = {} if tile is None else {"max_tokens": tile.max_tokens}         # untruncated rows: the windows are cut on the device
     device = torch.device("cuda", 0)
     torch.manual_seed(0)
-    model = lm.ChimeraLM.new(precision=a.precision)
+    if a.net == "hyena":
+        model = lm.ChimeraLM.new(precision=a.precision)
+    else:
+        from chimeralm_amd.basic_module import ClassificationLit
+        from chimeralm_amd.mamba import MambaSequenceClassificationSP
+
+        model = ClassificationLit(MambaSequenceClassificationSP(vocab_size=12, embedding_dim=512, number_of_layers=3, dropout=0.2, headdim=64,
+                                                                d_state=128, d_conv=4, expand=3, number_of_classes=2, precision="fp16x3"))
     if a.bam is not None:
         # one warm-up pass (filters, workspace, the guard's first hearing, the [PAD] tables), then `repeat` timed passes; with the
         # share of tail tiles that lie wholly inside a [PAD] prefix (what csrc/pad_prefix.hip does not compute)
@@ -73,22 +96,42 @@ def main():
                 t0, done = time.perf_counter(), 0
                 for r in range(reps):
                     with BamFeeder(a.bam, batch_size=a.batch, **feed) as f:
-                        done += run_predict_native(model, f, PredictionWriter(Path(td) / f"pred_{label}_{r}"), device, long_reads=tile)
+                        done += run_predict_native(model, f, PredictionWriter(Path(td) / f"pred_{label}_{r}"), device, long_reads=tile,
+                                                   batching=bucket)
                 dt = time.perf_counter() - t0
                 print(f"{tag(label)}: {done} reads in {reps} pass(es), {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
-            print("guard:", {k: v for k, v in model.net.selfcheck_report.items() if k != "samples"})
+            print("guard:", {k: v for k, v in (getattr(model.net, "selfcheck_report", None) or {}).items() if k != "samples"})
         return
     with tempfile.TemporaryDirectory() as td:
         path = Path(td) / "synthetic.bam"
-        write_bam(path, a.reads, a.bases, min_bases=a.min_bases)
+        lengths = None
+        if a.ragged:
+            import numpy as np
+
+            lengths = np.exp(np.random.default_rng(1).uniform(np.log(500), np.log(32768), a.reads)).round().astype(np.int64)
+            file_tokens = sum(min(a.batch, a.reads - i) * (int(lengths[i: i + a.batch].max()) + 1) for i in range(0, a.reads, a.batch))
+            print(f"ragged file: {a.reads} reads, {int(lengths.sum()) + a.reads:,} tokens, {lengths.min():,} ... {lengths.max():,} bases; "
+                  f"batches of {a.batch} in file order hold {file_tokens:,} tokens")
+        write_bam(path, a.reads, a.bases, min_bases=a.min_bases, lengths=lengths)
         for label, n in (("warm-up", 2 * a.batch), ("timed", None)):
             out = Path(td) / f"pred_{label}"
             t0 = time.perf_counter()
-            with BamFeeder(path, batch_size=a.batch, max_reads=n, **feed) as f:
-                done = run_predict_native(model, f, PredictionWriter(out), device, long_reads=tile)
+            if a.net != "hyena":                   # the native loop drives the Hyena engine's own staging: other nets take the Python data path
+                from chimeralm_amd import bam, tokenizer
+                from chimeralm_amd.predict import run_predict
+
+                dm = bam.BamDataModule(tokenizer=tokenizer.load_tokenizer_from_hyena_model("hyenadna-small-32k-seqlen"),
+                                       predict_data_path=path, batch_size=a.batch, max_predict_samples=n)
+                dm.setup("predict")
+                done = run_predict(model, dm, PredictionWriter(out), device, batching=bucket)
+            else:
+                with BamFeeder(path, batch_size=a.batch, max_reads=n, **feed) as f:
+                    done = run_predict_native(model, f, PredictionWriter(out), device, long_reads=tile, batching=bucket)
             dt = time.perf_counter() - t0
             files = len(list(out.glob("*.txt")))
             print(f"{tag(label)}: {done} reads, {files} prediction files, {dt:.2f} s -> {done / dt:,.0f} reads/s end to end")
+            if label == "timed" and getattr(model.net, "selfcheck_report", None):
+                print("guard:", {k: v for k, v in model.net.selfcheck_report.items() if k != "samples"})
 
 
 if __name__ == "__main__":

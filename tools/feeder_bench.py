@@ -21,8 +21,9 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
-def write_bam(path: Path, n_reads: int, n_bases: int, seed: int = 0, min_bases: int | None = None) -> int:
-    """`n_reads` records of `n_bases` bases, or of lengths uniform in [min_bases, n_bases] (real long-read files are ragged)."""
+def write_bam(path: Path, n_reads: int, n_bases: int, seed: int = 0, min_bases: int | None = None, lengths=None) -> int:
+    """`n_reads` records of `n_bases` bases, or of lengths uniform in [min_bases, n_bases] (real long-read files are ragged), or of
+    the given `lengths` [n_reads]."""
     rng = np.random.default_rng(seed)
     max_bases = n_bases
     sa = b"SAZchr1,100,+,50M,60,0;\0"
@@ -42,6 +43,8 @@ def write_bam(path: Path, n_reads: int, n_bases: int, seed: int = 0, min_bases: 
                 total += len(chunk)
         for i in range(n_reads):
             n_bases = max_bases if min_bases is None else int(rng.integers(min_bases, max_bases + 1))
+            if lengths is not None:
+                n_bases = int(lengths[i])
             name = f"read_{i:08d}".encode()
             b = codes[rng.integers(0, 4, n_bases)]
             bp = b if n_bases % 2 == 0 else np.append(b, np.uint8(0))
