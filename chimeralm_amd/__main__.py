@@ -13,6 +13,12 @@ has no CPU path.  `filter` (reference :320-331) is the host-only step after pred
 
 has no command in the reference: it is `Mamba2Analyzer.get_position_importance` (chimeralm/explain/motif.py:64-82) as an engine
 capability, for the released Hyena model (`python explain.py model=...` at the repository's root serves every net).
+
+    python -m chimeralm_amd finetune TRAIN.parquet [--val VAL.parquet] [-o OUT] [--epochs 10 --lr 1e-4 -b 16 --precision fp16x3
+                                              --seed 12345] [--weights DIR | --ckpt FILE]
+
+is the reference's `train.py` with `freeze_backbone=True`, cut down to one GPU: the classifier head is fitted to labelled reads, the
+backbone stays as released (headtrain.py).
 """
 from __future__ import annotations
 
@@ -257,6 +263,62 @@ def explain(
     n = loop.run_explain(model, dm, writer, device, max_reads=max_reads, batch_size=batch_size, window=opts.window, stride=opts.stride,
                          substitute=opts.substitute, score=opts.score, top_k=opts.top_k)
     log.info(f"{n} reads scanned; results saved to {output_path}")
+
+
+@app.command()
+def finetune(
+    train_path: Path = typer.Argument(..., help="Labelled reads (parquet; ids end in |0 or |1)"),
+    val_path: Path | None = typer.Option(None, "--val", help="Validation reads (parquet); without it the training file is split "
+                                         "70 / 20 / 10 percent as the reference does and the middle slice validates"),
+    output_path: Path | None = typer.Option(None, "--output", "-o", help="Output directory (default: TRAIN with suffix .finetune)"),
+    epochs: int = typer.Option(10, "--epochs", help="Epochs"),
+    lr: float = typer.Option(1e-4, "--lr", help="AdamW learning rate (weight decay 0.01; ReduceLROnPlateau on val/loss)"),
+    batch_size: int = typer.Option(16, "--batch-size", "-b", help="Reads per optimizer step"),
+    precision: str = typer.Option("fp16x3", "--precision", help="arithmetic of the frozen backbone: fp16x3 (default) | fp32"),
+    seed: int = typer.Option(12345, "--seed", help="Seed of the per-epoch shuffle and of the head's dropout"),
+    ckpt_path: Path | None = typer.Option(None, "--ckpt", "-c", help="Path to the checkpoint file to start from"),
+    weights: str = typer.Option("yangliz5/chimeralm", "--weights", help="Directory/file with model.safetensors to start from"),
+    verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
+):
+    """Fine-tune the classifier head on labelled reads with the backbone frozen (writes model.safetensors and metrics.tsv)."""
+    logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
+    from .headtrain import TRAIN_PRECISIONS
+
+    if precision not in TRAIN_PRECISIONS:
+        raise typer.BadParameter("--precision must be fp16x3 or fp32: the head trains on the rows of the exact kernels")
+    if epochs < 1:
+        raise typer.BadParameter("--epochs must be >= 1")
+    if not 1 <= batch_size <= 65535:
+        raise typer.BadParameter("--batch-size must be 1 ... 65535")
+    if not lr > 0:
+        raise typer.BadParameter("--lr must be > 0")
+    for f in (train_path, val_path):
+        if f is not None and f.suffix != ".parquet":
+            raise typer.BadParameter(f"{f} is not in Parquet format")
+        if f is not None and not f.is_file():
+            raise typer.BadParameter(f"{f}: no such file")
+    if ckpt_path is not None and weights != "yangliz5/chimeralm":
+        raise typer.BadParameter("--ckpt and --weights exclude each other: the fit starts from one set of weights")
+    if ckpt_path is not None and not ckpt_path.is_file():
+        raise typer.BadParameter(f"--ckpt {ckpt_path}: no such file")
+    if output_path is None:
+        output_path = train_path.with_suffix(".finetune")
+
+    from . import headtrain, lm
+
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    kw = dict(precision=precision, selfcheck=False, freeze_backbone=True)
+    if ckpt_path is not None:
+        log.info(f"Loading model from {ckpt_path}")
+        model = lm.ChimeraLM.new(**kw).load_reference_checkpoint(ckpt_path)
+    else:
+        log.info(f"Loading model weights {weights}")
+        model = lm.ChimeraLM.from_pretrained(weights, **kw)
+    model.to(device)
+    train_rows, val_rows = headtrain.split_rows(train_path, val_path)
+    hist = headtrain.fit_head(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
+    log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 
 @app.command()

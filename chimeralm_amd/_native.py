@@ -182,6 +182,11 @@ SYMBOLS = {
                                      C.c_int64, C.c_void_p]),
     "clm_bucket_last_error": (C.c_char_p, [_H]),
     "clm_bucket_destroy": (C.c_int, [_H]),
+    "clm_chunk_reads": (C.c_int, [_H, C.c_int]),
+    "clm_rows": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "clm_rows_generation": (C.c_int64, [_H]),
+    "clm_pool_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "clm_pool_backward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_float, C.c_void_p]),
     "clm_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_debug_stop_after": (C.c_int, [_H, C.c_int, C.c_int]),
     "clm_profile_enable": (C.c_int, [_H, C.c_int]),

@@ -46,6 +46,16 @@ class ClassificationLit(_Base):
         loss = self.criterion(logits.reshape(-1, logits.size(-1)), targets.long().view(-1))
         return loss, torch.argmax(logits, dim=-1), targets
 
+    def training_step(self, batch: dict[str, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
+        """The batch's loss with a graph to the head's parameters (basic_module.py `training_step`): for a net built with
+        `freeze_backbone=True`, in training mode.  The backbone's backward does not exist on this engine."""
+        if not getattr(self.net, "freeze_backbone", False):
+            raise NotImplementedError("only the head trains on this engine: freeze_backbone=True")
+        loss, _, _ = self.model_step(batch)
+        if not loss.requires_grad:
+            raise RuntimeError("training_step: the loss has no graph -- the module is in eval() or autograd is off (model.train(), no no_grad)")
+        return loss
+
     def test_step(self, batch: dict[str, torch.Tensor], batch_idx: int = 0) -> None:
         """Forward, then the batch's loss and confusion counts added to `self.test_metrics` by one kernel on the same stream."""
         if self.test_metrics is None:

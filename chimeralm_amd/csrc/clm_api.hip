@@ -167,6 +167,14 @@ struct clm_handle {
     bool no_pad_skip = false;                       // CLM_DEBUG=no_pad_skip: every tile of every read is computed (A/B runs, tests)
     bool no_seg_skip = false;                       // CLM_DEBUG=no_seg_skip: ... but every segment of the long-read convolution is transformed
     int last_B = 0, last_L = 0, last_Lp = 0;
+    // The final residual rows as an output (clm_rows; the head fine-tune, pool_train.hip): what the last forward left in `h`, and a
+    // counter that moves whenever anything may have rewritten that buffer (every chunk of every forward, a weight reload)
+    struct RowsState {
+        bool valid = false, one_chunk = false, exact = false;   // a forward completed / in ONE chunk / on the exact-fp32 or fp16x3 kernels
+        int B = 0, L = 0;
+        int64_t generation = 0;
+    } rows;
+    DevBuf pt_w1s, pt_w1t, pt_partial;    // clm_pool_forward / _backward: W1 packed for the score GEMM / the tiles, partials
     // How forwards run right now.  clm_selfcheck / clm_set_fallback: the exact-fp32 kernels of the same handle as referee of, and
     // replacement for, the 16-bit path; clm_selfcheck and the build of a [PAD] table change it for a scope (ScopedRun)
     struct RunMode {
@@ -650,6 +658,8 @@ int size_workspace(ChunkCtx& c) {
     auto& [h, p, st, fs, kr, ptab] = c;
     if (int rc = ensure_workspace(h, p, st)) return rc;
     h->last_B = p.Bc; h->last_L = p.L; h->last_Lp = p.Lp;
+    h->rows.valid = false;                   // (this chunk rewrites the residual rows: whoever held them must not read them again)
+    ++h->rows.generation;
     if (h->ws_es != p.es) {                  // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
         if (h->ws_es) {                      // columns may read as NaN in the other
             HIPCHK(h, hipMemsetAsync(h->z.get(), 0, h->z.bytes(), st));
@@ -939,6 +949,10 @@ int forward_all(clm_handle* h, const void* ids, int ids_dtype, int64_t row_strid
         const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * row_stride * ids_elem_size(ids_dtype);
         if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st, attn, b0)) return rc;
     }
+    h->rows.valid = h->stop_stage < 0;                        // (a debug stop ends the forward before the last block)
+    h->rows.one_chunk = B <= chunk;
+    h->rows.exact = !plan_chunk(h, B < chunk ? B : chunk, L).tuned16;
+    h->rows.B = B; h->rows.L = L;
     return CLM_OK;
 }
 
@@ -1046,6 +1060,8 @@ int clm_finalize(clm_handle* h) {
         *s.dst = it->second.d.get<float>();
     }
     HIPCHK(h, hipDeviceSynchronize());
+    h->rows.valid = false;
+    ++h->rows.generation;
     h->filters.clear();                                      // (functions of the weights; each packing below replaces its own)
     h->pad_tables.clear();
     const int prec = h->cfg.precision;
@@ -1297,6 +1313,91 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
     if (!src) return fail(h, CLM_E_INVALID, "clm_debug_fetch: unknown or empty buffer " + n);
     if (bytes > have) return fail(h, CLM_E_INVALID, "clm_debug_fetch: " + n + " holds only " + std::to_string(have) + " bytes");
     HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    return CLM_OK;
+}
+
+// ---- the head fine-tune: residual rows out, attention pooling forward / backward on the caller's weights (pool_train.hip)
+int clm_rows(clm_handle* h, const float** rows, int* B, int* L) {
+    if (!h) return CLM_E_INVALID;
+    if (!rows || !B || !L) return fail(h, CLM_E_INVALID, "clm_rows: bad argument");
+    if (!h->finalized) return fail(h, CLM_E_STATE, "clm_rows before clm_finalize");
+    if (!h->rows.valid) return fail(h, CLM_E_STATE, "clm_rows: no completed forward on this handle since its weights were loaded");
+    if (!h->rows.one_chunk)
+        return fail(h, CLM_E_STATE, "clm_rows: the last forward ran " + std::to_string(h->rows.B) + " reads in chunks of chunk_reads = " +
+                                        std::to_string(h->cfg.chunk_reads) + "; only its last chunk's rows are left");
+    if (!h->rows.exact)
+        return fail(h, CLM_E_UNSUPPORTED, "clm_rows: the last forward ran 16-bit kernels; the rows are an output of the exact-fp32 and fp16x3 kernels only");
+    *rows = h->h.get<float>();
+    *B = h->rows.B;
+    *L = h->rows.L;
+    return CLM_OK;
+}
+
+int64_t clm_rows_generation(const clm_handle* h) { return h ? h->rows.generation : -1; }
+
+int clm_chunk_reads(const clm_handle* h, int L) {
+    if (!h || L < 1 || !h->finalized) return CLM_E_INVALID;
+    return chunk_for(h, L);
+}
+
+namespace {
+// the kernels read rows, weights and pooled vectors 16 bytes at a time
+bool aligned16(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) % 16) return false;
+    return true;
+}
+int check_pool_args(clm_handle* h, const char* who, bool any_null, bool aligned, int B, int L) {
+    const std::string w(who);
+    if (any_null || B < 1 || L < 1) return fail(h, CLM_E_INVALID, w + ": bad argument (a null pointer, or B or L < 1)");
+    if (!aligned) return fail(h, CLM_E_INVALID, w + ": rows, the weights and the pooled vectors must be 16-byte aligned");
+    if (!h->finalized) return fail(h, CLM_E_STATE, w + " before clm_finalize");
+    if (B > 65535 || L > h->cfg.max_seq_len) return fail(h, CLM_E_UNSUPPORTED, w + ": at most 65535 reads of max_seq_len tokens");
+    return CLM_OK;
+}
+// the call's workspace: W1 in the packing its kernels read, and the partials -- grown behind the stream's queued work
+int pool_workspace(clm_handle* h, DevBuf& w1, size_t partial_bytes, hipStream_t st) {
+    if (w1 && partial_bytes <= h->pt_partial.bytes()) return CLM_OK;
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, w1.reserve((size_t)D * D * 4));
+    HIPCHK(h, h->pt_partial.reserve(partial_bytes));
+    return CLM_OK;
+}
+}  // namespace
+
+int clm_pool_forward(clm_handle* h, const float* rows, int B, int L, const float* w1, const float* b1, const float* w2, const float* b2,
+                     float* scores_out, float* stats_out, float* pooled_out, void* stream) {
+    if (!h) return CLM_E_INVALID;
+    if (int rc = check_pool_args(h, "clm_pool_forward", !rows || !w1 || !b1 || !w2 || !b2 || !scores_out || !stats_out || !pooled_out,
+                                 aligned16({rows, w1, b1, w2, scores_out, pooled_out}), B, L)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = pool_workspace(h, h->pt_w1s, (size_t)B * POOL_SPLIT * 4 * D * 4, st)) return rc;
+    const float eps = h->cfg.ln_eps;
+    HIPCHK(h, hipMemsetAsync(h->pt_w1s.get(), 0, h->pt_w1s.bytes(), st));
+    launch_pack_weight(PREC_F32, w1, h->pt_w1s.get(), D, D, st);
+    launch_score(rows, h->net.lnf_g, h->net.lnf_b, h->pt_w1s.get(), b1, w2, b2, scores_out, B, L, eps, st);
+    launch_softmax_stats(scores_out, stats_out, B, L, st);
+    launch_pool(rows, h->net.lnf_g, h->net.lnf_b, scores_out, stats_out, h->pt_partial.get<float>(), B, L, eps, st);
+    launch_pool_combine(h->pt_partial.get<float>(), pooled_out, B, st);
+    HIPCHK(h, hipGetLastError());
+    return CLM_OK;
+}
+
+int clm_pool_backward(clm_handle* h, const float* rows, int B, int L, const float* w1, const float* b1, const float* w2,
+                      const float* scores, const float* stats, const float* pooled, const float* dpooled, float* d_w1, float* d_b1,
+                      float* d_w2, float* d_b2, float beta, void* stream) {
+    if (!h) return CLM_E_INVALID;
+    if (int rc = check_pool_args(h, "clm_pool_backward", !rows || !w1 || !b1 || !w2 || !scores || !stats || !pooled || !dpooled || !d_w1 ||
+                                 !d_b1 || !d_w2 || !d_b2, aligned16({rows, w1, b1, w2, scores, pooled, dpooled}), B, L)) return rc;
+    if (beta != 0.f && beta != 1.f) return fail(h, CLM_E_INVALID, "clm_pool_backward: beta must be 0 or 1");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = pool_workspace(h, h->pt_w1t, (size_t)pool_bwd_grid(B, L) * POOL_BWD_PSTRIDE * 4, st)) return rc;
+    launch_pack_f32t(w1, h->pt_w1t.get(), D, D, st);
+    launch_pool_bwd(rows, h->net.lnf_g, h->net.lnf_b, h->pt_w1t.get(), b1, w2, scores, stats, pooled, dpooled, h->pt_partial.get<float>(),
+                    d_w1, d_b1, d_w2, d_b2, beta, B, L, h->cfg.ln_eps, st);
+    HIPCHK(h, hipGetLastError());
     return CLM_OK;
 }
 

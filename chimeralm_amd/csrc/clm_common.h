@@ -616,6 +616,18 @@ void launch_head_tiles(const float* partial, int ntiles, const HeadW& hw, float*
                        hipStream_t st);
 void launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t st);
 
+// the attention pooling as a trainable layer (pool_train.hip): forward = launch_score + launch_softmax_stats + launch_pool + this
+// combine of the POOL_SPLIT * 4 partials (head_mlp_kernel's order); backward = one tiled kernel on the fp32 MFMA whose workgroups
+// each leave one partial [dW1 | db1 | dw2 | db2], then their sum in workgroup order: out = beta out + sum (beta 0 or 1)
+constexpr int POOL_BWD_GRID = 256;                          // workgroups at most; tile i belongs to workgroup i mod grid
+constexpr int POOL_BWD_PSTRIDE = D * D + D + D + 1;         // floats of one workgroup's partial
+void launch_pool_combine(const float* partial /*[B][POOL_SPLIT][4][256]*/, float* pooled /*[B][256]*/, int B, hipStream_t st);
+int pool_bwd_grid(int B, int L);                            // workgroups launch_pool_bwd starts (its `partial` holds that many)
+void launch_pool_bwd(const float* rows, const float* lnf_g, const float* lnf_b, const void* w1_packed /*launch_pack_f32t*/,
+                     const float* b1, const float* w2, const float* scores, const float* stats, const float* pooled,
+                     const float* dpooled, float* partial, float* d_w1, float* d_b1, float* d_w2, float* d_b2, float beta, int B, int L,
+                     float eps, hipStream_t st);
+
 // attention as an output (attn_weights.hip): softmax of the chunk's pooling scores [Bc][L] to weights (rows w_stride floats apart; null:
 // not wanted), and per read the summary record with its top_k peaks among the bases (null together: not wanted).  ids8 [Bc][Lp].
 constexpr int ATTN_MAX_L = 32832;   // tokens whose scores fit one workgroup's LDS (128.25 KiB of the CU's 160)

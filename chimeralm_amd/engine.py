@@ -68,6 +68,17 @@ class AttentionOutput:
         return out
 
 
+class _DevicePtr:
+    """fp32 device memory somebody else owns, as torch sees it through `__cuda_array_interface__`."""
+
+    def __init__(self, ptr: int, shape: tuple[int, ...]):
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f4", "data": (ptr, False), "version": 2, "strides": None}
+
+
+def _device_view(ptr: int, shape: tuple[int, ...], device: torch.device) -> torch.Tensor:
+    return torch.as_tensor(_DevicePtr(ptr, shape), device=device)
+
+
 class Engine:
     """One MI355X inference engine instance bound to `device` (e.g. "cuda:0")."""
 
@@ -245,6 +256,75 @@ class Engine:
 
     def stage_wait(self, staged: int):
         self._check(self._lib.clm_stage_wait(self._h, int(staged)))
+
+    # ------------------------------------------------------------------ the head fine-tune (headtrain.py)
+    def chunk_reads_for(self, length: int) -> int:
+        """Reads of `length` tokens this engine runs as ONE chunk (`clm_chunk_reads`): the most whose rows `rows()` hands out."""
+        n = int(self._lib.clm_chunk_reads(self._h, int(length)))
+        if n < 1:
+            raise EngineError(n, "clm_chunk_reads: the engine is not finalized, or length < 1")
+        return n
+
+    def rows_generation(self) -> int:
+        """Moves whenever the engine may have rewritten the rows `rows()` returned (every forward, every weight load)."""
+        return int(self._lib.clm_rows_generation(self._h))
+
+    def rows(self) -> torch.Tensor:
+        """The final residual rows fp32 [B, L, 256] (before ln_f) the last forward left: a VIEW of the engine's workspace, not a copy
+        -- valid until `rows_generation()` moves.  Raises unless that forward ran one chunk (B <= chunk_reads) on the exact-fp32 or
+        fp16x3 kernels (`clm_rows`)."""
+        ptr, B, L = C.c_void_p(), C.c_int(), C.c_int()
+        self._check(self._lib.clm_rows(self._h, C.byref(ptr), C.byref(B), C.byref(L)))
+        return _device_view(ptr.value, (B.value, L.value, 256), self.device)
+
+    def _f32(self, name: str, t: torch.Tensor | None, numel: int | None = None) -> C.c_void_p:
+        if t is None:
+            return C.c_void_p(None)
+        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 tensor on {self.device}")
+        if numel is not None and t.numel() != numel:
+            raise ValueError(f"{name} must hold {numel} values, got {tuple(t.shape)}")
+        return C.c_void_p(t.data_ptr()) if t.numel() else C.c_void_p(None)
+
+    @staticmethod
+    def _rows_shape(rows: torch.Tensor | None) -> tuple[int, int]:
+        if rows is None:
+            return 0, 0
+        if rows.dim() != 3 or rows.shape[2] != 256:
+            raise ValueError("rows must be [batch, length, 256]")
+        return int(rows.shape[0]), int(rows.shape[1])
+
+    def pool_forward(self, rows, w1, b1, w2, b2):
+        """Attention pooling of `rows` [B, L, 256] under the given weights (attention.0 weight [256, 256] and bias [256], attention.2
+        weight [256] values and bias [1]; ln_f is the engine's) -> (scores [B, L], stats [B, 2] = max and sum, pooled [B, 256]).
+        Asynchronous on torch's current stream (`clm_pool_forward`)."""
+        B, L = self._rows_shape(rows)
+        args = [self._f32("rows", rows), B, L, self._f32("w1", w1, 65536), self._f32("b1", b1, 256), self._f32("w2", w2, 256),
+                self._f32("b2", b2, 1)]
+        scores = torch.empty((B, L), dtype=torch.float32, device=self.device)
+        stats = torch.empty((B, 2), dtype=torch.float32, device=self.device)
+        pooled = torch.empty((B, 256), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.clm_pool_forward(self._h, *args, self._f32("scores", scores), self._f32("stats", stats),
+                                               self._f32("pooled", pooled), C.c_void_p(stream)))
+        return scores, stats, pooled
+
+    def pool_backward(self, rows, w1, b1, w2, scores, stats, pooled, dpooled, out=None, beta: float = 0.0):
+        """Gradients of the pooling's four tensors given dloss/dpooled [B, 256] and what `pool_forward` returned for the same rows and
+        weights -> (d_w1 [256, 256], d_b1 [256], d_w2 [256], d_b2 [1]); with `out` (such a tuple) and beta = 1 they are added to it.
+        Exact fp32, bitwise repeatable (`clm_pool_backward`)."""
+        B, L = self._rows_shape(rows)
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("beta = 1 accumulates into `out`")
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in ((256, 256), (256,), (256,), (1,)))
+        args = [self._f32("rows", rows), B, L, self._f32("w1", w1, 65536), self._f32("b1", b1, 256), self._f32("w2", w2, 256),
+                self._f32("scores", scores, B * L), self._f32("stats", stats, B * 2), self._f32("pooled", pooled, B * 256),
+                self._f32("dpooled", dpooled, B * 256), self._f32("d_w1", out[0], 65536), self._f32("d_b1", out[1], 256),
+                self._f32("d_w2", out[2], 256), self._f32("d_b2", out[3], 1)]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.clm_pool_backward(self._h, *args, C.c_float(beta), C.c_void_p(stream)))
+        return out
 
     # ------------------------------------------------------------------ taps
     def debug_stop_after(self, layer: int = -1, stage: int = -1):

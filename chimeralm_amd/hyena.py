@@ -234,6 +234,7 @@ class HyenaDna(nn.Module):
         self.attention_top_k = None if attention_top_k is None else int(attention_top_k)
         self.attention_device_weights = False
         self.last_attention = None
+        self.freeze_backbone = bool(freeze_backbone)
         if freeze_backbone:
             for p in self.backbone.parameters():
                 p.requires_grad = False
@@ -453,7 +454,18 @@ class HyenaDna(nn.Module):
             self._selfcheck(eng, input_ids() if callable(input_ids) else input_ids)
 
     def forward(self, input_ids: torch.Tensor, input_quals: torch.Tensor | None = None) -> torch.Tensor:
-        """`input_quals` is accepted and ignored, exactly as the reference does (hyena.py:244-256)."""
+        """`input_quals` is accepted and ignored, exactly as the reference does (hyena.py:244-256).
+
+        `freeze_backbone=True`, in training mode with autograd on: the logits carry a graph to the head's parameters (the fine-tune,
+        headtrain.py: the backbone runs as in inference, the attention pooling forward and backward in the engine, the classifier in
+        torch); `precision` must be "fp32" or "fp16x3".  Every other call is inference and returns logits without a graph -- also a
+        module with an unfrozen backbone in training mode, which is how a freshly built module is called everywhere: its backbone does
+        not train on this engine, and `ClassificationLit.training_step` says so."""
+        if self.freeze_backbone and self.training and torch.is_grad_enabled():
+            from .headtrain import check_train_precision, differentiable_logits
+
+            check_train_precision(self.precision)             # (before anything touches a GPU)
+            return differentiable_logits(self, input_ids)
         if input_ids.device.type != "cuda":
             raise RuntimeError("chimeralm_amd.HyenaDna runs on an MI355X only (move the batch to 'cuda'); "
                                "there is no CPU forward")
@@ -470,6 +482,12 @@ class HyenaDna(nn.Module):
             # in the arithmetic the forward ran in, brought over by one D2H copy
             self.head.attention_weights = att.weights.cpu().unsqueeze(-1)
         return logits
+
+    def micro_reads(self, n_tokens: int, device: torch.device) -> int:
+        """Reads of `n_tokens` tokens the engine runs as one chunk (`clm_chunk_reads`): the micro-batch of the head fine-tune."""
+        from .headtrain import train_engine
+
+        return train_engine(self, torch.device(device)).chunk_reads_for(n_tokens)
 
     def attention_request(self):
         """The `engine.AttentionRequest` this module's forwards make (None: none): peaks for `attention_top_k`, weights for

@@ -563,6 +563,39 @@ int clm_bucket_scatter(clm_bucket_handle* h, const unsigned char* ids, int64_t r
 const char* clm_bucket_last_error(const clm_bucket_handle* h); /* h may be NULL: the last failed clm_bucket_create */
 int clm_bucket_destroy(clm_bucket_handle* h);
 
+/* ---- fine-tuning the head with the backbone frozen (chimeralm_amd/headtrain.py) -------------------
+ * The backbone runs as in inference and leaves the final residual rows h fp32 [B, L, 256] (before ln_f) on the device; the attention
+ * pooling -- the one part of the head that sees L tokens per read -- runs forward and backward here on the CALLER's current weights
+ * (device pointers, fp32: attention.0.weight w1 [256, 256] and bias b1 [256], attention.2.weight w2 [256] and bias b2 [1]); ln_f and
+ * its eps come from the finalized handle.  The classifier behind the pooling sees one 256-vector per read and is the caller's.
+ *   per read, x_t = ln_f(h_t):  s_t = w2 . gelu(w1 x_t + b1) + b2,  a = softmax_t(s) over all L positions,  pooled = sum_t a_t x_t
+ *
+ * clm_rows      device pointer, reads and tokens of the rows the LAST forward on this handle left.  CLM_E_STATE if there was none
+ *               (since the weights were loaded) or it ran more than one chunk (B > chunk_reads: only the last chunk's rows are left);
+ *               CLM_E_UNSUPPORTED unless it ran the exact-fp32 or fp16x3 kernels.  The pointer is the handle's workspace: the next
+ *               forward (or weight load) rewrites or frees it.  clm_rows_generation moves whenever that may have happened: compare
+ *               it before reading rows taken earlier.
+ * clm_pool_forward   rows [B, L, 256] (any device pointer) -> scores_out [B, L] (before the softmax), stats_out [B, 2] (max, sum of
+ *               exp(s - max)), pooled_out [B, 256].
+ * clm_pool_backward  with the forward's scores, stats and pooled and dpooled [B, 256] = dloss/dpooled:
+ *               d_w1 [256, 256], d_b1 [256], d_w2 [256], d_b2 [1] = beta * (what they hold) + the gradients; beta is 0 (they are not
+ *               read) or 1 (micro-batches accumulate).  Exact fp32 (v_mfma_f32_32x32x2_f32), no floating-point atomics: the same
+ *               inputs give the same bits.  d_b2 is 0 in exact arithmetic (softmax is shift-invariant); what the sum gives is returned.
+ * Both: asynchronous on `stream`; CLM_E_INVALID for B or L < 1, a null pointer, another beta, or rows / weights / scores / pooled /
+ * dpooled that are not 16-byte aligned (the kernels read them 16 bytes at a time), CLM_E_STATE before clm_finalize,
+ * CLM_E_UNSUPPORTED for B > 65535 or L > max_seq_len -- and nothing is launched.  One call at a time per handle (they share its
+ * workspace, in stream order). */
+/* Reads of L tokens the handle pushes through all layers as ONE chunk right now (chunk_reads, capped by tokens, even above one):
+ * the largest B whose forward leaves all its rows for clm_rows.  After clm_finalize; otherwise, or for L < 1, CLM_E_INVALID. */
+int clm_chunk_reads(const clm_handle* h, int L);
+int clm_rows(clm_handle* h, const float** rows, int* B, int* L);
+int64_t clm_rows_generation(const clm_handle* h); /* -1 for NULL */
+int clm_pool_forward(clm_handle* h, const float* rows, int B, int L, const float* w1, const float* b1, const float* w2, const float* b2,
+                     float* scores_out, float* stats_out, float* pooled_out, void* stream);
+int clm_pool_backward(clm_handle* h, const float* rows, int B, int L, const float* w1, const float* b1, const float* w2,
+                      const float* scores, const float* stats, const float* pooled, const float* dpooled, float* d_w1, float* d_b1,
+                      float* d_w2, float* d_b2, float beta, void* stream);
+
 /* ---- test / measurement taps (not on the product path) -------------------------------------------- */
 
 /* Copy a named intermediate of the LAST clm_forward to host memory (synchronises the device).  Names:
