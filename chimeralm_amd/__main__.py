@@ -3,6 +3,7 @@
     python -m chimeralm_amd predict DATA_PATH [-g GPUS] [-o OUTPUT] [-b BATCH] [-w WORKERS] [-c CKPT] [-r] [-v]
                                               [--long-reads truncate|tile --long-overlap 4096 --long-max-bases 262144]
                                               [--batching file|bucket --bucket-steps 3]
+                                              [--save-trajectory --trajectory-stride 128 --trajectory-values]
 
 plus engine-only options `--weights` (directory/file with the released `model.safetensors`; the reference downloads
 `yangliz5/chimeralm` from the Hub) and `--precision`.  `--gpus 0` (the reference's CPU mode) is refused: this engine
@@ -63,6 +64,14 @@ def predict(
     attention_top_k: int = typer.Option(10, "--attention-top-k", help="bases listed per read by --save-attention (1 ... 32)"),
     attention_weights: bool = typer.Option(False, "--attention-weights", help="with --save-attention (implied): also write "
                                            "{rank}_{batch}.attn.npz with the pooling weight of every base of every read"),
+    save_trajectory: bool = typer.Option(False, "--save-trajectory", help="also write {rank}_{batch}.traj.tsv per batch: the verdict as "
+                                         "a function of how much of the read has been seen -- per read the bases seen where its label "
+                                         "settles and either side of the largest step towards it -- from the one forward predict runs "
+                                         "anyway.  Whether these points track a real junction has not been measured"),
+    trajectory_stride: int = typer.Option(128, "--trajectory-stride", help="--save-trajectory: tokens between two points (a multiple of "
+                                          "128 in 128 ... 4096)"),
+    trajectory_values: bool = typer.Option(False, "--trajectory-values", help="with --save-trajectory (implied): also write "
+                                           "{rank}_{batch}.traj.npz with the logits at every point of every read"),
     long_reads: str = typer.Option("truncate", "--long-reads", help="reads longer than the model's context (32,768 bases): truncate "
                                    "(the reference's: only the first 32,768 bases are seen) | tile: cut them into overlapping "
                                    "context-sized windows, judge every window, call the read an artifact if any window is one and "
@@ -108,6 +117,17 @@ def predict(
         raise typer.BadParameter("--attention-top-k must be 1 ... 32")
     if long_reads not in ("truncate", "tile"):
         raise typer.BadParameter("--long-reads must be truncate or tile")
+    save_trajectory = save_trajectory or trajectory_values
+    if save_trajectory:
+        if long_reads == "tile":
+            raise typer.BadParameter("--long-reads tile and --save-trajectory exclude each other: a read reduced from several windows "
+                                     "has no single row to follow")
+        from .engine import check_trajectory_stride
+
+        try:
+            check_trajectory_stride(trajectory_stride)
+        except ValueError as e:
+            raise typer.BadParameter(f"--trajectory-stride: {e}") from None
     tile = None
     if long_reads == "tile":
         if save_attention:
@@ -148,14 +168,17 @@ def predict(
     if ckpt_path is not None:
         log.info(f"Loading model from {ckpt_path}")
         model = lm.ChimeraLM.new(precision=precision, selfcheck=None if selfcheck_tol > 0 else False, selfcheck_tol=selfcheck_tol,
-                                 attention_top_k=attention_top_k if save_attention else None).load_reference_checkpoint(ckpt_path)
+                                 attention_top_k=attention_top_k if save_attention else None,
+                                 trajectory_stride=trajectory_stride if save_trajectory else None).load_reference_checkpoint(ckpt_path)
     else:
         log.info(f"Loading model weights {weights}")
         model = lm.ChimeraLM.from_pretrained(weights, precision=precision, selfcheck=None if selfcheck_tol > 0 else False,
-                                             selfcheck_tol=selfcheck_tol, attention_top_k=attention_top_k if save_attention else None)
+                                             selfcheck_tol=selfcheck_tol, attention_top_k=attention_top_k if save_attention else None,
+                                             trajectory_stride=trajectory_stride if save_trajectory else None)
     output_path.mkdir(parents=True, exist_ok=True)
     writer = callbacks.PredictionWriter(output_dir=output_path, write_interval="batch")
     attn_writer = callbacks.AttentionWriter(output_dir=output_path, weights=attention_weights) if save_attention else None
+    traj_writer = callbacks.TrajectoryWriter(output_dir=output_path, values=trajectory_values) if save_trajectory else None
     if feeder == "native":
         from .feeder import BamFeeder
 
@@ -172,7 +195,7 @@ def predict(
                        world=world, pad_left=tok.padding_side == "left") as fd:
             n = loop.run_predict_native(model, fd, writer, device, rank=rank, gather=world > 1 and gather_logits,
                                         on_batch=_gathered_sink(output_path, rank) if gather_logits else None,
-                                        attention_writer=attn_writer, long_reads=tile, batching=bucket)
+                                        attention_writer=attn_writer, long_reads=tile, batching=bucket, trajectory_writer=traj_writer)
             log.info(f"[rank {rank}] feeder: {fd.stats()}")
     else:
         dm = bam.BamDataModule(tokenizer=tok, train_data_path=Path("dummy.bam"), predict_data_path=data_path,
@@ -180,7 +203,7 @@ def predict(
         dm.setup("predict", world_size=world, rank=rank)
         n = loop.run_predict(model, dm, writer, device, rank=rank, gather=world > 1 and gather_logits,
                              on_batch=_gathered_sink(output_path, rank) if gather_logits else None, attention_writer=attn_writer,
-                             long_reads=tile, batching=bucket)
+                             long_reads=tile, batching=bucket, trajectory_writer=traj_writer)
     distributed.barrier()
     rep = getattr(model.net, "selfcheck_report", None)
     if rep:

@@ -24,6 +24,7 @@ STAGES = ["embed", "ln1_in_proj", "short_long_conv", "out_proj", "ln2_fc1_gelu",
 N_STAGES = len(STAGES)
 ABI_VERSION = 6
 ATTN_MAX_TOP_K = 32                   # clm_attn_out.top_k: 1 ... 32
+TRAJ_STRIDE_UNIT, TRAJ_STRIDE_MAX = 128, 4096   # clm_traj_out.stride: a multiple of 128 in 128 ... 4096
 EXPLAIN_SUB_N, EXPLAIN_SUB_ALL = 0, 1   # clm_explain_plan substitutes (CLM_EXPLAIN_SUB_*)
 EXPLAIN_MAX_BASES = 32768             # bases of one read the explain calls take
 LONGREAD_SEP = 1                      # clm_longread_span.flags bit 0 (CLM_LONGREAD_SEP)
@@ -68,6 +69,16 @@ class ClmAttnOut(C.Structure):                # include/chimeralm_hip.h: struct 
                 ("summary", C.c_void_p), ("peak_pos", C.c_void_p), ("peak_weight", C.c_void_p)]
 
 
+class ClmTrajSummary(C.Structure):            # include/chimeralm_hip.h: struct clm_traj_summary (one record per read)
+    _fields_ = [(n, C.c_int32) for n in ("n_pad", "n_bases", "has_sep", "n_points", "first_k", "label", "onset_k", "jump_k",
+                                         "n_nonfinite", "reserved")] + [("jump_dgap", C.c_float), ("final_gap", C.c_float)]
+
+
+class ClmTrajOut(C.Structure):                # include/chimeralm_hip.h: struct clm_traj_out
+    _fields_ = [("struct_size", C.c_int32), ("stride", C.c_int32), ("logits", C.c_void_p), ("point_stride", C.c_int64),
+                ("summary", C.c_void_p)]
+
+
 class ClmLongreadSpan(C.Structure):           # include/chimeralm_hip.h: struct clm_longread_span
     _fields_ = [("read", C.c_int32), ("src_col", C.c_int32), ("n_copy", C.c_int32), ("flags", C.c_int32)]
 
@@ -99,6 +110,9 @@ SYMBOLS = {
     "clm_forward_attn": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut),
                                    C.c_void_p]),
     "clm_forward_staged_attn": (C.c_int, [_H, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut), C.c_void_p]),
+    "clm_forward_traj": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut),
+                                   C.POINTER(ClmTrajOut), C.c_void_p]),
+    "clm_forward_staged_traj": (C.c_int, [_H, C.c_int, C.c_void_p, C.POINTER(ClmAttnOut), C.POINTER(ClmTrajOut), C.c_void_p]),
     "clm_stage_ids": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "clm_forward_staged": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p]),
     "clm_stage_wait": (C.c_int, [_H, C.c_int]),

@@ -16,6 +16,9 @@ per batch next to the predictions, under names `filter` does not glob (`*.txt`, 
 
 `WindowWriter` writes the per-window table of `predict --long-reads tile` (longread.py, csrc/longread.hip); the reference truncates
 a long read and has nothing to write.
+
+`TrajectoryWriter` writes the running verdict of `predict --save-trajectory` (csrc/trajectory.hip): after how many bases the model's
+label settles and where the evidence arrives; the reference has no counterpart.
 """
 from __future__ import annotations
 
@@ -237,3 +240,50 @@ class WindowWriter:
         rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
         with (self.output_dir / f"{rank}_{batch_idx}.windows.tsv").open("w") as fh:
             fh.writelines(lines)
+
+
+class TrajectoryWriter:
+    """After how many bases the model decides (engine.TrajectoryOutput, csrc/trajectory.hip): one `{rank}_{batch_idx}.traj.tsv` per
+    batch, one line per read,
+
+        name<TAB>label<TAB>n_bases<TAB>K<TAB>first<TAB>onset<TAB>before_jump<TAB>at_jump<TAB>jump_dgap<TAB>final_gap
+
+    with the label of the whole row (the sign of logit1 - logit0, a tie is 0), the number of points K, and as BASES SEEN -- the read's
+    bases inside the point, clamp(n_k - n_pad, 0, n_bases) -- the first point that holds a base, the point from which the label no
+    longer changes (onset_k), and the two points either side of the largest step of the gap towards the label (jump_k - 1, jump_k)
+    with that step and the final gap as %.7g; a point that does not exist (a non-finite curve, a read of one informative point) is
+    -1.  With `values=True` also one `{rank}_{batch_idx}.traj.npz` holding `names`, `traj` fp32 [B, K, 2] (logits at every point)
+    and `bases_seen` int32 [B, K].  `trajectory` is an `engine.TrajectoryOutput` of HOST tensors with a summary.  `filter`'s `*.txt`
+    glob sees neither name."""
+
+    def __init__(self, output_dir: str | Path, values: bool = False) -> None:
+        self.output_dir = Path(output_dir)
+        self.values = bool(values)
+
+    def write_on_batch_end(self, trainer: Any, trajectory: Any, batch: dict[str, Any], batch_idx: int) -> None:
+        if trajectory is None or trajectory.summary is None or "id" not in batch:
+            log.error("batch %d: missing trajectory summary or 'id'", batch_idx)
+            return
+        ids = batch["id"].cpu() if isinstance(batch["id"], torch.Tensor) else batch["id"]
+        f = {k: v.tolist() for k, v in trajectory.fields().items()}
+        if len(ids) != len(f["label"]):
+            log.error("Size mismatch: trajectories of %d reads, batch_ids=%d for batch %d", len(f["label"]), len(ids), batch_idx)
+            return
+        names = _read_names(ids)
+        seen = trajectory.bases_seen()
+
+        def at(i: int, k: int) -> int:
+            return int(seen[i, k]) if k >= 0 else -1
+
+        lines = []
+        for i, name in enumerate(names):
+            jump = f["jump_k"][i]
+            lines.append(f"{name}\t{f['label'][i]}\t{f['n_bases'][i]}\t{f['n_points'][i]}\t{at(i, f['first_k'][i])}\t{at(i, f['onset_k'][i])}\t"
+                         f"{at(i, jump - 1 if jump >= 0 else -1)}\t{at(i, jump)}\t{f['jump_dgap'][i]:.7g}\t{f['final_gap'][i]:.7g}\n")
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
+        with (self.output_dir / f"{rank}_{batch_idx}.traj.tsv").open("w") as fh:
+            fh.writelines(lines)
+        if self.values:
+            (self.output_dir / f"{rank}_{batch_idx}.traj.npz").write_bytes(_npz_bytes(
+                {"names": np.asarray(names, dtype=np.str_), "traj": trajectory.logits.numpy(), "bases_seen": seen}))

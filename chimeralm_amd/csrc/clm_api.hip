@@ -142,6 +142,7 @@ struct clm_handle {
     DevBuf gscratch;                                // float2: segment spectra of the long-read convolution
     DevBuf ylo;                                     // PREC_F16C: lo bytes of y [B][256][Lp] (round 4, clm_common.h lo8_pack4)
     DevBuf ids8;                                    // clamped ids [B][Lp]
+    DevBuf traj_pooled, traj_npad;                  // the running verdict (trajectory.hip): fp32 [B][K][256], int [B]; grown by the first request
     // Round 5, the [PAD] prefix of left-padded batches (pad_prefix.hip): per read the 128-token tiles wholly inside its leading run
     // of [PAD], the list of tiles the tail kernels compute, and per arithmetic one table of what an all-[PAD] read leaves behind
     DevBuf pad_p0;                                  // int [3][B]: p0 | pair order | pair partner (launch_pair_order)
@@ -578,7 +579,7 @@ int chunk_for(const clm_handle* h, int L) {
 }
 
 int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st,
-                  const clm_attn_out* attn = nullptr, int b0 = 0);
+                  const clm_attn_out* attn = nullptr, int b0 = 0, const clm_traj_out* traj = nullptr);
 
 // The all-[PAD] table of the arithmetic the reads of this chunk run in (pad_prefix.hip), long enough for its L tokens: built on
 // first use -- ONE forward of one all-[PAD] read through this very engine, with the stages' capture hooks copying out what the
@@ -653,10 +654,21 @@ struct ChunkCtx {
     bool seg_skip(int j) const { return p.seg_skip[j] && ptab->gspec[j] && (!kr || p.L == ptab->L); }
 };
 
-// the workspace sized for this chunk
-int size_workspace(ChunkCtx& c) {
+// points of a trajectory with stride S along rows of L tokens
+int traj_points(int L, int S) { return (L + S - 1) / S; }
+
+// the workspace sized for this chunk (and for its trajectory request, if there is one)
+int size_workspace(ChunkCtx& c, const clm_traj_out* traj = nullptr) {
     auto& [h, p, st, fs, kr, ptab] = c;
     if (int rc = ensure_workspace(h, p, st)) return rc;
+    if (traj) {
+        const size_t need = (size_t)p.Bc * traj_points(p.L, traj->stride) * D * 4;
+        if (need > h->traj_pooled.bytes() || (size_t)p.Bc * 4 > h->traj_npad.bytes()) {
+            HIPCHK(h, hipStreamSynchronize(st));
+            HIPCHK(h, h->traj_pooled.reserve(need));
+            HIPCHK(h, h->traj_npad.reserve((size_t)p.Bc * 4));
+        }
+    }
     h->last_B = p.Bc; h->last_L = p.L; h->last_Lp = p.Lp;
     h->rows.valid = false;                   // (this chunk rewrites the residual rows: whoever held them must not read them again)
     ++h->rows.generation;
@@ -882,13 +894,32 @@ int stage_attn(ChunkCtx& c, const clm_attn_out& a, int b0) {
     return CLM_OK;
 }
 
+// The chunk's running verdict (clm_forward_traj), at the rows of its reads [b0, b0 + Bc) in the caller's buffers: the prefix merge of
+// the pooling partials every fused path has completed by then (tail kernels, the lone token, tiles from the [PAD] table), the
+// classifier over the interior points, then the chunk's own logits into the last point and the summary (trajectory.hip)
+int stage_traj(ChunkCtx& c, const clm_traj_out& t, int b0, const float* logits) {
+    auto& [h, p, st, fs, kr, ptab] = c;
+    const int tile = p.tuned16 ? 128 : T32_TILE, per = t.stride / tile, K = traj_points(p.L, t.stride), rows = p.Bc * (K - 1);
+    if (!p.fused || p.nt_pool != tiles_of(p.L, tile) || tiles_of(p.nt_pool, per) != K || t.point_stride < K ||
+        (size_t)p.Bc * K * D * 4 > h->traj_pooled.bytes() || (size_t)p.Bc * 4 > h->traj_npad.bytes())
+        return fail(h, CLM_E_STATE, "stage_traj: the chunk's plan and workspace do not fit the request");   // (check_traj_arg saw to it)
+    float* const out = t.logits + (size_t)b0 * t.point_stride * NCLS;
+    launch_traj_prefix(h->partial.get<float>(), p.nt_pool, per, K, h->traj_pooled.get<float>(), h->ids8.get<unsigned char>(), p.L, p.Lp,
+                       h->traj_npad.get<int>(), p.Bc, st);
+    launch_traj_classifier(h->traj_pooled.get<float>(), K, rows, h->hw, out, t.point_stride, st);
+    launch_traj_summary(logits, out, t.point_stride, p.Bc, K, t.stride, p.L, h->traj_npad.get<int>(), h->ids8.get<unsigned char>(), p.Lp,
+                        t.summary ? t.summary + b0 : nullptr, st);
+    HIPCHK(h, hipGetLastError());
+    return CLM_OK;
+}
+
 int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st,
-                  const clm_attn_out* attn, int b0) {
+                  const clm_attn_out* attn, int b0, const clm_traj_out* traj) {
     ChunkCtx c{h, plan_chunk(h, Bc, L), st};
     const ChunkPlan& p = c.p;
     // filters of the length class, workspace, [PAD] table
     if (int rc = ensure_filters(h, L, st, &c.fs, &c.kr)) return rc;
-    if (int rc = size_workspace(c)) return rc;
+    if (int rc = size_workspace(c, traj)) return rc;
     if (p.pad_skip) {                                        // (before this chunk's ids land in the workspace: the build runs through it)
         if (int rc = ensure_pad_table(h, p, st, &c.ptab)) return rc;
         if (int rc = size_workspace(c)) return rc;           // (the build may have regrown -- never shrunk -- the buffers; cheap when not)
@@ -909,6 +940,7 @@ int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_str
     for (int i = 0; i < NLAYER && !rc; ++i) rc = run_block(c, i);
     if (!rc) rc = stage_head(c, logits);
     if (!rc && attn) rc = stage_attn(c, *attn, b0);
+    if (!rc && traj) rc = stage_traj(c, *traj, b0, logits);
     return rc == STOPPED ? CLM_OK : rc;
 }
 
@@ -930,6 +962,25 @@ int check_attn_arg(clm_handle* h, const char* who, const clm_attn_out* a, int L)
     return CLM_OK;
 }
 
+// The trajectory request of clm_forward_traj / clm_forward_staged_traj for reads of L tokens (null: none, nothing to check)
+int check_traj_arg(clm_handle* h, const char* who, const clm_traj_out* t, int L) {
+    if (!t) return CLM_OK;
+    const std::string w(who);
+    if (t->struct_size != (int32_t)sizeof(clm_traj_out)) return fail(h, CLM_E_INVALID, w + ": clm_traj_out size mismatch");
+    if (t->stride < 128 || t->stride > 4096 || t->stride % 128)
+        return fail(h, CLM_E_INVALID, w + ": the trajectory's stride must be a multiple of 128 in 128 ... 4096");
+    if (!t->logits) return fail(h, CLM_E_INVALID, w + ": the trajectory request has no logits buffer");
+    if (t->point_stride < traj_points(L, t->stride))
+        return fail(h, CLM_E_INVALID, w + ": point_stride is shorter than the " + std::to_string(traj_points(L, t->stride)) + " points of a read");
+    if (L > ATTN_MAX_L)
+        return fail(h, CLM_E_UNSUPPORTED, w + ": trajectories exist for reads of up to " + std::to_string(ATTN_MAX_L) + " tokens");
+    if (h->stop_stage >= 0)
+        return fail(h, CLM_E_UNSUPPORTED, w + ": a debug stop is set (clm_debug_stop_after): the forward ends before the head");
+    if (!plan_chunk(h, 1, L).fused)
+        return fail(h, CLM_E_UNSUPPORTED, w + ": the unfused exact path (CLM_DEBUG=unfused_fp32) leaves no per-tile pooling partials");
+    return CLM_OK;
+}
+
 size_t ids_elem_size(int dtype) { return dtype == CLM_DT_I64 ? 8 : (dtype == CLM_DT_I32 ? 4 : 1); }
 // The ids argument of `who` (clm_forward, clm_stage_ids, clm_selfcheck); out: the pointer that call writes its result through
 int check_ids_arg(clm_handle* h, const char* who, const void* ids, const void* out, int ids_dtype, int64_t row_stride, int B, int L) {
@@ -939,15 +990,15 @@ int check_ids_arg(clm_handle* h, const char* who, const void* ids, const void* o
     return CLM_OK;
 }
 
-// `attn`: the caller's attention outputs for all B reads, or null -- the self-check, the [PAD]-table build and every other forward the
-// engine runs for itself pass none
+// `attn`, `traj`: the caller's attention and trajectory outputs for all B reads, or null -- the self-check, the [PAD]-table build and
+// every other forward the engine runs for itself pass none
 int forward_all(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int B, int L, float* logits, hipStream_t st,
-                const clm_attn_out* attn = nullptr) {
+                const clm_attn_out* attn = nullptr, const clm_traj_out* traj = nullptr) {
     const int chunk = chunk_for(h, L);
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = B - b0 < chunk ? B - b0 : chunk;
         const char* p = reinterpret_cast<const char*>(ids) + (size_t)b0 * row_stride * ids_elem_size(ids_dtype);
-        if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st, attn, b0)) return rc;
+        if (int rc = forward_chunk(h, p, ids_dtype, row_stride, Bc, L, logits + (size_t)b0 * NCLS, st, attn, b0, traj)) return rc;
     }
     h->rows.valid = h->stop_stage < 0;                        // (a debug stop ends the forward before the last block)
     h->rows.one_chunk = B <= chunk;
@@ -1117,16 +1168,22 @@ int clm_reserve(clm_handle* h, int B, int L) {
     return ensure_workspace(h, plan_chunk(h, B < chunk ? B : chunk, L), 0);
 }
 
-int clm_forward_attn(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
-                     const clm_attn_out* attn, void* stream) {
+int clm_forward_traj(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                     const clm_attn_out* attn, const clm_traj_out* traj, void* stream) {
     if (!h) return CLM_E_INVALID;
-    const char* const who = attn ? "clm_forward_attn" : "clm_forward";
+    const char* const who = traj ? "clm_forward_traj" : (attn ? "clm_forward_attn" : "clm_forward");
     if (!h->finalized) return fail(h, CLM_E_STATE, std::string(who) + " before clm_finalize");
     if (int rc = check_ids_arg(h, who, ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
     if (int rc = check_attn_arg(h, who, attn, L)) return rc;
+    if (int rc = check_traj_arg(h, who, traj, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = check_bad_ids(h)) return rc;
-    return forward_all(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, reinterpret_cast<hipStream_t>(stream), attn);
+    return forward_all(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, reinterpret_cast<hipStream_t>(stream), attn, traj);
+}
+
+int clm_forward_attn(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                     const clm_attn_out* attn, void* stream) {
+    return clm_forward_traj(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, attn, nullptr, stream);
 }
 
 int clm_forward(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
@@ -1166,6 +1223,11 @@ int clm_forward_staged(clm_handle* h, int staged, float* logits_out, void* strea
 }
 
 int clm_forward_staged_attn(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, void* stream) {
+    return clm_forward_staged_traj(h, staged, logits_out, attn, nullptr, stream);
+}
+
+int clm_forward_staged_traj(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, const clm_traj_out* traj,
+                            void* stream) {
     if (!h) return CLM_E_INVALID;
     if (staged < 0 || staged > 1 || !h->stage[staged].pending)
         return fail(h, CLM_E_STATE, "clm_forward_staged: no batch staged in that buffer");
@@ -1173,7 +1235,7 @@ int clm_forward_staged_attn(clm_handle* h, int staged, float* logits_out, const 
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(h, hipStreamWaitEvent(st, s.copied, 0));
-    const int rc = clm_forward_attn(h, s.buf.get(), s.dtype, s.stride, s.B, s.L, logits_out, attn, stream);
+    const int rc = clm_forward_traj(h, s.buf.get(), s.dtype, s.stride, s.B, s.L, logits_out, attn, traj, stream);
     // whatever happened, the buffer is no longer "staged and waiting": a failed forward must not wedge it for good
     s.pending = false;
     s.used = true;

@@ -635,4 +635,15 @@ constexpr int ATTN_MAX_TOP_K = 32;
 void launch_attn_weights(const float* scores, const unsigned char* ids8, int Bc, int L, int Lp, float* weights, int64_t w_stride,
                          clm_attn_summary* summary, int* peak_pos, float* peak_w, int top_k, hipStream_t st);
 
+// the running verdict (trajectory.hip): per read the pooled vector of every prefix that ends at a point (`per` tile partials per point,
+// K = ceil(ntiles / per) points; pooled [B][K][256]) and its n_pad; the classifier over the n_rows = B * (K - 1) interior rows (row r:
+// read r / (K - 1), point r % (K - 1)) into traj [B][pstride][2], TRAJ_ROWS rows per workgroup; then per read point K - 1 <- logits[b]
+// and, unless null, the summary record
+constexpr int TRAJ_ROWS = 8;
+void launch_traj_prefix(const float* partial, int ntiles, int per, int K, float* pooled, const unsigned char* ids8, int L, int Lp,
+                        int* npad, int B, hipStream_t st);
+void launch_traj_classifier(const float* pooled, int K, int n_rows, const HeadW& hw, float* traj, int64_t pstride, hipStream_t st);
+void launch_traj_summary(const float* logits, float* traj, int64_t pstride, int B, int K, int S, int L, const int* npad,
+                         const unsigned char* ids8, int Lp, clm_traj_summary* summary, hipStream_t st);
+
 }  // namespace clm

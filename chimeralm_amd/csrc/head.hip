@@ -7,6 +7,7 @@
 //     pooled = sum_L a * ln_f(h);  classifier (hyena.py:56-71), ResidualBlock (:160-180), output_layer (:74)
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "head_dense.h"
 
 namespace clm {
 
@@ -179,65 +180,7 @@ void launch_head_mlp(const float* partial, const HeadW& hw, float* pooled_out, f
 // workgroup.  The classifier is a chain of four small matrix-vector products whose cost is the latency of streaming
 // the weights from L2, so: every weight element is fetched once per HR reads, each dot product is split in two halves
 // (1024 threads = 512 outputs x 2), and the weight stream runs 16 elements ahead of the FMAs in a register ping-pong.
-constexpr int HR = 4, HT = 1024, MAXTILES = (32770 + 63) / 64;     // (the exact path's partials are per 64-token tile: tail32.hip)
-
-template <int IN, bool GELU>
-__device__ __forceinline__ void dense_rows(const float* __restrict__ wt, const float* __restrict__ bias,
-                                           const float (*xin)[HH], float (*xout)[HH], const float (*resid)[HH],
-                                           float (*part)[HH]) {
-    constexpr int HALF = IN / 2, PF = 16;
-    static_assert(HALF % (2 * PF) == 0, "two prefetch sets per loop trip");
-    const int o = threadIdx.x & (HH - 1), kh = threadIdx.x >> 9;
-    const float* w = wt + (size_t)kh * HALF * HH + o;
-    float acc[HR];
-#pragma unroll
-    for (int r = 0; r < HR; ++r) acc[r] = 0.f;
-    float wa[PF], wb[PF];
-#pragma unroll
-    for (int j = 0; j < PF; ++j) wa[j] = w[(size_t)j * HH];
-#pragma unroll 1
-    for (int i0 = 0; i0 < HALF; i0 += 2 * PF) {
-#pragma unroll
-        for (int j = 0; j < PF; ++j) wb[j] = w[(size_t)(i0 + PF + j) * HH];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < PF; j += 4)
-#pragma unroll
-            for (int r = 0; r < HR; ++r) {
-                const float4 x = *reinterpret_cast<const float4*>(&xin[r][kh * HALF + i0 + j]);
-                acc[r] = fmaf(wa[j + 3], x.w, fmaf(wa[j + 2], x.z, fmaf(wa[j + 1], x.y, fmaf(wa[j], x.x, acc[r]))));
-            }
-        __builtin_amdgcn_sched_barrier(0);
-        const int nx = i0 + 2 * PF < HALF ? i0 + 2 * PF : 0;     // wrap-around keeps the prefetch unconditional
-#pragma unroll
-        for (int j = 0; j < PF; ++j) wa[j] = w[(size_t)(nx + j) * HH];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < PF; j += 4)
-#pragma unroll
-            for (int r = 0; r < HR; ++r) {
-                const float4 x = *reinterpret_cast<const float4*>(&xin[r][kh * HALF + i0 + PF + j]);
-                acc[r] = fmaf(wb[j + 3], x.w, fmaf(wb[j + 2], x.z, fmaf(wb[j + 1], x.y, fmaf(wb[j], x.x, acc[r]))));
-            }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (kh == 1) {
-#pragma unroll
-        for (int r = 0; r < HR; ++r) part[r][o] = acc[r];
-    }
-    __syncthreads();
-    if (kh == 0) {
-        const float bo = bias[o];
-#pragma unroll
-        for (int r = 0; r < HR; ++r) {
-            float v = (acc[r] + part[r][o]) + bo;
-            if (GELU) v = gelu_erf(v);
-            if (resid) v += resid[r][o];
-            xout[r][o] = v;
-        }
-    }
-    __syncthreads();
-}
+constexpr int HR = 4, HT = HEAD_DENSE_THREADS, MAXTILES = (32770 + 63) / 64;     // (the exact path's partials are per 64-token tile: tail32.hip)
 
 __global__ __launch_bounds__(HT) void head_tiles_kernel(const float* __restrict__ partial, int ntiles, HeadW hw,
                                                         float* __restrict__ pooled_out, float* __restrict__ logits,
@@ -278,10 +221,10 @@ __global__ __launch_bounds__(HT) void head_tiles_kernel(const float* __restrict_
         x0[r][c] = pooled;
     }
     __syncthreads();
-    dense_rows<D, true>(hw.w0t, hw.b0, x0, x1, nullptr, part);       // classifier.0 + GELU
-    dense_rows<HH, true>(hw.w3t, hw.b3, x1, x2, nullptr, part);      // classifier.3 + GELU
-    dense_rows<HH, true>(hw.w60t, hw.b60, x2, x3, nullptr, part);    // ResidualBlock.layers.0 + GELU
-    dense_rows<HH, false>(hw.w63t, hw.b63, x3, x1, x2, part);        // ResidualBlock.layers.3 + residual
+    dense_rows<HR, D, true>(hw.w0t, hw.b0, x0, x1, nullptr, part);       // classifier.0 + GELU
+    dense_rows<HR, HH, true>(hw.w3t, hw.b3, x1, x2, nullptr, part);      // classifier.3 + GELU
+    dense_rows<HR, HH, true>(hw.w60t, hw.b60, x2, x3, nullptr, part);    // ResidualBlock.layers.0 + GELU
+    dense_rows<HR, HH, false>(hw.w63t, hw.b63, x3, x1, x2, part);        // ResidualBlock.layers.3 + residual
     if (tid < HR * NCLS) {
         const int r = tid / NCLS, k = tid % NCLS;
         if (b0 + r < B) {

@@ -68,6 +68,69 @@ class AttentionOutput:
         return out
 
 
+TRAJ_FIELDS = ("n_pad", "n_bases", "has_sep", "n_points", "first_k", "label", "onset_k", "jump_k", "n_nonfinite", "reserved",
+               "jump_dgap", "final_gap")             # clm_traj_summary: ten int32, then two fp32
+
+
+def check_trajectory_stride(stride: int) -> int:
+    stride = int(stride)
+    if not N.TRAJ_STRIDE_UNIT <= stride <= N.TRAJ_STRIDE_MAX or stride % N.TRAJ_STRIDE_UNIT:
+        raise ValueError(f"a trajectory's stride must be a multiple of {N.TRAJ_STRIDE_UNIT} in {N.TRAJ_STRIDE_UNIT} ... {N.TRAJ_STRIDE_MAX}")
+    return stride
+
+
+def bases_seen(n_points: int, stride: int, length: int, n_pad, n_bases) -> np.ndarray:
+    """int32 [B, K]: the bases of each read that lie inside point k, clamp(n_k - n_pad, 0, n_bases) with n_k = min((k + 1) S, L)."""
+    n_k = np.minimum((np.arange(n_points, dtype=np.int64) + 1) * int(stride), int(length))
+    n_pad, n_bases = np.asarray(n_pad, np.int64)[:, None], np.asarray(n_bases, np.int64)[:, None]
+    return np.clip(n_k[None, :] - n_pad, 0, n_bases).astype(np.int32)
+
+
+@dataclass(frozen=True)
+class TrajectoryRequest:
+    """What a forward should also leave on the device (`clm_forward_traj`): the logits the model would give if a row ended after
+    (k + 1) * `stride` of its tokens, for every such point (the last point is the row itself), and per read the summary record."""
+    stride: int = 128
+    summary: bool = True
+
+    def __post_init__(self):
+        check_trajectory_stride(self.stride)
+
+
+@dataclass
+class TrajectoryOutput:
+    """Device tensors of one batch, complete when the forward's stream reaches them (nothing here synchronises).  `logits` fp32
+    [B, K, 2], K = ceil(length / stride) points per row of `length` tokens; `summary` int32 [B, 12], the batch's `clm_traj_summary`
+    records (`fields()` names the columns), or None."""
+    stride: int
+    length: int
+    logits: torch.Tensor
+    summary: torch.Tensor | None
+
+    def tensors(self) -> dict[str, torch.Tensor]:
+        return {k: v for k, v in (("logits", self.logits), ("summary", self.summary)) if v is not None}
+
+    def to_host(self, non_blocking: bool = True) -> "TrajectoryOutput":
+        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
+        host = {}
+        for k, v in self.tensors().items():
+            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
+            host[k].copy_(v, non_blocking=non_blocking)
+        return TrajectoryOutput(self.stride, self.length, host["logits"], host.get("summary"))
+
+    def fields(self) -> dict[str, torch.Tensor]:
+        """The summary's columns by name (views): ten int32, then jump_dgap and final_gap fp32."""
+        if self.summary is None:
+            return {}
+        f = self.summary.view(torch.float32)
+        return {n: (self.summary if i < 10 else f)[:, i] for i, n in enumerate(TRAJ_FIELDS)}
+
+    def bases_seen(self) -> np.ndarray:
+        """int32 [B, K] from HOST tensors with a summary: the bases of each read inside each point."""
+        f = self.fields()
+        return bases_seen(self.logits.shape[1], self.stride, self.length, f["n_pad"].numpy(), f["n_bases"].numpy())
+
+
 class _DevicePtr:
     """fp32 device memory somebody else owns, as torch sees it through `__cuda_array_interface__`."""
 
@@ -161,9 +224,21 @@ class Engine:
             c.top_k, c.summary, c.peak_pos, c.peak_weight = a.top_k, a.summary.data_ptr(), a.peak_pos.data_ptr(), a.peak_weight.data_ptr()
         return a, c
 
-    def forward(self, input_ids: torch.Tensor, out: torch.Tensor | None = None, attention: AttentionRequest | None = None):
+    def _traj_out(self, req: TrajectoryRequest, B: int, L: int) -> tuple[TrajectoryOutput, N.ClmTrajOut]:
+        """Device tensors for a trajectory request and the `clm_traj_out` that points at them."""
+        K = (L + req.stride - 1) // req.stride
+        t = TrajectoryOutput(int(req.stride), L, torch.empty((B, K, 2), dtype=torch.float32, device=self.device),
+                             torch.empty((B, len(TRAJ_FIELDS)), dtype=torch.int32, device=self.device) if req.summary else None)
+        c = N.ClmTrajOut()
+        c.struct_size, c.stride, c.logits, c.point_stride = C.sizeof(N.ClmTrajOut), t.stride, t.logits.data_ptr(), K
+        c.summary = t.summary.data_ptr() if t.summary is not None else None
+        return t, c
+
+    def forward(self, input_ids: torch.Tensor, out: torch.Tensor | None = None, attention: AttentionRequest | None = None,
+                trajectory: TrajectoryRequest | None = None):
         """input_ids [B, L] (int64 / int32 / uint8) on this engine's device -> logits fp32 [B, 2]; with an `attention` request
-        -> (logits, AttentionOutput), written by the same call for every chunk of the batch (`clm_forward_attn`).
+        -> (logits, AttentionOutput), with a `trajectory` request -> (logits, TrajectoryOutput), with both -> (logits,
+        AttentionOutput, TrajectoryOutput), written by the same call for every chunk of the batch (`clm_forward_traj`).
         Asynchronous on torch's current stream."""
         if input_ids.dim() != 2:
             raise ValueError("input_ids must be [batch, length]")
@@ -178,14 +253,21 @@ class Engine:
         if out is None:
             out = torch.empty((B, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if attention is None:
+        if attention is None and trajectory is None:
             self._check(self._lib.clm_forward(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
                                               input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
             return out
-        att, c = self._attn_out(attention, B, L)
-        self._check(self._lib.clm_forward_attn(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
-                                               input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
-        return out, att
+        if trajectory is None:
+            att, c = self._attn_out(attention, B, L)
+            self._check(self._lib.clm_forward_attn(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
+                                                   input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
+            return out, att
+        att, c = self._attn_out(attention, B, L) if attention is not None else (None, None)
+        trj, ct = self._traj_out(trajectory, B, L)
+        self._check(self._lib.clm_forward_traj(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
+                                               C.c_void_p(out.data_ptr()), C.byref(c) if c is not None else None, C.byref(ct),
+                                               C.c_void_p(stream)))
+        return (out, trj) if att is None else (out, att, trj)
 
     __call__ = forward
 
@@ -199,20 +281,26 @@ class Engine:
         return k.value
 
     def forward_staged(self, staged: int, batch: int, out: torch.Tensor | None = None,
-                       attention: AttentionRequest | None = None, length: int | None = None):
-        """The forward of a staged batch of `batch` reads; with an `attention` request (then `length`, the batch's tokens per read,
-        is needed to size the weights) -> (logits, AttentionOutput), as `forward`."""
+                       attention: AttentionRequest | None = None, length: int | None = None,
+                       trajectory: TrajectoryRequest | None = None):
+        """The forward of a staged batch of `batch` reads; with an `attention` and / or `trajectory` request (then `length`, the
+        batch's tokens per read, is needed to size the outputs) the same tuples as `forward`."""
         if out is None:
             out = torch.empty((batch, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if attention is None:
+        if attention is None and trajectory is None:
             self._check(self._lib.clm_forward_staged(self._h, int(staged), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
             return out
         if length is None:
-            raise ValueError("forward_staged with an attention request needs the batch's `length`")
-        att, c = self._attn_out(attention, int(batch), int(length))
-        self._check(self._lib.clm_forward_staged_attn(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
-        return out, att
+            raise ValueError("forward_staged with an attention or trajectory request needs the batch's `length`")
+        att, c = self._attn_out(attention, int(batch), int(length)) if attention is not None else (None, None)
+        if trajectory is None:
+            self._check(self._lib.clm_forward_staged_attn(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
+            return out, att
+        trj, ct = self._traj_out(trajectory, int(batch), int(length))
+        self._check(self._lib.clm_forward_staged_traj(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c) if c is not None else None,
+                                                      C.byref(ct), C.c_void_p(stream)))
+        return (out, trj) if att is None else (out, att, trj)
 
     def check(self):
         """Wait for the current stream and raise for errors only the device can see (token ids outside the embedding table:

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from ._reload import reload_signature
-from .engine import Engine
+from .engine import Engine, check_trajectory_stride
 
 # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_finalize)
 X3_WEIGHT_LIMIT = 64.0
@@ -210,7 +210,7 @@ class HyenaDna(nn.Module):
     def __init__(self, number_of_classes: int, head: nn.Module, backbone_name: str = "hyenadna-small-32k-seqlen", *,
                  freeze_backbone: bool = False, precision: str = "fp16c", chunk_reads: int = 256,
                  selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
-                 attention_top_k: int | None = None):
+                 attention_top_k: int | None = None, trajectory_stride: int | None = None):
         super().__init__()
         if number_of_classes != 2:
             raise NotImplementedError("the engine implements the binary (2-class) head only")
@@ -234,6 +234,11 @@ class HyenaDna(nn.Module):
         self.attention_top_k = None if attention_top_k is None else int(attention_top_k)
         self.attention_device_weights = False
         self.last_attention = None
+        # the running verdict (an engine knob, csrc/trajectory.hip): with `trajectory_stride` set every forward also leaves
+        # `last_trajectory`, an engine.TrajectoryOutput of DEVICE tensors -- the logits the model would give if a row ended at each
+        # multiple of the stride, and per read the summary (where the verdict settles, where it moves most)
+        self.trajectory_stride = None if trajectory_stride is None else check_trajectory_stride(trajectory_stride)
+        self.last_trajectory = None
         self.freeze_backbone = bool(freeze_backbone)
         if freeze_backbone:
             for p in self.backbone.parameters():
@@ -471,10 +476,15 @@ class HyenaDna(nn.Module):
                                "there is no CPU forward")
         eng = self.engine(input_ids.device)
         self.guard(eng, input_ids)
-        req = self.attention_request()
-        if req is None:
+        req, traj = self.attention_request(), self.trajectory_request()
+        if req is None and traj is None:
             return eng.forward(input_ids)
-        logits, att = eng.forward(input_ids, attention=req)
+        logits, *extra = eng.forward(input_ids, attention=req, trajectory=traj)
+        if traj is not None:
+            self.last_trajectory = extra.pop()              # device tensors; nothing waits for them here
+        if req is None:
+            return logits
+        att = extra[0]
         if self.attention_top_k is not None:
             self.last_attention = att                       # device tensors; nothing waits for them here
         if getattr(self.head, "save_attention", False):
@@ -488,6 +498,13 @@ class HyenaDna(nn.Module):
         from .headtrain import train_engine
 
         return train_engine(self, torch.device(device)).chunk_reads_for(n_tokens)
+
+    def trajectory_request(self):
+        """The `engine.TrajectoryRequest` this module's forwards make (None: `trajectory_stride` is not set).  Loops that drive the
+        engine directly pass it on themselves."""
+        from .engine import TrajectoryRequest
+
+        return None if self.trajectory_stride is None else TrajectoryRequest(stride=self.trajectory_stride, summary=True)
 
     def attention_request(self):
         """The `engine.AttentionRequest` this module's forwards make (None: none): peaks for `attention_top_k`, weights for

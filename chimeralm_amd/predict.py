@@ -14,6 +14,9 @@ With an `attention_writer` (callbacks.AttentionWriter; `predict --save-attention
 if asked for -- per-position weights (csrc/attn_weights.hip) take the same road: device -> page-locked host memory behind the forward,
 read one batch behind, after the same event as the logits.  No wait is added per batch.
 
+With a `trajectory_writer` (callbacks.TrajectoryWriter; `predict --save-trajectory`) every batch's running verdict -- the logits at
+every multiple of the stride along each read and the per-read summary (csrc/trajectory.hip) -- takes that road as well.
+
 `run_test` is the loop of `lightning.Trainer.test` over the same double buffer: `model.test_step(batch)` queues the batch's metric
 update (csrc/eval_metrics.hip) behind its forward, so neither logits nor labels come back and the host waits for nothing per batch.
 
@@ -99,8 +102,9 @@ class _Deferred:
 
     def __init__(self, logits: torch.Tensor | None, labels, batch: dict | None, batch_idx: int,
                  gather: LogitsGather | None = None, rows: int = 0, device: torch.device | None = None, attention=None,
-                 windows=None, window_writer=None):
+                 windows=None, window_writer=None, trajectory=None, trajectory_writer=None):
         self.host, self.event = None, None
+        self.trajectory, self.trajectory_writer = None, trajectory_writer   # engine.TrajectoryOutput of host tensors, behind the same event
         self.attention = None                                  # engine.AttentionOutput of host tensors, behind the same event
         self.windows, self.window_writer = None, window_writer  # longread.TiledLogits of host tensors, behind the same event
         if logits is not None and logits.is_cuda:
@@ -110,11 +114,14 @@ class _Deferred:
                 self.attention = attention.to_host()
             if windows is not None and window_writer is not None and windows.plan.n_extra:
                 self.windows = windows.to_host()
+            if trajectory is not None and trajectory_writer is not None:
+                self.trajectory = trajectory.to_host()
             self.event = torch.cuda.Event()
             self.event.record()
         elif logits is not None:                               # host tensors: the CPU rehearsal of the multi-rank protocol (tests)
             self.host = logits
             self.attention = attention
+            self.trajectory = trajectory if trajectory_writer is not None else None
         self.gathered, self.gathered_done = None, None
         if gather is not None:
             mine = torch.zeros((rows, 3), dtype=torch.float32, device=device if logits is None else logits.device)
@@ -150,6 +157,8 @@ class _Deferred:
                 attention_writer.write_on_batch_end(trainer, model, (self.host, self.labels), self.attention, self.batch, self.batch_idx)
             if self.windows is not None:
                 self.window_writer.write_on_batch_end(trainer, self.windows, self.batch, self.batch_idx)
+            if self.trajectory is not None:
+                self.trajectory_writer.write_on_batch_end(trainer, self.trajectory, self.batch, self.batch_idx)
         return alive
 
 
@@ -179,6 +188,24 @@ def _attention_setup(model, attention_writer):
     return net.attention_request()
 
 
+def _trajectory_setup(model, trajectory_writer, long_reads=None):
+    """The net's trajectory request for a loop that writes trajectory files (None without a writer), after the refusals."""
+    if trajectory_writer is None:
+        return None
+    from .hyena import HyenaDna
+
+    net = model.net
+    if not isinstance(net, HyenaDna):
+        raise ValueError(f"a trajectory needs a causal net: a prefix of a read must not know what follows it.  {type(net).__name__} is "
+                         "not the Hyena net (the transformer attends in both directions, the CNN's windows straddle every cut; the "
+                         "Mamba nets are causal and could follow, they are not built)")
+    if long_reads is not None and getattr(long_reads, "mode", None) == "tile":
+        raise ValueError("a read reduced from several windows has no single row to follow: no trajectory writer with long_reads")
+    if net.trajectory_stride is None:
+        raise ValueError("a trajectory writer needs a net built with trajectory_stride (HyenaDna(trajectory_stride=...))")
+    return net.trajectory_request()
+
+
 def _long_read_setup(long_reads, writer, attention_writer):
     """The options of a loop that tiles long reads (None: it does not) and the writer of its window tables, next to the predictions."""
     if long_reads is None or long_reads.mode != "tile":
@@ -204,7 +231,8 @@ def _batching_setup(batching, long_reads, gather: bool, on_batch, pad_left: bool
     return batching
 
 
-def _run_predict_bucket(model, staged, writer, device: torch.device, rows: int, batching, *, rank: int, attention_writer) -> int:
+def _run_predict_bucket(model, staged, writer, device: torch.device, rows: int, batching, *, rank: int, attention_writer,
+                        trajectory_writer=None) -> int:
     """The predict loop over `bucket.regroup(staged)`: each emitted batch through `predict_step` (the module's own forward, so the
     16-bit guard hears every batch), its logits on the `_Deferred` road like any batch's."""
     import logging
@@ -216,12 +244,14 @@ def _run_predict_bucket(model, staged, writer, device: torch.device, rows: int, 
     n_reads, batch_idx = 0, 0
     pending: _Deferred | None = None
     want_attention = _attention_setup(model, attention_writer) is not None
+    want_trajectory = _trajectory_setup(model, trajectory_writer) is not None
     regrouper = Regrouper(device, rows, batching)
     try:
         with torch.inference_mode():
             for cur in regroup(staged, regrouper):
                 logits, labels = model.predict_step(cur, batch_idx)
-                now = _Deferred(logits, labels, cur, batch_idx, attention=model.net.last_attention if want_attention else None)
+                now = _Deferred(logits, labels, cur, batch_idx, attention=model.net.last_attention if want_attention else None,
+                                trajectory=model.net.last_trajectory if want_trajectory else None, trajectory_writer=trajectory_writer)
                 if pending is not None:
                     pending.flush(writer, trainer, model, None, attention_writer)
                 pending = now
@@ -238,12 +268,13 @@ def _run_predict_bucket(model, staged, writer, device: torch.device, rows: int, 
 
 
 def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                on_batch=None, attention_writer=None, long_reads=None, batching=None) -> int:
+                on_batch=None, attention_writer=None, long_reads=None, batching=None, trajectory_writer=None) -> int:
     """Returns the number of reads this rank classified.  `gather`: every batch's logits are also all-gathered over the process
     group (RCCL over xGMI when the backend is "nccl"), off the compute stream, and handed to `on_batch(batch_idx, tensor)` one
     batch behind as a `[world * rows, 3]` host tensor (logit0, logit1, valid), rank r's rows at [r * rows, (r + 1) * rows).
     `long_reads`: see the module docstring; the datamodule must deliver untruncated reads (`max_length=long_reads.max_tokens`).
     `batching`: see the module docstring; the reads of this rank's shard are regrouped at the datamodule's per-device batch size."""
+    want_trajectory = _trajectory_setup(model, trajectory_writer, long_reads) is not None
     batching = _batching_setup(batching, long_reads, gather, on_batch,
                                getattr(getattr(datamodule, "tokenizer", None), "padding_side", "left") == "left")
     if batching is not None:
@@ -251,7 +282,8 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
         if not rows:
             raise ValueError("batching 'bucket' needs a datamodule that knows its batch size (batch_size_per_device)")
         return _run_predict_bucket(model, _staged_batches(datamodule.predict_dataloader(), device, lengths=batching), writer, device,
-                                   int(rows), batching, rank=rank, attention_writer=attention_writer)
+                                   int(rows), batching, rank=rank, attention_writer=attention_writer,
+                                   trajectory_writer=trajectory_writer)
     long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
     if long_reads is not None:
         from .longread import tiled_forward
@@ -276,7 +308,8 @@ def run_predict(model, datamodule, writer, device: torch.device, *, rank: int = 
                 logits, labels = tiled.logits, cur["labels"]
             now = _Deferred(logits, labels, cur, batch_idx, gatherer, rows,
                             attention=model.net.last_attention if want_attention else None,   # (left by this batch's forward)
-                            windows=tiled, window_writer=window_writer)
+                            windows=tiled, window_writer=window_writer,
+                            trajectory=model.net.last_trajectory if want_trajectory else None, trajectory_writer=trajectory_writer)
             if pending is not None:
                 pending.flush(writer, trainer, model, on_batch, attention_writer)   # batch i-1: its copy finished while batch i was enqueued
             pending = now
@@ -470,16 +503,17 @@ def _native_staged(feeder, device: torch.device):
 
 
 def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int = 0, gather: bool = False,
-                       on_batch=None, attention_writer=None, long_reads=None, batching=None) -> int:
+                       on_batch=None, attention_writer=None, long_reads=None, batching=None, trajectory_writer=None) -> int:
     """Predict loop over a `chimeralm_amd.feeder.BamFeeder`; same files as `run_predict` over `BamDataModule`.  `long_reads`: see the
     module docstring; the feeder must be opened with `max_tokens=long_reads.max_tokens`.  `batching`: see the module docstring; the
     reads are regrouped at the feeder's batch size."""
     from ._native import DT_U8
 
+    traj_request = _trajectory_setup(model, trajectory_writer, long_reads)
     batching = _batching_setup(batching, long_reads, gather, on_batch, getattr(feeder, "pad_left", True))
     if batching is not None:
         return _run_predict_bucket(model, _native_staged(feeder, device), writer, device, feeder.batch_size, batching, rank=rank,
-                                   attention_writer=attention_writer)
+                                   attention_writer=attention_writer, trajectory_writer=trajectory_writer)
     long_reads, window_writer = _long_read_setup(long_reads, writer, attention_writer)
     if long_reads is not None:
         return _run_predict_native_tiled(model, feeder, writer, window_writer, long_reads, device, rank=rank, gather=gather,
@@ -504,16 +538,19 @@ def run_predict_native(model, feeder, writer, device: torch.device, *, rank: int
             # (a callable: the host copy + H2D of the sampled rows happens only on the few batches a check is due for)
             model.net.guard(eng, lambda c=cur: torch.from_numpy(c.ids[: c.n_reads, : c.n_tokens][
                 model.net._sample_rows(c.n_reads, model.net._BATCH_ROWS)].copy()).to(device), n_tokens=cur.n_tokens, n_reads=cur.n_reads)
-            attention = None
-            if request is None:
+            attention = trajectory = None
+            if request is None and traj_request is None:
                 logits = eng.forward_staged(staged, cur.n_reads)
             else:
-                logits, attention = eng.forward_staged(staged, cur.n_reads, attention=request, length=cur.n_tokens)
+                logits, *extra = eng.forward_staged(staged, cur.n_reads, attention=request, length=cur.n_tokens, trajectory=traj_request)
+                trajectory = extra.pop() if traj_request is not None else None
+                attention = extra[0] if request is not None else None
             eng.stage_wait(staged)                            # the copy has left the slot ...
             feeder.release(cur)                               # ... which goes back to the decoder
             labels = torch.full((cur.n_reads,), -1, dtype=torch.int64)   # tokenizer.py:113: predict labels are all -1
             batch = {"id": torch.from_numpy(cur.names), "labels": labels}
-            now = _Deferred(logits, labels, batch, batch_idx, gatherer, rows, attention=attention)
+            now = _Deferred(logits, labels, batch, batch_idx, gatherer, rows, attention=attention, trajectory=trajectory,
+                            trajectory_writer=trajectory_writer)
             if pending is not None:
                 pending.flush(writer, trainer, model, on_batch, attention_writer)
             pending = now

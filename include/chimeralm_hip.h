@@ -168,6 +168,53 @@ int clm_forward_attn(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_
                      const clm_attn_out* attn, void* stream);
 int clm_forward_staged_attn(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, void* stream);
 
+/* ---- the running verdict: prefix logits along a read from one forward ---------------------------------------------------
+ * No counterpart in the reference.  The backbone is causal and the head (hyena.py:117-146) is a softmax-weighted sum over
+ * positions followed by the classifier, so the logits the model would give if a row ENDED after its first n tokens follow from what
+ * one forward of the whole row leaves behind: its per-tile pooling partials, merged prefix by prefix, then the classifier.
+ *   points      a batch row of L tokens (its pads included) and a stride S (a multiple of 128 in 128 ... 4,096) have
+ *               K = ceil(L / S) points; point k < K - 1 covers tokens [0, (k + 1) S), point K - 1 all L; n_k = tokens point k covers.
+ *   trajectory  logits[b][k][:] = classifier(pool(ln_f(h[b, :n_k]))): the reference head applied to the first n_k rows of the
+ *               final residual stream, the softmax normalised over those n_k positions only -- HyenaDna.forward(ids[b:b+1, :n_k]) up
+ *               to the arithmetic's rounding.  fp32, row b at logits + b * point_stride * 2.  Point K - 1 is the call's own
+ *               logits_out[b], copied bit for bit, not recomputed.
+ *               A truncated row does not end in [SEP]: no point but the last shows the model a complete read.  Points inside the
+ *               [PAD] prefix of a left-padded row describe pads only.  The values are those of the arithmetic the forward ran in
+ *               (precision, fall-back level, short-read switch); a short prefix averages the roundings of fewer tokens than the
+ *               read it comes from, so a 16-bit mode's interior points may be further from fp32 than its logits are.
+ *   summary     per read, computed on the device, with gap_k = (double)logit1 - (double)logit0 of point k:
+ *               n_pad, n_bases, has_sep as clm_attn_summary defines them; n_points = K;
+ *               first_k   the first point with n_k > n_pad, min(n_pad / S, K - 1) (an all-[PAD] row: K - 1);
+ *               label     gap_{K-1} > 0 (a tie is class 0); final_gap = gap_{K-1};
+ *               onset_k   the smallest k >= first_k such that every point in [k, K - 1] has the final label;
+ *               jump_k    the k in (first_k, K - 1] that maximises sgn * (gap_k - gap_{k-1}), sgn = +1 for label 1, -1 for label 0,
+ *                         ties to the lowest k; jump_dgap is that value; first_k = K - 1: jump_k = -1, jump_dgap = 0;
+ *               n_nonfinite   points >= first_k with a NaN or +-inf logit; if any, onset_k = jump_k = -1 and jump_dgap = 0.
+ *               "Bases seen at point k" is clamp(n_k - n_pad, 0, n_bases).
+ * `summary` may be NULL.  CLM_E_INVALID: a stride that is not such a multiple, point_stride < K, logits NULL, a struct_size
+ * mismatch.  CLM_E_UNSUPPORTED: L above 32,832 tokens, a debug stop, the unfused exact path (CLM_DEBUG=unfused_fp32: its partials
+ * have another form).  Device pointers for the B reads of the call, written chunk by chunk at their rows by three kernels behind
+ * the head on `stream` (csrc/trajectory.hip: fixed order, no atomics -- bitwise the same from run to run); the workspace is the
+ * handle's.  Nothing else writes these buffers: not clm_selfcheck, not the forwards the engine runs for itself.  `attn` and `traj`
+ * may each be NULL; with both NULL the two calls ARE clm_forward / clm_forward_staged. */
+typedef struct clm_traj_summary {
+    int32_t n_pad, n_bases, has_sep, n_points;
+    int32_t first_k, label, onset_k, jump_k;
+    int32_t n_nonfinite, reserved;
+    float jump_dgap, final_gap;
+} clm_traj_summary;
+typedef struct clm_traj_out {
+    int32_t struct_size;          /* = sizeof(clm_traj_out), ABI guard */
+    int32_t stride;               /* S: tokens between points */
+    float* logits;                /* fp32 [B][point_stride][2] */
+    int64_t point_stride;         /* points between rows, >= K */
+    clm_traj_summary* summary;    /* [B] or NULL */
+} clm_traj_out;
+int clm_forward_traj(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
+                     const clm_attn_out* attn, const clm_traj_out* traj, void* stream);
+int clm_forward_staged_traj(clm_handle* h, int staged, float* logits_out, const clm_attn_out* attn, const clm_traj_out* traj,
+                            void* stream);
+
 /* Errors a forward can only detect on the device after the call has returned: a token id outside [0, vocab_rows), for
  * which the reference's nn.Embedding raises IndexError inside HyenaDna.forward (hyena.py:249).  The id kernels clamp such an
  * id (no wild read) and flag the handle; the flag is reported ONCE, as CLM_E_INVALID with the message in clm_last_error,
