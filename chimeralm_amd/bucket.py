@@ -182,7 +182,7 @@ class Regrouper:
                  batch_size, 1 << opt.steps_log2)
         self._host: dict[int, tuple[np.ndarray, np.ndarray]] = {}       # Lc -> (id rows [batch_size, W], labels [batch_size])
         self._slab: dict[int, int] = {}                                # Lc -> the slab's offset in the pool
-        self.n_rows = self.n_tokens = 0                                # emitted so far: what the forwards were given
+        self.n_batches = self.n_rows = self.n_tokens = 0               # emitted so far: what the forwards were given
 
     def _class(self, lc: int, first_offset: int, id_rows: np.ndarray, labels: np.ndarray):
         if lc not in self._host:                                       # the class's first read is row 0 of its slab
@@ -195,6 +195,7 @@ class Regrouper:
         lc, rows, stride = int(step["length"]), int(step["count"]), int(step["stride"])
         slab = self.pool[int(step["offset"]): int(step["offset"]) + rows * stride].view(rows, stride)
         ids, labels = self._host[lc]
+        self.n_batches += 1
         self.n_rows += rows
         self.n_tokens += rows * lc
         return {"input_ids": slab[:, :lc], "id": torch.from_numpy(ids[:rows].copy()), "labels": torch.from_numpy(labels[:rows].copy())}

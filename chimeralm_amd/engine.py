@@ -20,6 +20,15 @@ class EngineError(RuntimeError):
         self.code = code
 
 
+def pinned_copy(tensors: dict[str, torch.Tensor], non_blocking: bool = True) -> dict[str, torch.Tensor]:
+    """Copies of `tensors` in page-locked host memory, queued on the current stream: wait for an event behind them before reading.
+    (Host tensors -- the CPU rehearsals of the tests -- are copied to ordinary memory.)"""
+    host = {k: torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda) for k, v in tensors.items()}
+    for k, v in tensors.items():
+        host[k].copy_(v, non_blocking=non_blocking)
+    return host
+
+
 @dataclass(frozen=True)
 class AttentionRequest:
     """What a forward should also leave on the device (`clm_forward_attn`): per read the summary record and the `top_k` (1 ... 32)
@@ -41,22 +50,18 @@ class AttentionOutput:
     0-based positions among a read's bases (token index = position + n_pad; -1 beyond n_peaks), `peak_weight` fp32 [B, top_k],
     `weights` fp32 [B, L] the softmax over all positions, [PAD] and [SEP] included.  Parts not asked for are None."""
     top_k: int | None
-    summary: torch.Tensor | None
-    peak_pos: torch.Tensor | None
-    peak_weight: torch.Tensor | None
-    weights: torch.Tensor | None
+    summary: torch.Tensor | None = None
+    peak_pos: torch.Tensor | None = None
+    peak_weight: torch.Tensor | None = None
+    weights: torch.Tensor | None = None
 
     def tensors(self) -> dict[str, torch.Tensor]:
         return {k: v for k, v in (("summary", self.summary), ("peak_pos", self.peak_pos), ("peak_weight", self.peak_weight),
                                   ("weights", self.weights)) if v is not None}
 
     def to_host(self, non_blocking: bool = True) -> "AttentionOutput":
-        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
-        host = {}
-        for k, v in self.tensors().items():
-            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
-            host[k].copy_(v, non_blocking=non_blocking)
-        return AttentionOutput(self.top_k, host.get("summary"), host.get("peak_pos"), host.get("peak_weight"), host.get("weights"))
+        """`pinned_copy` of the parts that are there."""
+        return AttentionOutput(self.top_k, **pinned_copy(self.tensors(), non_blocking))
 
     def fields(self) -> dict[str, torch.Tensor]:
         """The summary's columns by name (views): n_pad, n_bases, has_sep, n_peaks int32; pad_weight, sep_weight, base_weight fp32."""
@@ -105,18 +110,14 @@ class TrajectoryOutput:
     stride: int
     length: int
     logits: torch.Tensor
-    summary: torch.Tensor | None
+    summary: torch.Tensor | None = None
 
     def tensors(self) -> dict[str, torch.Tensor]:
         return {k: v for k, v in (("logits", self.logits), ("summary", self.summary)) if v is not None}
 
     def to_host(self, non_blocking: bool = True) -> "TrajectoryOutput":
-        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
-        host = {}
-        for k, v in self.tensors().items():
-            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
-            host[k].copy_(v, non_blocking=non_blocking)
-        return TrajectoryOutput(self.stride, self.length, host["logits"], host.get("summary"))
+        """`pinned_copy` of the parts that are there."""
+        return TrajectoryOutput(self.stride, self.length, **pinned_copy(self.tensors(), non_blocking))
 
     def fields(self) -> dict[str, torch.Tensor]:
         """The summary's columns by name (views): ten int32, then jump_dgap and final_gap fp32."""
@@ -209,9 +210,13 @@ class Engine:
         self._check(self._lib.clm_reserve(self._h, int(batch), int(length)))
 
     # ------------------------------------------------------------------ forward
-    def _attn_out(self, req: AttentionRequest, B: int, L: int) -> tuple[AttentionOutput, N.ClmAttnOut]:
-        """Device tensors for a request (torch's allocator, like the logits) and the `clm_attn_out` that points at them."""
-        a = AttentionOutput(None if req.top_k is None else int(req.top_k), None, None, None, None)
+    def _attn_out(self, req: AttentionRequest | None, B: int, L: int):
+        """Device tensors for a request (torch's allocator, like the logits) and a reference to the `clm_attn_out` that points at
+        them, as the C call takes it; (None, None) without a request."""
+        if req is None:
+            return None, None
+        B, L = int(B), int(L)
+        a = AttentionOutput(None if req.top_k is None else int(req.top_k))
         c = N.ClmAttnOut()
         c.struct_size = C.sizeof(N.ClmAttnOut)
         if req.weights:
@@ -222,17 +227,25 @@ class Engine:
             a.peak_pos = torch.empty((B, a.top_k), dtype=torch.int32, device=self.device)
             a.peak_weight = torch.empty((B, a.top_k), dtype=torch.float32, device=self.device)
             c.top_k, c.summary, c.peak_pos, c.peak_weight = a.top_k, a.summary.data_ptr(), a.peak_pos.data_ptr(), a.peak_weight.data_ptr()
-        return a, c
+        return a, C.byref(c)
 
-    def _traj_out(self, req: TrajectoryRequest, B: int, L: int) -> tuple[TrajectoryOutput, N.ClmTrajOut]:
-        """Device tensors for a trajectory request and the `clm_traj_out` that points at them."""
+    def _traj_out(self, req: TrajectoryRequest | None, B: int, L: int):
+        """The same for a trajectory request and its `clm_traj_out`."""
+        if req is None:
+            return None, None
+        B, L = int(B), int(L)
         K = (L + req.stride - 1) // req.stride
         t = TrajectoryOutput(int(req.stride), L, torch.empty((B, K, 2), dtype=torch.float32, device=self.device),
                              torch.empty((B, len(TRAJ_FIELDS)), dtype=torch.int32, device=self.device) if req.summary else None)
         c = N.ClmTrajOut()
         c.struct_size, c.stride, c.logits, c.point_stride = C.sizeof(N.ClmTrajOut), t.stride, t.logits.data_ptr(), K
         c.summary = t.summary.data_ptr() if t.summary is not None else None
-        return t, c
+        return t, C.byref(c)
+
+    @staticmethod
+    def _result(out, att, trj):
+        """`out`, `(out, att)`, `(out, trj)` or `(out, att, trj)`: the logits alone, or a tuple with what was asked for."""
+        return out if att is None and trj is None else tuple(x for x in (out, att, trj) if x is not None)
 
     def forward(self, input_ids: torch.Tensor, out: torch.Tensor | None = None, attention: AttentionRequest | None = None,
                 trajectory: TrajectoryRequest | None = None):
@@ -252,22 +265,11 @@ class Engine:
         B, L = input_ids.shape
         if out is None:
             out = torch.empty((B, self.cfg.n_classes), dtype=torch.float32, device=self.device)
+        (att, c), (trj, ct) = self._attn_out(attention, B, L), self._traj_out(trajectory, B, L)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if attention is None and trajectory is None:
-            self._check(self._lib.clm_forward(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
-                                              input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-            return out
-        if trajectory is None:
-            att, c = self._attn_out(attention, B, L)
-            self._check(self._lib.clm_forward_attn(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
-                                                   input_ids.stride(0), B, L, C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
-            return out, att
-        att, c = self._attn_out(attention, B, L) if attention is not None else (None, None)
-        trj, ct = self._traj_out(trajectory, B, L)
         self._check(self._lib.clm_forward_traj(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
-                                               C.c_void_p(out.data_ptr()), C.byref(c) if c is not None else None, C.byref(ct),
-                                               C.c_void_p(stream)))
-        return (out, trj) if att is None else (out, att, trj)
+                                               C.c_void_p(out.data_ptr()), c, ct, C.c_void_p(stream)))
+        return self._result(out, att, trj)
 
     __call__ = forward
 
@@ -287,20 +289,12 @@ class Engine:
         batch's tokens per read, is needed to size the outputs) the same tuples as `forward`."""
         if out is None:
             out = torch.empty((batch, self.cfg.n_classes), dtype=torch.float32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if attention is None and trajectory is None:
-            self._check(self._lib.clm_forward_staged(self._h, int(staged), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
-            return out
-        if length is None:
+        if length is None and (attention is not None or trajectory is not None):
             raise ValueError("forward_staged with an attention or trajectory request needs the batch's `length`")
-        att, c = self._attn_out(attention, int(batch), int(length)) if attention is not None else (None, None)
-        if trajectory is None:
-            self._check(self._lib.clm_forward_staged_attn(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c), C.c_void_p(stream)))
-            return out, att
-        trj, ct = self._traj_out(trajectory, int(batch), int(length))
-        self._check(self._lib.clm_forward_staged_traj(self._h, int(staged), C.c_void_p(out.data_ptr()), C.byref(c) if c is not None else None,
-                                                      C.byref(ct), C.c_void_p(stream)))
-        return (out, trj) if att is None else (out, att, trj)
+        (att, c), (trj, ct) = self._attn_out(attention, batch, length), self._traj_out(trajectory, batch, length)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.clm_forward_staged_traj(self._h, int(staged), C.c_void_p(out.data_ptr()), c, ct, C.c_void_p(stream)))
+        return self._result(out, att, trj)
 
     def check(self):
         """Wait for the current stream and raise for errors only the device can see (token ids outside the embedding table:

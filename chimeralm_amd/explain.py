@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .engine import pinned_copy
 from .tokenizer import load_tokenizer_from_hyena_model
 
 SUBSTITUTES = {"N": N.EXPLAIN_SUB_N, "all": N.EXPLAIN_SUB_ALL}
@@ -116,12 +117,8 @@ class Importance:
         return {k: getattr(self, k) for k in ("logits", "dp1", "dgap", "importance", "peak_pos", "peak_val", "n_nonfinite")}
 
     def to_host(self, non_blocking: bool = True) -> "Importance":
-        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
-        host = {}
-        for k, v in self.tensors().items():
-            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
-            host[k].copy_(v, non_blocking=non_blocking)
-        return Importance(self.options, self.n_bases, **host)
+        """`engine.pinned_copy` of the tensors."""
+        return Importance(self.options, self.n_bases, **pinned_copy(self.tensors(), non_blocking))
 
 
 class Explainer:

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .engine import pinned_copy
 from .tokenizer import load_tokenizer_from_hyena_model
 
 MODES = ("truncate", "tile")
@@ -158,12 +159,8 @@ class TiledLogits:
         return {k: getattr(self, k) for k in ("logits", "window_logits", "chosen", "gap", "nonfinite") if getattr(self, k) is not None}
 
     def to_host(self, non_blocking: bool = True) -> "TiledLogits":
-        """Copies to page-locked host memory, queued on the current stream: wait for an event behind them before reading."""
-        host = {}
-        for k, v in self.tensors().items():
-            host[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)
-            host[k].copy_(v, non_blocking=non_blocking)
-        return TiledLogits(self.plan, **host)
+        """`engine.pinned_copy` of the tensors."""
+        return TiledLogits(self.plan, **pinned_copy(self.tensors(), non_blocking))
 
 
 class LongReads:

@@ -64,11 +64,9 @@ def _gather_worker(rank: int, world: int, port: int, tmp: str):
     same gathered rounds, padding rows are marked invalid."""
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
-    from types import SimpleNamespace
-
     from chimeralm_amd import distributed as cd
     from chimeralm_amd.callbacks import PredictionWriter
-    from chimeralm_amd.predict import _Deferred, _drain_gather
+    from chimeralm_amd.predict import _deferred_loop
     from chimeralm_amd.tokenizer import pack_read_name
 
     cd.init_process_group("gloo")
@@ -77,17 +75,12 @@ def _gather_worker(rank: int, world: int, port: int, tmp: str):
     my_batches = [3, 3, 2] if rank == 0 else [3]                            # rank 1 runs out two rounds earlier; one short batch
     seen = []
     writer = PredictionWriter(Path(tmp), "batch")
-    trainer = SimpleNamespace(global_rank=rank)
-    pending, batch_idx = None, 0
-    for n in my_batches:
-        logits = torch.full((n, 2), float(10 * rank + batch_idx))
-        ids = torch.tensor([pack_read_name(f"r{rank}b{batch_idx}i{i}") for i in range(n)], dtype=torch.int64).to(torch.int8)
-        now = _Deferred(logits, torch.full((n,), -1), {"id": ids}, batch_idx, gatherer, rows)
-        if pending is not None:
-            pending.flush(writer, trainer, None, lambda b, g: seen.append((b, g.clone())))
-        pending = now
-        batch_idx += 1
-    _drain_gather(pending, gatherer, rows, device, batch_idx, writer, trainer, None, lambda b, g: seen.append((b, g.clone())))
+    source = [{"id": torch.tensor([pack_read_name(f"r{rank}b{b}i{i}") for i in range(n)], dtype=torch.int64).to(torch.int8),
+               "logits": torch.full((n, 2), float(10 * rank + b))} for b, n in enumerate(my_batches)]
+    # the real loop on host tensors: a list for its source, a step that hands over the batch's CPU logits
+    n_reads = _deferred_loop(source, lambda batch, idx: (batch["logits"], torch.full((batch["logits"].shape[0],), -1), ()), writer, None,
+                             device, rank=rank, gatherer=gatherer, rows=rows, on_batch=lambda b, g: seen.append((b, g.clone())))
+    assert n_reads == sum(my_batches)
     assert [b for b, _ in seen] == [0, 1, 2], seen                          # three rounds had reads somewhere, on BOTH ranks
     g0, g1, g2 = (g for _, g in seen)
     assert g0.shape == (world * rows, 3)
