@@ -95,7 +95,13 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             }
         }
     }
-    // ---- 1. r = h + b_out + W_out y: the accumulators start from the residual rows
+    // ---- 1. r = h + b_out + W_out y.  The products are summed from zero and the residual row joins the finished sum: with the
+    //         residual in the accumulator from the start (rounds 4-5) every one of the 128 + 512 MFMA steps of out_proj and fc2
+    //         rounded at the RESIDUAL's magnitude, not the sum's -- ~2.5e-6 of a row's largest value per token and block tail
+    //         whatever the read length, ten times the reference's own fp32 error at the first tokens of a read
+    //         (tests/test_gpu_per_token.py: 1 and 2 tokens).  `res` holds the residual next to the accumulators: 32 registers more,
+    //         of the 256 a wave has at the two waves per SIMD that the LDS tiles allow anyway
+    f32x16 res[2];
     {
         const float* bo = m.b_out + wave * 32 + 4 * lhalf;
 #pragma unroll
@@ -107,30 +113,31 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             for (int q = 0; q < 4; ++q) {
                 const float4 hv = *reinterpret_cast<const float4*>(row + 8 * q);
                 const float4 bb = *reinterpret_cast<const float4*>(bo + 8 * q);
-                acc2[mt][4 * q + 0] = (hv.x + bb.x) * WS;
-                acc2[mt][4 * q + 1] = (hv.y + bb.y) * WS;
-                acc2[mt][4 * q + 2] = (hv.z + bb.z) * WS;
-                acc2[mt][4 * q + 3] = (hv.w + bb.w) * WS;
+                res[mt][4 * q + 0] = hv.x + bb.x;
+                res[mt][4 * q + 1] = hv.y + bb.y;
+                res[mt][4 * q + 2] = hv.z + bb.z;
+                res[mt][4 * q + 3] = hv.w + bb.w;
             }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[mt][r] = 0.f;
         }
     }
     __syncthreads();
     product256<true, AR>(Ys, m.w_out, 0, D / 8, 0, wset_ptr(m.w_fc1, 0, D / 8, 0, wave, lane), wave, lane, ws, acc2);
-    if constexpr (AR == AR_X3) {
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc2[mt][r] *= WSI;
-    }
-    // ---- 2. LayerNorm-2 -> As
+        for (int r = 0; r < 16; ++r) acc2[mt][r] = acc2[mt][r] * WSI + res[mt][r];
+    // ---- 2. LayerNorm-2 -> As; r moves to `res`, the accumulators take fc2's sum from zero
     ln_to_tile<false, AR>(acc2, P1, P2, m.ln2_g, m.ln2_b, m.eps, As, valid, wave, lrow, lhalf);
-    if constexpr (AR == AR_X3) {                             // (the fc2 products land on r in the weights' scale)
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc2[mt][r] *= WS;
-    }
-    // ---- 3. MLP in four 256-wide chunks of the hidden layer (acc2 holds r)
+        for (int r = 0; r < 16; ++r) {
+            res[mt][r] = acc2[mt][r];
+            acc2[mt][r] = 0.f;
+        }
+    // ---- 3. MLP in four 256-wide chunks of the hidden layer (acc2: fc2's sum)
 #pragma unroll 1
     for (int j = 0; j < DI / 256; ++j) {
 #pragma unroll
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
         product256<false, AR>(Hs, m.w_fc2, 0, DI / 8, j * 32, nxt, wave, lane, ws, acc2);
         __syncthreads();                                    // every wave is done reading Hs before the next chunk lands in it
     }
-    // ---- 4. h' = acc2 + b_2: 16 bytes per lane and feature quad (a lane = a token row of h)
+    // ---- 4. h' = r + acc2 + b_2: 16 bytes per lane and feature quad (a lane = a token row of h)
     {
         const float* b2p = m.b_fc2 + wave * 32 + 4 * lhalf;
 #pragma unroll
@@ -165,10 +172,10 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             const float4 bb = *reinterpret_cast<const float4*>(b2p + 8 * q);
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                acc2[mt][4 * q + 0] = acc2[mt][4 * q + 0] * WSI + bb.x;
-                acc2[mt][4 * q + 1] = acc2[mt][4 * q + 1] * WSI + bb.y;
-                acc2[mt][4 * q + 2] = acc2[mt][4 * q + 2] * WSI + bb.z;
-                acc2[mt][4 * q + 3] = acc2[mt][4 * q + 3] * WSI + bb.w;
+                acc2[mt][4 * q + 0] = (acc2[mt][4 * q + 0] * WSI + bb.x) + res[mt][4 * q + 0];
+                acc2[mt][4 * q + 1] = (acc2[mt][4 * q + 1] * WSI + bb.y) + res[mt][4 * q + 1];
+                acc2[mt][4 * q + 2] = (acc2[mt][4 * q + 2] * WSI + bb.z) + res[mt][4 * q + 2];
+                acc2[mt][4 * q + 3] = (acc2[mt][4 * q + 3] * WSI + bb.w) + res[mt][4 * q + 3];
                 if (mt * 32 + lrow < valid)
                     *reinterpret_cast<float4*>(m.h + ((size_t)b * L + t0 + mt * 32 + lrow) * D + wave * 32 + 4 * lhalf + 8 * q) =
                         make_float4(acc2[mt][4 * q + 0], acc2[mt][4 * q + 1], acc2[mt][4 * q + 2], acc2[mt][4 * q + 3]);

@@ -20,7 +20,8 @@ DT = torch.float64
 
 
 def rnd(x, mode):
-    """mode: None exact | 'h' fp16 | 'b' bf16 | 'hh' fp16 hi + fp16 lo | 'h8' fp16 + e4m3-grade lo (4 significant bits)"""
+    """mode: None exact | 'h' fp16 | 'b' bf16 | 'hh' fp16 hi + fp16 lo | 'h8' fp16 + e4m3-grade lo (4 significant bits)
+    | 'h5' fp16 + e5m2-grade lo (3 significant bits: the lo bytes of fp16c's activations, gemm_common.h lo8_pack4)"""
     if mode is None:
         return x
     if mode == "h":
@@ -35,40 +36,64 @@ def rnd(x, mode):
         lo = x - hi
         m, e = torch.frexp(lo)
         return hi + torch.ldexp(torch.round(m * 16) / 16, e)
+    if mode == "h5":
+        hi = x.to(torch.float16).to(DT)
+        m, e = torch.frexp(x - hi)
+        return hi + torch.ldexp(torch.round(m * 8) / 8, e)
     raise ValueError(mode)
 
 
-def lin(x, sd, key, am, wm):
+def lin(x, sd, key, am, wm, peel=False):
+    """peel: the last token's row takes the product of the unrounded operands (the fp32 matrix-vector chain of lone_token.hip)"""
     if isinstance(wm, dict):
         wm = next((v for k, v in wm.items() if k in key), None)
     b = sd.get(key + ".bias")
-    return F.linear(rnd(x, am), rnd(sd[key + ".weight"].to(DT), wm), None if b is None else b.to(DT))
+    b = None if b is None else b.to(DT)
+    out = F.linear(rnd(x, am), rnd(sd[key + ".weight"].to(DT), wm), b)
+    if peel:
+        out[:, -1] = F.linear(x[:, -1], sd[key + ".weight"].to(DT), b)
+    return out
 
 
-def forward(ids, sd, cfg):
+def forward(ids, sd, cfg, trace=None):
     """cfg keys: a_ln1, a_y, a_ln2, a_gelu, a_lnf (activation operand modes), w (weights), z, y (storage), pool (pooled
-    vector taken from the rounded ln_f tile)"""
+    vector taken from the rounded ln_f tile); zg: z is stored behind the short filter and the gate (x0f and g = x1f * vf, the gated
+    hand-over of gemm16.hip inproj_blocks_gated) instead of in front of them; peel: reads of 128 k + 1 > 128 tokens run their last
+    token through unrounded products (clm_api.hip plan_chunk, p.peel) -- its y and z are still stored rounded.
+    trace: a dict that receives every block's residual rows `l{i}.out` [B, L, 256] (l3.out: the rows in front of ln_f) and the
+    pooling `scores` [B, L]"""
     g = cfg.get
     ids = torch.as_tensor(ids, dtype=torch.int64)
     h = F.embedding(ids, sd[ho.BB + "embeddings.word_embeddings.weight"].to(DT))
     L = h.shape[1]
+    pl = bool(g("peel")) and L > 128 and L % 128 == 1
     for i in range(ho.N_LAYER):
         p = f"{ho.BB}layers.{i}."
         u = ho._ln(h, sd, p + "norm1", DT)
         if i == 0 and g("block0_exact", True):       # the engine looks block 0's in_proj up in an fp32 table by token id
             z = lin(u, sd, p + "mixer.in_proj", None, None).transpose(1, 2)
+            zmode = None
         else:
-            z = rnd(lin(u, sd, p + "mixer.in_proj", g("a_ln1"), g("w")).transpose(1, 2), g("z"))
-        uc = ho.short_filter(z, sd, i, DT)
-        x0, x1, v = uc.split(ho.D_MODEL, dim=1)
+            z = lin(u, sd, p + "mixer.in_proj", g("a_ln1"), g("w"), pl).transpose(1, 2)
+            zmode = g("z")
+        if g("zg"):
+            x0, x1, v = ho.short_filter(z, sd, i, DT).split(ho.D_MODEL, dim=1)
+            x0, gate = rnd(x0, zmode), rnd(v * x1, zmode)
+        else:
+            x0, x1, v = ho.short_filter(rnd(z, zmode), sd, i, DT).split(ho.D_MODEL, dim=1)
+            gate = v * x1
         k = ho.hyena_filter(sd, i, L, DT).transpose(0, 1)
-        v = ho.fftconv(v * x1, k, sd[p + "mixer.filter_fn.bias"].to(DT))
+        v = ho.fftconv(gate, k, sd[p + "mixer.filter_fn.bias"].to(DT))
         y = rnd(v * x0, g("y"))
-        r = lin(y.transpose(1, 2), sd, p + "mixer.out_proj", g("a_y"), g("w")) + h
-        m = lin(ho._ln(r, sd, p + "norm2", DT), sd, p + "mlp.fc1", g("a_ln2"), g("w"))
-        h = lin(F.gelu(m, approximate="tanh"), sd, p + "mlp.fc2", g("a_gelu"), g("w")) + r
+        r = lin(rnd(y.transpose(1, 2), g("a_y")), sd, p + "mixer.out_proj", None, g("w"), pl) + h
+        m = lin(ho._ln(r, sd, p + "norm2", DT), sd, p + "mlp.fc1", g("a_ln2"), g("w"), pl)
+        h = lin(F.gelu(m, approximate="tanh"), sd, p + "mlp.fc2", g("a_gelu"), g("w"), pl) + r
+        if trace is not None:
+            trace[f"l{i}.out"] = h
     hid = ho._ln(h, sd, ho.BB + "ln_f", DT)
-    s = ho._lin(F.gelu(lin(hid, sd, ho.HD + "attention.0", g("a_lnf"), g("w"))), sd, ho.HD + "attention.2", DT)
+    s = ho._lin(F.gelu(lin(hid, sd, ho.HD + "attention.0", g("a_lnf"), g("w"), pl)), sd, ho.HD + "attention.2", DT)
+    if trace is not None:
+        trace["scores"] = s[..., 0]
     a = torch.softmax(s, dim=1)
     pooled = (rnd(hid, g("pool")) * a).sum(dim=1)
     x = F.gelu(ho._lin(pooled, sd, ho.HD + "classifier.0", DT))
@@ -79,6 +104,20 @@ def forward(ids, sd, cfg):
 
 ACT = ("a_ln1", "a_y", "a_ln2", "a_gelu", "a_lnf")
 ALL16 = {**{k: "h" for k in ACT}, "w": "h", "z": "h", "y": "h", "pool": "h"}
+
+# The engine's 16-bit modes as they run without a debug switch (clm_api.hip plan_chunk: fused tails, id-table block 0, the gated
+# hand-over, the peeled last token).  fp16 / bf16: every GEMM operand, the packed weights and the stored z / y in the mode's type.
+# fp16c (gemm_common.h, gemm16_common.h): in_proj / out_proj / attention.0 on fp16 hi + e4m3 lo weights; fc1 / fc2 on plain fp16
+# weights (first level; clm_set_mlp_compensation is not modelled); the LayerNorm-1 and ln_f tiles, y and the gated rows of z as
+# fp16 hi + one e5m2 lo byte; LayerNorm-2 and GELU tiles plain fp16.  Not modelled: the byte truncation of the hi operand inside the
+# two lo products (5 % of a 2^-11 term), the fp32 arithmetic of the kernels themselves (two orders below a 16-bit rounding).
+_W16C = {"in_proj": "h8", "out_proj": "h8", "attention": "h8", "fc1": "h", "fc2": "h"}
+ENGINE_MODES = {
+    "fp16": {**ALL16, "zg": True, "peel": True},
+    "bf16": {**{k: "b" for k in ACT}, "w": "b", "z": "b", "y": "b", "pool": "b", "zg": True, "peel": True},
+    "fp16c": {"a_ln1": "h5", "a_y": "h5", "a_lnf": "h5", "a_ln2": "h", "a_gelu": "h", "w": _W16C, "z": "h5", "y": "h5", "pool": None,
+              "zg": True, "peel": True},
+}
 
 
 def main():
