@@ -152,6 +152,8 @@ SYMBOLS = {
     "clm_mamba_finalize": (C.c_int, [_H]),
     "clm_mamba_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p]),
+    "clm_mamba_forward_traj": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.POINTER(ClmTrajOut), C.c_void_p]),
     "clm_mamba_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_mamba_last_error": (C.c_char_p, [_H]),
     "clm_mamba_destroy": (C.c_int, [_H]),

@@ -646,4 +646,14 @@ void launch_traj_classifier(const float* pooled, int K, int n_rows, const HeadW&
 void launch_traj_summary(const float* logits, float* traj, int64_t pstride, int B, int K, int S, int L, const int* npad,
                          const unsigned char* ids8, int Lp, clm_traj_summary* summary, hipStream_t st);
 
+// the running verdict of the Mamba nets (mamba_verdict.hip): the same from mamba.hip's partials, part [reads][tiles][2][d] (channel sums |
+// maxima per 64-token tile; `per` tiles per point, K = ceil(L / (64 per)) points) -> pooled [reads][K][d] and npad [reads]; then pooler
+// and classifier (weights as mamba_head_kernel takes them) over the n_rows = reads * (K - 1) interior rows, SSM_VERDICT_ROWS rows per
+// workgroup, into traj [reads][pstride][2].  The last point and the summary are launch_traj_summary's.
+constexpr int SSM_VERDICT_ROWS = 8;
+void launch_ssm_verdict_pool(const float* part, int tiles, int per, int K, int L, int d, float* pooled, const unsigned char* ids8, int Lp,
+                             int* npad, int reads, hipStream_t st);
+void launch_ssm_verdict_head(const float* pooled, int K, int n_rows, int d, const float* wpt, const float* bp, const float* w0t,
+                             const float* b0, const float* w3, const float* b3, float* traj, int64_t pstride, hipStream_t st);
+
 }  // namespace clm

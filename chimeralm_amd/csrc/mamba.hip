@@ -534,6 +534,7 @@ struct clm_mamba_handle {
     DevBuf front, poolert, cls0t;                 // finalize products: input_block.0 packed; pooler.0 / classifier.0 weights transposed
     bool finalized = false;
     DevBuf ids8, h, zx, xc, g, ssq, part, pooled, dbg_front, dbg_layer0;   // workspace (clm_mamba_forward)
+    DevBuf verdict_pooled, verdict_npad;          // the running verdict (mamba_verdict.hip): fp32 [chunk reads][K][d], int [chunk reads]; grown by the first request
     int last_B = 0, last_L = 0;
     bool last_dbg = false;
 };
@@ -585,6 +586,20 @@ int mamba_pack(clm_mamba_handle* h, DevBuf& dst, const std::vector<float>& W, in
     else launch_pack_f32t(src.get<float>(), q.get(), rows_pad, K, 0);
     HIPCHK(h, hipDeviceSynchronize());                 // (`src` is freed on return)
     dst = std::move(q);
+    return CLM_OK;
+}
+
+// The trajectory request of clm_mamba_forward_traj for reads of L tokens (null: none, nothing to check)
+int check_verdict_arg(clm_mamba_handle* h, const clm_traj_out* t, int L) {
+    if (!t) return CLM_OK;
+    const std::string w = "clm_mamba_forward_traj";
+    if (t->struct_size != (int32_t)sizeof(clm_traj_out)) return fail(h, CLM_E_INVALID, w + ": clm_traj_out size mismatch");
+    if (t->stride < 128 || t->stride > 4096 || t->stride % 128)
+        return fail(h, CLM_E_INVALID, w + ": the trajectory's stride must be a multiple of 128 in 128 ... 4096");
+    if (!t->logits) return fail(h, CLM_E_INVALID, w + ": the trajectory request has no logits buffer");
+    const int K = (L + t->stride - 1) / t->stride;
+    if (t->point_stride < K)
+        return fail(h, CLM_E_INVALID, w + ": point_stride is shorter than the " + std::to_string(K) + " points of a read");
     return CLM_OK;
 }
 
@@ -687,6 +702,11 @@ int clm_mamba_finalize(clm_mamba_handle* h) {
 
 int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, const float* mask,
                       int64_t mask_row_stride, float* logits_out, void* stream) {
+    return clm_mamba_forward_traj(h, ids, ids_dtype, ids_row_stride, B, L, mask, mask_row_stride, logits_out, nullptr, stream);
+}
+
+int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, const float* mask,
+                           int64_t mask_row_stride, float* logits_out, const clm_traj_out* traj, void* stream) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_mamba_forward before clm_mamba_finalize");
     if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return fail(h, CLM_E_INVALID, "clm_mamba_forward: bad argument");
@@ -696,6 +716,7 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
         return fail(h, CLM_E_INVALID, "clm_mamba_forward: read length " + std::to_string(L) + " exceeds model_max_length " +
                                           std::to_string(h->max_len) + " (the positional embedding's length)");
     if (mask && mask_row_stride < L) return fail(h, CLM_E_INVALID, "clm_mamba_forward: mask row stride shorter than the read");
+    if (int rc = check_verdict_arg(h, traj, L)) return rc;
     if (h->variant == CLM_MAMBA_SP) mask = nullptr;              // (the reference's mambasp ignores its second argument)
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -713,6 +734,12 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
             HIPCHK(h, hipDeviceSynchronize());
             HIPCHK(h, buf[i]->reserve(need[i]));
         }
+    const int vK = traj ? (L + traj->stride - 1) / traj->stride : 0;          // points per read of the request
+    if (traj && ((size_t)nb * vK * d * 4 > h->verdict_pooled.bytes() || (size_t)nb * 4 > h->verdict_npad.bytes())) {
+        HIPCHK(h, hipDeviceSynchronize());
+        HIPCHK(h, h->verdict_pooled.reserve((size_t)nb * vK * d * 4));
+        HIPCHK(h, h->verdict_npad.reserve((size_t)nb * 4));
+    }
     const MambaNetF32& net = h->net;
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
     float *const hs = h->h.get<float>(), *const zx = h->zx.get<float>(), *const g = h->g.get<float>(), *const ssq = h->ssq.get<float>();
@@ -765,6 +792,19 @@ int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64
         hipLaunchKernelGGL(mamba::mamba_head_kernel, dim3((unsigned)n), dim3(512), 0, st, h->part.get<float>(), tiles_x, L, d,
                            h->poolert.get<float>(), net.pool_b, h->cls0t.get<float>(), net.cls0_b, net.cls3_w, net.cls3_b,
                            h->pooled.get<float>() + (size_t)r0 * d, logits_out + (size_t)r0 * NCLS);
+        if (traj) {
+            // the chunk's running verdict at the rows of its reads in the caller's buffers: the prefix pooling of the partials the
+            // forward left, pooler and classifier over the interior points, then the chunk's own logits into the last point and the
+            // summary (mamba_verdict.hip, trajectory.hip)
+            float* const out = traj->logits + (size_t)r0 * traj->point_stride * NCLS;
+            int* const npad = h->verdict_npad.get<int>();
+            launch_ssm_verdict_pool(h->part.get<float>(), tiles_x, traj->stride / 64, vK, L, d, h->verdict_pooled.get<float>(), id8, Lp,
+                                    npad, n, st);
+            launch_ssm_verdict_head(h->verdict_pooled.get<float>(), vK, n * (vK - 1), d, h->poolert.get<float>(), net.pool_b,
+                                    h->cls0t.get<float>(), net.cls0_b, net.cls3_w, net.cls3_b, out, traj->point_stride, st);
+            launch_traj_summary(logits_out + (size_t)r0 * NCLS, out, traj->point_stride, n, vK, traj->stride, L, npad, id8, Lp,
+                                traj->summary ? traj->summary + r0 : nullptr, st);
+        }
     }
     h->last_B = B, h->last_L = L, h->last_dbg = dbg;
     const hipError_t e = hipGetLastError();

@@ -132,6 +132,21 @@ class TrajectoryOutput:
         return bases_seen(self.logits.shape[1], self.stride, self.length, f["n_pad"].numpy(), f["n_bases"].numpy())
 
 
+def trajectory_out(req: TrajectoryRequest | None, B: int, L: int, device: torch.device):
+    """Device tensors for a trajectory request (torch's allocator, like the logits) and a reference to the `clm_traj_out` that points
+    at them, as the C calls take it (`clm_forward_traj`, `clm_mamba_forward_traj`); (None, None) without a request."""
+    if req is None:
+        return None, None
+    B, L = int(B), int(L)
+    K = (L + req.stride - 1) // req.stride
+    t = TrajectoryOutput(int(req.stride), L, torch.empty((B, K, 2), dtype=torch.float32, device=device),
+                         torch.empty((B, len(TRAJ_FIELDS)), dtype=torch.int32, device=device) if req.summary else None)
+    c = N.ClmTrajOut()
+    c.struct_size, c.stride, c.logits, c.point_stride = C.sizeof(N.ClmTrajOut), t.stride, t.logits.data_ptr(), K
+    c.summary = t.summary.data_ptr() if t.summary is not None else None
+    return t, C.byref(c)
+
+
 class _DevicePtr:
     """fp32 device memory somebody else owns, as torch sees it through `__cuda_array_interface__`."""
 
@@ -231,16 +246,7 @@ class Engine:
 
     def _traj_out(self, req: TrajectoryRequest | None, B: int, L: int):
         """The same for a trajectory request and its `clm_traj_out`."""
-        if req is None:
-            return None, None
-        B, L = int(B), int(L)
-        K = (L + req.stride - 1) // req.stride
-        t = TrajectoryOutput(int(req.stride), L, torch.empty((B, K, 2), dtype=torch.float32, device=self.device),
-                             torch.empty((B, len(TRAJ_FIELDS)), dtype=torch.int32, device=self.device) if req.summary else None)
-        c = N.ClmTrajOut()
-        c.struct_size, c.stride, c.logits, c.point_stride = C.sizeof(N.ClmTrajOut), t.stride, t.logits.data_ptr(), K
-        c.summary = t.summary.data_ptr() if t.summary is not None else None
-        return t, C.byref(c)
+        return trajectory_out(req, B, L, self.device)
 
     @staticmethod
     def _result(out, att, trj):

@@ -16,6 +16,11 @@ fp16 MFMAs on hi + lo halfs per product) or "fp32" (the exact-fp32 MFMA).  The s
 packs weights x 2^10 as fp16 halfs, which saturates for |w| >= 64 (out_proj counted with norm.weight folded in): such weights run
 the exact-fp32 kernels, with a warning and a `precision_report` entry.  An activation beyond fp16's range makes the fp16x3 kernels
 return NaN for it; a batch whose fp16x3 logits are not all finite is rerun on the exact-fp32 kernels, logged and recorded.
+
+The running verdict, as for `HyenaDna` (csrc/mamba_verdict.hip): both nets are causal, so with the keyword `trajectory_stride` set
+every forward also leaves `last_trajectory`, an `engine.TrajectoryOutput` of DEVICE tensors -- the logits the model would give if a
+row ended at each multiple of the stride, and the per-read summary -- from the same call (`clm_mamba_forward_traj`).  After a
+non-finite fp16x3 rerun it is the trajectory of the exact-fp32 handle, whose logits were returned.
 """
 from __future__ import annotations
 
@@ -29,6 +34,7 @@ from torch import nn
 
 from . import _native as N
 from ._reload import reload_signature
+from .engine import TrajectoryRequest, check_trajectory_stride, trajectory_out
 
 X3_WEIGHT_LIMIT = 64.0                     # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates
 HEADDIM, D_CONV, VOCAB, PAD = 64, 4, 12, 4
@@ -79,7 +85,7 @@ def _check_shape(vocab_size, d_model, d_state, d_conv, expand, headdim, number_o
 class _MambaNet(nn.Module):
     _variant = None
 
-    def _setup(self, d_model, n_layers, d_state, expand, headdim, max_len, precision):
+    def _setup(self, d_model, n_layers, d_state, expand, headdim, max_len, precision, trajectory_stride=None):
         if precision not in ("fp32", "fp16x3"):
             raise ValueError("precision must be fp32 (exact fp32 products) or fp16x3 (every projection operand as two halfs, three "
                              "fp16 MFMAs per product: fp32-class logits)")
@@ -87,6 +93,13 @@ class _MambaNet(nn.Module):
         self.precision_report: dict = {}
         self._shape = (d_model, n_layers, d_state, expand, headdim, max_len)
         self._h, self._h32, self._last_h, self._dev, self._sig, self._hprec = None, None, None, None, None, None
+        # the running verdict (an engine knob, csrc/mamba_verdict.hip): see the module docstring
+        self.trajectory_stride = None if trajectory_stride is None else check_trajectory_stride(trajectory_stride)
+        self.last_trajectory = None
+
+    def trajectory_request(self):
+        """The `engine.TrajectoryRequest` this module's forwards make (None: `trajectory_stride` is not set)."""
+        return None if self.trajectory_stride is None else TrajectoryRequest(stride=self.trajectory_stride, summary=True)
 
     def _layer(self, i) -> Mamba2:
         raise NotImplementedError
@@ -148,12 +161,16 @@ class _MambaNet(nn.Module):
         """The next forward rebuilds the handles from this module's tensors: for edits the signature cannot see (`p.data.mul_()`)."""
         self._sig = None
 
-    def _run(self, lib, h, ids, dt, mask, out):
+    def _run(self, lib, h, ids, dt, mask, out, req=None):
+        """One forward of handle `h` into `out`; with a trajectory request also its `engine.TrajectoryOutput` (else None)."""
         B, L = ids.shape
         mptr = C.c_void_p(mask.data_ptr()) if mask is not None else None
         mstride = mask.stride(0) if mask is not None else 0
-        self._check(h, lib.clm_mamba_forward(h, C.c_void_p(ids.data_ptr()), dt, ids.stride(0), B, L, mptr, mstride,
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream)))
+        trj, ct = trajectory_out(req, B, L, ids.device)
+        self._check(h, lib.clm_mamba_forward_traj(h, C.c_void_p(ids.data_ptr()), dt, ids.stride(0), B, L, mptr, mstride,
+                                                  C.c_void_p(out.data_ptr()), ct,
+                                                  C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream)))
+        return trj
 
     def _forward(self, input_ids: torch.Tensor, mask: torch.Tensor | None) -> torch.Tensor:
         if input_ids.device.type != "cuda":
@@ -177,13 +194,14 @@ class _MambaNet(nn.Module):
         lib = self._prepare(input_ids.device)
         dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[input_ids.dtype]
         out = torch.empty((B, self.number_of_classes), dtype=torch.float32, device=input_ids.device)
-        self._run(lib, self._h, input_ids, dt, mask, out)
+        req = self.trajectory_request()
+        self.last_trajectory = self._run(lib, self._h, input_ids, dt, mask, out, req)
         self._last_h = self._h
         if self._hprec == "fp16x3" and not bool(torch.isfinite(out).all()):
             # an activation outside fp16x3's range (the kernels return NaN for it): this batch again on the exact-fp32 kernels
             if self._h32 is None:
                 self._h32 = self._new_handle(lib, input_ids.device, "fp32")
-            self._run(lib, self._h32, input_ids, dt, mask, out)
+            self.last_trajectory = self._run(lib, self._h32, input_ids, dt, mask, out, req)
             self._last_h = self._h32
             self.precision_report["nonfinite_reruns"] = self.precision_report.get("nonfinite_reruns", 0) + 1
             _LOG.warning(f"chimeralm_amd: {type(self).__name__} fp16x3 returned non-finite logits (an activation beyond fp16's "
@@ -220,10 +238,10 @@ class MambaSequenceClassification(_MambaNet):
 
     def __init__(self, vocab_size, embedding_dim: int, number_of_layers: int, model_max_length: int, dropout: float,
                  number_of_classes: int, d_state: int = 128, d_conv: int = 4, expand: int = 2, headdim: int = 64,
-                 padding_idx: int = 4, *, precision: str = "fp16x3"):
+                 padding_idx: int = 4, *, precision: str = "fp16x3", trajectory_stride: int | None = None):
         super().__init__()
         _check_shape(vocab_size, embedding_dim, d_state, d_conv, expand, headdim, number_of_classes, padding_idx)
-        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, model_max_length, precision)
+        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, model_max_length, precision, trajectory_stride)
         self.number_of_classes = number_of_classes
         self.embedding = nn.Embedding(vocab_size, embedding_dim, padding_idx=padding_idx)
         self.pos_embedding = nn.Parameter(torch.zeros(1, model_max_length, embedding_dim))
@@ -249,10 +267,10 @@ class MambaSequenceClassificationSP(_MambaNet):
 
     def __init__(self, vocab_size, embedding_dim: int, number_of_layers: int, number_of_classes: int, dropout: float,
                  d_state: int = 128, d_conv: int = 4, expand: int = 2, headdim: int = 64, padding_idx: int = 4, *,
-                 precision: str = "fp16x3"):
+                 precision: str = "fp16x3", trajectory_stride: int | None = None):
         super().__init__()
         _check_shape(vocab_size, embedding_dim, d_state, d_conv, expand, headdim, number_of_classes, padding_idx)
-        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, None, precision)
+        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, None, precision, trajectory_stride)
         self.number_of_classes = number_of_classes
         self.embedding = nn.Embedding(vocab_size, embedding_dim, padding_idx=padding_idx)
         self.mamba_layers = nn.ModuleList([Mamba2(embedding_dim, d_state, d_conv, expand, headdim) for _ in range(number_of_layers)])

@@ -229,16 +229,17 @@ def _trajectory_setup(model, trajectory_writer, long_reads=None):
     if trajectory_writer is None:
         return None
     from .hyena import HyenaDna
+    from .mamba import MambaSequenceClassification, MambaSequenceClassificationSP
 
     net = model.net
-    if not isinstance(net, HyenaDna):
+    if not isinstance(net, (HyenaDna, MambaSequenceClassification, MambaSequenceClassificationSP)):
         raise ValueError(f"a trajectory needs a causal net: a prefix of a read must not know what follows it.  {type(net).__name__} is "
-                         "not the Hyena net (the transformer attends in both directions, the CNN's windows straddle every cut; the "
-                         "Mamba nets are causal and could follow, they are not built)")
+                         "neither the Hyena net nor one of the two Mamba nets (the transformer attends in both directions, the CNN's "
+                         "windows and pools straddle every cut)")
     if long_reads is not None and getattr(long_reads, "mode", None) == "tile":
         raise ValueError("a read reduced from several windows has no single row to follow: no trajectory writer with long_reads")
     if net.trajectory_stride is None:
-        raise ValueError("a trajectory writer needs a net built with trajectory_stride (HyenaDna(trajectory_stride=...))")
+        raise ValueError(f"a trajectory writer needs a net built with trajectory_stride ({type(net).__name__}(trajectory_stride=...))")
     return net.trajectory_request()
 
 

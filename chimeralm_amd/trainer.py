@@ -50,11 +50,12 @@ class Trainer:
         return rank, world, device
 
     def predict(self, model, dataloaders=None, datamodule=None, ckpt_path: str | Path | None = None,
-                return_predictions: bool = False, *, long_reads=None, batching=None):
+                return_predictions: bool = False, *, long_reads=None, batching=None, trajectory_writer=None):
         """`long_reads` (a `longread.Options` of mode "tile"): reads longer than the window are judged in overlapping windows, for
         any net; the datamodule must deliver them untruncated (`max_length=long_reads.max_tokens`).  `batching` (a `bucket.Options`
         of mode "bucket"): every read is padded to a canonical length of its own and reads of one such length are forwarded
-        together, for any net; each rank regroups its own shard."""
+        together, for any net; each rank regroups its own shard.  `trajectory_writer` (a `callbacks.TrajectoryWriter`): the running
+        verdict of every batch is written too, for a causal net built with `trajectory_stride`."""
         dm = datamodule if datamodule is not None else dataloaders
         if dm is None or not hasattr(dm, "predict_dataloader"):
             raise ValueError("Trainer.predict needs a datamodule with predict_dataloader()")
@@ -66,7 +67,8 @@ class Trainer:
         writers = [cb for cb in self.callbacks if hasattr(cb, "write_on_batch_end")]
         if not writers:
             raise ValueError("no prediction-writer callback configured (configs/callbacks/write.yaml)")
-        n = run_predict(model, dm, writers[0], device, rank=rank, long_reads=long_reads, batching=batching)
+        n = run_predict(model, dm, writers[0], device, rank=rank, long_reads=long_reads, batching=batching,
+                        trajectory_writer=trajectory_writer)
         distributed.barrier()
         log.info("[rank %d] %d reads predicted", rank, n)
         return None

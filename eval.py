@@ -13,6 +13,9 @@ longer than the model's context into overlapping windows for whichever net `mode
 `{rank}_{batch}.windows.tsv` next to the predictions; unknown keys are refused.
 `+batching.mode=bucket [+batching.steps_log2=3]` on the predict route pads every read to a canonical length of its own and forwards reads
 of one such length together (chimeralm_amd/bucket.py): a read's logits do not depend on its batch-mates; unknown keys are refused.
+`+trajectory.stride=128 [+trajectory.values=true]` on the predict route also writes the running verdict of every read, from the same
+forward, as `{rank}_{batch}.traj.tsv` (and `.traj.npz`) next to the predictions (chimeralm_amd/callbacks.py TrajectoryWriter), for the
+causal nets (`model=` the Hyena net, mamba or mambasp); unknown keys are refused, and so is `+long_reads.mode=tile` with it.
 Multi-GPU: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 eval.py trainer=ddp ...`.
 """
 from __future__ import annotations
@@ -61,14 +64,54 @@ def batching_options(cfg):
     return options if options.mode == "bucket" else None
 
 
+TRAJECTORY_KEYS = ("stride", "values")
+
+
+def trajectory_options(cfg):
+    """`(stride, values)` of `+trajectory.*` (None: no such node); unknown keys, a missing or bad stride and a `values` that is not a
+    boolean are a ValueError."""
+    from chimeralm_amd.engine import check_trajectory_stride
+
+    node = dict(cfg.get("trajectory") or {})
+    unknown = sorted(set(node) - set(TRAJECTORY_KEYS))
+    if unknown:
+        raise ValueError(f"unknown trajectory option(s) {unknown}; known: {list(TRAJECTORY_KEYS)}")
+    if not node:
+        return None
+    stride, values = node.get("stride"), node.get("values", False)
+    if isinstance(stride, bool) or not isinstance(stride, int):
+        raise ValueError(f"+trajectory.stride must be an integer (a multiple of 128 in 128 ... 4096), got {stride!r}")
+    if not isinstance(values, bool):
+        raise ValueError(f"+trajectory.values must be true or false, got {values!r}")
+    return check_trajectory_stride(stride), values                  # a bad option fails before anything is loaded
+
+
+def _trajectory_writer(trajectory, model, trainer):
+    """The net told its stride, and the `TrajectoryWriter` into the prediction writer's folder.  A net that has no such knob is left
+    to the predict loop's refusal."""
+    from chimeralm_amd.callbacks import TrajectoryWriter
+
+    stride, values = trajectory
+    if hasattr(model.net, "trajectory_request"):
+        model.net.trajectory_stride = stride
+    writers = [cb for cb in trainer.callbacks if hasattr(cb, "write_on_batch_end")]
+    if not writers:
+        raise ValueError("no prediction-writer callback configured (configs/callbacks/write.yaml)")
+    return TrajectoryWriter(output_dir=writers[0].output_dir, values=values)
+
+
 def evaluate(cfg):
     from chimeralm_amd.config import instantiate, instantiate_callbacks
 
     assert cfg.ckpt_path
     long_reads = long_read_options(cfg)
     batching = batching_options(cfg)
+    trajectory = trajectory_options(cfg)
     if batching is not None and long_reads is not None:
         raise ValueError("+batching.mode=bucket and +long_reads.mode=tile exclude each other")
+    if trajectory is not None and long_reads is not None:
+        raise ValueError("+trajectory.stride and +long_reads.mode=tile exclude each other: a read reduced from several windows has no "
+                         "single row to follow")
     log.info(f"Instantiating datamodule <{cfg.data._target_}>")
     datamodule = instantiate(cfg.data)
     log.info(f"Instantiating model <{cfg.model._target_}>")
@@ -83,16 +126,19 @@ def evaluate(cfg):
             raise ValueError("+long_reads.mode=tile belongs to the predict route (+data.predict_data_path=<reads.bam>)")
         if batching is not None:
             raise ValueError("+batching.mode=bucket belongs to the predict route (+data.predict_data_path=<reads.bam>)")
+        if trajectory is not None:
+            raise ValueError("+trajectory.stride belongs to the predict route (+data.predict_data_path=<reads.bam>)")
         trainer.test(model=model, datamodule=datamodule, ckpt_path=cfg.ckpt_path)
     elif long_reads is not None:
         if not hasattr(datamodule, "max_length"):
             raise ValueError(f"+long_reads.mode=tile needs a datamodule that can deliver untruncated reads, not {cfg.data._target_}")
         datamodule.max_length = long_reads.max_tokens
         trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, long_reads=long_reads)
-    elif batching is not None:
-        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, batching=batching)
     else:
-        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False)
+        extra = {} if batching is None else {"batching": batching}
+        if trajectory is not None:
+            extra["trajectory_writer"] = _trajectory_writer(trajectory, model, trainer)
+        trainer.predict(model=model, dataloaders=datamodule, ckpt_path=cfg.ckpt_path, return_predictions=False, **extra)
     return trainer.callback_metrics, object_dict
 
 

@@ -378,6 +378,24 @@ int clm_mamba_load_weight(clm_mamba_handle* h, const char* key, const void* data
 int clm_mamba_finalize(clm_mamba_handle* h);
 int clm_mamba_forward(clm_mamba_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, const float* mask,
                       int64_t mask_row_stride, float* logits_out, void* stream);
+/* The running verdict of the Mamba nets (ABI 6, additive): clm_mamba_forward that also leaves the request of `traj`, the clm_traj_out
+ * / clm_traj_summary of clm_forward_traj above with its points, its stride contract (a multiple of 128 in 128 ... 4,096) and its
+ * summary, unchanged.  Both nets are causal end to end (embedding, positional term and mask per token, the causal 4-tap convolution,
+ * the scan from a zero state, the per-token RMSNorm), and a prefix of their pooling is a running sum and a running maximum, so the
+ * whole trajectory follows from the per-64-token partials one forward leaves behind.
+ *   trajectory  logits[b][k] = head((mean + max) / 2 over h[b, :n_k]), head = pooler Linear + GELU, classifier Linear + GELU + Linear.
+ *               The mean divides by n_k, pads and masked rows included (a masked row is a row of zeros: it counts in the mean and
+ *               takes part in the maximum), because that is what the reference's forward of ids[b:b+1, :n_k] (and mask[b:b+1, :n_k])
+ *               computes.  Point K - 1 is the call's own logits_out[b], copied bit for bit, not recomputed.  The values are those of
+ *               the arithmetic the handle ran (fp32 or fp16x3).  As above, a truncated row does not end in [SEP]: no point but the
+ *               last shows the model a complete read; points inside the [PAD] prefix of a left-padded row describe pads only.
+ * CLM_E_INVALID, each with a message in clm_mamba_last_error: a stride that is not such a multiple, point_stride < K, traj->logits
+ * NULL, a struct_size mismatch.  No length cap beyond the forward's own.  Device pointers for the B reads of the call, written chunk by
+ * chunk at their rows by two kernels behind the head on `stream` (csrc/mamba_verdict.hip) and the summary kernel of
+ * csrc/trajectory.hip: fixed order, no atomics -- bitwise the same from run to run; the workspace is the handle's and is reserved by
+ * the first request.  With traj NULL this IS clm_mamba_forward. */
+int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, const float* mask,
+                           int64_t mask_row_stride, float* logits_out, const clm_traj_out* traj, void* stream);
 int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out, size_t bytes);
 const char* clm_mamba_last_error(const clm_mamba_handle* h); /* h may be NULL: error of the last failed clm_mamba_create */
 int clm_mamba_destroy(clm_mamba_handle* h);

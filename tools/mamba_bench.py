@@ -3,6 +3,10 @@ tokens (the length of bench.py's headline batch) and at the long-read shapes 4 x
 4 x 32,769 (`mambasp`).
 
     python tools/mamba_bench.py [--nets mamba,mambasp] [--precisions fp32,fp16x3] [--shapes big,long] [--warmup 2] [--steps 5]
+                                [--trajectory-stride 128]
+
+`--trajectory-stride S`: every forward also makes the running-verdict request (csrc/mamba_verdict.hip), for its cost against a run
+without.
 
 Seeded random weights of the reference configs (the modules' own initialisation: mamba_ssm's A / dt / D ranges), token ids uniform
 over A/C/G/T.  Each step is timed with HIP events on the launch stream; the median of the timed steps after the warm-up is
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--shapes", default="big,long")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--trajectory-stride", type=int, default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(0)
@@ -64,6 +69,10 @@ def main():
         print(f"{netname}: FLOP per token, all layers: projections {proj / 1e6:.2f} M, scan {scan / 1e6:.2f} M", flush=True)
         for prec in a.precisions.split(","):
             net = make(netname, prec)
+            if a.trajectory_stride is not None:
+                from chimeralm_amd.engine import check_trajectory_stride
+
+                net.trajectory_stride = check_trajectory_stride(a.trajectory_stride)
             for shape in a.shapes.split(","):
                 B, L = SHAPES[shape][netname]
                 ids = torch.randint(7, 11, (B, L), generator=g, dtype=torch.int64).to(dev)
@@ -83,7 +92,7 @@ def main():
                 med = statistics.median(ms)
                 tok = B * L
                 res = {"net": netname, "precision": prec, "batch": B, "tokens": L, "median_ms": round(med, 2), "min_ms": round(min(ms), 2),
-                       "reads_per_s": round(B / (med / 1e3), 2), "steps": a.steps,
+                       "reads_per_s": round(B / (med / 1e3), 2), "steps": a.steps, "trajectory_stride": a.trajectory_stride,
                        "proj_tflops_if_all_time": round(tok * proj / (med / 1e3) / 1e12, 1),
                        "fp32_peak_fraction_if_all_time": round(tok * proj / (med / 1e3) / FP32_PEAK, 3)}
                 print(json.dumps(res), flush=True)
