@@ -20,6 +20,11 @@ capability, for the released Hyena model (`python explain.py model=...` at the r
 
 is the reference's `train.py` with `freeze_backbone=True`, cut down to one GPU: the classifier head is fitted to labelled reads, the
 backbone stays as released (headtrain.py).
+
+    python -m chimeralm_amd train TRAIN.parquet [--val VAL.parquet] [-o OUT] [--epochs 10 --lr 1e-4 -b 8 --seed 12345] [--ckpt FILE]
+
+is the reference's `train.py` with its default `model=cnn`, cut down to one GPU: DNAConvNet is trained end to end, forward and
+backward on the engine (cnntrain.py); `python eval.py ckpt_path=OUT/model.safetensors model=cnn ...` then runs the result.
 """
 from __future__ import annotations
 
@@ -341,6 +346,55 @@ def finetune(
     model.to(device)
     train_rows, val_rows = headtrain.split_rows(train_path, val_path)
     hist = headtrain.fit_head(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
+    log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
+
+
+@app.command()
+def train(
+    train_path: Path = typer.Argument(..., help="Labelled reads (parquet; ids end in |0 or |1)"),
+    val_path: Path | None = typer.Option(None, "--val", help="Validation reads (parquet); without it the training file is split "
+                                         "70 / 20 / 10 percent as the reference does and the middle slice validates"),
+    output_path: Path | None = typer.Option(None, "--output", "-o", help="Output directory (default: TRAIN with suffix .train)"),
+    epochs: int = typer.Option(10, "--epochs", help="Epochs"),
+    lr: float = typer.Option(1e-4, "--lr", help="Adam learning rate (ReduceLROnPlateau on val/loss)"),
+    batch_size: int = typer.Option(8, "--batch-size", "-b", help="Reads per optimizer step (BatchNorm couples them: never split)"),
+    seed: int = typer.Option(12345, "--seed", help="Seed of the initial weights, the per-epoch shuffle and the dropout masks"),
+    ckpt_path: Path | None = typer.Option(None, "--ckpt", "-c", help="Path to a DNAConvNet checkpoint to start from (default: "
+                                          "torch's initialisation under --seed)"),
+    verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
+):
+    """Train DNAConvNet (configs/model/cnn.yaml) on labelled reads (writes model.safetensors and metrics.tsv)."""
+    logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
+    if epochs < 1:
+        raise typer.BadParameter("--epochs must be >= 1")
+    if not 2 <= batch_size <= 65535:
+        raise typer.BadParameter("--batch-size must be 2 ... 65535: BatchNorm needs two reads")
+    if not lr > 0:
+        raise typer.BadParameter("--lr must be > 0")
+    for f in (train_path, val_path):
+        if f is not None and f.suffix != ".parquet":
+            raise typer.BadParameter(f"{f} is not in Parquet format")
+        if f is not None and not f.is_file():
+            raise typer.BadParameter(f"{f}: no such file")
+    if ckpt_path is not None and not ckpt_path.is_file():
+        raise typer.BadParameter(f"--ckpt {ckpt_path}: no such file")
+    if output_path is None:
+        output_path = train_path.with_suffix(".train")
+
+    from . import cnntrain, headtrain
+    from .config import compose, instantiate
+
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    torch.manual_seed(seed)                                  # the initial weights
+    cfg = compose(Path(__file__).resolve().parent.parent / "configs", "eval.yaml", ["ckpt_path=unused", "model=cnn"], output_dir=output_path)
+    model = instantiate(cfg.model, net=instantiate(cfg.model.net, trainable=True))
+    if ckpt_path is not None:
+        log.info(f"Loading model from {ckpt_path}")
+        model.load_reference_checkpoint(ckpt_path)
+    model.to(device)
+    train_rows, val_rows = headtrain.split_rows(train_path, val_path)
+    hist = cnntrain.fit_cnn(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 

@@ -147,6 +147,15 @@ SYMBOLS = {
     "clm_cnn_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_cnn_last_error": (C.c_char_p, [_H]),
     "clm_cnn_destroy": (C.c_int, [_H]),
+    "clm_cnn_train_create": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_H)]),
+    "clm_cnn_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "clm_cnn_train_forward": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "clm_cnn_train_generation": (C.c_int64, [_H]),
+    "clm_cnn_train_backward": (C.c_int, [_H, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_float, C.c_void_p]),
+    "clm_cnn_train_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "clm_cnn_train_last_error": (C.c_char_p, [_H]),
+    "clm_cnn_train_destroy": (C.c_int, [_H]),
     "clm_mamba_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "clm_mamba_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "clm_mamba_finalize": (C.c_int, [_H]),

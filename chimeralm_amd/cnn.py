@@ -12,6 +12,11 @@ Engine knob absent in the reference: `precision` -- "fp16x3" (the default: block
 on hi + lo halfs per product) or "fp32" (the exact-fp32 MFMA).  fp16x3 packs weights x 2^10 as fp16 halfs, which saturates for
 |w| >= 64: if any conv or fc weight is that large, the module runs the exact-fp32 kernels instead, records it in
 `precision_report` and logs a warning.
+
+Training (`trainable=True`, keyword-only, absent in the reference, where every net trains): in `train()` mode with autograd on, the
+forward runs on batch statistics with a graph to every parameter (cnntrain.py, csrc/cnn_train.hip: exact fp32, dropout masks from
+`torch.rand` on `dropout_generator`) and updates the running statistics.  Everything else -- `trainable=False`, `eval()`, `no_grad`
+-- is the inference forward above, unchanged.
 """
 from __future__ import annotations
 
@@ -37,7 +42,7 @@ class CnnEngineError(RuntimeError):
 class DNAConvNet(nn.Module):
     def __init__(self, vocab_size: int, embedding_dim: int, num_filters: list[int], kernel_sizes: list[int], pool_sizes: list[int],
                  hidden_dim: int, number_of_classes: int = 2, dropout: float = 0.1, padding_idx: int = 4, *,
-                 precision: str = "fp16x3"):
+                 precision: str = "fp16x3", trainable: bool = False):
         super().__init__()
         got = dict(vocab_size=vocab_size, embedding_dim=embedding_dim, num_filters=list(num_filters), kernel_sizes=list(kernel_sizes),
                    pool_sizes=list(pool_sizes), hidden_dim=hidden_dim, number_of_classes=number_of_classes, padding_idx=padding_idx)
@@ -61,6 +66,12 @@ class DNAConvNet(nn.Module):
         self.fc = nn.Sequential(nn.Linear(num_filters[-1], hidden_dim), nn.BatchNorm1d(hidden_dim), nn.GELU(), nn.Dropout(dropout),
                                 nn.Linear(hidden_dim, number_of_classes))
         self._h, self._dev, self._sig, self._hprec = None, None, None, None
+        self.trainable, self.dropout = bool(trainable), float(dropout)
+        self.dropout_generator: torch.Generator | None = None   # None: the device's default generator (torch.manual_seed)
+        self.last_dropout_masks = None                          # the keep masks of the last training forward (None at dropout 0)
+        self.last_batch_stats = None                            # its batch means and biased variances, [3, 256] each
+        self.train_workspace_limit: int | None = None           # bytes a training batch's workspace may take (None: the engine's default)
+        self._train = None
 
     # ------------------------------------------------------------------ engine plumbing
     def _check(self, rc: int):
@@ -120,6 +131,10 @@ class DNAConvNet(nn.Module):
             raise ValueError("input_ids must be [batch, length] of int64 / int32 / uint8")
         if input_ids.stride(1) != 1:
             input_ids = input_ids.contiguous()
+        if self.trainable and self.training and torch.is_grad_enabled():
+            from .cnntrain import train_forward
+
+            return train_forward(self, input_ids)
         lib = self._prepare(input_ids.device)
         B, L = input_ids.shape
         out = torch.empty((B, self.number_of_classes), dtype=torch.float32, device=input_ids.device)
@@ -135,7 +150,20 @@ class DNAConvNet(nn.Module):
         self._check(N.load().clm_cnn_debug_fetch(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
         return arr
 
+    def train_engine(self, device: torch.device):
+        """The module's training engine on `device` (cnntrain.CnnTrainEngine), made on first use."""
+        from .cnntrain import CnnTrainEngine
+
+        if self._train is None or self._train.device != device or self._train.workspace_limit != self.train_workspace_limit:
+            if self._train is not None:
+                self._train.close()
+            self._train = CnnTrainEngine(device, self.train_workspace_limit)
+        return self._train
+
     def close(self):
+        if getattr(self, "_train", None) is not None:
+            self._train.close()
+            self._train = None
         if getattr(self, "_h", None) is not None:
             N.load().clm_cnn_destroy(self._h)
             self._h = None

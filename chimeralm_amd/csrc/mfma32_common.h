@@ -163,6 +163,33 @@ __device__ __forceinline__ void product256(const float* T, const f32x4* wp, int 
     });
 }
 
+// acc[mt] += W x of the token-major tile T, 256 deep: product256's arithmetic on the same packed fragments (launch_pack_f32t; k-step
+// ks = fragment ks of this wave at wp), but with a ring of four fragments requested four k-steps (2,048 MFMA cycles) ahead instead of
+// product256's two 64-deep sets: those are 64 registers, which a kernel with other accumulators to hold does not have
+// (pool_train.hip: the 128 of dW1; cnn_train.hip: one accumulator per tap and their sum)
+__device__ __forceinline__ void product256_ring(const float* T, const f32x4* wp, int lrow, int lhalf, f32x16 (&acc)[2]) {
+    f32x4 w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = wp[(size_t)i * 64];
+    const float* a0 = T + lrow * RS32 + lhalf * 4;
+#pragma unroll 1
+    for (int s4 = 0; s4 < D / 8; s4 += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 af0 = *reinterpret_cast<const f32x4*>(a0 + (s4 + i) * 8);
+            const f32x4 af1 = *reinterpret_cast<const f32x4*>(a0 + 32 * RS32 + (s4 + i) * 8);
+            const f32x4 wc = w[i];
+            const int nx = s4 + 4 + i < D / 8 ? s4 + 4 + i : i;      // (wrap-around keeps the request unconditional)
+            w[i] = wp[(size_t)nx * 64];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[0] = mfma32(wc[j], af0[j], acc[0]);
+                acc[1] = mfma32(wc[j], af1[j], acc[1]);
+            }
+        }
+    }
+}
+
 // LayerNorm over the 256 features of the 64 tokens in accumulator layout (rows = this wave's 32 features, lane = token) -> T
 // (fp32, token-major); two-pass statistics like every fp32 LayerNorm of the engine (gemm_common.h stage_a_tile).  Ends with a
 // barrier (T complete); its first barrier also orders every earlier LDS read of the workgroup before the writes.

@@ -55,32 +55,6 @@ __device__ __forceinline__ float row_sum64(const float* Du, int tid) {
     return s + __shfl_xor(s, 1, 64);
 }
 
-// acc[mt] += W1 x of the token-major tile T, 256 deep: product256's arithmetic on the same packed fragments (launch_pack_f32t; k-step
-// ks = fragment ks of this wave), but with a ring of four fragments requested four k-steps (2,048 MFMA cycles) ahead instead of
-// product256's two 64-deep sets: those are 64 registers, and next to the 128 dW1 accumulators the kernel has 256 in all
-__device__ __forceinline__ void product_u(const float* T, const f32x4* wp, int lrow, int lhalf, f32x16 (&acc)[2]) {
-    f32x4 w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = wp[(size_t)i * 64];
-    const float* a0 = T + lrow * RS32 + lhalf * 4;
-#pragma unroll 1
-    for (int s4 = 0; s4 < D / 8; s4 += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f32x4 af0 = *reinterpret_cast<const f32x4*>(a0 + (s4 + i) * 8);
-            const f32x4 af1 = *reinterpret_cast<const f32x4*>(a0 + 32 * RS32 + (s4 + i) * 8);
-            const f32x4 wc = w[i];
-            const int nx = s4 + 4 + i < D / 8 ? s4 + 4 + i : i;      // (wrap-around keeps the request unconditional)
-            w[i] = wp[(size_t)nx * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[0] = mfma32(wc[j], af0[j], acc[0]);
-                acc[1] = mfma32(wc[j], af1[j], acc[1]);
-            }
-        }
-    }
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(512) void pool_bwd_kernel(PoolBwdArgs m) {
@@ -145,7 +119,7 @@ __global__ __launch_bounds__(512) void pool_bwd_kernel(PoolBwdArgs m) {
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-        product_u(As, w1frag, lrow, lhalf, acc);
+        product256_ring(As, w1frag, lrow, lhalf, acc);
         __syncthreads();                                    // the row-dot partials of all waves
         // ---- 4. ds_t of the lane's two tokens (every wave computes all 64: no second hand-over)
         float ds[2];

@@ -342,6 +342,49 @@ int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, siz
 const char* clm_cnn_last_error(const clm_cnn_handle* h); /* h may be NULL: error of the last failed clm_cnn_create */
 int clm_cnn_destroy(clm_cnn_handle* h);
 
+/* ---- DNAConvNet in training mode (ABI 6, additive; chimeralm_amd/cnntrain.py) ------------------------------------------------
+ * Forward on batch statistics and the full backward of the three convolution blocks and the mean over positions, on the CALLER's
+ * current fp32 parameters (device pointers); the classifier `fc` sees [B, 256] and is the caller's.  Exact fp32
+ * (v_mfma_f32_32x32x2_f32) whatever the inference precision; no floating-point atomics and every reduction in a fixed order: the
+ * same inputs give the same bits.  Rows are token-major [B, L_i, 256], L_0 = L, L_{i+1} = floor(L_i / 4); pads are ordinary tokens.
+ *   block i:  z = conv1d_same(x_i; W_i, b_i) on all L_i positions (x_0 = embedding rows; zero outside [0, L_i));
+ *             mu_c, v_c = mean and biased variance of z[:, :, c] over all B L_i positions (those past 4 L_{i+1} included);
+ *             xh = (z - mu) / sqrt(v + 1e-5);  y = gelu_erf(g xh + beta);  p[b, j, c] = max_{r < 4} y[b, 4 j + r, c], routed in the
+ *             backward to choice[b, j, c] = the LOWEST r that attains it (torch's rule);  x_{i+1} = p keep keep_scale
+ *   pooled[b] = mean_j x_3[b, j, :]
+ *   backward: dz = g rstd (dy - mean(dy) - xh mean(dy xh)), dg = sum dy xh, dbeta = sum dy, db_i = sum dz (0 in exact arithmetic;
+ *             what the sum gives is returned), dW_i[co, ci, k] = sum_{b, t} dz[b, t, co] x_i[b, t + k - 3, ci], dx_i = the "same"
+ *             convolution of dz with the taps flipped and ci / co exchanged, d embedding[tok] = sum of dx_0 over the positions
+ *             holding tok, row 4 (padding_idx) zero.
+ * params / grads: CLM_CNN_TRAIN_PARAMS pointers in the order embedding [12, 256], then per block i = 0, 1, 2: W_i [256, 256, 7],
+ * b_i, g_i, beta_i [256]; all 16-byte aligned.
+ * clm_cnn_train_create    workspace_limit_bytes = 0: 64 GiB.  BatchNorm couples the reads of a batch, so a batch is never computed
+ *               in pieces: one whose workspace (clm_cnn_train_workspace_bytes) exceeds the limit is CLM_E_INVALID, bytes in the message.
+ * clm_cnn_train_forward   ids as clm_cnn_forward takes them; keep: NULL (no dropout) or three byte masks [B, L_{i+1}, 256] (non-zero =
+ *               keep) that must stay alive until the backward has run; keep_scale = 1 / (1 - p).  Writes pooled_out [B, 256] and the
+ *               batch statistics mean_out, var_out [3, 256] (biased variance).  B >= 2 and L >= 64, otherwise CLM_E_INVALID; B > 65535
+ *               or B L > 2^30 is CLM_E_UNSUPPORTED.  A refused call launches nothing and leaves the handle as it was.
+ * clm_cnn_train_generation   moves with every forward on the handle (-1 for NULL).
+ * clm_cnn_train_backward  dpooled [B, 256]; grads = beta * (what they hold) + the gradients, beta 0 or 1.  `generation` is the value
+ *               after the forward to differentiate: CLM_E_STATE if no forward is pending (none ran, or its backward already did) or
+ *               another forward ran on the handle since -- and nothing is launched.
+ * Both are asynchronous on `stream` and do not synchronise (a forward that has to grow the workspace does, once).
+ * clm_cnn_train_debug_fetch names (synchronises): "z0".."z2", "y0".."y2" fp32 [B, L_i, 256]; "choice0".."choice2" u8
+ * [B, L_{i+1}, 256]; "dz0".."dz2" fp32 [B, L_i, 256] (after the backward, else CLM_E_STATE). */
+#define CLM_CNN_TRAIN_PARAMS 13
+typedef struct clm_cnn_train_handle clm_cnn_train_handle;
+int clm_cnn_train_create(int device, size_t workspace_limit_bytes, clm_cnn_train_handle** out);
+int64_t clm_cnn_train_workspace_bytes(int B, int L); /* < 0: CLM_E_INVALID (B < 1 or L < 64) */
+int clm_cnn_train_forward(clm_cnn_train_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
+                          const float* const* params, const unsigned char* const* keep, float keep_scale, float* pooled_out,
+                          float* mean_out, float* var_out, void* stream);
+int64_t clm_cnn_train_generation(const clm_cnn_train_handle* h);
+int clm_cnn_train_backward(clm_cnn_train_handle* h, int64_t generation, const float* dpooled, float* const* grads, float beta,
+                           void* stream);
+int clm_cnn_train_debug_fetch(clm_cnn_train_handle* h, const char* name, void* host_out, size_t bytes);
+const char* clm_cnn_train_last_error(const clm_cnn_train_handle* h); /* h may be NULL: the last failed clm_cnn_train_create */
+int clm_cnn_train_destroy(clm_cnn_train_handle* h);
+
 /* ---- Mamba2 classifiers (ABI 6, additive) -----------------------------------------------------------------------------
  * The reference's two Mamba nets (chimeralm/models/components/mamba.py) in eval mode, behind the same `net`
  * boundary: forward(input_ids[B, L], second argument) -> logits fp32 [B, 2].
