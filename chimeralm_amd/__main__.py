@@ -25,6 +25,8 @@ backbone stays as released (headtrain.py).
 
 is the reference's `train.py` with its default `model=cnn`, cut down to one GPU: DNAConvNet is trained end to end, forward and
 backward on the engine (cnntrain.py); `python eval.py ckpt_path=OUT/model.safetensors model=cnn ...` then runs the result.
+`--net mamba` / `--net mambasp` trains the reference's Mamba nets instead (mambatrain.py: the Mamba2 core forward and backward on the
+engine, the projections in torch); `python eval.py ckpt_path=OUT/model.safetensors model=mambasp ...` runs that result.
 """
 from __future__ import annotations
 
@@ -349,6 +351,9 @@ def finetune(
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 
+TRAIN_NETS = ("cnn", "mamba", "mambasp")              # `train --net`
+
+
 @app.command()
 def train(
     train_path: Path = typer.Argument(..., help="Labelled reads (parquet; ids end in |0 or |1)"),
@@ -362,12 +367,18 @@ def train(
     ckpt_path: Path | None = typer.Option(None, "--ckpt", "-c", help="Path to a DNAConvNet checkpoint to start from (default: "
                                           "torch's initialisation under --seed)"),
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
+    net: str = typer.Option("cnn", "--net", help="The net to train: cnn (DNAConvNet), mamba or mambasp (configs/model/NET.yaml; the "
+                            "Mamba nets take batches of one read too)"),
 ):
     """Train DNAConvNet (configs/model/cnn.yaml) on labelled reads (writes model.safetensors and metrics.tsv)."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
+    if net not in TRAIN_NETS:
+        raise typer.BadParameter(f"--net must be one of {', '.join(TRAIN_NETS)}")
     if epochs < 1:
         raise typer.BadParameter("--epochs must be >= 1")
-    if not 2 <= batch_size <= 65535:
+    if net != "cnn" and not 1 <= batch_size <= 65535:
+        raise typer.BadParameter("--batch-size must be 1 ... 65535")
+    if net == "cnn" and not 2 <= batch_size <= 65535:
         raise typer.BadParameter("--batch-size must be 2 ... 65535: BatchNorm needs two reads")
     if not lr > 0:
         raise typer.BadParameter("--lr must be > 0")
@@ -387,14 +398,18 @@ def train(
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
     torch.manual_seed(seed)                                  # the initial weights
-    cfg = compose(Path(__file__).resolve().parent.parent / "configs", "eval.yaml", ["ckpt_path=unused", "model=cnn"], output_dir=output_path)
+    cfg = compose(Path(__file__).resolve().parent.parent / "configs", "eval.yaml", ["ckpt_path=unused", f"model={net}"], output_dir=output_path)
     model = instantiate(cfg.model, net=instantiate(cfg.model.net, trainable=True))
     if ckpt_path is not None:
         log.info(f"Loading model from {ckpt_path}")
         model.load_reference_checkpoint(ckpt_path)
     model.to(device)
     train_rows, val_rows = headtrain.split_rows(train_path, val_path)
-    hist = cnntrain.fit_cnn(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
+    if net == "cnn":
+        fit = cnntrain.fit_cnn
+    else:
+        from .mambatrain import fit_mamba as fit
+    hist = fit(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 

@@ -166,6 +166,13 @@ SYMBOLS = {
     "clm_mamba_debug_fetch": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_size_t]),
     "clm_mamba_last_error": (C.c_char_p, [_H]),
     "clm_mamba_destroy": (C.c_int, [_H]),
+    "clm_mamba_train_create": (C.c_int, [C.c_int, C.POINTER(_H)]),
+    "clm_mamba_train_workspace_bytes": (C.c_int64, [C.c_int] * 5),
+    "clm_mamba_train_forward": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_void_p] * 6),
+    "clm_mamba_train_backward": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_void_p] * 6
+                                 + [C.POINTER(C.c_void_p), C.c_void_p]),
+    "clm_mamba_train_last_error": (C.c_char_p, [_H]),
+    "clm_mamba_train_destroy": (C.c_int, [_H]),
     "clm_eval_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.POINTER(_H)]),
     "clm_eval_update": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "clm_eval_read": (C.c_int, [_H, C.POINTER(ClmEvalResult), C.c_void_p]),

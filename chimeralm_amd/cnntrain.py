@@ -190,11 +190,20 @@ def fit_cnn(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_siz
     reference's Adam 1e-4 and ReduceLROnPlateau, configs/model/cnn.yaml); `lr` overrides the rate.  Writes `out_dir/metrics.tsv`
     (headtrain.METRIC_COLUMNS) and, for the epoch of the best `val/f1` (ties: the earlier), `out_dir/model.safetensors`; on return the
     model holds that epoch's weights too.  Returns the rows of metrics.tsv as dicts, with `val/f1_best`."""
+    if epochs < 1 or batch_size < 2:
+        raise ValueError("epochs must be >= 1 and batch_size >= 2 (BatchNorm needs two reads)")
+    return fit_all_parameters(model, train_rows, val_rows, out_dir, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
+                              tokenizer=tokenizer, metrics_factory=metrics_factory, min_reads=2, config="configs/model/cnn.yaml")
+
+
+def fit_all_parameters(model, train_rows, val_rows, out_dir, *, epochs: int, batch_size: int, lr: float | None, seed: int,
+                       device: torch.device | str, tokenizer, metrics_factory, min_reads: int, config: str) -> list[dict]:
+    """The loop of `fit_cnn` and `mambatrain.fit_mamba`: one optimizer step per batch over every parameter of `model.net`, validation
+    through the inference kernels, the best-`val/f1` checkpoint and metrics.tsv.  A last batch of fewer than `min_reads` reads is
+    skipped (2 where BatchNorm needs batch statistics, else 1: none is)."""
     from .headtrain import METRIC_COLUMNS, _f1, _load_reads, epoch_order, save_checkpoint
     from .tokenizer import DataCollator, load_tokenizer_from_hyena_model
 
-    if epochs < 1 or batch_size < 2:
-        raise ValueError("epochs must be >= 1 and batch_size >= 2 (BatchNorm needs two reads)")
     device = torch.device(device)
     tok = tokenizer if tokenizer is not None else load_tokenizer_from_hyena_model("hyenadna-small-32k-seqlen")
     collate = DataCollator(tok).torch_call
@@ -205,7 +214,7 @@ def fit_cnn(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_siz
     if not params:
         raise ValueError("the net has no trainable parameter")
     if model.optimizer_factory is None:
-        raise ValueError("the model has no optimizer factory (configs/model/cnn.yaml: optimizer)")
+        raise ValueError(f"the model has no optimizer factory ({config}: optimizer)")
     opt = model.optimizer_factory(params=params)
     if lr is not None:
         for g in opt.param_groups:
@@ -229,7 +238,7 @@ def fit_cnn(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_siz
             seen = 0
             for i0 in range(0, len(order), batch_size):
                 rows = order[i0:i0 + batch_size]
-                if len(rows) < 2:
+                if len(rows) < min_reads:
                     continue
                 batch = collate([train[i] for i in rows])
                 ids, y = batch["input_ids"].to(device), batch["labels"].to(device)

@@ -21,6 +21,10 @@ The running verdict, as for `HyenaDna` (csrc/mamba_verdict.hip): both nets are c
 every forward also leaves `last_trajectory`, an `engine.TrajectoryOutput` of DEVICE tensors -- the logits the model would give if a
 row ended at each multiple of the stride, and the per-read summary -- from the same call (`clm_mamba_forward_traj`).  After a
 non-finite fp16x3 rerun it is the trajectory of the exact-fp32 handle, whose logits were returned.
+
+Training (mambatrain.py, csrc/mamba_train.hip): with the keyword `trainable=True`, in `train()` and with autograd on, the forward runs
+the Mamba2 core forward and backward on the engine, the rest in torch, and returns logits with a graph to every parameter; dropout is
+then active.  Every other call -- `trainable=False`, `eval()`, `no_grad` -- is the inference forward above, bit for bit.
 """
 from __future__ import annotations
 
@@ -54,7 +58,8 @@ class _Norm(nn.Module):
 class Mamba2(nn.Module):
     """`mamba_ssm.Mamba2`'s parameters under its names, initialised as mamba_ssm does: A uniform in [1, 16] (A_log = log A), dt
     log-uniform in [1e-3, 0.1] (floored at 1e-4) through the inverse softplus into dt_bias, D = 1, norm.weight = 1; in_proj, conv1d
-    and out_proj keep torch's default initialisation.  No forward: the whole net runs on the MI355X engine."""
+    and out_proj keep torch's default initialisation.  No forward of its own: inference runs the whole net on the MI355X engine,
+    training runs this layer through `mambatrain.mamba2_layer`."""
 
     def __init__(self, d_model: int, d_state: int = 128, d_conv: int = 4, expand: int = 2, headdim: int = 64):
         super().__init__()
@@ -85,7 +90,7 @@ def _check_shape(vocab_size, d_model, d_state, d_conv, expand, headdim, number_o
 class _MambaNet(nn.Module):
     _variant = None
 
-    def _setup(self, d_model, n_layers, d_state, expand, headdim, max_len, precision, trajectory_stride=None):
+    def _setup(self, d_model, n_layers, d_state, expand, headdim, max_len, precision, trajectory_stride=None, trainable=False):
         if precision not in ("fp32", "fp16x3"):
             raise ValueError("precision must be fp32 (exact fp32 products) or fp16x3 (every projection operand as two halfs, three "
                              "fp16 MFMAs per product: fp32-class logits)")
@@ -96,6 +101,20 @@ class _MambaNet(nn.Module):
         # the running verdict (an engine knob, csrc/mamba_verdict.hip): see the module docstring
         self.trajectory_stride = None if trajectory_stride is None else check_trajectory_stride(trajectory_stride)
         self.last_trajectory = None
+        # training (mambatrain.py): with `trainable`, in train() and under autograd the forward builds a graph to every parameter
+        self.trainable = bool(trainable)
+        self._train = None
+        self.last_train_pooled, self.last_train_route = None, None   # of the last training forward: pooled [B, d], the max-pool's positions
+
+    def train_engine(self, device: torch.device):
+        """The module's training engine on `device` (mambatrain.MambaTrainEngine), made on first use."""
+        from .mambatrain import MambaTrainEngine
+
+        if self._train is None or self._train.device != device:
+            if self._train is not None:
+                self._train.close()
+            self._train = MambaTrainEngine(device)
+        return self._train
 
     def trajectory_request(self):
         """The `engine.TrajectoryRequest` this module's forwards make (None: `trajectory_stride` is not set)."""
@@ -191,6 +210,10 @@ class _MambaNet(nn.Module):
             mask = mask.to(device=input_ids.device, dtype=torch.float32)
             if mask.stride(1) != 1:
                 mask = mask.contiguous()
+        if self.trainable and self.training and torch.is_grad_enabled():
+            from .mambatrain import train_forward
+
+            return train_forward(self, input_ids, mask)
         lib = self._prepare(input_ids.device)
         dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[input_ids.dtype]
         out = torch.empty((B, self.number_of_classes), dtype=torch.float32, device=input_ids.device)
@@ -217,6 +240,9 @@ class _MambaNet(nn.Module):
         return arr
 
     def close(self):
+        if getattr(self, "_train", None) is not None:
+            self._train.close()
+            self._train = None
         for attr in ("_h", "_h32"):
             h = getattr(self, attr, None)
             if h is not None:
@@ -238,10 +264,11 @@ class MambaSequenceClassification(_MambaNet):
 
     def __init__(self, vocab_size, embedding_dim: int, number_of_layers: int, model_max_length: int, dropout: float,
                  number_of_classes: int, d_state: int = 128, d_conv: int = 4, expand: int = 2, headdim: int = 64,
-                 padding_idx: int = 4, *, precision: str = "fp16x3", trajectory_stride: int | None = None):
+                 padding_idx: int = 4, *, precision: str = "fp16x3", trajectory_stride: int | None = None,
+                 trainable: bool = False):
         super().__init__()
         _check_shape(vocab_size, embedding_dim, d_state, d_conv, expand, headdim, number_of_classes, padding_idx)
-        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, model_max_length, precision, trajectory_stride)
+        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, model_max_length, precision, trajectory_stride, trainable)
         self.number_of_classes = number_of_classes
         self.embedding = nn.Embedding(vocab_size, embedding_dim, padding_idx=padding_idx)
         self.pos_embedding = nn.Parameter(torch.zeros(1, model_max_length, embedding_dim))
@@ -267,10 +294,10 @@ class MambaSequenceClassificationSP(_MambaNet):
 
     def __init__(self, vocab_size, embedding_dim: int, number_of_layers: int, number_of_classes: int, dropout: float,
                  d_state: int = 128, d_conv: int = 4, expand: int = 2, headdim: int = 64, padding_idx: int = 4, *,
-                 precision: str = "fp16x3", trajectory_stride: int | None = None):
+                 precision: str = "fp16x3", trajectory_stride: int | None = None, trainable: bool = False):
         super().__init__()
         _check_shape(vocab_size, embedding_dim, d_state, d_conv, expand, headdim, number_of_classes, padding_idx)
-        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, None, precision, trajectory_stride)
+        self._setup(embedding_dim, number_of_layers, d_state, expand, headdim, None, precision, trajectory_stride, trainable)
         self.number_of_classes = number_of_classes
         self.embedding = nn.Embedding(vocab_size, embedding_dim, padding_idx=padding_idx)
         self.mamba_layers = nn.ModuleList([Mamba2(embedding_dim, d_state, d_conv, expand, headdim) for _ in range(number_of_layers)])

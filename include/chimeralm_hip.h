@@ -443,6 +443,40 @@ int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out,
 const char* clm_mamba_last_error(const clm_mamba_handle* h); /* h may be NULL: error of the last failed clm_mamba_create */
 int clm_mamba_destroy(clm_mamba_handle* h);
 
+/* ---- The Mamba2 core in training form (ABI 6, additive; chimeralm_amd/mambatrain.py) ---------------------------------------------
+ * What lies between in_proj and out_proj of one Mamba2 layer, forward and backward, on the CALLER's tensors (fp32 device pointers,
+ * 16-byte aligned, contiguous, token-major rows).  With di = expand x d_model, H = di / 64, P = 64, N = d_state, conv_dim = di + 2 N:
+ *   zxbcdt [B, L, 2 di + 2 N + H] = z | xBC | dt (the raw in_proj output)
+ *   xc = silu(causal depthwise conv of xBC, 4 taps, + bias) = x | B | C, inside each read;  dt = softplus(raw + dt_bias)
+ *   ys = scan(x, dt, A = -exp(A_log), B, C) + D x, from a zero state per read, in chunks of 64 tokens (tests/mamba_reference.py)
+ *   out [B, L, di] = norm.weight g rsqrt(mean_c g^2 + 1e-5),  g = ys silu(z)          (what out_proj consumes)
+ * Exact fp32 (products on v_mfma_f32_32x32x2_f32); no floating-point atomics and every reduction in a fixed order, partials of
+ * different workgroups combined in fp64 in workgroup order: the same inputs give the same bits.  Pads are ordinary tokens.
+ * params / dparams: CLM_MAMBA_TRAIN_PARAMS pointers in the order conv1d.weight [conv_dim, 1, 4], conv1d.bias [conv_dim], dt_bias [H],
+ * A_log [H], D [H], norm.weight [di].
+ * The op is stateless across calls: what the backward needs is written by the forward into buffers of the caller, who keeps them
+ * (and zxbcdt) until the backward has run --
+ *   xc [B, L, conv_dim], dt [B, L, H], ys [B, L, di], states [B, H, ceil(L / 64), N, 64] (every chunk's entry state).
+ * clm_mamba_train_backward  dout [B, L, di] -> dzxbcdt (zxbcdt's shape; every element written) and the six parameter gradients
+ *               (overwritten).  Its scratch belongs to the handle and is grown on demand (one synchronisation when it grows):
+ *   clm_mamba_train_workspace_bytes = 4 x (B L (2 di + H + 2 N H) + B ceil(L / 64) (di + 5 conv_dim + H) + 2 B H)
+ *               (dys, dx, ddt, the heads' dB | dC; the 64-row partials of norm.weight, conv1d.weight / bias and dt_bias; dA_log and dD
+ *               per (read, head)).  A negative value is the refusal's code.
+ * Calls on one handle are ordered by the caller (one stream at a time).  B < 1 or L < 1 is CLM_E_INVALID; d_model other than 256 /
+ * 512, d_state other than 16 / 32 / 64 / 128, expand outside 1 ... 1024, or a batch beyond the index range (B L or a launch grid
+ * >= 2^31) is CLM_E_UNSUPPORTED.  A refused call launches nothing.  Both calls are asynchronous on `stream`. */
+#define CLM_MAMBA_TRAIN_PARAMS 6
+typedef struct clm_mamba_train_handle clm_mamba_train_handle;
+int clm_mamba_train_create(int device, clm_mamba_train_handle** out);
+int64_t clm_mamba_train_workspace_bytes(int B, int L, int d_model, int expand, int d_state);
+int clm_mamba_train_forward(clm_mamba_train_handle* h, const float* zxbcdt, const float* const* params, int B, int L, int d_model,
+                            int expand, int d_state, float* xc, float* dt, float* ys, float* states, float* out, void* stream);
+int clm_mamba_train_backward(clm_mamba_train_handle* h, const float* zxbcdt, const float* const* params, int B, int L, int d_model,
+                             int expand, int d_state, const float* xc, const float* dt, const float* ys, const float* states,
+                             const float* dout, float* dzxbcdt, float* const* dparams, void* stream);
+const char* clm_mamba_train_last_error(const clm_mamba_train_handle* h); /* h may be NULL: the last failed clm_mamba_train_create */
+int clm_mamba_train_destroy(clm_mamba_train_handle* h);
+
 /* ---- test-stage metrics (ABI 6, additive) -----------------------------------------------------------------------------
  * What the reference's `test_step` feeds to torchmetrics on the host after a sync per batch (basic_module.py:153-175), summed on the
  * device instead: the logits of a batch never leave it and the host waits once, in clm_eval_read.
