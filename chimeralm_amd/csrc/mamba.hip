@@ -22,6 +22,8 @@
 //             residual, applies the mask; the last layer writes per-64-row-tile channel sums and maxima instead of the rows.
 //   head      mamba_head_kernel: the tiles' partials in a fixed order, pooler, classifier.
 // No atomics: the forward is bitwise deterministic and a read's logits do not depend on its batch-mates.
+// clm_mamba_debug_fetch also reads the workspace itself -- "zx", "xc", "g", "ssq", "part": the LAST layer's in_proj output, conv
+// output, scan output, per-head sums of squares and pooling partials -- after a forward that ran as one chunk of reads.
 #include <cmath>
 #include <map>
 #include <string>
@@ -535,7 +537,7 @@ struct clm_mamba_handle {
     bool finalized = false;
     DevBuf ids8, h, zx, xc, g, ssq, part, pooled, dbg_front, dbg_layer0;   // workspace (clm_mamba_forward)
     DevBuf verdict_pooled, verdict_npad;          // the running verdict (mamba_verdict.hip): fp32 [chunk reads][K][d], int [chunk reads]; grown by the first request
-    int last_B = 0, last_L = 0;
+    int last_B = 0, last_L = 0, last_nb = 0;     // ... and the reads per chunk of the last forward
     bool last_dbg = false;
 };
 
@@ -806,7 +808,7 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
                                 traj->summary ? traj->summary + r0 : nullptr, st);
         }
     }
-    h->last_B = B, h->last_L = L, h->last_dbg = dbg;
+    h->last_B = B, h->last_L = L, h->last_nb = nb, h->last_dbg = dbg;
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_mamba_forward: launch failed: ") + hipGetErrorString(e));
 }
@@ -826,6 +828,17 @@ int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out,
     } else if (n == "pooled") {
         src = h->pooled.get();
         have = B * d * 4;
+    } else if (n == "zx" || n == "xc" || n == "g" || n == "ssq" || n == "part") {
+        // the workspace as the last layer of the last chunk of reads left it: the whole batch only when it ran as one chunk
+        if (h->last_nb < h->last_B)
+            return fail(h, CLM_E_INVALID, "clm_mamba_debug_fetch: the last forward ran in chunks of " + std::to_string(h->last_nb) +
+                                              " reads; " + n + " holds the last chunk only");
+        const size_t T = B * L;
+        if (n == "zx") src = h->zx.get(), have = T * (size_t)h->n_in_pad * 4;
+        else if (n == "xc") src = h->xc.get(), have = T * (size_t)h->conv_dim * 4;
+        else if (n == "g") src = h->g.get(), have = T * (size_t)h->di * 4;
+        else if (n == "ssq") src = h->ssq.get(), have = T * (size_t)h->H * 4;
+        else src = h->part.get(), have = B * ((L + 63) / 64) * 2 * d * 4;
     } else {
         return fail(h, CLM_E_INVALID, "clm_mamba_debug_fetch: unknown name " + n);
     }

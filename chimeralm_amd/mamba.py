@@ -233,7 +233,9 @@ class _MambaNet(nn.Module):
 
     def debug_fetch(self, name: str, shape) -> np.ndarray:
         """Intermediates of the last forward, from the handle whose logits it returned (the exact-fp32 one after a non-finite
-        fp16x3 rerun): "front" / "layer0" [B, L, d], "pooled" [B, d]."""
+        fp16x3 rerun): "front" / "layer0" [B, L, d], "pooled" [B, d]; and, after a forward that ran as one chunk of reads, the LAST
+        layer's workspace: "zx" [B, L, n_in_pad], "xc" [B, L, conv_dim], "g" [B, L, d_inner], "ssq" [B, L, H], "part" [B, ceil(L / 64),
+        2, d] (include/chimeralm_hip.h)."""
         arr = np.empty(shape, dtype=np.float32)
         h = self._last_h
         self._check(h, N.load().clm_mamba_debug_fetch(h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes))

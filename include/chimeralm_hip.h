@@ -411,7 +411,11 @@ int clm_cnn_train_destroy(clm_cnn_train_handle* h);
  * Long batches run in chunks of whole reads (the in_proj output of one chunk is bounded at 4 GiB).  The forward is bitwise
  * deterministic (no atomics) and a read's logits do not depend on the other reads of its batch.
  * clm_mamba_debug_fetch names (the last forward): "front" fp32 [B, L, d] (the residual stream entering layer 0), "layer0" fp32
- * [B, L, d] (after layer 0) -- both only while B x L x d x 4 <= 256 MiB -- and "pooled" fp32 [B, d]. */
+ * [B, L, d] (after layer 0) -- both only while B x L x d x 4 <= 256 MiB -- and "pooled" fp32 [B, d].  The workspace of the LAST
+ * layer, as the forward left it and only when the batch ran as one chunk of reads (CLM_E_INVALID otherwise): "zx" fp32 [B, L,
+ * n_in_pad] (in_proj output z | x | B | C | dt with softplus applied | zero padding; n_in_pad = 2 di + 2 N + H rounded up to a multiple
+ * of 256), "xc" fp32 [B, L, di + 2 N] (conv + SiLU), "g" fp32 [B, L, di] (scan output, gated, before the RMS scale), "ssq" fp32 [B, L,
+ * H] (per-head sums of g^2), "part" fp32 [B, ceil(L / 64), 2, d] (per 64-token tile: channel sums | maxima of the last layer's rows). */
 #define CLM_MAMBA_SEQ 0
 #define CLM_MAMBA_SP 1
 typedef struct clm_mamba_handle clm_mamba_handle;

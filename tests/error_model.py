@@ -173,6 +173,56 @@ def rank(L=2048, B=16, wseeds=(4, 6, 7, 1)):
                 print(f"weights {wseed}  {B} x {L}  {n:36s} {stat(forward(ids, sd, c) - ref)}", flush=True)
 
 
+# ------------------------------------------------------------------------------------------------------------- fp16x3 (AR_X3)
+# The split of csrc/mfma32_common.h, operand by operand: hi = fp16(clamp(v)), lo = fp16(clamp(v - hi)) (split4; fp16's subnormals
+# kept), weights x 2^10 (pack_x3_kernel), the three products w_hi a_hi + w_lo a_hi + w_hi a_lo, accumulated in float64 -- so what is
+# left is the error of the FORMAT: an activation below ~2^-3 has its lo half in fp16's subnormal range (an absolute 2^-25 instead of
+# a relative 2^-22).  `flush`: fp16 subnormal halfs read as zero, what a matrix unit that flushes them would compute.
+X3_WS = 1024.0
+H_MAX, H_MIN_NORMAL = 65504.0, 2.0 ** -14
+
+
+def x3_split(v: torch.Tensor, flush: bool = False):
+    """(hi, lo) of v as float64 tensors holding fp16 values."""
+    v = v.double()
+    h16 = lambda t: t.clamp(-H_MAX, H_MAX).to(torch.float16).double()   # noqa: E731
+    hi = h16(v)
+    lo = h16(v - hi)
+    if flush:
+        hi = torch.where(hi.abs() < H_MIN_NORMAL, torch.zeros_like(hi), hi)
+        lo = torch.where(lo.abs() < H_MIN_NORMAL, torch.zeros_like(lo), lo)
+    return hi, lo
+
+
+def x3_linear(a: torch.Tensor, w: torch.Tensor, flush: bool = False) -> torch.Tensor:
+    """a [..., K] @ w [N, K]^T in the fp16x3 format (float64 result)."""
+    ah, al = x3_split(a, flush)
+    wh, wl = x3_split(w.double() * X3_WS, flush)
+    return (ah @ (wh + wl).T + al @ wh.T) / X3_WS
+
+
+def mamba_x3_forward(variant: str, sd: dict, ids, mask=None, flush: bool = False, exact: bool = False, trace: dict | None = None):
+    """Logits of a Mamba net (tests/mamba_stage_reference.py's stages in float64) with the three fp16x3 products of csrc/mamba.hip --
+    the `mamba` front Linear, in_proj, out_proj with norm.weight folded in -- in the split format; `exact`: plain float64 products
+    (the reference the split error is measured against).  `trace` receives the residual rows entering layer 0 ("front")."""
+    import mamba_stage_reference as S
+
+    lin = (lambda a, w: a @ w.T) if exact else (lambda a, w: x3_linear(a, w, flush))
+    w = {k: v.detach().double() for k, v in sd.items()}
+    ids = torch.as_tensor(np.asarray(ids), dtype=torch.int64)
+    m = None if mask is None or variant != "mamba" else torch.as_tensor(np.asarray(mask), dtype=DT)
+    pre = S.front_pre(variant, w, ids)
+    h = S.front_post(variant, w, lin(pre, w["input_block.0.weight"]) if variant == "mamba" else None, pre, m)
+    if trace is not None:
+        trace["front"] = h
+    for i in range(S.n_layers_of(sd)):
+        p = S.layer_params(variant, sd, i, DT)
+        zx = S.in_proj_post(p, lin(h, p["in_proj.weight"]))
+        g, ssq = S.scan(p, zx, S.conv(p, zx))
+        h = S.out_proj_post(p, h, lin(g, S.out_weight(p)), ssq, m)
+    return S.head(w, S.pooled_of(S.partials(h), ids.shape[1]))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "rank":
         rank(*(int(a) for a in sys.argv[2:4]))

@@ -114,6 +114,10 @@ def test_batch_rows_equal_reads_alone(built_lib, variant):
     net = _model(variant, sd, "fp16x3")
     full = net(big, mask).cpu().numpy()
     assert np.isfinite(full).all()
+    from chimeralm_amd.mamba import MambaEngineError
+    for tap in ("zx", "xc", "g", "ssq", "part"):                  # the workspace holds the last chunk only: its taps are refused
+        with pytest.raises(MambaEngineError, match="ran in chunks of"):
+            net.debug_fetch(tap, (1,))
     for r in (0, 1, 2, 3, 250):
         alone = net(big[r:r + 1], None if mask is None else mask[r:r + 1]).cpu().numpy()
         assert np.array_equal(alone[0], full[r]), r
@@ -221,6 +225,25 @@ def test_fp16x3_range_guard_and_nonfinite_rerun(built_lib, caplog):
     print(f"fp16x3 rerun on fp32 with |E| up to {float(sd['embedding.weight'].abs().max()):.3g}: relative logit error {err:.2e}")
     assert err < TOL
     net.close()
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16x3"])
+@pytest.mark.parametrize("k", [8, 16])
+def test_small_activations(built_lib, prec, k):
+    """The low side of fp16x3's activation range: the weights and reads of the 2^17 case above with `embedding.weight` x 2^-k.  An
+    unscaled fp16 split keeps an absolute 2^-25 of an activation below ~2^-3, and the RMS scale behind out_proj turns that back into
+    a relative error (tests/error_model.py x3_linear; tests/test_mamba_stage_host.py holds the CPU model of exactly these nets:
+    6.3e-5 at 2^-8, 2.3e-4 at 2^-16).  Both precisions are held to TOL of fp64, relative to max(1, max|ref|)."""
+    ids = mr.synthetic_ids(2500, 2, 300)
+    sd = mr.make_mamba_state_dict("mambasp", 26, n_layers=2)
+    sd["embedding.weight"] = sd["embedding.weight"] * 2.0 ** -k
+    ref = mr.mamba_forward_fp64("mambasp", sd, ids, device="cuda").cpu().numpy()
+    net = _model("mambasp", sd, prec, n_layers=2)
+    got = net(torch.from_numpy(ids).cuda()).cpu().numpy()
+    err = np.abs(got - ref).max() / max(1.0, float(np.abs(ref).max()))
+    print(f"SMALL {prec} embedding x 2^-{k}: relative logit error {err:.2e} (|ref| up to {np.abs(ref).max():.2f}); report {net.precision_report}")
+    net.close()
+    assert err < TOL
 
 
 @pytest.mark.parametrize("variant,L", [("mamba", 30000), ("mambasp", 32769)])
