@@ -30,6 +30,7 @@ EXPLAIN_MAX_BASES = 32768             # bases of one read the explain calls take
 LONGREAD_SEP = 1                      # clm_longread_span.flags bit 0 (CLM_LONGREAD_SEP)
 BUCKET_SCATTER, BUCKET_EMIT = 0, 1     # clm_bucket_step.kind (CLM_BUCKET_*)
 BUCKET_MAX_TOKENS = 32769             # tokens of the longest row the bucket calls take (CLM_BUCKET_MAX_TOKENS)
+X3_WEIGHT_LIMIT = 64.0                # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates (clm_common.h)
 MAMBA_SEQ, MAMBA_SP = 0, 1            # clm_mamba_create variants (CLM_MAMBA_SEQ, CLM_MAMBA_SP)
 
 

@@ -28,11 +28,11 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._native import X3_WEIGHT_LIMIT
 from ._reload import reload_signature
 
 PRODUCTION = dict(vocab_size=12, embedding_dim=256, num_filters=[256, 256, 256], kernel_sizes=[7, 7, 7], pool_sizes=[4, 4, 4],
                   hidden_dim=512, number_of_classes=2, padding_idx=4)
-X3_WEIGHT_LIMIT = 64.0                     # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates
 
 
 class CnnEngineError(RuntimeError):

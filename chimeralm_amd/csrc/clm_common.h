@@ -93,6 +93,8 @@ __device__ __forceinline__ float wave_sum(float v) {
     const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
     return (r0 + r1) + (r2 + r3);
 }
+// Row of register r (0 .. 15) of a 32 x 32 MFMA accumulator tile in the half-wave lhalf = lane >> 5 (the lane's column is lane & 31)
+__device__ __forceinline__ int acc_row(int r, int lhalf) { return 8 * (r >> 2) + 4 * lhalf + (r & 3); }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -305,6 +307,13 @@ int upload_f32(H* h, DevBuf& d, const std::vector<float>& src) {
     HIPCHK(h, d.alloc(src.size() * 4));
     HIPCHK(h, hipMemcpy(d.get(), src.data(), src.size() * 4, hipMemcpyHostToDevice));
     return CLM_OK;
+}
+// W [rows][cols] -> [cols][rows] on the host (a layer whose threads each own an output reads its weights coalesced)
+inline std::vector<float> transposed(const std::vector<float>& W, int rows, int cols) {
+    std::vector<float> t((size_t)rows * cols);
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = W[(size_t)r * cols + c];
+    return t;
 }
 // A convolution's taps, split as [taps][co][ci] fp32 on the device, each packed by pack(tap, dst) into tap_bytes of `out`.
 // Synchronises before it returns: the caller reuses or frees `split` next.

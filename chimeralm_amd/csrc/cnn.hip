@@ -17,6 +17,7 @@
 // No atomics: every reduction has a fixed order, so the forward is bitwise deterministic and a read's logits do not depend on the
 // batch it is in.  BatchNorm is applied as y = x * scale + shift with scale = g / sqrt(var + eps), shift = b - mean * scale, both
 // computed in fp64 at finalize (not folded into the weights).
+// The net's constants and block 0's two staging steps are cnn_common.h's, shared with cnn_train.hip (and tail32.hip's cnn_gemm7_kernel).
 #include <cmath>
 #include <map>
 #include <string>
@@ -24,17 +25,14 @@
 
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "cnn_common.h"
 
 namespace clm {
-namespace cnn {
+namespace cnn {                    // (VOC, K, HALO, TROWS, BN_EPS and block 0's staging: cnn_common.h)
 
-constexpr int VOC = 12;            // embedding rows
-constexpr int K = 7, HALO = 3;     // taps, "same" padding on each side
-constexpr int TROWS = VOC + 1;     // LDS table rows per tap: the 12 ids + a zero row for positions outside the read
 constexpr int HID = 512;           // fc hidden
 constexpr int PT0 = 128;           // block 0: pooled positions per workgroup (512 tokens)
 constexpr int ROWS2 = 16;          // block 2: pooled rows per 64-row tile of cnn_gemm7_kernel
-constexpr float BN_EPS = 1e-5f;
 
 // ------------------------------------------------------------------------------------------------ block 0
 // grid (tiles, B), 512 threads: thread = (channel tid & 255, half tid >> 8 of the tile's pooled positions).
@@ -45,22 +43,8 @@ __global__ __launch_bounds__(512) void cnn_block0_kernel(const unsigned char* __
     float* Ts = smem_c0;                                       // [K][TROWS][256]
     int* idl = reinterpret_cast<int*>(Ts + K * TROWS * D);     // [4 PT0 + 2 HALO]: LDS row of token 4 p0 - 3 + i
     const int tid = threadIdx.x, b = blockIdx.y, p0 = blockIdx.x * PT0, L4 = L / 4;
-    for (int i = tid; i < K * TROWS * D / 4; i += 512) {
-        const int row = i / (D / 4), dk = row / TROWS, tok = row % TROWS, c4 = i % (D / 4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tok < VOC) v = *reinterpret_cast<const float4*>(table + ((size_t)dk * VOC + tok) * D + 4 * c4);
-        *reinterpret_cast<float4*>(Ts + (size_t)row * D + 4 * c4) = v;
-    }
-    const int base = 4 * p0 - HALO;
-    for (int i = tid; i < 4 * PT0 + 2 * HALO; i += 512) {
-        const int t = base + i;
-        int id = VOC;                                          // outside [0, L): the zero row
-        if (t >= 0 && t < L) {
-            id = ids8[(size_t)b * Lp + t];
-            id = id < VOC ? id : VOC - 1;                      // (ids8 holds [0, 16); ids past the vocabulary clamp to its last row)
-        }
-        idl[i] = id;
-    }
+    stage_table(Ts, table, tid);
+    stage_token_rows(idl, ids8 + (size_t)b * Lp, 4 * p0 - HALO, 4 * PT0 + 2 * HALO, L, tid, 1);
     __syncthreads();
     const int c = tid & (D - 1), half = tid >> 8;
     const float bc = bias[c], sc = bn_scale[c], sh = bn_shift[c];
@@ -271,10 +255,7 @@ int clm_cnn_finalize(clm_cnn_handle* h) {
     {
         std::vector<float> W0;
         if ((rc = cnn_host(h, "fc.0.weight", W0))) return rc;
-        std::vector<float> W0t((size_t)D * cnn::HID);
-        for (int j = 0; j < cnn::HID; ++j)
-            for (int c = 0; c < D; ++c) W0t[(size_t)c * cnn::HID + j] = W0[(size_t)j * D + c];
-        if ((rc = upload_f32(h, h->dev.fc0t, W0t))) return rc;
+        if ((rc = upload_f32(h, h->dev.fc0t, transposed(W0, cnn::HID, D)))) return rc;
     }
     HIPCHK(h, hipDeviceSynchronize());
     h->finalized = true;

@@ -28,17 +28,17 @@
 //   dt, dt_reduce     block 0: dT[dk][tok][co] = sum of dz_0[b, t, co] over ids[b, t + dk - 3] = tok; one thread per channel walks
 //                     the workgroup's positions into a 7 x 13 x 256 LDS table (row 12: outside the read); partials in order.
 //   dw0, de           dW_0 and d embedding from dT: two tiny products in fp64.
+// Shared with inference: the net's constants and conv0's two staging steps (cnn_common.h), gemm7's input tile (mfma32_common.h stage_rows).
 #include <string>
 
 #include "chimeralm_hip.h"
 #include "clm_common.h"
-
+#include "cnn_common.h"
 #include "mfma32_common.h"
 
 namespace clm {
 namespace {
 
-constexpr int CT_VOC = 12, CT_K = 7, CT_HALO = 3, CT_TROWS = CT_VOC + 1;
 constexpr int CT_PT0 = 256;                        // conv0: positions per workgroup
 constexpr int CT_RSD = 68;                         // row stride (floats) of the feature-major dz tile [256][64] (pool_train.hip RSD)
 constexpr int CT_DW_GRID = 36;                     // dw: workgroups per tap at most (x 7 taps = 252 of the 256 CUs)
@@ -46,8 +46,7 @@ constexpr int CT_STAT_GRID = 512;                  // stats / dy: workgroups at 
 constexpr int CT_DT_GRID = 256;                    // dt: workgroups at most
 constexpr int CT_DT_SUB = 512;                     // dt: positions whose table rows are staged in LDS at a time
 constexpr int CT_SLICES = 4;                       // the small reductions: 1,024 threads = 256 columns x 4 slices of the summed index
-constexpr int CT_TSIZE = CT_K * CT_VOC * D;        // floats of T / dT
-constexpr float CT_EPS = 1e-5f;
+constexpr int CT_TSIZE = cnn::K * cnn::VOC * D;        // floats of T / dT
 constexpr float CT_INV_SQRT2 = 0.7071067811865476f, CT_INV_SQRT_2PI = 0.3989422804014327f;
 
 __device__ __forceinline__ float ct_gelu_grad(float u) {
@@ -74,14 +73,14 @@ __device__ __forceinline__ float ct_y(float z, float mu, float rstd, float g, fl
 __global__ __launch_bounds__(1024) void cnn_train_table_kernel(const float* __restrict__ E, const float* __restrict__ W, float* __restrict__ T) {
     __shared__ float Es[D];
     __shared__ double red[CT_SLICES * D];
-    const int dk = blockIdx.x / CT_VOC, tok = blockIdx.x % CT_VOC, co = threadIdx.x & (D - 1), slice = threadIdx.x >> 8;
+    const int dk = blockIdx.x / cnn::VOC, tok = blockIdx.x % cnn::VOC, co = threadIdx.x & (D - 1), slice = threadIdx.x >> 8;
     if (slice == 0) Es[co] = E[(size_t)tok * D + co];
     __syncthreads();
-    const float* w = W + (size_t)co * D * CT_K + dk;
+    const float* w = W + (size_t)co * D * cnn::K + dk;
     double s = 0.0;
-    for (int ci = slice * (D / CT_SLICES); ci < (slice + 1) * (D / CT_SLICES); ++ci) s += (double)w[(size_t)ci * CT_K] * (double)Es[ci];
+    for (int ci = slice * (D / CT_SLICES); ci < (slice + 1) * (D / CT_SLICES); ++ci) s += (double)w[(size_t)ci * cnn::K] * (double)Es[ci];
     s = ct_combine(s, red, slice, co);
-    if (slice == 0) T[((size_t)dk * CT_VOC + tok) * D + co] = (float)s;
+    if (slice == 0) T[((size_t)dk * cnn::VOC + tok) * D + co] = (float)s;
 }
 
 // grid (ceil(L / CT_PT0), B), 512 threads: thread = (channel, half of the workgroup's positions); z_0 on every position < L
@@ -89,23 +88,10 @@ __global__ __launch_bounds__(512) void cnn_train_conv0_kernel(const unsigned cha
                                                               const float* __restrict__ bias, float* __restrict__ z, int L) {
     extern __shared__ __attribute__((aligned(16))) float smem_ct0[];
     float* Ts = smem_ct0;                                      // [K][TROWS][256]
-    int* idl = reinterpret_cast<int*>(Ts + CT_K * CT_TROWS * D);   // [PT0 + 2 HALO]: LDS row offset of token t0 - 3 + i
+    int* idl = reinterpret_cast<int*>(Ts + cnn::K * cnn::TROWS * D);   // [PT0 + 2 HALO]: LDS row offset of token t0 - 3 + i
     const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * CT_PT0;
-    for (int i = tid; i < CT_K * CT_TROWS * D / 4; i += 512) {
-        const int row = i / (D / 4), dk = row / CT_TROWS, tok = row % CT_TROWS, c4 = i % (D / 4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tok < CT_VOC) v = *reinterpret_cast<const float4*>(table + ((size_t)dk * CT_VOC + tok) * D + 4 * c4);
-        *reinterpret_cast<float4*>(Ts + (size_t)row * D + 4 * c4) = v;
-    }
-    for (int i = tid; i < CT_PT0 + 2 * CT_HALO; i += 512) {
-        const int t = t0 - CT_HALO + i;
-        int id = CT_VOC;                                       // outside [0, L): the zero row
-        if (t >= 0 && t < L) {
-            id = ids8[(size_t)b * Lp + t];
-            id = id < CT_VOC ? id : CT_VOC - 1;
-        }
-        idl[i] = id * D;
-    }
+    cnn::stage_table(Ts, table, tid);
+    cnn::stage_token_rows(idl, ids8 + (size_t)b * Lp, t0 - cnn::HALO, CT_PT0 + 2 * cnn::HALO, L, tid, D);
     __syncthreads();
     const int c = tid & (D - 1), half = tid >> 8;
     const float bc = bias[c];
@@ -115,7 +101,7 @@ __global__ __launch_bounds__(512) void cnn_train_conv0_kernel(const unsigned cha
         const int* id = idl + (t - t0);                        // token t + dk - 3 -> id[dk]
         float v = bc;
 #pragma unroll
-        for (int dk = 0; dk < CT_K; ++dk) v += Tc[dk * CT_TROWS * D + id[dk]];
+        for (int dk = 0; dk < cnn::K; ++dk) v += Tc[dk * cnn::TROWS * D + id[dk]];
         z[((size_t)b * L + t) * D + c] = v;
     }
 }
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(256) void cnn_train_pack_kernel(const float* __rest
     f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        v[e] = flip ? W[((size_t)(k0 + e) * D + n) * CT_K + (CT_K - 1 - tap)] : W[((size_t)n * D + k0 + e) * CT_K + tap];
+        v[e] = flip ? W[((size_t)(k0 + e) * D + n) * cnn::K + (cnn::K - 1 - tap)] : W[((size_t)n * D + k0 + e) * cnn::K + tap];
     out[i] = v;
 }
 
@@ -149,18 +135,7 @@ __global__ __launch_bounds__(512) void cnn_train_gemm7_kernel(CnnTrainGemmArgs m
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lrow = lane & 31, lhalf = lane >> 5;
     const int b = (int)blockIdx.x / m.tiles_x, t0 = ((int)blockIdx.x % m.tiles_x) * BM32, Lin = m.Lin;
     f32x16 tot[2];
-    {
-        const float* src = m.x + (size_t)b * Lin * D + lane * 4;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const int r = wave + 8 * i, t = t0 - CT_HALO + r;
-            if (r < BM32 + 2 * CT_HALO) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
-                tile_store4<AR_F32>(Xs, r, lane * 4, v);
-            }
-        }
-    }
+    stage_rows<AR_F32, cnn::HALO>(Xs, m.x + (size_t)b * Lin * D, t0, Lin, wave, lane);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -170,7 +145,7 @@ __global__ __launch_bounds__(512) void cnn_train_gemm7_kernel(CnnTrainGemmArgs m
     // would be a chain of 896 -- the rounding of a running fp32 sum grows with its length, and training reads z closer than
     // inference does
 #pragma unroll 1
-    for (int dk = 0; dk < CT_K; ++dk) {
+    for (int dk = 0; dk < cnn::K; ++dk) {
         f32x16 acc[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(1024) void cnn_train_stats_final_kernel(const doubl
         const float muf = (float)mu, vf = (float)var;
         o0[c] = muf;
         o1[c] = vf;
-        o2[c] = (float)(1.0 / sqrt(var + (double)CT_EPS));
+        o2[c] = (float)(1.0 / sqrt(var + (double)cnn::BN_EPS));
         g0[c] = muf;
         g1[c] = vf;
     } else if (mode == 1) {
@@ -373,7 +348,7 @@ __global__ __launch_bounds__(512) void cnn_train_dw_kernel(CnnTrainDwArgs m) {
             const float* src = m.x + (size_t)b * Lin * D + lane * 4;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int r = wave + 8 * i, t = t0 + tap - CT_HALO + r;
+                const int r = wave + 8 * i, t = t0 + tap - cnn::HALO + r;
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
                 tile_store4<AR_F32>(As, r, lane * 4, v);
@@ -414,12 +389,12 @@ __global__ __launch_bounds__(512) void cnn_train_dw_kernel(CnnTrainDwArgs m) {
     }
     {
         const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), lr = ln & 31, lh = ln >> 5;
-        float* out = m.partial + ((size_t)blockIdx.x * CT_K + tap) * D * D;
+        float* out = m.partial + ((size_t)blockIdx.x * cnn::K + tap) * D * D;
         float* orow = out + (size_t)(wave * 32 + 4 * lh) * D + lr;
 #pragma unroll
         for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) orow[((r & 3) + 8 * (r >> 2)) * D + ct * 32] = dacc[ct][r];
+            for (int r = 0; r < 16; ++r) orow[acc_row(r, 0) * D + ct * 32] = dacc[ct][r];
     }
 }
 
@@ -428,8 +403,8 @@ __global__ __launch_bounds__(256) void cnn_train_dw_reduce_kernel(const float* _
     const int i = blockIdx.x * 256 + threadIdx.x;              // < 7 * 65536
     const int tap = i / (D * D), rem = i % (D * D);
     double s = 0.0;
-    for (int w = 0; w < parts; ++w) s += (double)partial[((size_t)w * CT_K + tap) * D * D + rem];
-    float* dst = dW + (size_t)rem * CT_K + tap;
+    for (int w = 0; w < parts; ++w) s += (double)partial[((size_t)w * cnn::K + tap) * D * D + rem];
+    float* dst = dW + (size_t)rem * cnn::K + tap;
     *dst = beta != 0.f ? fmaf(beta, *dst, (float)s) : (float)s;
 }
 
@@ -439,23 +414,23 @@ __global__ __launch_bounds__(256) void cnn_train_dw_reduce_kernel(const float* _
 __global__ __launch_bounds__(256) void cnn_train_dt_kernel(const float* __restrict__ dz, const unsigned char* __restrict__ ids8, int Lp, int L,
                                                            size_t n, size_t chunk, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float smem_ctt[];   // [K][TROWS][256] | int [CT_DT_SUB][K]
-    int* rowl = reinterpret_cast<int*>(smem_ctt + CT_K * CT_TROWS * D);
+    int* rowl = reinterpret_cast<int*>(smem_ctt + cnn::K * cnn::TROWS * D);
     const int c = threadIdx.x;
-    for (int i = c; i < CT_K * CT_TROWS * D; i += 256) smem_ctt[i] = 0.f;
+    for (int i = c; i < cnn::K * cnn::TROWS * D; i += 256) smem_ctt[i] = 0.f;
     float* Tc = smem_ctt + c;
     const size_t r0 = (size_t)blockIdx.x * chunk, r1 = r0 + chunk < n ? r0 + chunk : n;
     for (size_t s0 = r0; s0 < r1; s0 += CT_DT_SUB) {
         const int cnt = (int)(r1 - s0 < (size_t)CT_DT_SUB ? r1 - s0 : (size_t)CT_DT_SUB);
         __syncthreads();                                               // the zeroed table; the walk before this stretch
-        for (int i = c; i < cnt * CT_K; i += 256) {
-            const size_t r = s0 + i / CT_K;
-            const int dk = i % CT_K, b = (int)(r / (size_t)L), tt = (int)(r % (size_t)L) + dk - CT_HALO;
-            int tok = CT_VOC;
+        for (int i = c; i < cnt * cnn::K; i += 256) {
+            const size_t r = s0 + i / cnn::K;
+            const int dk = i % cnn::K, b = (int)(r / (size_t)L), tt = (int)(r % (size_t)L) + dk - cnn::HALO;
+            int tok = cnn::VOC;
             if (tt >= 0 && tt < L) {
                 tok = ids8[(size_t)b * Lp + tt];
-                tok = tok < CT_VOC ? tok : CT_VOC - 1;
+                tok = tok < cnn::VOC ? tok : cnn::VOC - 1;
             }
-            rowl[i] = (dk * CT_TROWS + tok) * D;
+            rowl[i] = (dk * cnn::TROWS + tok) * D;
         }
         __syncthreads();
         const float* src = dz + s0 * D + c;
@@ -466,16 +441,16 @@ __global__ __launch_bounds__(256) void cnn_train_dt_kernel(const float* __restri
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 if (i0 + u < cnt) {
-                    const int* rw = rowl + (i0 + u) * CT_K;
+                    const int* rw = rowl + (i0 + u) * cnn::K;
 #pragma unroll
-                    for (int dk = 0; dk < CT_K; ++dk) Tc[rw[dk]] += v[u];
+                    for (int dk = 0; dk < cnn::K; ++dk) Tc[rw[dk]] += v[u];
                 }
             }
         }
     }
     float* out = partial + (size_t)blockIdx.x * CT_TSIZE;
-    for (int dk = 0; dk < CT_K; ++dk)
-        for (int tok = 0; tok < CT_VOC; ++tok) out[(dk * CT_VOC + tok) * D + c] = Tc[(dk * CT_TROWS + tok) * D];
+    for (int dk = 0; dk < cnn::K; ++dk)
+        for (int tok = 0; tok < cnn::VOC; ++tok) out[(dk * cnn::VOC + tok) * D + c] = Tc[(dk * cnn::TROWS + tok) * D];
 }
 
 // dT = the partials in workgroup order, as four slices of them, in fp64.  grid 7 x 12, 1,024 threads (co, slice)
@@ -491,14 +466,14 @@ __global__ __launch_bounds__(1024) void cnn_train_dt_reduce_kernel(const float* 
 // grid 256 (co), 256 threads (ci): dW_0[co][ci][dk] = beta dW_0 + sum_tok dT[dk][tok][co] E[tok][ci]
 __global__ __launch_bounds__(256) void cnn_train_dw0_kernel(const float* __restrict__ dT, const float* __restrict__ E, float* __restrict__ dW, float beta) {
     const int co = blockIdx.x, ci = threadIdx.x;
-    float e[CT_VOC];
+    float e[cnn::VOC];
 #pragma unroll
-    for (int tok = 0; tok < CT_VOC; ++tok) e[tok] = E[tok * D + ci];
-    for (int dk = 0; dk < CT_K; ++dk) {
+    for (int tok = 0; tok < cnn::VOC; ++tok) e[tok] = E[tok * D + ci];
+    for (int dk = 0; dk < cnn::K; ++dk) {
         double s = 0.0;
 #pragma unroll
-        for (int tok = 0; tok < CT_VOC; ++tok) s += (double)dT[(dk * CT_VOC + tok) * D + co] * (double)e[tok];
-        float* dst = dW + ((size_t)co * D + ci) * CT_K + dk;
+        for (int tok = 0; tok < cnn::VOC; ++tok) s += (double)dT[(dk * cnn::VOC + tok) * D + co] * (double)e[tok];
+        float* dst = dW + ((size_t)co * D + ci) * cnn::K + dk;
         *dst = beta != 0.f ? fmaf(beta, *dst, (float)s) : (float)s;
     }
 }
@@ -511,9 +486,9 @@ __global__ __launch_bounds__(1024) void cnn_train_de_kernel(const float* __restr
     double s = 0.0;
     if (tok != PAD_ID)
         for (int co = slice * (D / CT_SLICES); co < (slice + 1) * (D / CT_SLICES); ++co) {
-            const float* w = W + ((size_t)co * D + ci) * CT_K;
+            const float* w = W + ((size_t)co * D + ci) * cnn::K;
 #pragma unroll
-            for (int dk = 0; dk < CT_K; ++dk) s += (double)dT[(dk * CT_VOC + tok) * D + co] * (double)w[dk];
+            for (int dk = 0; dk < cnn::K; ++dk) s += (double)dT[(dk * cnn::VOC + tok) * D + co] * (double)w[dk];
         }
     s = ct_combine(s, red, slice, ci);
     if (slice != 0) return;
@@ -542,15 +517,15 @@ struct clm_cnn_train_handle {
 namespace {
 
 constexpr size_t CT_DEFAULT_LIMIT = (size_t)64 << 30;
-constexpr size_t CT_PART_BYTES = (size_t)CT_DW_GRID * CT_K * D * D * 4;   // the largest of the three kinds of partials
+constexpr size_t CT_PART_BYTES = (size_t)CT_DW_GRID * cnn::K * D * D * 4;   // the largest of the three kinds of partials
 static_assert(CT_PART_BYTES >= (size_t)CT_DT_GRID * CT_TSIZE * 4 && CT_PART_BYTES >= (size_t)CT_STAT_GRID * 2 * D * 8, "part holds every kind");
 
 // offsets (floats) into `small`
 struct Small {
-    static constexpr size_t T = 0, DT = T + CT_TSIZE, E = DT + CT_TSIZE, W0 = E + CT_VOC * D, MEAN = W0 + (size_t)D * D * CT_K,
+    static constexpr size_t T = 0, DT = T + CT_TSIZE, E = DT + CT_TSIZE, W0 = E + cnn::VOC * D, MEAN = W0 + (size_t)D * D * cnn::K,
                             VAR = MEAN + 3 * D, RSTD = VAR + 3 * D, G = RSTD + 3 * D, BETA = G + 3 * D, M1 = BETA + 3 * D, M2 = M1 + D,
                             PACK = M2 + D,                                      // [block 1, 2][forward, flipped] x 7 x 65536
-                            END = PACK + 4 * (size_t)CT_K * D * D;
+                            END = PACK + 4 * (size_t)cnn::K * D * D;
 };
 
 void ct_lens(int L, int (&Ls)[4]) {
@@ -579,7 +554,7 @@ void ct_split(size_t n, int max_grid, size_t min_chunk, size_t& chunk, int& grid
 
 void ct_gemm(const float* x, const float* w, const float* bias, float* out, int B, int Lin, hipStream_t st) {
     CnnTrainGemmArgs m{x, reinterpret_cast<const f32x4*>(w), bias, out, Lin, (Lin + BM32 - 1) / BM32};
-    const size_t lds = (size_t)(BM32 + 2 * CT_HALO) * RS32 * sizeof(float);
+    const size_t lds = (size_t)(BM32 + 2 * cnn::HALO) * RS32 * sizeof(float);
     launch_lds<cnn_train_gemm7_kernel>(dim3((unsigned)(m.tiles_x * B)), dim3(512), lds, st, m);
 }
 
@@ -659,21 +634,21 @@ int clm_cnn_train_forward(clm_cnn_train_handle* h, const void* ids, int ids_dtyp
     const float *W[3], *bias[3], *g[3], *beta[3];
     for (int i = 0; i < 3; ++i) W[i] = params[1 + 4 * i], bias[i] = params[2 + 4 * i], g[i] = params[3 + 4 * i], beta[i] = params[4 + 4 * i];
     // what the backward reads of the parameters: the forward's own copies
-    HIPCHK(h, hipMemcpyAsync(sm + Small::E, E, (size_t)CT_VOC * D * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(sm + Small::W0, W[0], (size_t)D * D * CT_K * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(sm + Small::E, E, (size_t)cnn::VOC * D * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(sm + Small::W0, W[0], (size_t)D * D * cnn::K * 4, hipMemcpyDeviceToDevice, st));
     for (int i = 0; i < 3; ++i) {
         HIPCHK(h, hipMemcpyAsync(sm + Small::G + i * D, g[i], D * 4, hipMemcpyDeviceToDevice, st));
         HIPCHK(h, hipMemcpyAsync(sm + Small::BETA + i * D, beta[i], D * 4, hipMemcpyDeviceToDevice, st));
     }
     for (int i = 1; i < 3; ++i)
         for (int flip = 0; flip < 2; ++flip)
-            hipLaunchKernelGGL(cnn_train_pack_kernel, dim3(CT_K * D * D / 4 / 256), dim3(256), 0, st, W[i],
-                               reinterpret_cast<f32x4*>(sm + Small::PACK + (size_t)(2 * (i - 1) + flip) * CT_K * D * D), flip);
+            hipLaunchKernelGGL(cnn_train_pack_kernel, dim3(cnn::K * D * D / 4 / 256), dim3(256), 0, st, W[i],
+                               reinterpret_cast<f32x4*>(sm + Small::PACK + (size_t)(2 * (i - 1) + flip) * cnn::K * D * D), flip);
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
     launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, ids8, B, L, Lp, st);
-    hipLaunchKernelGGL(cnn_train_table_kernel, dim3(CT_K * CT_VOC), dim3(1024), 0, st, E, W[0], sm + Small::T);
+    hipLaunchKernelGGL(cnn_train_table_kernel, dim3(cnn::K * cnn::VOC), dim3(1024), 0, st, E, W[0], sm + Small::T);
     {
-        const size_t lds = (size_t)CT_K * CT_TROWS * D * 4 + (size_t)(CT_PT0 + 2 * CT_HALO) * 4;
+        const size_t lds = (size_t)cnn::K * cnn::TROWS * D * 4 + (size_t)(CT_PT0 + 2 * cnn::HALO) * 4;
         launch_lds<cnn_train_conv0_kernel>(dim3((unsigned)((L + CT_PT0 - 1) / CT_PT0), (unsigned)B), dim3(512), lds, st, ids8, Lp, sm + Small::T,
                                            bias[0], h->z[0].get<float>(), L);
     }
@@ -682,7 +657,7 @@ int clm_cnn_train_forward(clm_cnn_train_handle* h, const void* ids, int ids_dtyp
     for (int i = 0; i < 3; ++i) {
         const int Lin = Ls[i], Lout = Ls[i + 1];
         float* const z = h->z[i].get<float>();
-        if (i > 0) ct_gemm(h->xn[i - 1].get<float>(), sm + Small::PACK + (size_t)(2 * (i - 1)) * CT_K * D * D, bias[i], z, B, Lin, st);
+        if (i > 0) ct_gemm(h->xn[i - 1].get<float>(), sm + Small::PACK + (size_t)(2 * (i - 1)) * cnn::K * D * D, bias[i], z, B, Lin, st);
         ct_colsum(h, z, (size_t)B * Lin, 0, sm + Small::MEAN + i * D, sm + Small::VAR + i * D, sm + Small::RSTD + i * D, mean_out + i * D,
                   var_out + i * D, 0.f, st);
         h->keep[i] = keep ? keep[i] : nullptr;
@@ -739,22 +714,22 @@ int clm_cnn_train_backward(clm_cnn_train_handle* h, int64_t generation, const fl
                            sm + Small::M2, dz, Lin, Lout, total);
         ct_colsum(h, dz, (size_t)B * Lin, 2, nullptr, nullptr, nullptr, db, nullptr, beta, st);
         if (i > 0) {
-            ct_gemm(dz, sm + Small::PACK + (size_t)(2 * (i - 1) + 1) * CT_K * D * D, nullptr, dx, B, Lin, st);   // dx_i [B, L_i, 256]
+            ct_gemm(dz, sm + Small::PACK + (size_t)(2 * (i - 1) + 1) * cnn::K * D * D, nullptr, dx, B, Lin, st);   // dx_i [B, L_i, 256]
             const int tiles_x = (Lin + BM32 - 1) / BM32, tiles = tiles_x * B, grid = tiles < CT_DW_GRID ? tiles : CT_DW_GRID;
             CnnTrainDwArgs m{dz, h->xn[i - 1].get<float>(), h->part.get<float>(), Lin, tiles_x, tiles};
             const size_t lds = (size_t)(BM32 * RS32 + D * CT_RSD) * sizeof(float);
-            launch_lds<cnn_train_dw_kernel>(dim3((unsigned)grid, CT_K), dim3(512), lds, st, m);
-            hipLaunchKernelGGL(cnn_train_dw_reduce_kernel, dim3(CT_K * D * D / 256), dim3(256), 0, st, h->part.get<float>(), grid, dW, beta);
+            launch_lds<cnn_train_dw_kernel>(dim3((unsigned)grid, cnn::K), dim3(512), lds, st, m);
+            hipLaunchKernelGGL(cnn_train_dw_reduce_kernel, dim3(cnn::K * D * D / 256), dim3(256), 0, st, h->part.get<float>(), grid, dW, beta);
         } else {
             size_t chunk;
             int grid;
             const size_t n = (size_t)B * L;
             ct_split(n, CT_DT_GRID, 128, chunk, grid);
-            launch_lds<cnn_train_dt_kernel>(dim3((unsigned)grid), dim3(256), (size_t)CT_K * CT_TROWS * D * 4 + (size_t)CT_DT_SUB * CT_K * 4, st, dz, h->ids8.get<unsigned char>(), Lp,
+            launch_lds<cnn_train_dt_kernel>(dim3((unsigned)grid), dim3(256), (size_t)cnn::K * cnn::TROWS * D * 4 + (size_t)CT_DT_SUB * cnn::K * 4, st, dz, h->ids8.get<unsigned char>(), Lp,
                                             L, n, chunk, h->part.get<float>());
-            hipLaunchKernelGGL(cnn_train_dt_reduce_kernel, dim3(CT_K * CT_VOC), dim3(1024), 0, st, h->part.get<float>(), grid, sm + Small::DT);
+            hipLaunchKernelGGL(cnn_train_dt_reduce_kernel, dim3(cnn::K * cnn::VOC), dim3(1024), 0, st, h->part.get<float>(), grid, sm + Small::DT);
             hipLaunchKernelGGL(cnn_train_dw0_kernel, dim3(D), dim3(256), 0, st, sm + Small::DT, sm + Small::E, dW, beta);
-            hipLaunchKernelGGL(cnn_train_de_kernel, dim3(CT_VOC), dim3(1024), 0, st, sm + Small::DT, sm + Small::W0, grads[0], beta);
+            hipLaunchKernelGGL(cnn_train_de_kernel, dim3(cnn::VOC), dim3(1024), 0, st, sm + Small::DT, sm + Small::W0, grads[0], beta);
         }
     }
     h->pending = false;

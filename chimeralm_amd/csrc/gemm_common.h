@@ -252,7 +252,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[CT<PRE
         for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int nrow = nt * 32 + (r & 3) + 8 * (r >> 2);
+                const int nrow = nt * 32 + acc_row(r, 0);
                 const float bias = bb[nrow];
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
@@ -272,7 +272,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[CT<PRE
             for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int trow = mt * 32 + (r & 3) + 8 * (r >> 2);
+                    const int trow = mt * 32 + acc_row(r, 0);
                     if (!MASK || tl + trow < L)
                         ub[(size_t)trow * N + nt * 32] = from_float<elem>(gelu_tanh(acc[mt][nt][r] + bias));
                 }
@@ -289,7 +289,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[CT<PRE
             for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int trow = mt * 32 + (r & 3) + 8 * (r >> 2);
+                    const int trow = mt * 32 + acc_row(r, 0);
                     if (!MASK || tl + trow < L) {
                         float* p = hb + (size_t)trow * D + nt * 32;
                         *p = *p + (acc[mt][nt][r] + bias);
@@ -315,7 +315,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, f32x16 (&acc)[CT<PRE
                 float s = gelu_erf(acc[mt][0][r] + b1v[0]) * w2v[0] + gelu_erf(acc[mt][1][r] + b1v[1]) * w2v[1];
 #pragma unroll
                 for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                if (lrow == 0) part[wave * BM + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf] = s;
+                if (lrow == 0) part[wave * BM + mt * 32 + acc_row(r, lhalf)] = s;
             }
         __syncthreads();
         if (tid < BM && t0 + tid < L)

@@ -20,8 +20,10 @@
 //             mamba_proj_kernel<EPI_OUT / EPI_OUTPOOL>: out_proj with norm.weight folded into its columns (fp64, at finalize); the
 //             epilogue reduces the heads' sums of squares in a fixed order (the RMSNorm spans all heads), scales, adds the
 //             residual, applies the mask; the last layer writes per-64-row-tile channel sums and maxima instead of the rows.
-//   head      mamba_head_kernel: the tiles' partials in a fixed order, pooler, classifier.
+//   head      mamba_head_kernel<d>: the tiles' partials in a fixed order, pooler, classifier.
 // No atomics: the forward is bitwise deterministic and a read's logits do not depend on its batch-mates.
+// The constants, silu / softplus, ScanShape, the conv + SiLU body, the decay scan and the head's dense layer are mamba_common.h's,
+// shared with mamba_train.hip and mamba_verdict.hip.
 // clm_mamba_debug_fetch also reads the workspace itself -- "zx", "xc", "g", "ssq", "part": the LAST layer's in_proj output, conv
 // output, scan output, per-head sums of squares and pooling partials -- after a forward that ran as one chunk of reads.
 #include <cmath>
@@ -31,22 +33,17 @@
 
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "mamba_common.h"
 #include "mfma32_common.h"
 
 namespace clm {
 namespace mamba {
 
-constexpr int P = 64;              // headdim
-constexpr int Q = 64;              // scan chunk (tokens)
-constexpr int DCONV = 4;
+using namespace ssm;               // P, Q, DCONV, EPS, silu, softplus, ScanShape and the device routines shared with training (mamba_common.h)
 constexpr int VOC = 12;
-constexpr float EPS = 1e-5f;       // RMSNorm and LayerNorm
 constexpr float X3_RANGE = 65504.f;   // fp16x3 splits an activation exactly only below fp16's largest finite value
 
 enum { EPI_FRONT = 0, EPI_INPROJ = 1, EPI_OUT = 2, EPI_OUTPOOL = 3 };
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // torch's threshold 20
 
 // ------------------------------------------------------------------------------------------------ projections
 // out[row][c] = sum_k W[c][k] A[row][k] on 64-token tiles x 256 output features (8 waves x 32), K in chunks of 256 staged in LDS and
@@ -252,20 +249,7 @@ __global__ __launch_bounds__(256) void mamba_conv_kernel(const float* __restrict
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, per_row = (size_t)conv_dim / 4;
     if (i >= (size_t)rows * per_row) return;
     const size_t row = i / per_row;
-    const int c = 4 * (int)(i % per_row), t = (int)(row % L);
-    f32x4 v = *reinterpret_cast<const f32x4*>(bias + c);
-#pragma unroll
-    for (int k = 0; k < DCONV; ++k) {
-        const int tt = t - (DCONV - 1) + k;
-        if (tt >= 0) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(zx + (row - (DCONV - 1) + k) * ldz + di + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += w[(c + e) * DCONV + k] * u[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = silu(v[e]);
-    *reinterpret_cast<f32x4*>(xc + row * conv_dim + c) = v;
+    conv4_silu(zx, ldz, di, w, bias, xc, conv_dim, row, (int)(row % L), 4 * (int)(i % per_row));
 }
 
 // ------------------------------------------------------------------------------------------------ scan
@@ -290,12 +274,7 @@ struct ScanArgs {
 };
 
 template <int N>
-struct ScanShape {
-    static constexpr int NP = N < 32 ? 32 : N;     // state rows held (zero-padded)
-    static constexpr int NT = NP / 32;              // 32-row state tiles
-    static constexpr int BS = NP + 1;               // B / C row stride (floats)
-    static constexpr size_t lds_floats = (size_t)2 * Q * BS + 4 * Q + 2 * Q + 4;
-};
+constexpr size_t scan_lds_floats = (size_t)2 * Q * ScanShape<N>::BS + 4 * Q + 2 * Q + 4;   // B, C, sv | es | wj | dts, Rs, eL
 
 template <int N>
 __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (two workgroups per CU: <= 256 registers)
@@ -342,18 +321,13 @@ __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (
         for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int t = c0 + 32 * jt + 8 * (r >> 2) + 4 * lhalf + (r & 3);
+                const int t = c0 + 32 * jt + acc_row(r, lhalf);
                 xo[jt][r] = t < L ? xr_base[(size_t)t * m.ldx + hP + p0 + lrow] : 0.f;
             }
         __syncthreads();
         if (wave == 0) {                                    // cumulative decay: a fixed-order wave scan
-            float a = dts[lane] * A;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float u = __shfl_up(a, o, 64);
-                if (lane >= o) a += u;
-            }
-            const float last = __shfl(a, 63, 64);
+            float a, last;
+            decay_scan(lane, dts[lane] * A, a, last);
             sv[lane] = a;
             es[lane] = expf(a);
             wj[lane] = expf(last - a) * dts[lane];
@@ -378,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (
                 for (int s = 0; s < NP / 2; ++s) Gt = mfma32(ba[2 * s], cb[2 * s], Gt);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int j = 32 * jt + 8 * (r >> 2) + 4 * lhalf + (r & 3);
+                    const int j = 32 * jt + acc_row(r, lhalf);
                     const bool keep = j <= icol;
                     const float e = expf(keep ? si - sv[j] : 0.f);
                     Gt[r] = keep ? Gt[r] * e * dts[j] : 0.f;
@@ -396,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) yi = mfma32(S[nt][r], cb[32 * nt + 8 * (r >> 2) + (r & 3)], yi);
+                for (int r = 0; r < 16; ++r) yi = mfma32(S[nt][r], cb[32 * nt + acc_row(r, 0)], yi);
                 __builtin_amdgcn_sched_barrier(0);          // (bounds what the scheduler hoists: registers, not spills)
             }
             const float ei = es[icol];
@@ -437,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (
                 for (int jt = 0; jt < 2; ++jt) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int j = 32 * jt + 8 * (r >> 2) + 4 * lhalf + (r & 3);
+                        const int j = 32 * jt + acc_row(r, lhalf);
                         S[nt] = mfma32(Bs[j * BS + 32 * nt + lrow] * wj[j], xo[jt][r], S[nt]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -451,40 +425,41 @@ __global__ __launch_bounds__(256, 2) void mamba_scan_kernel(ScanArgs m) {   // (
 
 // ------------------------------------------------------------------------------------------------ head
 // one workgroup per read: the tiles' sums and maxima in a fixed order, pooled = (mean + max) / 2, pooler (Linear + GELU), classifier
-// (Linear + GELU + Linear); weights of the two d-wide layers transposed at finalize (coalesced)
-__global__ __launch_bounds__(512) void mamba_head_kernel(const float* __restrict__ part, int tiles, int L, int d, const float* __restrict__ wpt,
-                                                         const float* __restrict__ bp, const float* __restrict__ w0t, const float* __restrict__ b0,
-                                                         const float* __restrict__ w3, const float* __restrict__ b3, float* __restrict__ pooled,
-                                                         float* __restrict__ logits) {
-    __shared__ float Pv[512], X1[512], X2[256];
-    const int tid = threadIdx.x, b = blockIdx.x, d2 = d / 2;
-    if (tid < d) {
-        const float* src = part + (size_t)b * tiles * 2 * d + tid;
+// (Linear + GELU + Linear); DV = d threads; the d-wide layers (weights transposed at finalize: coalesced) are head_dense on one row
+template <int DV>
+__global__ __launch_bounds__(DV) void mamba_head_kernel(const float* __restrict__ part, int tiles, int L, const float* __restrict__ wpt,
+                                                        const float* __restrict__ bp, const float* __restrict__ w0t, const float* __restrict__ b0,
+                                                        const float* __restrict__ w3, const float* __restrict__ b3, float* __restrict__ pooled,
+                                                        float* __restrict__ logits) {
+    constexpr int D2 = DV / 2;
+    __shared__ __attribute__((aligned(16))) float Pv[1][DV];
+    __shared__ __attribute__((aligned(16))) float X1[1][DV];
+    __shared__ __attribute__((aligned(16))) float X2[1][D2];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    {
+        const float* src = part + (size_t)b * tiles * 2 * DV + tid;
         float s = 0.f, mx = -INFINITY;
         for (int i = 0; i < tiles; ++i) {
-            s += src[(size_t)i * 2 * d];
-            mx = fmaxf(mx, src[(size_t)i * 2 * d + d]);
+            s += src[(size_t)i * 2 * DV];
+            mx = fmaxf(mx, src[(size_t)i * 2 * DV + DV]);
         }
         const float v = (s / (float)L + mx) * 0.5f;
-        Pv[tid] = v;
-        pooled[(size_t)b * d + tid] = v;
+        Pv[0][tid] = v;
+        pooled[(size_t)b * DV + tid] = v;
     }
     __syncthreads();
-    if (tid < d) {
-        float a = bp[tid];
-        for (int c = 0; c < d; ++c) a = fmaf(wpt[(size_t)c * d + tid], Pv[c], a);
-        X1[tid] = gelu_erf(a);
+    float a;
+    head_dense<1, DV>(wpt, DV, tid, bp[tid], Pv, &a);                          // pooler.0 + GELU
+    X1[0][tid] = gelu_erf(a);
+    __syncthreads();
+    if (tid < D2) {
+        head_dense<1, DV>(w0t, D2, tid, b0[tid], X1, &a);                      // classifier.0 + GELU
+        X2[0][tid] = gelu_erf(a);
     }
     __syncthreads();
-    if (tid < d2) {
-        float a = b0[tid];
-        for (int c = 0; c < d; ++c) a = fmaf(w0t[(size_t)c * d2 + tid], X1[c], a);
-        X2[tid] = gelu_erf(a);
-    }
-    __syncthreads();
-    if (tid < NCLS) {
-        float a = 0.f;
-        for (int c = 0; c < d2; ++c) a = fmaf(w3[(size_t)tid * d2 + c], X2[c], a);
+    if (tid < NCLS) {                                                          // classifier.3: the bias last
+        a = 0.f;
+        for (int c = 0; c < D2; ++c) a = fmaf(w3[(size_t)tid * D2 + c], X2[0][c], a);
         logits[(size_t)b * NCLS + tid] = a + b3[tid];
     }
 }
@@ -500,10 +475,10 @@ void launch_proj(const ProjArgs& m, int reads, bool x3, hipStream_t st) {
 void launch_scan(const ScanArgs& m, int N, int reads, hipStream_t st) {
     const dim3 grid((unsigned)((size_t)m.H * reads)), block(256);            // (read, head) -> blockIdx.x = read * H + head
     switch (N) {
-        case 16: launch_lds<mamba_scan_kernel<16>>(grid, block, ScanShape<16>::lds_floats * 4, st, m); break;
-        case 32: launch_lds<mamba_scan_kernel<32>>(grid, block, ScanShape<32>::lds_floats * 4, st, m); break;
-        case 64: launch_lds<mamba_scan_kernel<64>>(grid, block, ScanShape<64>::lds_floats * 4, st, m); break;
-        default: launch_lds<mamba_scan_kernel<128>>(grid, block, ScanShape<128>::lds_floats * 4, st, m); break;
+        case 16: launch_lds<mamba_scan_kernel<16>>(grid, block, scan_lds_floats<16> * 4, st, m); break;
+        case 32: launch_lds<mamba_scan_kernel<32>>(grid, block, scan_lds_floats<32> * 4, st, m); break;
+        case 64: launch_lds<mamba_scan_kernel<64>>(grid, block, scan_lds_floats<64> * 4, st, m); break;
+        default: launch_lds<mamba_scan_kernel<128>>(grid, block, scan_lds_floats<128> * 4, st, m); break;
     }
 }
 
@@ -566,7 +541,7 @@ void mamba_expect(clm_mamba_handle* h) {
         const std::string p = layer_prefix(h, i);
         MambaLayer& l = h->layer[i];
         e[p + "in_proj.weight"] = {{h->n_in, d}, nullptr};
-        e[p + "conv1d.weight"] = {{h->conv_dim, 1, mamba::DCONV}, &l.conv_w}; e[p + "conv1d.bias"] = {{h->conv_dim}, &l.conv_b};
+        e[p + "conv1d.weight"] = {{h->conv_dim, 1, ssm::DCONV}, &l.conv_w}; e[p + "conv1d.bias"] = {{h->conv_dim}, &l.conv_b};
         e[p + "dt_bias"] = {{h->H}, &l.dt_bias}; e[p + "A_log"] = {{h->H}, &l.A_log}; e[p + "D"] = {{h->H}, &l.D};
         e[p + "norm.weight"] = {{h->di}, nullptr}; e[p + "out_proj.weight"] = {{d, h->di}, nullptr};
     }
@@ -605,13 +580,6 @@ int check_verdict_arg(clm_mamba_handle* h, const clm_traj_out* t, int L) {
     return CLM_OK;
 }
 
-std::vector<float> transposed(const std::vector<float>& W, int rows, int cols) {
-    std::vector<float> t((size_t)rows * cols);
-    for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = W[(size_t)r * cols + c];
-    return t;
-}
-
 }  // namespace
 
 extern "C" {
@@ -624,7 +592,7 @@ int clm_mamba_create(int device, int variant, int precision, int d_model, int n_
     if (precision != CLM_PREC_F32 && precision != CLM_PREC_F16X3)
         return fail<clm_mamba_handle>(nullptr, CLM_E_INVALID, "clm_mamba_create: precision must be CLM_PREC_F32 (exact) or CLM_PREC_F16X3");
     const bool ok = (d_model == 256 || d_model == 512) && n_layers >= 1 && (d_state == 16 || d_state == 32 || d_state == 64 || d_state == 128) &&
-                    expand >= 1 && (expand * d_model) % 64 == 0 && headdim == mamba::P && (variant == CLM_MAMBA_SP || model_max_length >= 1);
+                    expand >= 1 && (expand * d_model) % 64 == 0 && headdim == ssm::P && (variant == CLM_MAMBA_SP || model_max_length >= 1);
     if (!ok)
         return fail<clm_mamba_handle>(nullptr, CLM_E_INVALID, "clm_mamba_create: supported shapes are d_model 256 or 512, at least one layer, "
                                                               "d_state 16 / 32 / 64 / 128, headdim 64, expand >= 1 (and model_max_length >= 1 "
@@ -637,7 +605,7 @@ int clm_mamba_create(int device, int variant, int precision, int d_model, int n_
     h->d = d_model, h->n_layers = n_layers, h->N = d_state, h->expand = expand;
     h->max_len = variant == CLM_MAMBA_SEQ ? model_max_length : 0;
     h->di = expand * d_model;
-    h->H = h->di / mamba::P;
+    h->H = h->di / ssm::P;
     h->conv_dim = h->di + 2 * d_state;
     h->n_in = 2 * h->di + 2 * d_state + h->H;
     h->n_in_pad = (h->n_in + 255) / 256 * 256;
@@ -757,12 +725,8 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
             f.ids8 = id8, f.Lp = Lp, f.emb = net.emb, f.pos = net.pos, f.w = h->front.get<f32x4>(), f.K = d;
             f.out = zx, f.ldo = d, f.bias = net.front_b, f.L = L, f.tiles_x = tiles_x, f.nblocks = d / 256, f.n_real = d;
             mamba::launch_proj<mamba::EPI_FRONT>(f, n, x3, st);
-            if (d == 256)
-                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<4>, dim3(row_blocks), dim3(256), 0, st, zx, net.front_ln_g,
-                                   net.front_ln_b, mk, mask_row_stride, hs, rows, L);
-            else
-                hipLaunchKernelGGL(mamba::mamba_front_ln_kernel<8>, dim3(row_blocks), dim3(256), 0, st, zx, net.front_ln_g,
-                                   net.front_ln_b, mk, mask_row_stride, hs, rows, L);
+            hipLaunchKernelGGL(d == 256 ? mamba::mamba_front_ln_kernel<4> : mamba::mamba_front_ln_kernel<8>, dim3(row_blocks), dim3(256), 0, st,
+                               zx, net.front_ln_g, net.front_ln_b, mk, mask_row_stride, hs, rows, L);
         } else {
             hipLaunchKernelGGL(mamba::mamba_embed_kernel, dim3(row_blocks), dim3(256), 0, st, id8, Lp, net.emb, hs, rows, L, d);
         }
@@ -791,9 +755,9 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
             if (dbg && l == 0)
                 HIPCHK(h, hipMemcpyAsync(h->dbg_layer0.get<float>() + (size_t)r0 * L * d, hs, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, st));
         }
-        hipLaunchKernelGGL(mamba::mamba_head_kernel, dim3((unsigned)n), dim3(512), 0, st, h->part.get<float>(), tiles_x, L, d,
-                           h->poolert.get<float>(), net.pool_b, h->cls0t.get<float>(), net.cls0_b, net.cls3_w, net.cls3_b,
-                           h->pooled.get<float>() + (size_t)r0 * d, logits_out + (size_t)r0 * NCLS);
+        hipLaunchKernelGGL(d == 256 ? mamba::mamba_head_kernel<256> : mamba::mamba_head_kernel<512>, dim3((unsigned)n), dim3(d), 0, st,
+                           h->part.get<float>(), tiles_x, L, h->poolert.get<float>(), net.pool_b, h->cls0t.get<float>(), net.cls0_b, net.cls3_w,
+                           net.cls3_b, h->pooled.get<float>() + (size_t)r0 * d, logits_out + (size_t)r0 * NCLS);
         if (traj) {
             // the chunk's running verdict at the rows of its reads in the caller's buffers: the prefix pooling of the partials the
             // forward left, pooler and classifier over the interior points, then the chunk's own logits into the last point and the

@@ -17,29 +17,27 @@
 // Both scan kernels keep their operands in LDS (rows of 64 + 1 or N + 1 floats: row-wise and column-wise operand reads are both
 // conflict-free) and their 32 x 32 output tiles in the MFMA accumulators; the carried state (S forward, dS backward) lives in LDS
 // too and is updated in place, a tile at a time, by the wave that owns the tile.
+// What the inference kernels state alike -- constants, silu / softplus, ScanShape, the conv + SiLU body, the decay scan -- is
+// mamba_common.h's; acc_row is clm_common.h's.
 #include <algorithm>
 #include <string>
 
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "mamba_common.h"
 #include "mfma32_common.h"
 
 namespace clm {
 namespace mtrain {
 
-constexpr int P = 64;              // headdim
-constexpr int Q = 64;              // scan chunk (tokens)
-constexpr int DCONV = 4;
+using namespace ssm;               // P, Q, DCONV, EPS, silu, softplus, ScanShape and the device routines shared with inference (mamba_common.h)
 constexpr int XS = Q + 1;          // row stride (floats) of the 64-wide LDS tiles
-constexpr float EPS = 1e-5f;       // RMSNorm
 
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
 __device__ __forceinline__ float dsilu(float v) {
     const float s = sigm(v);
     return s * (1.0f + v * (1.0f - s));
 }
-__device__ __forceinline__ float softplus(float v) { return v > 20.f ? v : log1pf(expf(v)); }   // torch's threshold 20
 
 // sum over the 32 lanes of a half-wave in a fixed butterfly (every lane of the half receives it)
 __device__ __forceinline__ float half_sum(float v) {
@@ -47,17 +45,11 @@ __device__ __forceinline__ float half_sum(float v) {
     for (int o = 1; o < 32; o <<= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-// row r of an accumulator tile (lane = column lrow, register r = row 8 (r >> 2) + 4 lhalf + (r & 3))
-__device__ __forceinline__ int acc_row(int r, int lhalf) { return 8 * (r >> 2) + 4 * lhalf + (r & 3); }
-
-template <int N>
-struct Shape {
-    static constexpr int NP = N < 32 ? 32 : N;     // state rows held (zero-padded)
-    static constexpr int NT = NP / 32;
-    static constexpr int BS = NP + 1;               // B / C row stride (floats)
-    static constexpr size_t fwd_lds = ((size_t)2 * Q * XS + 2 * Q * BS + NP * XS + 4 * Q + 4) * 4;          // X, G, B, C, S, vectors
-    static constexpr size_t bwd_lds = ((size_t)3 * Q * XS + 2 * Q * BS + NP * XS + 4 * Q + 6 * Q + 2 * 4 * Q + 2 * 256 + 4) * 4;
-};
+// LDS bytes of the two scans: X, G (backward: + dys), B, C, the state, the vectors
+template <int N, int NP = ScanShape<N>::NP, int BS = ScanShape<N>::BS>
+constexpr size_t fwd_lds = ((size_t)2 * Q * XS + 2 * Q * BS + NP * XS + 4 * Q + 4) * 4;
+template <int N, int NP = ScanShape<N>::NP, int BS = ScanShape<N>::BS>
+constexpr size_t bwd_lds = ((size_t)3 * Q * XS + 2 * Q * BS + NP * XS + 4 * Q + 6 * Q + 2 * 4 * Q + 2 * 256 + 4) * 4;
 
 // ------------------------------------------------------------------------------------------------ forward
 // xc[row][c] = silu(b[c] + sum_k w[c][k] xBC[row - 3 + k][c]) inside the read (four channels per thread), dt[row][h] = softplus(raw + dt_bias)
@@ -68,26 +60,13 @@ __global__ __launch_bounds__(256) void mtrain_pre_kernel(const float* __restrict
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, per_row = (size_t)conv_dim / 4 + H;
     if (i >= rows * per_row) return;
     const size_t row = i / per_row;
-    const int k4 = (int)(i % per_row), t = (int)(row % L);
+    const int k4 = (int)(i % per_row);
     if (k4 >= conv_dim / 4) {
         const int h = k4 - conv_dim / 4;
         dt[row * H + h] = softplus(zx[row * ldz + di + conv_dim + h] + dt_bias[h]);
         return;
     }
-    const int c = 4 * k4;
-    f32x4 v = *reinterpret_cast<const f32x4*>(bias + c);
-#pragma unroll
-    for (int k = 0; k < DCONV; ++k) {
-        const int tt = t - (DCONV - 1) + k;
-        if (tt >= 0) {
-            const f32x4 u = *reinterpret_cast<const f32x4*>(zx + (row - (DCONV - 1) + k) * ldz + di + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] += w[(c + e) * DCONV + k] * u[e];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = silu(v[e]);
-    *reinterpret_cast<f32x4*>(xc + row * conv_dim + c) = v;
+    conv4_silu(zx, ldz, di, w, bias, xc, conv_dim, row, (int)(row % L), 4 * k4);
 }
 
 struct ScanArgs {
@@ -106,7 +85,7 @@ struct ScanArgs {
 // chunk loads shared by both scans: rows of the read past L stage as zeros (dt = 0: no decay, no input)
 template <int N>
 __device__ __forceinline__ void load_chunk(const ScanArgs& m, int b, int h, int c0, int tid, float* Xs, float* Bs, float* Cs, float* dts) {
-    constexpr int BS = Shape<N>::BS;
+    constexpr int BS = ScanShape<N>::BS;
     const float* xr = m.xc + (size_t)b * m.L * m.ldx;
     for (int k = tid; k < Q * P; k += 256) {
         const int i = k / P, p = k % P, t = c0 + i;
@@ -121,15 +100,10 @@ __device__ __forceinline__ void load_chunk(const ScanArgs& m, int b, int h, int 
     if (tid < Q) dts[tid] = c0 + tid < m.L ? m.dt[((size_t)b * m.L + c0 + tid) * m.H + h] : 0.f;
 }
 
-// s_i = sum_{k <= i} dt_k A in a fixed-order wave scan (wave 0): sv = s, es = exp(s), fs = exp(s_63 - s_j), eL = exp(s_63)
+// s_i = sum_{k <= i} dt_k A (wave 0; decay_scan): sv = s, es = exp(s), fs = exp(s_63 - s_j), eL = exp(s_63)
 __device__ __forceinline__ void chunk_decay(int lane, float A, const float* dts, float* sv, float* es, float* fs, float* eL) {
-    float a = dts[lane] * A;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float u = __shfl_up(a, o, 64);
-        if (lane >= o) a += u;
-    }
-    const float last = __shfl(a, 63, 64);
+    float a, last;
+    decay_scan(lane, dts[lane] * A, a, last);
     sv[lane] = a;
     es[lane] = expf(a);
     fs[lane] = expf(last - a);
@@ -140,7 +114,7 @@ __device__ __forceinline__ void chunk_decay(int lane, float A, const float* dts,
 // (only non-positive differences are exponentiated); ys = G X + exp(s_i) C S + D x; S = exp(s_63) S + (f dt B)^T X.
 template <int N>
 __global__ __launch_bounds__(256) void mtrain_scan_fwd_kernel(ScanArgs m) {
-    using SH = Shape<N>;
+    using SH = ScanShape<N>;
     constexpr int NP = SH::NP, NT = SH::NT, BS = SH::BS;
     extern __shared__ __attribute__((aligned(16))) float smem_mt[];
     float* Xs = smem_mt;                 // [Q][XS]
@@ -296,7 +270,7 @@ __global__ __launch_bounds__(256) void mtrain_gate_bwd_kernel(const float* __res
 //   ddt_j = sum_i Kl_ij + ub_j + A da_j ;  dA += sum da dt ;  dD += sum dys . x ;  dS <- e_63 dS + (e C)^T dys
 template <int N>
 __global__ __launch_bounds__(256) void mtrain_scan_bwd_kernel(ScanArgs m) {
-    using SH = Shape<N>;
+    using SH = ScanShape<N>;
     constexpr int NP = SH::NP, NT = SH::NT, BS = SH::BS;
     extern __shared__ __attribute__((aligned(16))) float smem_mt[];
     float* Xs = smem_mt;                 // [Q][XS] x
@@ -596,8 +570,8 @@ void launch_scan(const ScanArgs& m, int N, int reads, hipStream_t st) {
     const dim3 grid((unsigned)((size_t)m.H * reads)), block(256);
 #define CLM_MT_CASE(NN)                                                                                             \
     case NN:                                                                                                        \
-        if constexpr (BWD) launch_lds<mtrain_scan_bwd_kernel<NN>>(grid, block, Shape<NN>::bwd_lds, st, m);          \
-        else launch_lds<mtrain_scan_fwd_kernel<NN>>(grid, block, Shape<NN>::fwd_lds, st, m);                        \
+        if constexpr (BWD) launch_lds<mtrain_scan_bwd_kernel<NN>>(grid, block, bwd_lds<NN>, st, m);          \
+        else launch_lds<mtrain_scan_fwd_kernel<NN>>(grid, block, fwd_lds<NN>, st, m);                        \
         break;
     switch (N) {
         CLM_MT_CASE(16)
@@ -637,7 +611,7 @@ int train_dims(clm_mamba_train_handle* h, const char* who, int B, int L, int d_m
     if (!ok)
         return fail(h, CLM_E_UNSUPPORTED, w + ": supported shapes are d_model 256 or 512, d_state 16 / 32 / 64 / 128, headdim 64 and an "
                                               "integer expand in 1 ... 1024");
-    q.B = B, q.L = L, q.d = d_model, q.N = d_state, q.di = expand * d_model, q.H = q.di / mtrain::P;
+    q.B = B, q.L = L, q.d = d_model, q.N = d_state, q.di = expand * d_model, q.H = q.di / ssm::P;
     q.conv_dim = q.di + 2 * d_state, q.ldz = 2 * q.di + 2 * d_state + q.H;
     q.nch = q.tiles_x = (L + 63) / 64;
     q.rows = (size_t)B * L;

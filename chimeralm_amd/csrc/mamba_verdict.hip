@@ -15,17 +15,18 @@
 //                               boundary.  Also finds the read's n_pad.
 //   2. ssm_verdict_head_kernel  pooler, classifier.0 and classifier.3 of mamba_head_kernel over the reads x (K - 1) interior rows,
 //                               SSM_VERDICT_ROWS per workgroup: each weight of the two d-wide matrices is fetched once per group of
-//                               rows.  Per row the accumulation order is mamba_head_kernel's (bias first, fmaf over ascending input
-//                               index), so an interior point is the arithmetic of a forward of the truncated row.
+//                               rows.  The d-wide layers are mamba_common.h's head_dense, the routine mamba_head_kernel runs on its
+//                               one row (bias first, fmaf over ascending input index): an interior point is the arithmetic of a
+//                               forward of the truncated row.
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "mamba_common.h"
 
 namespace clm {
 
 namespace {
 
 constexpr int VP_AHEAD = 4;       // tile partials in flight per thread (as traj_prefix_kernel)
-constexpr int VH_PF = 8;          // weights in flight per thread of the head's dot products
 
 // part [reads][tiles][2][d]; pooled [reads][K][d]; `per` tiles per point (K = ceil(L / S), S = 64 per; the last point may be short and
 // may end in a partial tile); ids8 [reads][Lp] -> npad[b] = length of the leading run of [PAD]
@@ -86,34 +87,6 @@ __global__ __launch_bounds__(512) void ssm_verdict_pool_kernel(const float* __re
     }
 }
 
-// one layer for R rows: out[r][o] = bias[o] + sum_c wt[c][o] x[r][c], ascending c, one fmaf chain per (row, output); thread o
-template <int R, int IN>
-__device__ __forceinline__ void verdict_dense(const float* __restrict__ wt, int ldw, int o, float bias, const float (*x)[IN], float* acc) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = bias;
-    const float* w = wt + o;
-    float wa[VH_PF];
-#pragma unroll
-    for (int j = 0; j < VH_PF; ++j) wa[j] = w[(size_t)j * ldw];
-#pragma unroll 1
-    for (int c0 = 0; c0 < IN; c0 += VH_PF) {
-        float wc[VH_PF];
-        const int nx = c0 + VH_PF < IN ? c0 + VH_PF : 0;     // (wrap-around keeps the prefetch unconditional)
-#pragma unroll
-        for (int j = 0; j < VH_PF; ++j) {
-            wc[j] = wa[j];
-            wa[j] = w[(size_t)(nx + j) * ldw];
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int j = 0; j < VH_PF; j += 4) {
-                const float4 xv = *reinterpret_cast<const float4*>(&x[r][c0 + j]);
-                acc[r] = fmaf(wc[j + 3], xv.w, fmaf(wc[j + 2], xv.z, fmaf(wc[j + 1], xv.y, fmaf(wc[j], xv.x, acc[r]))));
-            }
-    }
-}
-
 // rows [n_rows][DV] of `pooled` laid out [reads][K][DV]: row r is read r / (K - 1), point r % (K - 1); logits to traj [reads][pstride][2]
 template <int DV>
 __global__ __launch_bounds__(DV) void ssm_verdict_head_kernel(const float* __restrict__ pooled, int K, int n_rows,
@@ -133,12 +106,12 @@ __global__ __launch_bounds__(DV) void ssm_verdict_head_kernel(const float* __res
     }
     __syncthreads();
     float acc[R];
-    verdict_dense<R, DV>(wpt, DV, tid, bp[tid], Pv, acc);                     // pooler.0 + GELU
+    ssm::head_dense<R, DV>(wpt, DV, tid, bp[tid], Pv, acc);                     // pooler.0 + GELU
 #pragma unroll
     for (int r = 0; r < R; ++r) X1[r][tid] = gelu_erf(acc[r]);
     __syncthreads();
     if (tid < D2) {
-        verdict_dense<R, DV>(w0t, D2, tid, b0[tid], X1, acc);                 // classifier.0 + GELU
+        ssm::head_dense<R, DV>(w0t, D2, tid, b0[tid], X1, acc);                 // classifier.0 + GELU
 #pragma unroll
         for (int r = 0; r < R; ++r) X2[r][tid] = gelu_erf(acc[r]);
     }
@@ -164,10 +137,8 @@ void launch_ssm_verdict_head(const float* pooled, int K, int n_rows, int d, cons
                              const float* b0, const float* w3, const float* b3, float* traj, int64_t pstride, hipStream_t st) {
     if (n_rows < 1) return;                                  // K = 1: no interior point
     const dim3 grid((n_rows + SSM_VERDICT_ROWS - 1) / SSM_VERDICT_ROWS);
-    if (d == 256)
-        hipLaunchKernelGGL(ssm_verdict_head_kernel<256>, grid, dim3(256), 0, st, pooled, K, n_rows, wpt, bp, w0t, b0, w3, b3, traj, pstride);
-    else
-        hipLaunchKernelGGL(ssm_verdict_head_kernel<512>, grid, dim3(512), 0, st, pooled, K, n_rows, wpt, bp, w0t, b0, w3, b3, traj, pstride);
+    hipLaunchKernelGGL(d == 256 ? ssm_verdict_head_kernel<256> : ssm_verdict_head_kernel<512>, grid, dim3(d), 0, st, pooled, K, n_rows, wpt,
+                       bp, w0t, b0, w3, b3, traj, pstride);
 }
 
 }  // namespace clm

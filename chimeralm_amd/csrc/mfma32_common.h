@@ -1,6 +1,7 @@
 // mfma32_common.h -- the 64-token tile machinery of the exact-fp32 / fp16x3 kernels, shared as device code by tail32.hip (Hyena
 // tail, transformer encoder and stem, DNAConvNet) and mamba.hip (Mamba2 projections): tile geometry, the packed weight-set pipeline,
-// the two arithmetics (AR_F32 / AR_X3) and the MFMA loops.  Moved out of tail32.hip unchanged; see the comments there for the design.
+// the two arithmetics (AR_F32 / AR_X3), the convolutions' input staging (stage_rows) and the MFMA loops.  Moved out of tail32.hip
+// unchanged; see the comments there for the design.
 #pragma once
 #include "clm_common.h"
 
@@ -69,6 +70,21 @@ __device__ __forceinline__ void tile_store4(float* T, int row, int col, f32x4 v)
         char* base = reinterpret_cast<char*>(T + row * RS32) + col * 2;
         *reinterpret_cast<h4_t*>(base) = hi;
         *reinterpret_cast<h4_t*>(base + 512) = lo;
+    }
+}
+// The implicit-GEMM convolutions' input tile: rows t0 - HALO .. t0 + 63 + HALO of one read x [Lin][256] -> Xs rows 0 .. 63 + 2 HALO,
+// zero outside [0, Lin): a wave per row, 16 bytes per lane, the eight waves in nine trips (the taps then read Xs shifted by rows)
+template <int AR, int HALO>
+__device__ __forceinline__ void stage_rows(float* Xs, const float* __restrict__ x, int t0, int Lin, int wave, int lane) {
+    const float* src = x + lane * 4;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int r = wave + 8 * i, t = t0 - HALO + r;
+        if (r < BM32 + 2 * HALO) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
+            tile_store4<AR>(Xs, r, lane * 4, v);
+        }
     }
 }
 

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512) void pool_bwd_kernel(PoolBwdArgs m) {
 #pragma unroll
         for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) orow[((r & 3) + 8 * (r >> 2)) * D + ct * 32] = dacc[ct][r];
+            for (int r = 0; r < 16; ++r) orow[acc_row(r, 0) * D + ct * 32] = dacc[ct][r];
         const int f = wave * 32 + (ln >> 1);                // = tid >> 1
         if (!(ln & 1)) {
             out[D * D + f] = db1_acc;

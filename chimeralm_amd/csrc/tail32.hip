@@ -24,6 +24,7 @@
 // (12 blocks x 256 MFMAs x 64 cycles x 2 waves per SIMD = 393k cycles per tile against ~25k of LayerNorm / GELU / epilogue VALU).
 #include "chimeralm_hip.h"
 #include "clm_common.h"
+#include "cnn_common.h"
 
 #include "mfma32_common.h"
 
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             float* zb = m.z + ((size_t)b * D3 + nb * 256 + wave * 32 + 4 * lhalf) * Lp + t0 + lrow;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int f = (r & 3) + 8 * (r >> 2);
+                const int f = acc_row(r, 0);
                 const float bias = bi[f];
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt)
@@ -462,18 +463,7 @@ __global__ __launch_bounds__(512) void conv32_kernel(Conv32Args m) {
     f32x4 ws[2][KS_SET];
     f32x16 acc[2];
     load_wset(wset_ptr(m.w, 0, D / 8, 0, wave, lane), ws[0]);
-    {
-        const float* src = m.x + (size_t)b * Lin * D + lane * 4;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const int r = wave + 8 * i, t = t0 - 1 + r;
-            if (r < BM32 + 2) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
-                tile_store4<AR>(Xs, r, lane * 4, v);
-            }
-        }
-    }
+    stage_rows<AR, 1>(Xs, m.x + (size_t)b * Lin * D, t0, Lin, wave, lane);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -518,8 +508,6 @@ struct CnnConvArgs {
     int B, Lin, tiles_x;
 };
 
-constexpr int CNN_K = 7, CNN_HALO = 3;
-
 template <bool POOLSUM, int AR = AR_F32>
 __global__ __launch_bounds__(512) void cnn_gemm7_kernel(CnnConvArgs m) {
     constexpr float WSI = WUNSCALE<AR>;
@@ -530,27 +518,16 @@ __global__ __launch_bounds__(512) void cnn_gemm7_kernel(CnnConvArgs m) {
     f32x4 ws[2][KS_SET];
     f32x16 acc[2];
     load_wset(wset_ptr(m.w, 0, D / 8, 0, wave, lane), ws[0]);
-    {
-        const float* src = m.x + (size_t)b * Lin * D + lane * 4;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const int r = wave + 8 * i, t = t0 - CNN_HALO + r;
-            if (r < BM32 + 2 * CNN_HALO) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (t >= 0 && t < Lin) v = *reinterpret_cast<const f32x4*>(src + (size_t)t * D);
-                tile_store4<AR>(Xs, r, lane * 4, v);
-            }
-        }
-    }
+    stage_rows<AR, cnn::HALO>(Xs, m.x + (size_t)b * Lin * D, t0, Lin, wave, lane);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
     __syncthreads();
-    static_for<0, CNN_K>([&](auto dkc) {
+    static_for<0, cnn::K>([&](auto dkc) {
         constexpr int dk = decltype(dkc)::value;
         const f32x4* wdk = m.w + (size_t)dk * (D * D / 4);
-        const f32x4* nxt = wset_ptr(dk + 1 < CNN_K ? m.w + (size_t)(dk + 1) * (D * D / 4) : m.w, 0, D / 8, 0, wave, lane);
+        const f32x4* nxt = wset_ptr(dk + 1 < cnn::K ? m.w + (size_t)(dk + 1) * (D * D / 4) : m.w, 0, D / 8, 0, wave, lane);
         product256<false, AR>(Xs + dk * RS32, wdk, 0, D / 8, 0, nxt, wave, lane, ws, acc);
     });
     const int c0 = wave * 32 + 4 * lhalf;
@@ -703,7 +680,7 @@ void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const fl
                       bool partial, int B, int Lin, hipStream_t st, bool x3) {
     const int Lout = Lin / 4;
     CnnConvArgs m{x, reinterpret_cast<const f32x4*>(w), bias, bn_scale, bn_shift, out, B, Lin, (4 * Lout + BM32 - 1) / BM32};
-    const size_t lds = (size_t)(BM32 + 2 * CNN_HALO) * RS32 * sizeof(float);
+    const size_t lds = (size_t)(BM32 + 2 * cnn::HALO) * RS32 * sizeof(float);
     const dim3 grid((unsigned)(m.tiles_x * B)), block(512);
     if (partial) {
         if (x3) launch_lds<cnn_gemm7_kernel<true, AR_X3>>(grid, block, lds, st, m);

@@ -18,11 +18,10 @@ import math
 import torch
 from torch import nn
 
+from ._native import X3_WEIGHT_LIMIT   # the engine measures the weights it packs as fp16x3 (clm_finalize)
 from ._reload import reload_signature
 from .engine import Engine, check_trajectory_stride
 
-# |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_finalize)
-X3_WEIGHT_LIMIT = 64.0
 _X3_PACKED = ("mixer.in_proj.weight", "mixer.out_proj.weight", "mlp.fc1.weight", "mlp.fc2.weight", "head.attention.0.weight")
 _SMALL_32K = dict(d_model=256, n_layer=4, d_inner=1024, vocab_rows=16, filter_order=64, emb_dim=5, max_seq_len=32770)
 

@@ -37,10 +37,10 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._native import X3_WEIGHT_LIMIT
 from ._reload import reload_signature
 from .engine import TrajectoryRequest, check_trajectory_stride, trajectory_out
 
-X3_WEIGHT_LIMIT = 64.0                     # |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates
 HEADDIM, D_CONV, VOCAB, PAD = 64, 4, 12, 4
 _LOG = logging.getLogger("chimeralm_amd")
 

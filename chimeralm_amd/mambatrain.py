@@ -23,10 +23,11 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from .mamba import HEADDIM, PAD, VOCAB
 
 log = logging.getLogger("chimeralm_amd")
 N_PARAMS = 6                                 # conv1d.weight, conv1d.bias, dt_bias, A_log, D, norm.weight: CLM_MAMBA_TRAIN_PARAMS
-HEADDIM, Q, VOCAB, PAD = 64, 64, 12, 4
+Q = 64                                       # tokens per scan chunk: one entry state each (csrc/mamba_common.h)
 
 
 class MambaTrainError(RuntimeError):

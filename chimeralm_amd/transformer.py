@@ -29,10 +29,9 @@ import torch
 from torch import nn
 
 from . import _native as N
+from ._native import X3_WEIGHT_LIMIT   # the engine measures the weights it packs as fp16x3 (clm_tf_finalize)
 from ._reload import reload_signature
 
-# |w| at which fp16x3's weight packing (w x 2^10 as fp16 hi + lo) saturates; the engine measures the weights it packs so (clm_tf_finalize)
-X3_WEIGHT_LIMIT = 64.0
 _X3_PACKED = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight", "cnn.0.weight",
               "cnn.3.weight", "cnn.6.weight")
 

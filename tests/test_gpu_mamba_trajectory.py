@@ -40,7 +40,7 @@ def _module(variant, sd, prec, stride=None, **shape):
     from chimeralm_amd import mamba
 
     d, nl, ds, ex, mml = mr.VARIANTS[variant]
-    d, nl = shape.get("d_model") or d, shape.get("n_layers") or nl
+    d, nl, ds = shape.get("d_model") or d, shape.get("n_layers") or nl, shape.get("d_state") or ds
     if variant == "mamba":
         net = mamba.MambaSequenceClassification(vocab_size=12, embedding_dim=d, number_of_layers=nl, model_max_length=mml, dropout=0.1,
                                                 number_of_classes=2, d_state=ds, expand=ex, precision=prec, trajectory_stride=stride)
@@ -139,6 +139,25 @@ def test_other_channel_widths(built_lib, variant, d_model):
         logits, traj, summary = _forward(net, ids, 128)
         _check_against(ref, logits, traj, summary, ids, 128, f"{variant} d_model {d_model} {prec}")
         net.close()
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16x3"])
+@pytest.mark.parametrize("variant,n_layers", [("mamba", 2), ("mambasp", 1)])
+def test_interior_points_are_the_forward_of_the_cut_row_bit_for_bit(built_lib, variant, n_layers, prec):
+    """The forward's head and the verdict's head run one dense routine (csrc/mamba_common.h head_dense), and everything in front
+    of the pooling is causal per 64-token tile: interior point k IS the logits of a forward of the rows cut at (k + 1) * stride."""
+    sd = mr.make_mamba_state_dict(variant, 35, d_state=16, n_layers=n_layers)
+    ids = mr.synthetic_ids(3500, 2, 384, pads=17)
+    net = _module(variant, sd, prec, n_layers=n_layers, d_state=16)
+    logits, traj, _ = _forward(net, ids, 128)
+    assert traj.shape == (2, 3, 2) and np.isfinite(traj).all() and np.array_equal(traj[:, 2], logits)
+    net.trajectory_stride = None
+    for k in range(2):
+        cut = net(torch.tensor(ids[:, :(k + 1) * 128]).cuda()).cpu().numpy()
+        print(f"{variant} {prec} point {k}: max |traj - forward of the cut row| = {np.abs(traj[:, k] - cut).max():.2e}")
+        assert np.array_equal(traj[:, k], cut), (variant, prec, k)
+    assert np.abs(traj[:, 0] - traj[:, 1]).max() > 1e-6                        # (the points differ)
+    net.close()
 
 
 # ------------------------------------------------------------------------------------------------ chunks, determinism, placement
