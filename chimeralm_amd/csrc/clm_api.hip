@@ -131,6 +131,7 @@ struct clm_handle {
     DevBuf fir[NLAYER];           // float4 [256][3]
     DevBuf edge_bnd, edge_read;   // float2
     bool raw_z = false;           // CLM_DEBUG=raw_z: the fused in_proj stage writes x0 | x1 | v as before round 3 (A/B runs, tests)
+    bool row_h = false;           // CLM_DEBUG=row_h: the fused 16-bit tail kernels keep h in row order in every tile (A/B runs, tests)
     DevBuf head_t[5];
     HeadW hw{};
     std::vector<FilterSet> filters;
@@ -168,6 +169,7 @@ struct clm_handle {
     bool no_pad_skip = false;                       // CLM_DEBUG=no_pad_skip: every tile of every read is computed (A/B runs, tests)
     bool no_seg_skip = false;                       // CLM_DEBUG=no_seg_skip: ... but every segment of the long-read convolution is transformed
     int last_B = 0, last_L = 0, last_Lp = 0;
+    int last_hreg_Lmain = 0;      // > 0: the last chunk left the 128-token tiles of rows [0, Lmain) of h in register order (ChunkPlan::hreg)
     // The final residual rows as an output (clm_rows; the head fine-tune, pool_train.hip): what the last forward left in `h`, and a
     // counter that moves whenever anything may have rewritten that buffer (every chunk of every forward, a weight reload)
     struct RowsState {
@@ -352,7 +354,7 @@ struct ChunkPlan {
     int Bc, L, prec, Lp, Lmain, S, nt128, nt_pool;
     size_t es;
     bool tuned16, fused16, fused32, fused, unfused32, alt32, x3, mlpc, lo, keep_lo;
-    bool id_conv, id_resid, peel, zgated, pad_skip, seg_tables, seg_skip[NLAYER];
+    bool id_conv, id_resid, peel, zgated, hreg, pad_skip, seg_tables, seg_skip[NLAYER];
 };
 
 ChunkPlan plan_chunk(const clm_handle* h, int Bc, int L) {
@@ -394,6 +396,11 @@ ChunkPlan plan_chunk(const clm_handle* h, int Bc, int L) {
     // is fp32 -- and h is first written by block 0's tail kernel, as in the 16-bit id path
     p.id_conv = !h->no_idconv && ((p.tuned16 && !stop_here(h, 0, CLM_STAGE_INPROJ)) || (p.fused32 && p.S == 1));
     p.id_resid = !h->no_idconv && (p.fused16 || (p.fused32 && p.S == 1));
+    // The fused 16-bit tail kernels hand h from launch to launch inside each 128-token tile's own 128 KiB in the order of the
+    // accumulator registers (gemm16.hip HREG): the lane that stores a value is the lane that loads it one launch later.  Whole tiles
+    // only (a partial last tile's block would run into the next read's rows), and only where block 0 gathers its residual from the
+    // embedding table, so that no launch of the forward reads rows another kernel wrote; every launch of a forward agrees
+    p.hreg = p.fused16 && p.id_resid && !h->row_h && p.Lmain % 128 == 0;
     // Round 5: tiles wholly inside a read's [PAD] prefix are not computed, their rows come from the all-[PAD] table (pad_prefix.hip).
     // In the fused paths only (the debug / unfused paths keep computing everything), never inside the forward that fills a table,
     // and only for reads long enough to hold a whole prefix tile next to a real token.
@@ -670,6 +677,7 @@ int size_workspace(ChunkCtx& c, const clm_traj_out* traj = nullptr) {
         }
     }
     h->last_B = p.Bc; h->last_L = p.L; h->last_Lp = p.Lp;
+    h->last_hreg_Lmain = p.hreg ? p.Lmain : 0;
     h->rows.valid = false;                   // (this chunk rewrites the residual rows: whoever held them must not read them again)
     ++h->rows.generation;
     if (h->ws_es != p.es) {                  // fp16c: fp32 and fp16 chunks share z / y -- what one type left in the padding
@@ -761,6 +769,7 @@ int tail16(ChunkCtx& c, int i, const BlockW& w) {
                 nullptr, nullptr, nullptr, nullptr, nullptr, spa};
     ta.ylo = c.ylo();
     ta.mlp_lo = p.mlpc;
+    ta.hreg = p.hreg;
     ta.tiles = h->tile_list.get<int>();
     const BlockF32* nf = last ? nullptr : &h->blk[i + 1];
     if (p.fused16 && !last) {
@@ -1047,6 +1056,8 @@ int clm_create(const clm_config* cfg, int device, clm_handle** out) {
     if (debug_flag("conv_no_xcd")) h->conv_flags |= CONV_NO_XCD;
     h->raw_z = debug_flag("raw_z");                    // the fused in_proj stage writes x0 | x1 | v as before round 3
     h->no_pad_skip = debug_flag("no_pad_skip");        // tiles inside a read's [PAD] prefix are computed like any other
+    h->row_h = debug_flag("row_h") || debug_flag("stamp");   // the fused 16-bit tail kernels keep h in row order inside every tile
+                                                             // (the stamped developer build of the tail kernel exists in that form only)
     h->no_seg_skip = debug_flag("no_seg_skip");        // ... and segments inside it are transformed like any other (pad_prefix.hip, SegPrefix)
     h->cfg = *cfg;
     if (cfg->precision == CLM_PREC_F16X3) {             // an exact-fp32 engine whose fused tails multiply hi + lo halfs
@@ -1375,6 +1386,25 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
     if (!src) return fail(h, CLM_E_INVALID, "clm_debug_fetch: unknown or empty buffer " + n);
     if (bytes > have) return fail(h, CLM_E_INVALID, "clm_debug_fetch: " + n + " holds only " + std::to_string(have) + " bytes");
     HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    if (src == h->h.get<float>() && h->last_hreg_Lmain > 0) {
+        // the tail kernels left the whole tiles in register order (gemm16.hip HREG): [mt][q][thread][4 floats] inside each tile's
+        // 128 KiB, thread = (wave, lhalf, lrow), value = token 32 mt + lrow, feature 32 wave + 8 q + 4 lhalf + j -- back to rows here
+        constexpr size_t TILE = (size_t)128 * D;
+        std::vector<float> blk(TILE);
+        float* const out = static_cast<float*>(host_out);
+        const size_t nf = bytes / 4;
+        for (size_t b = 0; b < B; ++b)
+            for (size_t t0 = 0; t0 + 128 <= (size_t)h->last_hreg_Lmain; t0 += 128) {
+                const size_t base = (b * L + t0) * D;
+                if (base >= nf) break;
+                if (base + TILE <= nf) std::copy(out + base, out + base + TILE, blk.begin());
+                else HIPCHK(h, hipMemcpy(blk.data(), h->h.get<float>() + base, TILE * 4, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < TILE && base + i < nf; ++i) {
+                    const size_t t = i / D, f = i % D, mt = t / 32, lrow = t % 32, wave = f / 32, q = f % 32 / 8, lhalf = f % 8 / 4, j = f % 4;
+                    out[base + i] = blk[((mt * 4 + q) * 512 + wave * 64 + lhalf * 32 + lrow) * 4 + j];
+                }
+            }
+    }
     return CLM_OK;
 }
 

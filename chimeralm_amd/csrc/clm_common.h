@@ -473,6 +473,11 @@ struct TailArgs {
     const unsigned char* ylo; // [B][256][Lp] lo bytes of y, written by the convolution (null: y is plain fp16)
     int zlo;                  // zg only: the gated in_proj stage also writes the lo bytes of x0f | g into rows 512.. of n_z ([2][256][Lp])
     int mlp_lo;               // PREC_F16C: w1 / w2 are packed as hi + lo too (tail16_kernel MLPC) instead of plain fp16
+    // Fused launches over whole tiles only (Lmain % 128 == 0): the 128 x 256 floats of tile (b, t0) keep their 128 KiB of h,
+    // h + (b L + t0) 256, but lie there as [mt 0..3][q 0..3][thread 0..511][4 floats] = the thread's acc2[mt][4 q .. 4 q + 3]
+    // (tail16_kernel HREG): stored by one launch and loaded by the next without a transposition.  Rows outside the tiles (the
+    // peeled lone token's) stay rows; block 0 still gathers from emb.  Every launch of a forward carries the same value.
+    int hreg;
     // Round 5 (pad_prefix.hip): the tiles this launch computes, as a device list -- tiles[0] = their number, tiles[1 + j] = entry j
     // (tile_entry / tile_b / tile_tx / tile_cont below), reads in order, tiles of a read ascending and contiguous from its first
     // computed tile on.  Tiles wholly inside a read's [PAD] prefix are not in it: their rows come from the all-[PAD] table.

@@ -25,9 +25,31 @@
 #include <cstdlib>
 #include <vector>
 
+#include "clm_lab.h"
 #include "gemm16_common.h"
 
 namespace clm {
+
+// 16-byte accesses of the tail kernel's once-touched streams, non-temporal where NT says so (tail16_kernel NTM)
+enum { NT_H_LOAD = 1, NT_H_STORE = 2, NT_Y = 4, NT_YLO = 8, NT_Z = 16, NT_ZLO = 32 };
+template <bool NT, typename V>
+__device__ __forceinline__ V stream_load(const V* p) {
+    if constexpr (NT) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        static_assert(sizeof(V) == 16, "16-byte vectors");
+        return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
+    } else
+        return *p;
+}
+template <bool NT, typename V>
+__device__ __forceinline__ void stream_store(V* p, const V v) {
+    if constexpr (NT) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        static_assert(sizeof(V) == 16, "16-byte vectors");
+        __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4*>(p));
+    } else
+        *p = v;
+}
 
 // h[b, t, 32 features of this wave] += acc + bias.  Accumulator rows = output features (lane = token, register quad =
 // 4 consecutive features).  Storing straight from that layout makes every wave instruction touch 64 different cache
@@ -335,7 +357,7 @@ __device__ __forceinline__ void zg_fir_range(f32x16 (&a)[4], const float4 f, flo
 }
 
 // tokens [64 hf, 64 hf + 64) of the wave's 32 channels: halfs to byte-row-free z row `row0 + lrow`, lo bytes to lo-plane row `row0 + lrow`
-template <int HF>
+template <int HF, int NTM = 0>
 __device__ __forceinline__ void zg_store_half(const f32x16 (&a)[4], f16_t* zs, void* zout, int b, int row0, int t0, int Lp, int lane_in) {
     constexpr int RSH = 72, RS8 = 80;                        // staged rows: 64 halfs + 8; 64 lo bytes + 16 (16-byte aligned rows)
     static_assert(32 * RSH * 2 <= ZG_WAVE_BYTES && 32 * RS8 <= ZG_WAVE_BYTES, "both stagings fit the wave's tile");
@@ -363,7 +385,7 @@ __device__ __forceinline__ void zg_store_half(const f32x16 (&a)[4], f16_t* zs, v
         for (int i = 0; i < 4; ++i) {
             const int row = i * 8 + (lane >> 3);
             const uint4 v = *reinterpret_cast<const uint4*>(zs + row * RSH + col8);
-            if (in_row) *reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8) = v;
+            if (in_row) stream_store<(NTM & NT_Z) != 0>(reinterpret_cast<uint4*>(zg + (size_t)row * Lp + col8), v);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -380,13 +402,13 @@ __device__ __forceinline__ void zg_store_half(const f32x16 (&a)[4], f16_t* zs, v
         for (int i = 0; i < 2; ++i) {
             const int row = i * 16 + (lane >> 2);
             const uint4 v = *reinterpret_cast<const uint4*>(z8 + row * RS8 + col16);
-            if (in_row) *reinterpret_cast<uint4*>(zl + (size_t)row * Lp + col16) = v;
+            if (in_row) stream_store<(NTM & NT_ZLO) != 0>(reinterpret_cast<uint4*>(zl + (size_t)row * Lp + col16), v);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <typename Hook>
+template <int NTM = 0, typename Hook>
 __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const unsigned char* Al, unsigned char* Zs, float* halo,
                                                        const u16x8* wp, const TailArgs& m, const GatedTile gt, int b, int t0, int wave,
                                                        int lane, u16x8 (&bs)[2][1][SETK], f32x16 (&accv)[4], f32x16 (&accx)[4],
@@ -460,7 +482,7 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) accv[mt][r] *= accx[mt][r];
-        zg_store_half<0>(accv, zs, m.n_z, b, 256 + wave * 32, t0, m.Lp, lane);
+        zg_store_half<0, NTM>(accv, zs, m.n_z, b, 256 + wave * 32, t0, m.Lp, lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) accv[2][r] = 0.f, accv[3][r] = 0.f;
         phase_tm<PREC, K, K, false, false, NoHook, PREC_SAME, true, 2, 2>(As, wp, q, 0, wp, 0, 0, wave, lane, bs, accv, NoHook(), 0, Al);
@@ -470,7 +492,7 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         for (int mt = 2; mt < 4; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) accv[mt][r] *= accx[mt][r];
-        zg_store_half<1>(accv, zs, m.n_z, b, 256 + wave * 32, t0, m.Lp, lane);
+        zg_store_half<1, NTM>(accv, zs, m.n_z, b, 256 + wave * 32, t0, m.Lp, lane);
     }
     // ---- x0 (block 0), all four row tiles, in accx (x1f is dead)
     {
@@ -490,8 +512,8 @@ __device__ __forceinline__ void inproj_blocks_gated_lo(const f16_t* As, const un
         leave_tail(q, c, hs, make_float2(accx[3][14], accx[3][15]));
         leave_head(q, c, make_float2(accx[0][0], accx[0][1]));
         zg_fir_inplace<PREC>(accx, firq, p2, p3, lane);
-        zg_store_half<0>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
-        zg_store_half<1>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
+        zg_store_half<0, NTM>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
+        zg_store_half<1, NTM>(accx, zs, m.n_z, b, wave * 32, t0, m.Lp, lane);
     }
 }
 
@@ -714,28 +736,40 @@ constexpr int TAIL_NSTAMP = 28;      // 0..20 phase boundaries, 21..26 the six h
 
 // residual rows of tile (b, t0) in accumulator layout (block 0 of the id path: embedding rows by token id); one piece =
 // the 32 token rows of one accumulator tile
+// HREG (TailArgs::hreg): the launch before this one stored the tile in register order -- hv[mt][q] is the thread's own 16 bytes of
+// slot [mt][q], a wave-wide load reads 1 KiB of whole lines (from rows: 32 lines, 32 bytes of each, and four instructions per line)
+template <bool HREG = false, int NTM = 0>
 __device__ __forceinline__ void tail_load_resid_piece(const TailArgs& m, float4 (&hv)[4], int mt, int b, int t0, int wave,
                                                       int lrow, int lhalf) {
+    if constexpr (HREG) {
+        if (!m.ids8) {                                       // (uniform)
+            const float* slot = m.h + ((size_t)b * m.L + t0) * D + (size_t)(mt * 4 * 512 + wave * 64 + lhalf * 32 + lrow) * 4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) hv[q] = stream_load<(NTM & NT_H_LOAD) != 0>(reinterpret_cast<const float4*>(slot + q * 512 * 4));
+            return;
+        }
+    }
     const int t = t0 + mt * 32 + lrow, tc = t < m.L ? t : 0;
     const float* row = m.ids8 ? m.emb + (size_t)m.ids8[(size_t)b * m.Lp + tc] * D + wave * 32 + 4 * lhalf
                               : m.h + ((size_t)b * m.L + tc) * D + wave * 32 + 4 * lhalf;
 #pragma unroll
     for (int q = 0; q < 4; ++q) hv[q] = *reinterpret_cast<const float4*>(row + 8 * q);
 }
+template <bool HREG = false, int NTM = 0>
 __device__ __forceinline__ void tail_load_resid(const TailArgs& m, float4 (&hv)[4][4], int b, int t0, int wave, int lrow,
                                                 int lhalf) {
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) tail_load_resid_piece(m, hv[mt], mt, b, t0, wave, lrow, lhalf);
+    for (int mt = 0; mt < 4; ++mt) tail_load_resid_piece<HREG, NTM>(m, hv[mt], mt, b, t0, wave, lrow, lhalf);
 }
 // hook for inproj_blocks: the four pieces of the next tile's residual, one per half-block
 // ... and the next tile's y tile (8 x 16 bytes per thread) behind the last two
-template <typename E>
+template <typename E, int NTM = 0>
 __device__ __forceinline__ void tail_load_y_piece(const TailArgs& m, uint4 (&yx)[8], int half, int b, int t0, int tid) {
     const E* src = reinterpret_cast<const E*>(m.y) + (size_t)b * D * m.Lp + t0;
     const int tk = (tid & 15) * 8, tkc = t0 + tk < m.Lp ? tk : 0;   // clamped, branch-free; masked at the LDS store
 #pragma unroll
     for (int i = 4 * half; i < 4 * half + 4; ++i)
-        yx[i] = *reinterpret_cast<const uint4*>(src + (size_t)((tid >> 4) + 32 * i) * m.Lp + tkc);
+        yx[i] = stream_load<(NTM & NT_Y) != 0>(reinterpret_cast<const uint4*>(src + (size_t)((tid >> 4) + 32 * i) * m.Lp + tkc));
 }
 // Round 4 (fp16c): the y tile's lo bytes, [256 channels][128 tokens] in HBM as y itself.  A thread takes 4 channels x 16 tokens
 // (four 16-byte loads, then 4 x 4 byte transposes into the token-major lo tile).  Thread -> (4-channel column cg, 16-token run):
@@ -748,11 +782,12 @@ __device__ __forceinline__ void tail_load_y_piece(const TailArgs& m, uint4 (&yx)
 // thread -> (4-channel column, 16-token run) of the y lo tile
 __device__ __forceinline__ int ylo_cg(int tid) { return (tid & 15) + 16 * ((tid >> 6) & 3); }
 __device__ __forceinline__ int ylo_tk(int tid) { return 16 * (((tid >> 4) & 3) + 4 * (tid >> 8)); }
+template <int NTM = 0>
 __device__ __forceinline__ void tail_load_ylo(const TailArgs& m, uint4 (&yl)[4], int b, int t0, int tid) {
     const int cg = ylo_cg(tid), tk = ylo_tk(tid), tkc = t0 + tk < m.Lp ? tk : 0;   // clamped, masked at the LDS store
     const unsigned char* src = m.ylo + ((size_t)b * D + 4 * cg) * m.Lp + t0 + tkc;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) yl[r] = *reinterpret_cast<const uint4*>(src + (size_t)r * m.Lp);
+    for (int r = 0; r < 4; ++r) yl[r] = stream_load<(NTM & NT_YLO) != 0>(reinterpret_cast<const uint4*>(src + (size_t)r * m.Lp));
 }
 // ... and turns them into the token-major lo tile the MFMA reads (RSL, lo_pos): per token quad a 4 x 4 byte transpose in
 // registers (8 v_perm_b32), then one dword (4 consecutive channels) per token.
@@ -780,7 +815,7 @@ __device__ __forceinline__ void tail_stage_ylo(unsigned char* Aly, const uint4 (
 // tile, and a scratch reload with its own vmcnt(0) in the next tile's out_proj epilogue).  All four are requested when the
 // stage's accumulators are dead (tail16_kernel, after inproj_blocks); same-box timings of the in_proj variant with 2 / 1 / 0
 // pieces in the hooks: 1.437 / 1.428 / 1.407 ms per launch.
-template <typename E, int PIECES, int NYL = 1>
+template <typename E, int PIECES, int NYL = 1, bool HREG = false, int NTM = 0>
 struct ResidHook {
     const TailArgs& m;
     float4 (&hv)[4][4];
@@ -790,19 +825,25 @@ struct ResidHook {
     unsigned long long* stamp;                             // developer build only (nullptr otherwise)
     __device__ __forceinline__ void operator()(int step) const {
         if (stamp && tid == 0) stamp[21 + step] = __builtin_amdgcn_s_memtime();
-        if (step < PIECES) tail_load_resid_piece(m, hv[step], step, b, t0, wave, lrow, lhalf);
+        if (step < PIECES) tail_load_resid_piece<HREG, NTM>(m, hv[step], step, b, t0, wave, lrow, lhalf);
         else if (step >= 4) {
-            tail_load_y_piece<E>(m, yx, step - 4, b, t0, tid);
+            tail_load_y_piece<E, NTM>(m, yx, step - 4, b, t0, tid);
             if constexpr (NYL == 4) {
-                if (step == 5) tail_load_ylo(m, yl, b, t0, tid);
+                if (step == 5) tail_load_ylo<NTM>(m, yl, b, t0, tid);
             }
         }
     }
 };
 
 // MLPC (fp16c only): fc1 / fc2 on hi + lo weights as well (TailArgs::mlp_lo; w1 / w2 are then packed as PREC_F16C).
-template <int PREC, bool STAMP = false, int NEXT = NEXT_NONE, bool ZG = false, bool MLPC = false>
+// HREG (TailArgs::hreg; fused launches over whole tiles): h lies inside each tile's 128 KiB in register order, see TailArgs.  No
+// LDS transposition and no barrier in front of the store, every line of h touched by one instruction -- on its own worth nothing
+// (same-box alternation, profiles/r06_h_order.txt), but it is what lets the stream be marked non-temporal (NTM): -3 % together.
+template <int PREC, bool STAMP = false, int NEXT = NEXT_NONE, bool ZG = false, bool MLPC = false, bool HREG = false>
 __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long long* stamps) {
+    static_assert(!HREG || NEXT != NEXT_NONE, "register-order tiles are handed from fused launch to fused launch");
+    // which of the once-touched streams are non-temporal (NT_*): lab::NT_MASK says what was measured -- in this form and mode only
+    constexpr int NTM = (HREG && PREC == PREC_F16C) ? lab::NT_MASK : 0;
     static_assert(!MLPC || PREC == PREC_F16C, "compensated MLP weights are a form of the fp16c mode");
     static_assert(!ZG || NEXT == NEXT_INPROJ, "the gated hand-over is a form of the fused in_proj stage");
 #define CLM_STAMP_AT(k)                                                                                   \
@@ -869,10 +910,10 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
     static_assert((size_t)D * RSKM * 2 % 16 == 0 && (size_t)D * RSKM * 2 + 128 * RSL <= (size_t)2 * BM * RS16 * 2, "y lo tile fits behind the y tile");
     {
         const int e0 = tlist[tile_begin], fb = tile_b(e0), ft0 = tile_tx(e0) * BM;
-        tail_load_resid(m, hv, fb, ft0, (int)threadIdx.x >> 6, (int)threadIdx.x & 31, ((int)threadIdx.x >> 5) & 1);
-        tail_load_y_piece<elem>(m, yx, 0, fb, ft0, threadIdx.x);
-        tail_load_y_piece<elem>(m, yx, 1, fb, ft0, threadIdx.x);
-        if constexpr (LOY) tail_load_ylo(m, yl, fb, ft0, threadIdx.x);
+        tail_load_resid<HREG, NTM>(m, hv, fb, ft0, (int)threadIdx.x >> 6, (int)threadIdx.x & 31, ((int)threadIdx.x >> 5) & 1);
+        tail_load_y_piece<elem, NTM>(m, yx, 0, fb, ft0, threadIdx.x);
+        tail_load_y_piece<elem, NTM>(m, yx, 1, fb, ft0, threadIdx.x);
+        if constexpr (LOY) tail_load_ylo<NTM>(m, yl, fb, ft0, threadIdx.x);
     }
 #pragma unroll 1
     for (int tile = tile_begin; tile < tile_end; ++tile) {
@@ -972,9 +1013,13 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
         phase_tm<PF, DI, D, true, true, NoHook, PREC_RAWNEXT>(Hs, w2, 0, j, nxt, 0, 0, wave, lane, bs, acc2);
         CLM_STAMP_AT(7 + 3 * j);
     }
-    __syncthreads();                                       // As / Hs are dead: reuse them as the staging tiles
+    // As / Hs are dead: reuse them as the staging tiles.  HREG stages nothing, and nothing else leans on this barrier: between here
+    // and the first barrier inside ln_acc_to_tile below a wave touches Bt (read-only since the prologue) and its own rows of P1 (last
+    // read in LayerNorm-2, eight barriers ago); As, the lo tile and P2 are written behind that barrier, which every wave reaches only
+    // with its last fc2 reads of Hs done
+    if constexpr (!HREG || lab::HREG_BARRIER) __syncthreads();
     CLM_STAMP_AT(17);
-    // ---- 5. h_new = acc2 + b2: transposed through LDS, stored as whole 128-byte lines (no read)
+    // ---- 5. h_new = acc2 + b2: transposed through LDS, stored as whole 128-byte lines (no read); HREG: straight from the registers
     {
         const float* b2p = Bt + BT_B2 + wave * 32 + 4 * lhalf;
 #pragma unroll
@@ -989,7 +1034,15 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
             }
         }
         // (the last block's output is consumed on chip by the score / pooling stage below and by nothing else: not stored)
-        if constexpr (NEXT != NEXT_SCORE) {
+        if constexpr (NEXT != NEXT_SCORE && HREG) {         // slot [mt][q]: one contiguous 8 KiB per instruction across the workgroup
+            float* slot = m.h + ((size_t)b * L + t0) * D + (size_t)tid * 4;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    stream_store<(NTM & NT_H_STORE) != 0>(reinterpret_cast<float4*>(slot + (mt * 4 + q) * 512 * 4),
+                                 make_float4(acc2[mt][4 * q + 0], acc2[mt][4 * q + 1], acc2[mt][4 * q + 2], acc2[mt][4 * q + 3]));
+        } else if constexpr (NEXT != NEXT_SCORE) {
             float* rs = reinterpret_cast<float*>(smem) + wave * (128 * 32);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
@@ -1016,10 +1069,10 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
     const int nentry = tlist[tile + 1 < tile_end ? tile + 1 : tile];
     const int nb_ = tile_b(nentry), nt0 = tile_tx(nentry) * BM;
     if constexpr (NEXT == NEXT_NONE) {
-        tail_load_resid(m, hv, nb_, nt0, wave, lrow, lhalf);
-        tail_load_y_piece<elem>(m, yx, 0, nb_, nt0, tid);
-        tail_load_y_piece<elem>(m, yx, 1, nb_, nt0, tid);
-        if constexpr (LOY) tail_load_ylo(m, yl, nb_, nt0, tid);
+        tail_load_resid<HREG, NTM>(m, hv, nb_, nt0, wave, lrow, lhalf);
+        tail_load_y_piece<elem, NTM>(m, yx, 0, nb_, nt0, tid);
+        tail_load_y_piece<elem, NTM>(m, yx, 1, nb_, nt0, tid);
+        if constexpr (LOY) tail_load_ylo<NTM>(m, yl, nb_, nt0, tid);
     }
     // ---- 6. what follows, on the tile still in registers
     if constexpr (NEXT != NEXT_NONE) {
@@ -1049,25 +1102,25 @@ __global__ __launch_bounds__(512) void tail16_kernel(TailArgs m, unsigned long l
                 const GatedTile gt{tile == tile_begin || !cont, tile == tile_begin && cont,
                                    tile + 1 == tile_end && tile + 1 < total && tile_cont(tlist[tile + 1 < total ? tile + 1 : tile]),
                                    tx == tiles_x - 1 && m.edge_read != nullptr, (int)blockIdx.x};
-                const ResidHook<elem, PIECES, LOY ? 4 : 1> rhook{m, hv, yx, yl, nb_, nt0, wave, lrow, lhalf, tid,
+                const ResidHook<elem, PIECES, LOY ? 4 : 1, HREG, NTM> rhook{m, hv, yx, yl, nb_, nt0, wave, lrow, lhalf, tid,
                                                                  STAMP ? stamps + (size_t)tile * TAIL_NSTAMP : nullptr};
                 if constexpr (PREC == PREC_F16C)
-                    inproj_blocks_gated_lo(As, Alf, Alf + 128 * RSL, Bt + BT_NB, wn, m, gt, b, t0, wave, lane, bs, acc1, acc2, rhook);
+                    inproj_blocks_gated_lo<NTM>(As, Alf, Alf + 128 * RSL, Bt + BT_NB, wn, m, gt, b, t0, wave, lane, bs, acc1, acc2, rhook);
                 else
                     inproj_blocks_gated<PREC>(As, Hs, Bt + BT_NB, wn, m, gt, b, t0, wave, lane, bs, acc1, acc2, rhook);
             } else
             inproj_blocks<PREC>(As, Hs, wn, Bt + BT_NB, m.n_z, b, t0, Lp, wave, lane, bs, acc1,
-                                ResidHook<elem, PIECES, LOY ? 4 : 1>{m, hv, yx, yl, nb_, nt0, wave, lrow, lhalf, tid,
+                                ResidHook<elem, PIECES, LOY ? 4 : 1, HREG, NTM>{m, hv, yx, yl, nb_, nt0, wave, lrow, lhalf, tid,
                                                                      STAMP ? stamps + (size_t)tile * TAIL_NSTAMP : nullptr});
 #pragma unroll
-            for (int mt = PIECES; mt < 4; ++mt) tail_load_resid_piece(m, hv[mt], mt, nb_, nt0, wave, lrow, lhalf);
+            for (int mt = PIECES; mt < 4; ++mt) tail_load_resid_piece<HREG, NTM>(m, hv[mt], mt, nb_, nt0, wave, lrow, lhalf);
         } else {
             score_pool_tile<PREC, LOF>(m.sp, As, reinterpret_cast<float*>(Hs), b, tx, tid, bs, acc1, Alf);
             // (requested before the score stage these 96 registers spill through its erf epilogue: one launch in four)
-            tail_load_resid(m, hv, nb_, nt0, wave, lrow, lhalf);
-            tail_load_y_piece<elem>(m, yx, 0, nb_, nt0, tid);
-            tail_load_y_piece<elem>(m, yx, 1, nb_, nt0, tid);
-            if constexpr (LOY) tail_load_ylo(m, yl, nb_, nt0, tid);
+            tail_load_resid<HREG, NTM>(m, hv, nb_, nt0, wave, lrow, lhalf);
+            tail_load_y_piece<elem, NTM>(m, yx, 0, nb_, nt0, tid);
+            tail_load_y_piece<elem, NTM>(m, yx, 1, nb_, nt0, tid);
+            if constexpr (LOY) tail_load_ylo<NTM>(m, yl, nb_, nt0, tid);
         }
         CLM_STAMP_AT(20);
     }
@@ -1156,6 +1209,12 @@ void tail16_dump_stamps() {
 template <int PREC, int NEXT, bool ZG = false, bool MLPC = false>
 static void launch_tail_inst(const TailArgs& m, dim3 grid, size_t lds, hipStream_t st) {
     if (ZG) lds += (size_t)(ZG_HALO_FLOATS - D3) * 4;        // the stash takes the in_proj bias table's place and 3 KiB more
+    if constexpr (NEXT != NEXT_NONE) {                       // (the fused launches: h in register order where the plan says so)
+        if (m.hreg) {
+            launch_lds<tail16_kernel<PREC, false, NEXT, ZG, MLPC, true>>(grid, dim3(512), lds, st, m, (unsigned long long*)nullptr);
+            return;
+        }
+    }
     launch_lds<tail16_kernel<PREC, false, NEXT, ZG, MLPC>>(grid, dim3(512), lds, st, m, (unsigned long long*)nullptr);
 }
 

@@ -4,12 +4,11 @@
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/chimeralm_amd/csrc; name=$1; shift
 T=$(mktemp -d)
-srcs="clm_api gemm gemm16 tail32 hyena_conv head pad_prefix lone_token attention tf_model tf_fp32"
+# (the product's own source list: chimeralm_amd/build.py SOURCES)
+srcs=$(cd $R && python3 -c "from chimeralm_amd.build import SOURCES; print(' '.join(SOURCES))")
 for s in $srcs; do
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-function -Wno-pass-failed "$@" -I$R/include -I$C -c $C/$s.hip -o $T/$s.o &
-done
-for s in bam_feeder bam_filter; do
-  hipcc -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-function "$@" -I$R/include -I$C -c $C/$s.cpp -o $T/$s.o &
+  arch="--offload-arch=gfx950 -Wno-pass-failed"; [ "${s##*.}" = cpp ] && arch=""
+  hipcc $arch -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-function "$@" -I$R/include -I$C -c $C/$s -o $T/${s%.*}.o &
 done
 wait
 hipcc --offload-arch=gfx950 -shared -fPIC -o $C/libclm_$name.so $T/*.o -lz -lpthread
