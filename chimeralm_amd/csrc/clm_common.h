@@ -409,7 +409,7 @@ struct TfPacking {                // one packing of the matrices the MFMA kernel
 // tf_fp32.hip: the forward with exact-fp32 products (the reference's precision; x3: on hi + lo halfs), up to the encoder output h
 size_t tf32_workspace_floats(int B, int L);
 int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
-                 const TfLayerF32* lay, const TfPacking& pk /*t32, or x3's*/, hipStream_t st, bool unfused, bool x3);
+                 const TfLayerF32* lay, const TfPacking& pk /*t32, or x3's*/, hipStream_t st, bool unfused, bool x3, int stop_after = -1);
 
 // GEMM family (gemm.hip): exact fp32, the unfused path (CLM_DEBUG=unfused_fp32, debug stops); activations fp32.
 // z  = in_proj(LN1(h))      -> channel-major [B, 768, Lp]

@@ -316,7 +316,7 @@ __device__ __forceinline__ void stage_rows32(const float* __restrict__ src, size
 
 template <bool FIRST, int AR = AR_F32>
 __global__ __launch_bounds__(512) void enc32_kernel(Enc32Args m) {
-    constexpr float WS = WSCALE<AR>, WSI = WUNSCALE<AR>;
+    constexpr float WSI = WUNSCALE<AR>;
     extern __shared__ __attribute__((aligned(16))) float smem32[];
     float* As = smem32;
     float* Hs = As + BM32 * RS32;
@@ -334,7 +334,10 @@ __global__ __launch_bounds__(512) void enc32_kernel(Enc32Args m) {
     } else {
         load_wset(wset_ptr(m.w_o, 0, D / 8, 0, wave, lane), ws[0]);
         stage_rows32<AR>(m.att, row0, m.M, As, tid);
-        {   // acc2 = h + b_o
+        // Both sublayer sums start from zero and meet their residual once, behind the last MFMA step (as tail32_kernel): summed onto the
+        // residual, every step rounds at the residual's magnitude, which a small sublayer (|W_o att| << |h|) pays for in full.
+        f32x16 res[2];
+        {   // res = h + b_o
             const float* bo = m.b_o + wave * 32 + 4 * lhalf;
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
@@ -344,28 +347,28 @@ __global__ __launch_bounds__(512) void enc32_kernel(Enc32Args m) {
                 for (int q = 0; q < 4; ++q) {
                     const float4 hv = *reinterpret_cast<const float4*>(row + 8 * q);
                     const float4 bb = *reinterpret_cast<const float4*>(bo + 8 * q);
-                    acc2[mt][4 * q + 0] = (hv.x + bb.x) * WS;
-                    acc2[mt][4 * q + 1] = (hv.y + bb.y) * WS;
-                    acc2[mt][4 * q + 2] = (hv.z + bb.z) * WS;
-                    acc2[mt][4 * q + 3] = (hv.w + bb.w) * WS;
+                    res[mt][4 * q + 0] = hv.x + bb.x;
+                    res[mt][4 * q + 1] = hv.y + bb.y;
+                    res[mt][4 * q + 2] = hv.z + bb.z;
+                    res[mt][4 * q + 3] = hv.w + bb.w;
+                    acc2[mt][4 * q + 0] = acc2[mt][4 * q + 1] = acc2[mt][4 * q + 2] = acc2[mt][4 * q + 3] = 0.f;
                 }
             }
         }
         __syncthreads();
         product256<false, AR>(As, m.w_o, 0, D / 8, 0, wset_ptr(m.w1, 0, D / 8, 0, wave, lane), wave, lane, ws, acc2);
-        if constexpr (AR == AR_X3) {
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[mt][r] *= WSI;
-        }
+            for (int r = 0; r < 16; ++r) acc2[mt][r] = acc2[mt][r] * WSI + res[mt][r];
         ln_to_tile<true, AR>(acc2, P1, P2, m.ln1_g, m.ln1_b, m.eps, As, valid, wave, lrow, lhalf);   // As = x1, acc2 = x1
-        if constexpr (AR == AR_X3) {                         // (the fc2 products land on x1 in the weights' scale)
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[mt][r] *= WS;
-        }
+            for (int r = 0; r < 16; ++r) {                     // x1 waits in `res`; acc2 is fc2's sum
+                res[mt][r] = acc2[mt][r];
+                acc2[mt][r] = 0.f;
+            }
 #pragma unroll 1
         for (int j = 0; j < DI / 256; ++j) {
 #pragma unroll
@@ -399,10 +402,10 @@ __global__ __launch_bounds__(512) void enc32_kernel(Enc32Args m) {
                 const float4 bb = *reinterpret_cast<const float4*>(b2p + 8 * q);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    acc2[mt][4 * q + 0] = acc2[mt][4 * q + 0] * WSI + bb.x;
-                    acc2[mt][4 * q + 1] = acc2[mt][4 * q + 1] * WSI + bb.y;
-                    acc2[mt][4 * q + 2] = acc2[mt][4 * q + 2] * WSI + bb.z;
-                    acc2[mt][4 * q + 3] = acc2[mt][4 * q + 3] * WSI + bb.w;
+                    acc2[mt][4 * q + 0] = (acc2[mt][4 * q + 0] * WSI + bb.x) + res[mt][4 * q + 0];
+                    acc2[mt][4 * q + 1] = (acc2[mt][4 * q + 1] * WSI + bb.y) + res[mt][4 * q + 1];
+                    acc2[mt][4 * q + 2] = (acc2[mt][4 * q + 2] * WSI + bb.z) + res[mt][4 * q + 2];
+                    acc2[mt][4 * q + 3] = (acc2[mt][4 * q + 3] * WSI + bb.w) + res[mt][4 * q + 3];
                 }
             }
         }

@@ -472,6 +472,11 @@ struct clm_tf_handle {
     bool unfused_fp32 = false;                    // CLM_DEBUG=unfused_fp32 at creation: the separate fp32 launches of round 2 (tests cross-check the fused kernels)
     DevBuf ws32;                                  // fp32 mode: activations of tf_fp32.hip
     int last_B = 0, last_L3 = 0;
+    // clm_tf_debug_stop_after (tests): a forward returns right after the launch of this CLM_TF_STAGE_* (< 0: the whole forward).
+    // What the last forward was -- its length, its path, where it stopped -- decides which clm_tf_debug_fetch names it produced.
+    int stop_after = -1;
+    int last_L = 0, last_stop = -1;
+    bool last_path32 = false;
     // clm_tf_set_fallback (as clm_set_fallback): 0 = the handle's mode; 1 = the next arithmetic inside the gate (16-bit handle: the
     // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
     int fallback = 0;
@@ -536,7 +541,12 @@ void tf_pool_head(clm_tf_handle* h, int B, int L3, float* logits, hipStream_t st
     const TfNetF32& n = h->net;
     hipLaunchKernelGGL(tf::pool_head_kernel, dim3(B), dim3(256), 0, st, h->h.get<float>(), n.pool_w, n.pool_b, n.cls0_w, n.cls0_b, n.cls3_w,
                        n.cls3_b, h->scores.get<float>(), h->pooled.get<float>(), logits, L3);
-    h->last_B = B; h->last_L3 = L3;
+}
+
+// what clm_tf_debug_fetch may hand out after this forward
+void tf_note(clm_tf_handle* h, int B, int L, bool path32, int stop) {
+    h->last_B = B; h->last_L = L; h->last_L3 = L / 8;
+    h->last_path32 = path32; h->last_stop = stop;
 }
 
 template <int PREC>
@@ -546,20 +556,27 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
     const size_t M = (size_t)B * L3;
     const TfNetF32& n = h->net;
     const TfPacking& pk = h->pk_mode;
+    const int stop = h->stop_after;                            // (< 0: never equal to a stage)
+    auto done = [] { return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP; };
     {
         TfTimer t(h, st, 0);
         launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);   // ids of any dtype -> clamped uint8
+        if (stop == CLM_TF_STAGE_EMBED) return done();         // (this path has no embedding launch: the first convolution reads the ids)
         constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
         constexpr auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
         constexpr auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
         launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8.get<unsigned char>(), Lp, n.emb,
                        (const elem*)nullptr, pk.conv[0].get(), n.conv_b[0], h->x1.get<elem>(), L, L1);
+        if (stop == CLM_TF_STAGE_CONV1) return done();
         launch_lds<k2>(dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
                        (const float*)nullptr, h->x1.get<const elem>(), pk.conv[1].get(), n.conv_b[1], h->x2.get<elem>(), L1, L2);
+        if (stop == CLM_TF_STAGE_CONV2) return done();
         launch_lds<k2>(dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
                        (const float*)nullptr, h->x2.get<const elem>(), pk.conv[2].get(), n.conv_b[2], h->x3.get<elem>(), L2, L3);
+        if (stop == CLM_TF_STAGE_CONV3) return done();
         hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, h->x3.get<const elem>(), n.pe, n.norm_g,
                            n.norm_b, h->h.get<float>(), h->hx.get<elem>(), M, L3, 1e-5f);
+        if (stop == CLM_TF_STAGE_PE_LN) return done();
     }
     for (int i = 0; i < h->n_layers; ++i) {
         const TfLayerF32& l = h->lay[i];
@@ -569,11 +586,13 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
             const tf::LinArgs a{h->hx.get(), m[0].get(), l.b_in, h->qkv.get(), M, 0};
             constexpr size_t lds = (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2;
             launch_lds<tf::linear16_kernel<PREC, tf::E_ACT, D, tf::TQKV>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, a);
+            if (stop == CLM_TF_STAGE_IN_PROJ) return done();
         }
         {
             TfTimer t(h, st, 1);
             if (!launch_attention_fwd(PREC, h->qkv.get(), h->att.get(), B, L3, st, PREC == PREC_F16C))   // fp16c: hi and lo planes (attention.hip)
                 return CLM_E_INVALID;
+            if (stop == CLM_TF_STAGE_ATTENTION(i)) return done();
         }
         TfTimer tl(h, st, 2);
         // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel
@@ -583,6 +602,7 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
                             h->att.get(), m[1].get(), l.b_out, l.ln1_g, l.ln1_b};
         constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
         launch_lds<tf::enc_ffn16_kernel<PREC>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
+        if (stop == CLM_TF_STAGE_LAYER(i)) return done();
     }
     {
         TfTimer t(h, st, 3);
@@ -719,8 +739,10 @@ static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype,
         // hi + lo halfs on the fp32 path: an fp16x3 handle unless told to fall back; a 16-bit handle at fall-back level 1
         const bool use_x3 = tf_fp32_path_is_x3(h);
         if (tf32_forward(h->ids8.get<unsigned char>(), Lp, B, L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), h->net, h->lay.data(),
-                         use_x3 ? h->pk_x3 : h->pk_t32, st, h->unfused_fp32, use_x3))
+                         use_x3 ? h->pk_x3 : h->pk_t32, st, h->unfused_fp32, use_x3, h->stop_after))
             return fail(h, CLM_E_HIP, std::string("clm_tf_forward (fp32): ") + hipGetErrorString(hipGetLastError()));
+        tf_note(h, B, L, true, h->stop_after);
+        if (h->stop_after >= 0) return CLM_OK;                 // stopped: nothing behind that launch, the pooling head included
         tf_pool_head(h, B, L3, logits_out, st);
         return hipGetLastError() == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
     }
@@ -739,6 +761,7 @@ static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype,
                    : h->prec == PREC_F16C ? tf_forward_t<PREC_F16C>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st)
                                           : tf_forward_t<PREC_F16>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st);
     if (rc) return fail(h, rc, std::string("clm_tf_forward: ") + hipGetErrorString(hipGetLastError()));
+    tf_note(h, B, L, false, h->stop_after);
     return CLM_OK;
 }
 
@@ -780,14 +803,16 @@ int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t i
         }
         float* lm = h->sc_logits.get<float>();
         float* lx = lm + (size_t)B * NCLS;
-        const int fallback = h->fallback;
+        const int fallback = h->fallback, stop = h->stop_after;
         h->fallback = 0;                                       // the MODE is on trial, whatever clm_tf_set_fallback says
+        h->stop_after = -1;                                    // ... on whole forwards, whatever clm_tf_debug_stop_after says
         const int rc1 = tf_run(h, h->arith_x3, ids, ids_dtype, ids_row_stride, B, L, lm, st);
         h->fallback = fallback;
-        if (rc1) return rc1;
+        if (rc1) { h->stop_after = stop; return rc1; }
         h->referee = true;
         const int rc2 = tf_run(h, true, ids, ids_dtype, ids_row_stride, B, L, lx, st);
         h->referee = false;
+        h->stop_after = stop;
         if (rc2) return rc2;
         std::vector<float> a((size_t)B * NCLS), b((size_t)B * NCLS);
         HIPCHK(h, hipMemcpyAsync(a.data(), lm, a.size() * 4, hipMemcpyDeviceToHost, st));
@@ -819,15 +844,46 @@ int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     const std::string n(name);
-    const size_t M = (size_t)h->last_B * h->last_L3;
+    const size_t B = (size_t)h->last_B, M = B * h->last_L3;
+    const int L = h->last_L, s = h->last_stop;
+    const bool p32 = h->last_path32;
+    const bool fused32 = p32 && !h->unfused_fp32;              // the exact path's names below describe the fused launches' workspace
+    const size_t es = p32 ? 4 : 2;                             // bytes per element of the path's activations
+    auto ran = [&](int stage) { return h->last_B > 0 && (s < 0 || s >= stage); };   // the last forward launched `stage`
     const void* src = nullptr;
     size_t have = 0;
-    if (n == "hidden") { src = h->h.get(); have = M * D * 4; }
-    else if (n == "scores") { src = h->scores.get(); have = M * 4; }
-    else if (n == "pooled") { src = h->pooled.get(); have = (size_t)h->last_B * D * 4; }
-    else return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: unknown name " + n);
+    bool produced = true;
+    if (n == "hidden") { src = h->h.get(); have = M * D * 4; produced = ran(CLM_TF_STAGE_PE_LN); }
+    else if (n == "scores") { src = h->scores.get(); have = M * 4; produced = h->last_B > 0 && s < 0; }
+    else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; produced = h->last_B > 0 && s < 0; }
+    else if (n == "x0") {       // exact path: the embedding rows, gone once the second convolution has written over them
+        src = h->ws32.get(); have = B * L * D * 4; produced = fused32 && (s == CLM_TF_STAGE_EMBED || s == CLM_TF_STAGE_CONV1);
+    } else if (n == "x1") {     // exact path: the other half of the ping-pong, until the third convolution
+        src = p32 ? (const void*)(h->ws32.get<float>() + B * L * D) : h->x1.get(); have = B * (L / 2) * D * es;
+        produced = p32 ? fused32 && (s == CLM_TF_STAGE_CONV1 || s == CLM_TF_STAGE_CONV2) : ran(CLM_TF_STAGE_CONV1);
+    } else if (n == "x2") {
+        src = p32 ? h->ws32.get() : h->x2.get(); have = B * (L / 4) * D * es; produced = (fused32 || !p32) && ran(CLM_TF_STAGE_CONV2);
+    } else if (n == "x3") {
+        src = p32 ? (const void*)(h->ws32.get<float>() + B * L * D) : h->x3.get(); have = M * D * es; produced = (fused32 || !p32) && ran(CLM_TF_STAGE_CONV3);
+    } else if (n == "hx") { src = h->hx.get(); have = M * D * 2; produced = !p32 && ran(CLM_TF_STAGE_PE_LN); }
+    else if (n == "qkv") {
+        src = p32 ? (const void*)(h->ws32.get<float>() + (size_t)2 * B * L * D) : h->qkv.get(); have = M * tf::TQKV * es;
+        produced = (fused32 || !p32) && ran(CLM_TF_STAGE_IN_PROJ);
+    } else if (n == "att") {    // fp16c: both planes
+        src = p32 ? (const void*)(h->ws32.get<float>() + (size_t)2 * B * L * D + M * tf::TQKV) : h->att.get();
+        have = M * D * es * (!p32 && h->prec == PREC_F16C ? 2 : 1); produced = (fused32 || !p32) && ran(CLM_TF_STAGE_ATTENTION(0));
+    } else return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: unknown name " + n);
+    if (!produced) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: the last forward did not produce (or has overwritten) " + n);
     if (bytes > have) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: more bytes requested than the last forward produced");
     HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    return CLM_OK;
+}
+
+int clm_tf_debug_stop_after(clm_tf_handle* h, int stage) {
+    if (!h) return CLM_E_INVALID;
+    if (stage >= 0 && h->unfused_fp32) return fail(h, CLM_E_UNSUPPORTED, "clm_tf_debug_stop_after: the fused launches only (CLM_DEBUG=unfused_fp32 is set)");
+    if (stage > CLM_TF_STAGE_LAYER(h->n_layers - 1)) return fail(h, CLM_E_INVALID, "clm_tf_debug_stop_after: no such stage in this net");
+    h->stop_after = stage < 0 ? -1 : stage;
     return CLM_OK;
 }
 

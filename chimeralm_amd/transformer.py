@@ -88,6 +88,7 @@ class SequenceCNNTransformer(nn.Module):
         self.classifier = nn.Sequential(nn.Linear(d_model, d_model // 2), nn.ReLU(), nn.Dropout(dropout),
                                         nn.Linear(d_model // 2, number_of_classes))
         self._h, self._dev, self._sig = None, None, None
+        self._stop = -1                                        # debug_stop_after
 
     # ------------------------------------------------------------------ engine plumbing
     def _check(self, rc: int):
@@ -103,6 +104,8 @@ class SequenceCNNTransformer(nn.Module):
             if rc != 0:
                 raise TransformerEngineError(lib.clm_tf_last_error(None).decode())
             self._h, self._dev, self._sig = h, device, None
+            if self._stop >= 0:
+                self._check(lib.clm_tf_debug_stop_after(self._h, self._stop))
         sig = reload_signature(self)
         if sig != self._sig:                                   # weights replaced or modified in place -> reload
             for k, t in self.state_dict().items():
@@ -243,8 +246,29 @@ class SequenceCNNTransformer(nn.Module):
         self._check(N.load().clm_tf_profile_read(self._h, ms, n, int(reset)))
         return {self.TF_STAGES[i]: (ms[i], n[i]) for i in range(4)}
 
-    def debug_fetch(self, name: str, shape) -> np.ndarray:
-        arr = np.empty(shape, dtype=np.float32)
+    # the launches of a forward, in order: include/chimeralm_hip.h CLM_TF_STAGE_*, CLM_TF_STAGE_ATTENTION(i) and CLM_TF_STAGE_LAYER(i)
+    # (tests/test_tf_stage_host.py compares these with the header); ("attention", i) and ("layer", i) per layer
+    TF_STOPS = {"embed": 0, "conv1": 1, "conv2": 2, "conv3": 3, "pe_ln": 4, "in_proj": 5}
+    _STOP_ATTENTION0, _STOP_LAYER0, _STOP_PER_LAYER = 6, 7, 2
+
+    def debug_stop_after(self, stage=None) -> None:
+        """Tests only: every later forward returns right after the launch `stage` -- a name of TF_STOPS, ("attention", i) or
+        ("layer", i) -- and launches nothing behind it (the returned logits are then uninitialised); None: whole forwards again.
+        Set before the first forward it takes effect when the engine is created."""
+        if stage is None:
+            code = -1
+        elif isinstance(stage, tuple):
+            code = {"attention": self._STOP_ATTENTION0, "layer": self._STOP_LAYER0}[stage[0]] + self._STOP_PER_LAYER * int(stage[1])
+        else:
+            code = self.TF_STOPS[stage]
+        if self._h is not None:
+            self._check(N.load().clm_tf_debug_stop_after(self._h, code))
+        self._stop = code
+
+    def debug_fetch(self, name: str, shape, dtype=np.float32) -> np.ndarray:
+        """A buffer of the last forward (names and shapes: include/chimeralm_hip.h).  The 16-bit path's activations are raw bits:
+        fetch them as np.uint16 (bf16) or np.float16."""
+        arr = np.empty(shape, dtype=dtype)
         self._check(N.load().clm_tf_debug_fetch(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
         return arr
 

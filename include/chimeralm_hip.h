@@ -308,6 +308,35 @@ int clm_tf_set_fallback(clm_tf_handle* h, int level);
  * level 1 -- and says CLM_PREC_F32 here.  The Hyena engine does the same (clm_effective_precision). */
 int clm_tf_effective_precision(const clm_tf_handle* h);
 int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_t bytes);
+/* Test-only observability of the kernels between the ids and the logits (tests/test_gpu_tf_stages.py).  Off by default; with it off
+ * a forward launches exactly what it launches without it (the cost is a host-side comparison per launch, no device code).
+ * clm_tf_debug_stop_after(h, stage): every later clm_tf_forward of the handle returns right after the launch named `stage` and
+ * launches nothing behind it, the pooling head included (logits_out is left untouched); stage < 0 ends that.  clm_tf_selfcheck always
+ * runs whole forwards.  CLM_E_UNSUPPORTED on a handle created under CLM_DEBUG=unfused_fp32, CLM_E_INVALID for a stage the net
+ * does not have.  The launches, in order:
+ *   CLM_TF_STAGE_EMBED          exact path: the embedding rows (the 16-bit path has no such launch: it stops behind the ids conversion)
+ *   CLM_TF_STAGE_CONV1 .. 3     a stem level: convolution + ReLU + max-pool
+ *   CLM_TF_STAGE_PE_LN          + positional encoding, LayerNorm -> the residual stream
+ *   CLM_TF_STAGE_IN_PROJ        layer 0's in_proj (the later layers' is the tail of the layer kernel before them)
+ *   CLM_TF_STAGE_ATTENTION(i)   layer i's attention
+ *   CLM_TF_STAGE_LAYER(i)       layer i's kernel: out_proj + LN1 + feed-forward + LN2 (+ layer i + 1's in_proj)
+ * clm_tf_debug_fetch names beyond the three above, each in the type the kernels store it in (B, L of the last forward, M = B * (L/8)):
+ *   exact path (fp32, fp16x3), fp32:   "x0" [B, L, 256] embedding rows, "x1" [B, L/2, 256], "x2" [B, L/4, 256], "x3" [M, 256] stem
+ *                                      levels, "qkv" [M, 768], "att" [M, 256].  The stem ping-pongs between two buffers: "x0" lives
+ *                                      until CONV2 has run, "x1" until CONV3 (fetch them from a forward stopped before that).
+ *   16-bit path, raw fp16 / bf16 bits: "x1", "x2", "x3" as above, "hx" [M, 256] (the residual stream rounded once, the GEMM operand),
+ *                                      "qkv" [M, 768], "att" [M, 256]; fp16c: "att" is [2][M, 256], the planes fp16(64 a), fp16(64 a - hi)
+ *   both: "hidden" is the residual stream fp32 [M, 256] as the last launched stage left it (PE_LN: the encoder's input; LAYER(i): layer
+ *   i's output; the layer kernel updates it in place), "qkv" / "att" those of the last in_proj / attention launched.
+ * A name the last forward did not produce, or has overwritten since, is CLM_E_INVALID with a message ("scores" and "pooled" after a
+ * stopped forward included; on a handle created under CLM_DEBUG=unfused_fp32, whose separate launches lay the workspace out
+ * differently, every exact-path name but "hidden").  chimeralm_amd/transformer.py repeats the stage codes (TF_STOPS,
+ * _STOP_ATTENTION0, _STOP_LAYER0); tests/test_tf_stage_host.py holds the two together. */
+enum { CLM_TF_STAGE_EMBED = 0, CLM_TF_STAGE_CONV1 = 1, CLM_TF_STAGE_CONV2 = 2, CLM_TF_STAGE_CONV3 = 3, CLM_TF_STAGE_PE_LN = 4,
+       CLM_TF_STAGE_IN_PROJ = 5 };
+#define CLM_TF_STAGE_ATTENTION(i) (6 + 2 * (i))
+#define CLM_TF_STAGE_LAYER(i) (7 + 2 * (i))
+int clm_tf_debug_stop_after(clm_tf_handle* h, int stage);
 /* Profiling taps of the 16-bit path (bench.py --net transformer): accumulated HIP-event time on the launch stream and number of
  * spans per stage -- 0 conv stack + positional encoding / LayerNorm, 1 attention, 2 encoder layer kernel (out_proj + LayerNorm-1
  * + feed-forward + LayerNorm-2 + next layer's QKV), 3 pooling head.  clm_tf_profile_read synchronises the device. */
