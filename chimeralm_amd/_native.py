@@ -244,6 +244,16 @@ SYMBOLS = {
     "clm_bam_last_error": (C.c_char_p, []),
 }
 
+
+
+def upload_state_dict(items, load_weight, check) -> None:
+    """Every `(key, tensor)` to an engine as contiguous fp32: `load_weight` is a `clm_*_load_weight` bound to its handle, `check` takes its code."""
+    for k, t in items:
+        t = t.detach().float().contiguous()
+        shape = (C.c_int64 * t.dim())(*t.shape)
+        check(load_weight(k.encode(), C.c_void_p(t.data_ptr()), DT_F32, shape, t.dim()))
+
+
 _lib = None
 
 

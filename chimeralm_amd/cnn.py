@@ -21,15 +21,16 @@ forward runs on batch statistics with a graph to every parameter (cnntrain.py, c
 from __future__ import annotations
 
 import ctypes as C
-import logging
+from functools import partial
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _native as N
-from ._native import X3_WEIGHT_LIMIT
+from ._guard import x3_range_report
 from ._reload import reload_signature
+from .engine import IDS_DT
 
 PRODUCTION = dict(vocab_size=12, embedding_dim=256, num_filters=[256, 256, 256], kernel_sizes=[7, 7, 7], pool_sizes=[4, 4, 4],
                   hidden_dim=512, number_of_classes=2, padding_idx=4)
@@ -80,20 +81,9 @@ class DNAConvNet(nn.Module):
 
     def _arith(self) -> str:
         """The arithmetic the loaded weights allow: fp16x3 only while every conv / fc weight is inside its packing's range."""
-        if self.precision == "fp32":
-            self.precision_report = {"precision": "fp32", "fallback": False}
-            return "fp32"
         ws = [b[0].weight for b in self.conv_blocks] + [self.fc[0].weight, self.fc[4].weight]
-        wmax = max(float(w.detach().abs().max()) for w in ws)
-        fallback = not wmax < X3_WEIGHT_LIMIT                  # (NaN falls back too)
-        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
-        if not fallback:
-            return "fp16x3"
-        self.precision_report["fallback_precision"] = "fp32"
-        logging.getLogger("chimeralm_amd").warning(
-            f"chimeralm_amd: DNAConvNet precision='fp16x3' packs weights as fp16 halfs x 2^10, which saturate at |w| >= "
-            f"{X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so this model runs the exact-fp32 kernels")
-        return "fp32"
+        self.precision_report = x3_range_report("DNAConvNet", self.precision, ws)
+        return self.precision_report.get("fallback_precision", self.precision)
 
     def _prepare(self, device: torch.device):
         # (not `_engine`: predict.py's end-of-run device check reads `net._engine` as the Hyena engine object)
@@ -109,12 +99,8 @@ class DNAConvNet(nn.Module):
             if lib.clm_cnn_create(dev, N.PRECISIONS[prec], C.byref(h)) != 0:
                 raise CnnEngineError(lib.clm_cnn_last_error(None).decode())
             self._h, self._dev, self._hprec = h, device, prec
-        for k, t in self.state_dict().items():                 # weights replaced or modified in place -> reload
-            if k.endswith("num_batches_tracked"):
-                continue
-            t = t.detach().float().contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            self._check(lib.clm_cnn_load_weight(self._h, k.encode(), C.c_void_p(t.data_ptr()), N.DT_F32, shape, t.dim()))
+        items = [(k, t) for k, t in self.state_dict().items() if not k.endswith("num_batches_tracked")]
+        N.upload_state_dict(items, partial(lib.clm_cnn_load_weight, self._h), self._check)   # weights replaced or modified in place -> reload
         self._check(lib.clm_cnn_finalize(self._h))
         self._sig = sig
         return lib
@@ -138,8 +124,7 @@ class DNAConvNet(nn.Module):
         lib = self._prepare(input_ids.device)
         B, L = input_ids.shape
         out = torch.empty((B, self.number_of_classes), dtype=torch.float32, device=input_ids.device)
-        dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[input_ids.dtype]
-        self._check(lib.clm_cnn_forward(self._h, C.c_void_p(input_ids.data_ptr()), dt, input_ids.stride(0), B, L,
+        self._check(lib.clm_cnn_forward(self._h, C.c_void_p(input_ids.data_ptr()), IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
                                         C.c_void_p(out.data_ptr()),
                                         C.c_void_p(torch.cuda.current_stream(input_ids.device).cuda_stream)))
         return out

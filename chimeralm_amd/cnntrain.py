@@ -21,10 +21,10 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .engine import IDS_DT
 
 log = logging.getLogger("chimeralm_amd")
 N_PARAMS = 13                                # embedding, then (W, b, g, beta) of blocks 0, 1, 2: CLM_CNN_TRAIN_PARAMS
-_DT = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}
 
 
 class CnnTrainError(RuntimeError):
@@ -86,7 +86,7 @@ class CnnTrainEngine:
                 if k.dtype != torch.uint8 or not k.is_contiguous() or tuple(k.shape) != (B, Ls[i + 1], 256):
                     raise ValueError("keep masks are contiguous uint8 [B, L_{i+1}, 256]")
             kp = (C.c_void_p * 3)(*[k.data_ptr() for k in keeps])
-        self._check(self.lib.clm_cnn_train_forward(self._h, C.c_void_p(ids.data_ptr()), _DT[ids.dtype], ids.stride(0), B, L, pp, kp, float(scale),
+        self._check(self.lib.clm_cnn_train_forward(self._h, C.c_void_p(ids.data_ptr()), IDS_DT[ids.dtype], ids.stride(0), B, L, pp, kp, float(scale),
                                                    C.c_void_p(pooled.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()),
                                                    self._stream()))
         self.shape = (B, L)

@@ -11,7 +11,7 @@ import torch
 from . import _native as N
 
 _TORCH_DT = {torch.float32: N.DT_F32, torch.float64: N.DT_F64, torch.bfloat16: N.DT_BF16, torch.float16: N.DT_F16}
-_IDS_DT = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}
+IDS_DT = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}
 
 
 class EngineError(RuntimeError):
@@ -264,7 +264,7 @@ class Engine:
         if input_ids.device != self.device:
             raise EngineError(N.E_INVALID, f"input_ids is on {input_ids.device}, engine on {self.device}; "
                                            "no CPU execution path exists")
-        if input_ids.dtype not in _IDS_DT:
+        if input_ids.dtype not in IDS_DT:
             raise ValueError("input_ids dtype must be int64, int32 or uint8")
         if input_ids.stride(1) != 1:
             input_ids = input_ids.contiguous()
@@ -273,7 +273,7 @@ class Engine:
             out = torch.empty((B, self.cfg.n_classes), dtype=torch.float32, device=self.device)
         (att, c), (trj, ct) = self._attn_out(attention, B, L), self._traj_out(trajectory, B, L)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self._lib.clm_forward_traj(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
+        self._check(self._lib.clm_forward_traj(self._h, C.c_void_p(input_ids.data_ptr()), IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
                                                C.c_void_p(out.data_ptr()), c, ct, C.c_void_p(stream)))
         return self._result(out, att, trj)
 
@@ -312,14 +312,14 @@ class Engine:
     def selfcheck(self, input_ids: torch.Tensor) -> tuple[float, int]:
         """Run `input_ids` through this engine's mode AND through the exact-fp32 kernels of the same handle; returns
         (max |logit difference|, number of reads whose label differs).  Synchronises the current stream (`clm_selfcheck`)."""
-        if input_ids.dim() != 2 or input_ids.device != self.device or input_ids.dtype not in _IDS_DT:
+        if input_ids.dim() != 2 or input_ids.device != self.device or input_ids.dtype not in IDS_DT:
             raise ValueError("selfcheck wants input_ids [batch, length] (int64 / int32 / uint8) on the engine's device")
         if input_ids.stride(1) != 1:
             input_ids = input_ids.contiguous()
         B, L = input_ids.shape
         diff, differ = C.c_float(0.0), C.c_int(0)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self._lib.clm_selfcheck(self._h, C.c_void_p(input_ids.data_ptr()), _IDS_DT[input_ids.dtype],
+        self._check(self._lib.clm_selfcheck(self._h, C.c_void_p(input_ids.data_ptr()), IDS_DT[input_ids.dtype],
                                             input_ids.stride(0), B, L, C.c_void_p(stream), C.byref(diff), C.byref(differ)))
         return float(diff.value), int(differ.value)
 

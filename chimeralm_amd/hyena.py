@@ -13,12 +13,13 @@ HIP library or with CPU tensors raises.
 """
 from __future__ import annotations
 
+import logging
 import math
 
 import torch
 from torch import nn
 
-from ._native import X3_WEIGHT_LIMIT   # the engine measures the weights it packs as fp16x3 (clm_finalize)
+from ._guard import GuardSchedule, announce_fallback, finite_or_inf, sample_rows, x3_range_report
 from ._reload import reload_signature
 from .engine import Engine, check_trajectory_stride
 
@@ -199,7 +200,8 @@ class HyenaDna(nn.Module):
     (`clm_set_mlp_compensation`, ~10 % slower), heard again from the start -- and only if that form fails on the batch too does the
     engine fall back for good (logged, RuntimeWarning): to fp16x3, the next-fastest arithmetic inside the gate
     (`clm_set_fallback` level 1; an "fp16x3" module that was asked to check itself falls back to exact fp32).  `selfcheck_report`
-    holds what was measured.
+    holds what was measured; WHICH batches are measured is kept in `self._guard` (`_guard.GuardSchedule`: what was heard, the length
+    range checked, the batches and reads since; shared with `SequenceCNNTransformer`), reset by every weight load.
     fp16x3 -- the "fp16x3" mode, fp16c's short reads and the first fall-back level of the 16-bit modes -- packs weights x 2^10 as
     fp16 halfs, which saturate at |w| >= 64: if an in_proj / out_proj / fc1 / fc2 / score weight is that large (or NaN), the engine
     runs exact fp32 wherever it would run fp16x3; the module reads that back at every weight load, records it in `precision_report`
@@ -244,12 +246,8 @@ class HyenaDna(nn.Module):
                 p.requires_grad = False
         self._engine: Engine | None = None
         self._engine_sig = None
-        self._heard = False                               # the seeded samples ran since the last weight load
-        self._checked_min_len: int | None = None          # shortest / longest batch MEASURED in the mode since the last weight
-        self._checked_max_len: int | None = None          # load, and the batches that went by since the last check
-        self._batches_since_check = 0
-        self._reads_since_check = 0
-        self._recheck_next = False                        # the last measurement was kept within 10 % of the threshold
+        # when the mode is measured again since the last weight load (`heard`: the seeded samples ran); knobs: `guard_due`
+        self._guard = GuardSchedule(self.selfcheck_tol, self.selfcheck_every, self.selfcheck_min_reads)
         self._mlp_lo = False                              # fp16c: the guard's second level is on (fc1 / fc2 on hi + lo weights)
 
     # -------------------------------------------------------------------------------- engine plumbing
@@ -276,10 +274,7 @@ class HyenaDna(nn.Module):
                 self._engine.set_f16c_min_len(self._DEFAULT_MIN_LEN)   # ... the length switch its unmeasured default ...
                 self._engine.set_mlp_compensation(False)   # ... and the MLP its plain-fp16 weights
             self._mlp_lo = False
-            self._heard = self._recheck_next = False
-            self._checked_min_len = self._checked_max_len = None
-            self._batches_since_check = 0
-            self._reads_since_check = 0
+            self._guard.reset()
             self.selfcheck_report = {}
             self._report_x3(self._engine)
         return self._engine
@@ -288,38 +283,23 @@ class HyenaDna(nn.Module):
         """`precision_report` of the weights just loaded: the arithmetic the engine runs where this mode uses fp16x3 (see the class
         docstring), read back from the engine, and a warning when the weights pushed it to exact fp32."""
         if self.precision == "fp32":
-            self.precision_report = {"precision": "fp32", "fallback": False}
-            return
-        if self.precision in ("fp16x3", "fp16c"):             # its own mode / its short reads (level 0, one-token reads)
+            x3 = None
+        elif self.precision in ("fp16x3", "fp16c"):           # its own mode / its short reads (level 0, one-token reads)
             x3 = eng.effective_precision(1)
         else:                                                 # fp16 / bf16: only their first fall-back level is fp16x3
             eng.set_fallback(1)
             x3 = eng.effective_precision(1)
             eng.set_fallback(0)
-        ws = [t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)]
-        wmax = max(float(t.detach().abs().max()) for t in ws)
-        fallback = x3 != "fp16x3"
-        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
-        if not fallback:
-            return
-        import logging
-
-        self.precision_report["fallback_precision"] = x3
-        where = {"fp16x3": "", "fp16c": " (its reads below f16c_min_len and its first fall-back level)"}.get(
-            self.precision, " (its first fall-back level)")
-        logging.getLogger("chimeralm_amd").warning(
-            f"chimeralm_amd: HyenaDna precision={self.precision!r} packs weights as fp16 halfs x 2^10 for fp16x3{where}, which "
-            f"saturate at |w| >= {X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so it runs the exact-fp32 kernels there")
+        where = {"fp16x3": "", "fp16c": " (its reads below f16c_min_len and its first fall-back level)"}.get(self.precision, " (its first fall-back level)")
+        self.precision_report = x3_range_report(
+            "HyenaDna", self.precision, (t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)), effective=x3,
+            where=f" for fp16x3{where}", tail="it runs the exact-fp32 kernels there")
 
     # -------------------------------------------------------------------------------- the 16-bit mode on trial
     _SAMPLE_LENGTHS = (4097, 2048, 1024, 512, 256)       # descending: the mode's error grows like 1 / sqrt(L)
     _BATCH_ROWS = 4                                       # reads of a batch that a check runs through both arithmetics
     _DEFAULT_MIN_LEN = 2048                               # fp16c's length switch before anything was measured
-
-    @staticmethod
-    def _sample_rows(B: int, n: int) -> list[int]:
-        """`n` rows spread evenly over a batch of B (not its first rows: a file sorted by anything would make those alike)."""
-        return list(range(B)) if B <= n else sorted({round(i * (B - 1) / (n - 1)) for i in range(n)})
+    _sample_rows = staticmethod(sample_rows)              # (predict.py's native loop picks the same rows on the host)
 
     def _measure(self, eng: Engine, input_ids: torch.Tensor, first: bool) -> tuple[float, bool]:
         """One hearing of the mode in its current form: the seeded samples (`first`: they also place the short-read switch) and rows
@@ -334,7 +314,7 @@ class HyenaDna(nn.Module):
             diff, differ = eng.selfcheck(ids)
             rep.setdefault("samples", []).append({"sample": name, "max_abs_dlogit": diff, "labels_differ": differ,
                                                   "mlp_compensation": self._mlp_lo})
-            return diff if diff == diff else float("inf")
+            return finite_or_inf(diff)
 
         if first:
             g = torch.Generator().manual_seed(20240)
@@ -374,13 +354,10 @@ class HyenaDna(nn.Module):
         return worst, measured
 
     def _selfcheck(self, eng: Engine, input_ids: torch.Tensor) -> None:
-        """See the class docstring.  Runs on torch's current stream and synchronises it (a few ms per sample)."""
-        import logging
-
-        L = input_ids.shape[1]
-        rep = self.selfcheck_report
-        log = logging.getLogger("chimeralm_amd")
-        first = not self._heard
+        """See the class docstring; `guard` calls it where `guard_due` said so.  Runs on torch's current stream and synchronises it (a
+        few ms per sample)."""
+        L, rep, sched = input_ids.shape[1], self.selfcheck_report, self._guard
+        first = not sched.heard
         worst, measured = self._measure(eng, input_ids, first)
         if not worst <= self.selfcheck_tol and self.precision == "fp16c" and not self._mlp_lo:
             # second level of the mode: fc1 / fc2 on hi + lo weights as well (their rounding shows on SOME weights: DESIGN.md
@@ -388,35 +365,19 @@ class HyenaDna(nn.Module):
             self._mlp_lo = True
             eng.set_mlp_compensation(True)
             rep["mlp_compensation"] = True
-            log.info("chimeralm_amd: fp16c with plain-fp16 MLP weights measures %.2e on the loaded weights (threshold %.1e): "
-                     "switching the MLP to hi + lo weights (~10 %% slower) and measuring again", worst, self.selfcheck_tol)
+            logging.getLogger("chimeralm_amd").info(
+                "chimeralm_amd: fp16c with plain-fp16 MLP weights measures %.2e on the loaded weights (threshold %.1e): "
+                "switching the MLP to hi + lo weights (~10 %% slower) and measuring again", worst, self.selfcheck_tol)
             worst, measured = self._measure(eng, input_ids, True)
         rep.setdefault("mlp_compensation", False)
         rep["max_abs_dlogit"] = worst if first else max(rep.get("max_abs_dlogit", 0.0), worst)   # (of the form the mode is kept in)
         rep["tol"], rep["precision"] = self.selfcheck_tol, self.precision
-        self._heard = True
-        if measured:            # only a batch that really ran in the mode widens the checked range
-            self._checked_min_len = L if self._checked_min_len is None else min(L, self._checked_min_len)
-            self._checked_max_len = max(L, self._checked_max_len or 0)
-        self._batches_since_check = 0
-        self._reads_since_check = 0
-        # kept, but within 10 % of the threshold: the spread from batch to batch at fixed weights is 2-3x (profiles/r04_fp16c_margin.txt),
-        # so the NEXT batch is measured too instead of the 16th from now
-        self._recheck_next = measured and 0.9 * self.selfcheck_tol < worst <= self.selfcheck_tol
+        sched.record(L, worst, measured=measured)
         rep["checks"] = rep.get("checks", 0) + 1
         if not worst <= self.selfcheck_tol and not rep.get("fallback"):
             eng.set_fallback(1)
-            rep["fallback"] = True
-            rep["fallback_precision"] = eng.effective_precision(L)
-            import warnings
-
-            what = ("exact fp32 (the reference's arithmetic)" if rep["fallback_precision"] == "fp32" else
-                    "fp16x3 (every operand as two halfs, three fp16 MFMAs per product: fp32-class logits, about half the rate)")
-            msg = (f"chimeralm_amd: precision={self.precision!r} differs from the exact-fp32 kernels by "
-                   f"{worst:.2e} in the logits on the loaded weights (threshold {self.selfcheck_tol:.1e}); "
-                   f"falling back to {what} for this model")
-            log.warning(msg)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
+            announce_fallback(rep, subject="", precision=self.precision, worst=worst, tol=self.selfcheck_tol,
+                              fallback_precision=eng.effective_precision(L))
         rep.setdefault("fallback", False)
 
     # The periodic re-check is meant to cost ~1 % of the work between two checks: two passes over 4 reads, one of them in exact fp32
@@ -426,26 +387,14 @@ class HyenaDna(nn.Module):
     selfcheck_min_reads = 1024
 
     def guard_due(self, n_tokens: int, n_reads: int | None = None) -> bool:
-        """Is a self-check due for a batch of `n_tokens`-token reads?  The first batch since a weight load (the seeded samples); then,
-        for batches that run in the mode (fp16c: not those below the length switch -- they take the fp16x3 kernels, which are not on
-        trial): the first such batch, a batch whose length leaves the range already measured by more than a factor 1.5 in EITHER
-        direction (the mode's error is neither monotone in the length nor the same from batch to batch:
-        profiles/r03_fp16c_margin.txt), the batch after a measurement within 10 % of the threshold, and every `selfcheck_every`-th
-        batch (default 16) once `selfcheck_min_reads` reads went by as well (`n_reads` unknown: not waited for) -- two passes over
-        4 reads, ~1 % of the work between two checks.  Counts the batch."""
+        """Is a self-check due for a batch of `n_tokens`-token reads (`GuardSchedule.due`)?  Never without `selfcheck`, in fp32 or once
+        fallen back; fp16c's batches below the length switch are not on trial -- they take the fp16x3 kernels.  Counts the batch."""
         if not self.selfcheck or self.precision == "fp32" or self.selfcheck_report.get("fallback"):
             return False
-        if not self._heard:
-            return True
-        if self.precision == "fp16c" and n_tokens < self.selfcheck_report.get("f16c_min_len", self._DEFAULT_MIN_LEN):
-            return False
-        if self._checked_min_len is None:
-            return True
-        self._batches_since_check += 1
-        self._reads_since_check += int(n_reads) if n_reads is not None else self.selfcheck_min_reads
-        return (self._recheck_next or 3 * n_tokens < 2 * self._checked_min_len or 2 * n_tokens > 3 * self._checked_max_len
-                or (self.selfcheck_every > 0 and self._batches_since_check >= self.selfcheck_every
-                    and self._reads_since_check >= self.selfcheck_min_reads))
+        g = self._guard                                   # with this module's knobs as they are NOW: assignable after construction
+        g.tol, g.every, g.min_reads = self.selfcheck_tol, self.selfcheck_every, self.selfcheck_min_reads
+        return g.due(n_tokens, n_reads, on_trial=self.precision != "fp16c" or n_tokens >= self.selfcheck_report.get(
+            "f16c_min_len", self._DEFAULT_MIN_LEN))
 
     def guard(self, eng: Engine, input_ids, n_tokens: int | None = None, n_reads: int | None = None) -> None:
         """Self-check of the 16-bit mode where one is due (`guard_due`).  `forward` calls it; loops that drive the engine directly

@@ -31,15 +31,16 @@ from __future__ import annotations
 import ctypes as C
 import logging
 import math
+from functools import partial
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _native as N
-from ._native import X3_WEIGHT_LIMIT
+from ._guard import x3_range_report
 from ._reload import reload_signature
-from .engine import TrajectoryRequest, check_trajectory_stride, trajectory_out
+from .engine import IDS_DT, TrajectoryRequest, check_trajectory_stride, trajectory_out
 
 HEADDIM, D_CONV, VOCAB, PAD = 64, 4, 12, 4
 _LOG = logging.getLogger("chimeralm_amd")
@@ -130,22 +131,12 @@ class _MambaNet(nn.Module):
 
     def _arith(self) -> str:
         """The arithmetic the loaded weights allow: fp16x3 only while every projection weight is inside its packing's range."""
-        if self.precision == "fp32":
-            self.precision_report = {"precision": "fp32", "fallback": False}
-            return "fp32"
-        ws = [self._layer(i).in_proj.weight for i in range(self._shape[1])]
-        ws += [self._layer(i).out_proj.weight * self._layer(i).norm.weight for i in range(self._shape[1])]
+        layers = [self._layer(i) for i in range(self._shape[1])]
+        ws = [m.in_proj.weight for m in layers] + [m.out_proj.weight * m.norm.weight for m in layers]
         if hasattr(self, "input_block"):
             ws.append(self.input_block[0].weight)
-        wmax = max(float(w.detach().abs().max()) for w in ws)
-        fallback = not wmax < X3_WEIGHT_LIMIT                  # (NaN falls back too)
-        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
-        if not fallback:
-            return "fp16x3"
-        self.precision_report["fallback_precision"] = "fp32"
-        _LOG.warning(f"chimeralm_amd: {type(self).__name__} precision='fp16x3' packs weights as fp16 halfs x 2^10, which saturate at "
-                     f"|w| >= {X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so this model runs the exact-fp32 kernels")
-        return "fp32"
+        self.precision_report = x3_range_report(type(self).__name__, self.precision, ws)
+        return self.precision_report.get("fallback_precision", self.precision)
 
     def _new_handle(self, lib, device: torch.device, prec: str):
         d, nl, ds, ex, hd, ml = self._shape
@@ -153,10 +144,7 @@ class _MambaNet(nn.Module):
         dev = device.index if device.index is not None else torch.cuda.current_device()
         if lib.clm_mamba_create(dev, self._variant, N.PRECISIONS[prec], d, nl, ds, ex, hd, ml or 0, C.byref(h)) != 0:
             raise MambaEngineError(lib.clm_mamba_last_error(None).decode())
-        for k, t in self.state_dict().items():
-            t = t.detach().float().contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            self._check(h, lib.clm_mamba_load_weight(h, k.encode(), C.c_void_p(t.data_ptr()), N.DT_F32, shape, t.dim()))
+        N.upload_state_dict(self.state_dict().items(), partial(lib.clm_mamba_load_weight, h), partial(self._check, h))
         self._check(h, lib.clm_mamba_finalize(h))
         return h
 
@@ -215,7 +203,7 @@ class _MambaNet(nn.Module):
 
             return train_forward(self, input_ids, mask)
         lib = self._prepare(input_ids.device)
-        dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[input_ids.dtype]
+        dt = IDS_DT[input_ids.dtype]
         out = torch.empty((B, self.number_of_classes), dtype=torch.float32, device=input_ids.device)
         req = self.trajectory_request()
         self.last_trajectory = self._run(lib, self._h, input_ids, dt, mask, out, req)

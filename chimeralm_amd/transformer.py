@@ -14,23 +14,26 @@ after a weight load (and again every `selfcheck_every`-th batch, for a batch mor
 far, and for the batch after a measurement within 10 % of the threshold) the mode is measured against the exact-fp32 kernels of the
 same engine on seeded reads and on rows of the batch (`clm_tf_selfcheck`); above the threshold the module falls back for good --
 a 16-bit mode to fp16x3, the next-fastest arithmetic inside the tolerance (`clm_tf_set_fallback` level 1), fp16x3 to exact fp32 --
-and says so.  On by default for fp16c.  fp16x3 -- the default mode, and the first fall-back level of the 16-bit modes -- packs
-weights x 2^10 as fp16 halfs, which saturate at |w| >= 64: if a CNN-stem or encoder weight is that large (or NaN), the engine runs
-exact fp32 wherever it would run fp16x3; the module reads that back at every weight load (`clm_tf_effective_precision`), records
-it in `precision_report` and logs a warning.
+and says so.  On by default for fp16c.  WHICH batches are measured is the rule `HyenaDna` follows too, kept in `self._guard`
+(`_guard.GuardSchedule`, reset by every weight load); this module's own are its one seeded sample and its verdict.  fp16x3 -- the
+default mode, and the first fall-back level of the 16-bit modes -- packs weights x 2^10 as fp16 halfs, which saturate at
+|w| >= 64: if a CNN-stem or encoder weight is that large (or NaN), the engine runs exact fp32 wherever it would run fp16x3; the
+module reads that back at every weight load (`clm_tf_effective_precision`), records it in `precision_report` and logs a warning.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _native as N
-from ._native import X3_WEIGHT_LIMIT   # the engine measures the weights it packs as fp16x3 (clm_tf_finalize)
+from ._guard import GuardSchedule, announce_fallback, finite_or_inf, sample_rows, x3_range_report
 from ._reload import reload_signature
+from .engine import IDS_DT
 
 _X3_PACKED = ("self_attn.in_proj_weight", "self_attn.out_proj.weight", "linear1.weight", "linear2.weight", "cnn.0.weight",
               "cnn.3.weight", "cnn.6.weight")
@@ -71,10 +74,7 @@ class SequenceCNNTransformer(nn.Module):
         self.selfcheck_report: dict = {}
         self.precision_report: dict = {}
         self.selfcheck_every = int(selfcheck_every)
-        self._checked_min_len: int | None = None
-        self._checked_max_len: int | None = None
-        self._batches_since_check = 0
-        self._recheck_next = False
+        self._guard = GuardSchedule(self.selfcheck_tol, self.selfcheck_every)   # (`heard` here: something was measured)
         self.embedding = nn.Embedding(vocab_size, d_model, padding_idx=padding_idx)
         self.pos_encoder = _PosEnc(d_model, max_len)
         conv = lambda: nn.Conv1d(d_model, d_model, kernel_size=cnn_kernel_size, padding=1)  # noqa: E731
@@ -108,14 +108,11 @@ class SequenceCNNTransformer(nn.Module):
                 self._check(lib.clm_tf_debug_stop_after(self._h, self._stop))
         sig = reload_signature(self)
         if sig != self._sig:                                   # weights replaced or modified in place -> reload
-            for k, t in self.state_dict().items():
-                t = t.detach().float().contiguous()
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                self._check(lib.clm_tf_load_weight(self._h, k.encode(), C.c_void_p(t.data_ptr()), N.DT_F32, shape, t.dim()))
+            N.upload_state_dict(self.state_dict().items(), partial(lib.clm_tf_load_weight, self._h), self._check)
             self._check(lib.clm_tf_finalize(self._h))
             self._check(lib.clm_tf_set_fallback(self._h, 0))
-            self._sig, self._checked_min_len, self._checked_max_len, self._batches_since_check, self.selfcheck_report = sig, None, None, 0, {}
-            self._recheck_next = False
+            self._sig, self.selfcheck_report = sig, {}
+            self._guard.reset()
             self._report_x3(lib)
         return lib
 
@@ -134,88 +131,61 @@ class SequenceCNNTransformer(nn.Module):
         """`precision_report` of the weights just loaded: what the engine runs where this mode uses fp16x3 (its own mode; the first
         fall-back level of a 16-bit mode), read back from it, and a warning when the weights pushed it to exact fp32."""
         if self.precision == "fp32":
-            self.precision_report = {"precision": "fp32", "fallback": False}
-            return
-        if self.precision == "fp16x3":
+            x3 = None
+        elif self.precision == "fp16x3":
             x3 = self._arith(lib)
         else:
             self._check(lib.clm_tf_set_fallback(self._h, 1))
             x3 = self._arith(lib)
             self._check(lib.clm_tf_set_fallback(self._h, 0))
-        ws = [t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)]
-        wmax = max(float(t.detach().abs().max()) for t in ws)
-        fallback = x3 != "fp16x3"
-        self.precision_report = {"precision": self.precision, "max_abs_weight": wmax, "fallback": fallback}
-        if not fallback:
-            return
-        import logging
-
-        self.precision_report["fallback_precision"] = x3
         where = "" if self.precision == "fp16x3" else " (its first fall-back level)"
-        logging.getLogger("chimeralm_amd").warning(
-            f"chimeralm_amd: SequenceCNNTransformer precision={self.precision!r} packs weights as fp16 halfs x 2^10 for fp16x3{where}, "
-            f"which saturate at |w| >= {X3_WEIGHT_LIMIT:g}; the loaded weights reach {wmax:.3g}, so it runs the exact-fp32 kernels there")
+        self.precision_report = x3_range_report(
+            "SequenceCNNTransformer", self.precision, (t for k, t in self.state_dict().items() if k.endswith(_X3_PACKED)),
+            effective=x3, where=f" for fp16x3{where}", tail="it runs the exact-fp32 kernels there")
 
     # ------------------------------------------------------------------ the 16-bit mode on trial
-    def _measure(self, lib, name: str, ids: torch.Tensor) -> float:
+    def _selfcheck_call(self, lib, ids: torch.Tensor) -> tuple[float, int]:
+        """`clm_tf_selfcheck` on `ids`: the largest logit difference between the mode and exact fp32, and whether a label differs."""
         diff, differ = C.c_float(), C.c_int()
-        dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[ids.dtype]
-        self._check(lib.clm_tf_selfcheck(self._h, C.c_void_p(ids.data_ptr()), dt, ids.stride(0), ids.shape[0], ids.shape[1],
-                                         C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream), C.byref(diff),
+        self._check(lib.clm_tf_selfcheck(self._h, C.c_void_p(ids.data_ptr()), IDS_DT[ids.dtype], ids.stride(0), ids.shape[0],
+                                         ids.shape[1], C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream), C.byref(diff),
                                          C.byref(differ)))
-        self.selfcheck_report.setdefault("samples", []).append(
-            {"sample": name, "max_abs_dlogit": diff.value, "labels_differ": differ.value})
-        return diff.value
+        return diff.value, differ.value
+
+    def _measure(self, lib, name: str, ids: torch.Tensor) -> float:
+        diff, differ = self._selfcheck_call(lib, ids)
+        self.selfcheck_report.setdefault("samples", []).append({"sample": name, "max_abs_dlogit": diff, "labels_differ": differ})
+        return diff
 
     def guard_due(self, n_tokens: int) -> bool:
-        """As `HyenaDna.guard_due`: the first batch since a weight load, a batch more than 1.5x shorter or longer than every batch
-        checked so far, the batch after a measurement within 10 % of the threshold, and every `selfcheck_every`-th batch."""
+        """Is a self-check due for a batch of `n_tokens`-token reads (`GuardSchedule.due`)?  Never without `selfcheck`, in fp32 or once
+        fallen back.  No length switch here (every batch is on trial) and no wait for reads.  Counts the batch."""
         if not self.selfcheck or self.precision == "fp32" or self.selfcheck_report.get("fallback"):
             return False
-        if self._checked_min_len is None:
-            return True
-        self._batches_since_check += 1
-        return (self._recheck_next or 3 * n_tokens < 2 * self._checked_min_len or 2 * n_tokens > 3 * self._checked_max_len
-                or (self.selfcheck_every > 0 and self._batches_since_check >= self.selfcheck_every))
+        self._guard.tol, self._guard.every = self.selfcheck_tol, self.selfcheck_every   # as they are NOW: assignable after construction
+        return self._guard.due(n_tokens)
 
     def guard(self, lib, input_ids: torch.Tensor) -> None:
         """Self-check of the 16-bit mode where one is due (see the module docstring)."""
-        rep = self.selfcheck_report
-        L = input_ids.shape[1]
+        rep, L = self.selfcheck_report, input_ids.shape[1]
         if not self.guard_due(L):
             return
-        worst = rep.get("max_abs_dlogit", 0.0)
-        now = 0.0
-        if self._checked_min_len is None:                      # first batch since the weights were loaded: seeded reads
-            g = torch.Generator().manual_seed(20241)
+        sched, now = self._guard, 0.0
+        if not sched.heard:                                    # first batch since the weights were loaded: ONE seeded sample,
+            g = torch.Generator().manual_seed(20241)           # without [SEP], and no second level behind it
             Ls = min(4096, 8 * self.pos_encoder.pe.shape[1])   # (a model built with a short max_len cannot take 4,096 tokens)
             ids = torch.randint(7, 11, (4, Ls), generator=g, dtype=torch.uint8)
             ids[0, : Ls // 3] = 4                              # one read left-padded, as the collator pads
             now = max(now, self._measure(lib, f"synthetic 4 x {Ls}", ids.to(input_ids.device)))
-        B = input_ids.shape[0]
-        rows = list(range(B)) if B <= 4 else sorted({round(i * (B - 1) / 3) for i in range(4)})   # spread over the batch
-        now = max(now, self._measure(lib, f"batch rows {rows} x {L}", input_ids[rows].contiguous()))
-        now = now if now == now else float("inf")
-        worst = max(worst, now)
-        self._recheck_next = 0.9 * self.selfcheck_tol < now <= self.selfcheck_tol
+        rows = sample_rows(input_ids.shape[0], 4)
+        now = finite_or_inf(max(now, self._measure(lib, f"batch rows {rows} x {L}", input_ids[rows].contiguous())))
+        worst = max(rep.get("max_abs_dlogit", 0.0), now)       # the verdict is taken on the running maximum, the re-arm on `now`
         rep.update(max_abs_dlogit=worst, tol=self.selfcheck_tol, precision=self.precision)
-        self._checked_min_len = L if self._checked_min_len is None else min(L, self._checked_min_len)
-        self._checked_max_len = max(L, self._checked_max_len or 0)
-        self._batches_since_check = 0
+        sched.record(L, now)                                   # every check widens the range; no `checks` counter
         if not worst <= self.selfcheck_tol:                    # (NaN fails too)
             self._check(lib.clm_tf_set_fallback(self._h, 1))
-            rep["fallback"] = True
-            rep["fallback_precision"] = self._arith(lib)
-            import logging
-            import warnings
-
-            what = ("exact fp32 (the reference's arithmetic)" if rep["fallback_precision"] == "fp32" else
-                    "fp16x3 (every operand as two halfs, three fp16 MFMAs per product: fp32-class logits, about half the rate)")
-            msg = (f"chimeralm_amd: SequenceCNNTransformer precision={self.precision!r} differs from the exact-fp32 kernels by "
-                   f"{worst:.2e} in the logits on the loaded weights (threshold {self.selfcheck_tol:.1e}); falling back to {what} "
-                   "for this model")
-            logging.getLogger("chimeralm_amd").warning(msg)
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
+            announce_fallback(rep, subject="SequenceCNNTransformer ", precision=self.precision, worst=worst, tol=self.selfcheck_tol,
+                              fallback_precision=self._arith(lib))
         rep.setdefault("fallback", False)
 
     def forward(self, input_ids: torch.Tensor, input_quals: torch.Tensor | None = None) -> torch.Tensor:
@@ -230,8 +200,7 @@ class SequenceCNNTransformer(nn.Module):
         self.guard(lib, input_ids)
         B, L = input_ids.shape
         out = torch.empty((B, 2), dtype=torch.float32, device=input_ids.device)
-        dt = {torch.int64: N.DT_I64, torch.int32: N.DT_I32, torch.uint8: N.DT_U8}[input_ids.dtype]
-        self._check(lib.clm_tf_forward(self._h, C.c_void_p(input_ids.data_ptr()), dt, input_ids.stride(0), B, L,
+        self._check(lib.clm_tf_forward(self._h, C.c_void_p(input_ids.data_ptr()), IDS_DT[input_ids.dtype], input_ids.stride(0), B, L,
                                        C.c_void_p(out.data_ptr()),
                                        C.c_void_p(torch.cuda.current_stream(input_ids.device).cuda_stream)))
         return out

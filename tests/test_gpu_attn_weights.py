@@ -245,7 +245,7 @@ def test_a_self_check_between_two_forwards_leaves_the_users_buffers_alone(built_
     att_a = net.last_attention
     assert net.selfcheck_report.get("checks") == 1
     keep = {k: v.clone() for k, v in att_a.tensors().items()}
-    net._recheck_next = True                                    # a check is due on the next batch (guard_due)
+    net._guard.recheck_next = True                                    # a check is due on the next batch (guard_due)
     lb = model(b_ids, None)
     att_b = net.last_attention
     assert net.selfcheck_report.get("checks") == 2 and att_b is not att_a

@@ -148,11 +148,11 @@ def test_batches_below_the_switch_are_not_on_trial_and_do_not_widen_the_checked_
     net = _net()
     eng = StubEngine({4097: 2e-4, 2048: 6e-4})                                     # switch at 4,097
     net.guard(eng, _ids(4, 3000))                                                  # runs in the fp16x3 kernels: samples only
-    assert [c[1] for c in eng.calls] == [4097, 2048] and net._checked_min_len is None
+    assert [c[1] for c in eng.calls] == [4097, 2048] and net._guard.checked_min_len is None
     net.guard(eng, _ids(4, 3500))                                                  # below the switch: nothing on trial, nothing counted
     assert len(eng.calls) == 2
     net.guard(eng, _ids(4, 4400))                                                  # the first batch that runs the mode IS measured
-    assert eng.calls[-1] == (4, 4400) and net._checked_min_len == 4400
+    assert eng.calls[-1] == (4, 4400) and net._guard.checked_min_len == 4400
 
 
 def test_an_fp16x3_module_asked_to_check_itself_falls_back_to_exact_fp32():
