@@ -356,8 +356,8 @@ void launch_embed(const void* ids, int ids_dtype, int64_t row_stride, const floa
                   unsigned char* ids8 /*[B][Lp] clamped ids, may be null*/, int B, int L, int Lp, hipStream_t st,
                   int* bad_ids = nullptr /*device-visible flag set when an id is outside [0, 16)*/);
 
-// exact fp32, fused (tail32.hip): out_proj + LN2 + MLP + both residuals on h in place, then -- w_in_next != null -- the next
-// block's LayerNorm-1 + in_proj into z (rows x0 | x1 | v, fp32), or -- score != null, the last block -- ln_f + the pooling scores and
+// exact fp32, fused (tail32.hip): out_proj + LN2 + MLP + both residuals on h in place, then EXACTLY ONE of: w_in_next != null -- the
+// next block's LayerNorm-1 + in_proj into z (rows x0 | x1 | v, fp32); score != null, the last block -- ln_f + the pooling scores and
 // one online-softmax pooling partial per 64-token tile (T32_TILE; merged by launch_head_tiles).  Weights in launch_pack_f32t's order.
 constexpr int T32_TILE = 64;
 struct Tail32Score {

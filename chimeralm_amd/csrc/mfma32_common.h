@@ -88,6 +88,13 @@ __device__ __forceinline__ void stage_rows(float* Xs, const float* __restrict__ 
     }
 }
 
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2]) {
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+}
+
 // acc[mt] += W-set x T[tokens mt*32.., k = 64 part ..): token-major tile
 template <int AR>
 __device__ __forceinline__ void compute_set_tm(const float* T, int part, int lrow, int lhalf, const f32x4 (&ws)[KS_SET], f32x16 (&acc)[2]) {

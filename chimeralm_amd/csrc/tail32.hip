@@ -33,7 +33,7 @@ namespace clm {
 struct Tail32Args {
     const float* y;           // [B, 256, Lp] fp32
     float* h;                 // [B, L, 256] residual stream, updated in place
-    const f32x4 *w_out, *w_fc1, *w_fc2, *w_in;   // packed (pack_f32t_kernel); w_in: the NEXT block's in_proj, or null
+    const f32x4 *w_out, *w_fc1, *w_fc2, *w_in;   // packed (pack_f32t_kernel); w_in: the NEXT block's in_proj
     const float *b_out, *b_fc1, *b_fc2, *b_in, *ln2_g, *ln2_b, *n_g, *n_b;
     float* z;                 // [B, 768, Lp] fp32 (NEXT)
     int B, L, Lp, tiles_x;
@@ -49,16 +49,16 @@ struct Tail32Args {
     const float* emb;            // [16, 256]
 };
 
-// NEXT: what follows the block on the tile still in registers -- nothing / the next block's LayerNorm-1 + in_proj / (round 5, the
+// NEXT: what follows the block on the tile still in registers -- the next block's LayerNorm-1 + in_proj / (round 5, the
 // last block) ln_f + attention.0 + GELU(erf) + attention.2 = the pooling scores and this tile's online-softmax pooling partial, as
 // the 16-bit tail kernel has it (gemm16.hip score_pool_tile; /root/reference/chimeralm/models/components/hyena.py:117-132): the
 // separate score GEMM (3.5 ms per 256 x 8,193 launch), softmax-statistics and pooling kernels of rounds 1-4 read the fp32 residual
 // stream twice more; head_tiles_kernel (head.hip) merges the partials in a fixed order.
-enum { T32_NONE = 0, T32_INPROJ = 1, T32_SCORE = 2 };
+enum { T32_INPROJ = 1, T32_SCORE = 2 };
 
 template <int NEXT, int AR = AR_F32>
 __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
-    constexpr float WS = WSCALE<AR>, WSI = WUNSCALE<AR>;
+    constexpr float WSI = WUNSCALE<AR>;
     extern __shared__ __attribute__((aligned(16))) float smem32[];
     float* As = smem32;                                     // LN2(r) / LN1'(h') tile [64][RS32]      (the y tile aliases As + Hs)
     float* Hs = As + BM32 * RS32;                           // gelu(fc1) chunk [64][RS32]
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
         }
         __syncthreads();
         const f32x4* nxt = j + 1 < DI / 256 ? wset_ptr(m.w_fc1, j + 1, D / 8, 0, wave, lane)
-                                            : wset_ptr(NEXT != T32_NONE ? m.w_in : m.w_fc1, 0, D / 8, 0, wave, lane);
+                                            : wset_ptr(m.w_in, 0, D / 8, 0, wave, lane);
         product256<false, AR>(Hs, m.w_fc2, 0, DI / 8, j * 32, nxt, wave, lane, ws, acc2);
         __syncthreads();                                    // every wave is done reading Hs before the next chunk lands in it
     }
@@ -183,15 +183,12 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             }
         }
     }
-    // ---- 5. the next block's LayerNorm-1 + in_proj on the tile still in registers: z rows x0 | x1 | v
+    // ---- 5. the next block's LayerNorm-1 (the last block: ln_f) -> As, and on the tile still in registers: in_proj, z rows x0 | x1 | v
+    ln_to_tile<false, AR>(acc2, P1, P2, m.n_g, m.n_b, m.eps, As, valid, wave, lrow, lhalf);
     if constexpr (NEXT == T32_INPROJ) {
-        ln_to_tile<false, AR>(acc2, P1, P2, m.n_g, m.n_b, m.eps, As, valid, wave, lrow, lhalf);
 #pragma unroll 1
         for (int nb = 0; nb < D3 / 256; ++nb) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc1[mt][r] = 0.f;
+            zero_acc(acc1);
             product256<false, AR>(As, m.w_in, nb, D / 8, 0, wset_ptr(m.w_in, nb + 1 < D3 / 256 ? nb + 1 : 0, D / 8, 0, wave, lane), wave,
                                   lane, ws, acc1);
             // rows = features: 32 lanes = 32 consecutive tokens of one channel row (128 bytes)
@@ -207,14 +204,10 @@ __global__ __launch_bounds__(512) void tail32_kernel(Tail32Args m) {
             }
         }
     }
-    // ---- 5'. the last block: ln_f -> As, scores, and this tile's pooling partial  m = max s_t, S = sum exp(s_t - m),
+    // ---- 5'. the last block: scores, and this tile's pooling partial  m = max s_t, S = sum exp(s_t - m),
     //          vec[c] = sum_t exp(s_t - m) ln_f(h')[t][c]   (softmax over ALL positions, pads included: hyena.py:121-132, mask None)
     if constexpr (NEXT == T32_SCORE) {
-        ln_to_tile<false, AR>(acc2, P1, P2, m.n_g, m.n_b, m.eps, As, valid, wave, lrow, lhalf);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[mt][r] = 0.f;
+        zero_acc(acc1);
         product256<false, AR>(As, m.w_in, 0, D / 8, 0, wset_ptr(m.w_in, 0, D / 8, 0, wave, lane), wave, lane, ws, acc1);   // (last slot: unused re-request)
         float* P = Hs;                                      // [8][64] score partials of the waves (Hs is dead: every wave is past the MLP)
         float* E = P + 8 * BM32;                            // [64] exp(s - m)
@@ -422,10 +415,7 @@ __global__ __launch_bounds__(512) void enc32_kernel(Enc32Args m) {
     // qkv = W_qkv As + b_qkv, rows = features: a lane writes 4 consecutive features of its token row
 #pragma unroll 1
     for (int nb = 0; nb < D3 / 256; ++nb) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[mt][r] = 0.f;
+        zero_acc(acc1);
         product256<false, AR>(As, m.w_qkv, nb, D / 8, 0, wset_ptr(m.w_qkv, nb + 1 < D3 / 256 ? nb + 1 : 0, D / 8, 0, wave, lane), wave, lane,
                               ws, acc1);
         const float* bq = m.b_qkv + nb * 256 + wave * 32 + 4 * lhalf;
@@ -467,10 +457,7 @@ __global__ __launch_bounds__(512) void conv32_kernel(Conv32Args m) {
     f32x16 acc[2];
     load_wset(wset_ptr(m.w, 0, D / 8, 0, wave, lane), ws[0]);
     stage_rows<AR, 1>(Xs, m.x + (size_t)b * Lin * D, t0, Lin, wave, lane);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    zero_acc(acc);
     __syncthreads();
     static_for<0, 3>([&](auto dkc) {
         constexpr int dk = decltype(dkc)::value;
@@ -522,10 +509,7 @@ __global__ __launch_bounds__(512) void cnn_gemm7_kernel(CnnConvArgs m) {
     f32x16 acc[2];
     load_wset(wset_ptr(m.w, 0, D / 8, 0, wave, lane), ws[0]);
     stage_rows<AR, cnn::HALO>(Xs, m.x + (size_t)b * Lin * D, t0, Lin, wave, lane);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    zero_acc(acc);
     __syncthreads();
     static_for<0, cnn::K>([&](auto dkc) {
         constexpr int dk = decltype(dkc)::value;
@@ -623,8 +607,16 @@ void launch_pack_f32t(const float* w, void* out, int n, int k, hipStream_t st) {
     hipLaunchKernelGGL(pack_f32t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, reinterpret_cast<f32x4*>(out), n, k);
 }
 
-// x3: the products as three fp16 MFMAs on hi + lo halfs (weights from launch_pack_x3) instead of the fp32 MFMA.
-// score != null (the last block; w_in_next must be null): ln_f + pooling scores + per-64-token-tile pooling partials follow on the tile.
+// f(the arithmetic as a compile-time constant): x3 = the products as three fp16 MFMAs on hi + lo halfs (weights from launch_pack_x3)
+// instead of the fp32 MFMA
+template <class F>
+void with_arith(bool x3, F f) {
+    if (x3) f(std::integral_constant<int, AR_X3>{});
+    else f(std::integral_constant<int, AR_F32>{});
+}
+
+// Exactly one of `score` / `w_in_next` is given: score (the last block) -- ln_f + pooling scores + per-64-token-tile pooling partials
+// follow on the tile; w_in_next (every other block) -- the next block's LayerNorm-1 + in_proj.  There is no tail without either.
 void launch_tail32(const float* y, float* h, const void* w_out, const void* w_fc1, const void* w_fc2, const void* w_in_next,
                    const float* b_out, const float* b_fc1, const float* b_fc2, const float* b_in_next, const float* ln2_g,
                    const float* ln2_b, const float* n_g, const float* n_b, float* z, int B, int L, int Lp, float eps, hipStream_t st,
@@ -638,15 +630,10 @@ void launch_tail32(const float* y, float* h, const void* w_out, const void* w_fc
     static_assert(8 * BM32 + BM32 + 4 * D <= BM32 * RS32, "score stage: P / E / V fit the Hs region");
     const dim3 grid((unsigned)(m.tiles_x * B));
     const dim3 block(512);
-    if (x3) {
-        if (score) launch_lds<tail32_kernel<T32_SCORE, AR_X3>>(grid, block, lds, st, m);
-        else if (w_in_next) launch_lds<tail32_kernel<T32_INPROJ, AR_X3>>(grid, block, lds, st, m);
-        else launch_lds<tail32_kernel<T32_NONE, AR_X3>>(grid, block, lds, st, m);
-    } else {
-        if (score) launch_lds<tail32_kernel<T32_SCORE, AR_F32>>(grid, block, lds, st, m);
-        else if (w_in_next) launch_lds<tail32_kernel<T32_INPROJ, AR_F32>>(grid, block, lds, st, m);
-        else launch_lds<tail32_kernel<T32_NONE, AR_F32>>(grid, block, lds, st, m);
-    }
+    with_arith(x3, [&](auto ar) {
+        if (score) launch_lds<tail32_kernel<T32_SCORE, ar()>>(grid, block, lds, st, m);
+        else launch_lds<tail32_kernel<T32_INPROJ, ar()>>(grid, block, lds, st, m);
+    });
 }
 
 // FIRST (att == null): qkv of the tile of h as it is (the first layer's in_proj); otherwise the whole layer after its attention,
@@ -658,13 +645,10 @@ void launch_enc32(const float* att, float* h, const void* w_o, const void* w1, c
                 reinterpret_cast<const f32x4*>(w_qkv), b_o, b1, b2, b_qkv, ln1_g, ln1_b, ln2_g, ln2_b, qkv, M, eps};
     const size_t lds = (size_t)(2 * BM32 * RS32 + 2 * 8 * BM32) * sizeof(float);
     const dim3 grid((unsigned)((M + BM32 - 1) / BM32)), block(512);
-    if (!att) {
-        if (x3) launch_lds<enc32_kernel<true, AR_X3>>(grid, block, lds, st, m);
-        else launch_lds<enc32_kernel<true, AR_F32>>(grid, block, lds, st, m);
-    } else {
-        if (x3) launch_lds<enc32_kernel<false, AR_X3>>(grid, block, lds, st, m);
-        else launch_lds<enc32_kernel<false, AR_F32>>(grid, block, lds, st, m);
-    }
+    with_arith(x3, [&](auto ar) {
+        if (!att) launch_lds<enc32_kernel<true, ar()>>(grid, block, lds, st, m);
+        else launch_lds<enc32_kernel<false, ar()>>(grid, block, lds, st, m);
+    });
 }
 
 // x [B, Lin, 256] -> relu(conv1d_k3(x) + bias) pooled by 2 -> out [B, Lin / 2, 256]; w: three taps, each packed by launch_pack_f32t
@@ -672,8 +656,7 @@ void launch_conv32(const float* x, const void* w, const float* bias, float* out,
     Conv32Args m{x, reinterpret_cast<const f32x4*>(w), bias, out, B, Lin, (Lin + BM32 - 1) / BM32};
     const size_t lds = (size_t)(BM32 + 2) * RS32 * sizeof(float);
     const dim3 grid((unsigned)(m.tiles_x * B)), block(512);
-    if (x3) launch_lds<conv32_kernel<AR_X3>>(grid, block, lds, st, m);
-    else launch_lds<conv32_kernel<AR_F32>>(grid, block, lds, st, m);
+    with_arith(x3, [&](auto ar) { launch_lds<conv32_kernel<ar()>>(grid, block, lds, st, m); });
 }
 
 // DNAConvNet block 1 / 2 (cnn.hip): x [B, Lin, 256] -> maxpool4(gelu(bn(conv1d_k7(x) + bias))) -> out [B, Lin / 4, 256], or with
@@ -685,13 +668,10 @@ void launch_cnn_gemm7(const float* x, const void* w, const float* bias, const fl
     CnnConvArgs m{x, reinterpret_cast<const f32x4*>(w), bias, bn_scale, bn_shift, out, B, Lin, (4 * Lout + BM32 - 1) / BM32};
     const size_t lds = (size_t)(BM32 + 2 * cnn::HALO) * RS32 * sizeof(float);
     const dim3 grid((unsigned)(m.tiles_x * B)), block(512);
-    if (partial) {
-        if (x3) launch_lds<cnn_gemm7_kernel<true, AR_X3>>(grid, block, lds, st, m);
-        else launch_lds<cnn_gemm7_kernel<true, AR_F32>>(grid, block, lds, st, m);
-    } else {
-        if (x3) launch_lds<cnn_gemm7_kernel<false, AR_X3>>(grid, block, lds, st, m);
-        else launch_lds<cnn_gemm7_kernel<false, AR_F32>>(grid, block, lds, st, m);
-    }
+    with_arith(x3, [&](auto ar) {
+        if (partial) launch_lds<cnn_gemm7_kernel<true, ar()>>(grid, block, lds, st, m);
+        else launch_lds<cnn_gemm7_kernel<false, ar()>>(grid, block, lds, st, m);
+    });
 }
 
 }  // namespace clm

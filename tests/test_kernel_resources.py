@@ -51,7 +51,7 @@ def test_hot_kernels_have_no_scratch_in_their_loops():
         (r"enc_ffn16_kernelILi[123]E", 0),                        # transformer layer kernel, all three 16-bit modes
         (r"conv3_relu_pool_kernelILi[123]E", 0),
         (r"attention_fwd_kernelILi2ELb[01]E", 0),                 # fp16 attention, one plane and hi + lo planes
-        (r"tail32_kernelILi[012]ELi[01]E", 0),                    # exact fp32 / fp16x3, round 4: the fused block tail (round 5: + its score variant) ...
+        (r"tail32_kernelILi[12]ELi[01]E", 0),                     # exact fp32 / fp16x3, round 4: the fused block tail (round 5: + its score variant) ...
         (r"enc32_kernelILb[01]E", 0),                             # ... and the transformer's encoder layer, CNN stem and attention
         (r"conv32_kernel", 0),
         (r"attention32_kernel", 0),
@@ -63,6 +63,9 @@ def test_hot_kernels_have_no_scratch_in_their_loops():
     # the three MFMA attention kernels (attention.hip, one tile loop under three arithmetics) hide their exp latency with resident
     # waves: none may drop below the occupancy it had as a kernel of its own
     floors = [(r"attention_fwd_kernel", 4, 3), (r"attention32_kernel", 4, 1), (r"attention_x3_kernel", 3, 1)]
+    # the exact layer kernels (tail32.hip), counted the same way so that a dead or a missing variant shows here: in_proj and score
+    # tails, first-layer and whole-layer encoders, each under both arithmetics; two waves per SIMD is what their LDS tiles allow
+    floors += [(r"tail32_kernel", 2, 4), (r"enc32_kernel", 2, 4)]
     for pattern, waves, count in floors:
         hits = {n: int(r["Occupancy [waves/SIMD]"]) for n, r in res.items() if re.search(pattern, n)}
         assert len(hits) == count, f"{pattern}: {sorted(hits)}"
