@@ -351,7 +351,8 @@ def finetune(
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 
-TRAIN_NETS = ("cnn", "mamba", "mambasp")              # `train --net`
+TRAIN_NETS = ("cnn", "mamba", "mambasp")              # `train --net`: the nets whose layers train on engine kernels of their own ...
+TRAIN_NET_CHOICES = TRAIN_NETS + ("transformer",)     # ... and the one that trains in torch around the engine's attention core
 
 
 @app.command()
@@ -368,12 +369,13 @@ def train(
                                           "torch's initialisation under --seed)"),
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
     net: str = typer.Option("cnn", "--net", help="The net to train: cnn (DNAConvNet), mamba or mambasp (configs/model/NET.yaml; the "
-                            "Mamba nets take batches of one read too)"),
+                            "Mamba nets take batches of one read too) or transformer (SequenceCNNTransformer; --ckpt starts from a "
+                            "reference checkpoint)"),
 ):
     """Train DNAConvNet (configs/model/cnn.yaml) on labelled reads (writes model.safetensors and metrics.tsv)."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
-    if net not in TRAIN_NETS:
-        raise typer.BadParameter(f"--net must be one of {', '.join(TRAIN_NETS)}")
+    if net not in TRAIN_NET_CHOICES:
+        raise typer.BadParameter(f"--net must be one of {', '.join(TRAIN_NET_CHOICES)}")
     if epochs < 1:
         raise typer.BadParameter("--epochs must be >= 1")
     if net != "cnn" and not 1 <= batch_size <= 65535:
@@ -407,6 +409,8 @@ def train(
     train_rows, val_rows = headtrain.split_rows(train_path, val_path)
     if net == "cnn":
         fit = cnntrain.fit_cnn
+    elif net == "transformer":
+        from .tftrain import fit_transformer as fit
     else:
         from .mambatrain import fit_mamba as fit
     hist = fit(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)

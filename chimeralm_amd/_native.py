@@ -128,6 +128,10 @@ SYMBOLS = {
     "clm_set_mlp_compensation": (C.c_int, [_H, C.c_int]),
     "clm_attention_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "clm_attention_exact_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "clm_attn_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "clm_attn_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p]),
+    "clm_attn_train_backward": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p]),
+    "clm_attn_train_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p]),
     "clm_tf_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "clm_tf_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "clm_tf_finalize": (C.c_int, [_H]),

@@ -453,7 +453,7 @@ def _check_engine(model, device: torch.device, batch_idx: int) -> None:
     is written.  The message names the batch range it can belong to."""
     net = getattr(model, "net", None)
     eng = getattr(net, "_engine", None)
-    if eng is None:
+    if eng is None or not hasattr(eng, "check"):           # (SequenceCNNTransformer._engine is a method: its calls report their own errors)
         return
     from .engine import EngineError
 

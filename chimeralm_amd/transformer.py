@@ -19,6 +19,11 @@ and says so.  On by default for fp16c.  WHICH batches are measured is the rule `
 default mode, and the first fall-back level of the 16-bit modes -- packs weights x 2^10 as fp16 halfs, which saturate at
 |w| >= 64: if a CNN-stem or encoder weight is that large (or NaN), the engine runs exact fp32 wherever it would run fp16x3; the
 module reads that back at every weight load (`clm_tf_effective_precision`), records it in `precision_report` and logs a warning.
+
+Training (`trainable=True`, keyword-only; tftrain.py): in `train()` mode and with autograd on, `forward` builds a
+graph to every parameter in exact fp32 -- the attention core forward and backward on the engine (`attention_core="engine"`,
+csrc/attention_train.hip) or through `F.scaled_dot_product_attention` (`"torch"`), everything around it in torch.  Every other call
+is the inference forward above, bit for bit.
 """
 from __future__ import annotations
 
@@ -58,7 +63,7 @@ class SequenceCNNTransformer(nn.Module):
     def __init__(self, vocab_size: int, max_len: int, d_model: int = 256, cnn_kernel_size: int = 3, dropout: float = 0.1,
                  num_encoder_layers: int = 2, nhead: int = 8, dim_feedforward: int = 1024, number_of_classes: int = 2,
                  padding_idx: int = 4, *, precision: str = "fp16x3", selfcheck: bool | None = None, selfcheck_tol: float = 5e-4,
-                 selfcheck_every: int = 16):
+                 selfcheck_every: int = 16, trainable: bool = False, attention_core: str = "engine"):
         super().__init__()
         if (vocab_size, d_model, cnn_kernel_size, nhead, dim_feedforward, number_of_classes) != (12, 256, 3, 8, 1024, 2):
             raise NotImplementedError("the MI355X encoder implements the production shape: vocab 12, d_model 256, kernel 3, "
@@ -89,6 +94,32 @@ class SequenceCNNTransformer(nn.Module):
                                         nn.Linear(d_model // 2, number_of_classes))
         self._h, self._dev, self._sig = None, None, None
         self._stop = -1                                        # debug_stop_after
+        # training (tftrain.py): with `trainable`, in train() and under autograd the forward builds a graph to every parameter, in
+        # exact fp32 whatever `precision` says; `attention_core` = "engine" (csrc/attention_train.hip) or "torch" (the comparison path)
+        if attention_core not in ("engine", "torch"):
+            raise ValueError('attention_core must be "engine" (the HIP op) or "torch" (F.scaled_dot_product_attention)')
+        self.trainable, self.attention_core, self.dropout = bool(trainable), attention_core, float(dropout)
+        self._dropout_generator, self._attn_draws = None, 0
+
+    @property
+    def dropout_generator(self):
+        """The generator of the training forward's dropout masks (None: torch's default one).  Assigning one restarts the stream of
+        attention seeds: two nets given equally seeded generators draw the same masks."""
+        return self._dropout_generator
+
+    @dropout_generator.setter
+    def dropout_generator(self, gen):
+        self._dropout_generator, self._attn_draws = gen, 0
+
+    def next_attention_seed(self) -> int:
+        """The 64-bit seed of the next attention call: host arithmetic on the generator's seed and a call counter, so that drawing it
+        never waits for the device."""
+        from .tftrain import layer_seed
+
+        gen = self._dropout_generator
+        base = gen.initial_seed() if gen is not None else torch.initial_seed()
+        self._attn_draws += 1
+        return layer_seed(base, self._attn_draws - 1)
 
     # ------------------------------------------------------------------ engine plumbing
     def _check(self, rc: int):
@@ -196,6 +227,10 @@ class SequenceCNNTransformer(nn.Module):
             raise ValueError("input_ids must be [batch, length] of int64 / int32 / uint8")
         if input_ids.stride(1) != 1:
             input_ids = input_ids.contiguous()
+        if self.trainable and self.training and torch.is_grad_enabled():
+            from .tftrain import train_forward
+
+            return train_forward(self, input_ids)
         lib = self._engine(input_ids.device)
         self.guard(lib, input_ids)
         B, L = input_ids.shape

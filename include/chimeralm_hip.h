@@ -280,6 +280,35 @@ int clm_attention_fwd(const void* qkv, void* out, int B, int L, int precision, v
  * at most 2^31 - 1, else CLM_E_INVALID and nothing is launched.  Asynchronous on `stream`; writes nothing beyond out[B * L * 256]. */
 int clm_attention_exact_fwd(const float* qkv, float* out, int B, int L, int precision, void* stream);
 
+/* ---- the attention core for training (csrc/attention_train.hip; additive under ABI 6) ---------------
+ * The same attention, exact fp32, forward with dropout on the probabilities and backward.  Stateless, no handle: the caller owns
+ * every tensor.  Shape as above: qkv device fp32 [B, L, 768] (q | k | v), L positions, 8 heads of 32.
+ *   forward    out [B, L, 256] = sum_j keep_ij p_ij v_j / (1 - dropout_p), p = softmax_j(q_i . k_j / sqrt(32)) (the row sum is taken
+ *              over the undropped probabilities), and lse [B, 8, L] = log2 sum_j exp(q_i . k_j / sqrt(32)), in LOG2 units
+ *              (torch.logsumexp of the scaled scores times log2 e: the exponent the kernels' exp2 takes).  With dropout_p == 0 out equals clm_attention_exact_fwd(CLM_PREC_F32)
+ *              bit for bit.
+ *   backward   dqkv [B, L, 768] (dq | dk | dv, every element written) of dout [B, L, 256], from qkv and the forward's out and lse,
+ *              with the forward's dropout_p and seed.  P is recomputed as 2^(s log2 e - lse); delta_i = sum_d dout_id out_id goes to
+ *              `workspace` (clm_attn_train_workspace_bytes(B, L) bytes: 4 * B * 8 * L rounded up to 16).  Two passes (dq per query
+ *              tile over the keys, dk | dv per key tile over the queries); no floating-point atomics: two identical calls give
+ *              identical bits, and a read's results do not depend on the other reads of the batch.
+ *   keep mask  keep_ij = bits(seed, b * 8 + h, i, j) >= round(dropout_p * 2^32), with mix32 the xor-shift / multiply avalanche
+ *              mixer  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16  applied twice:
+ *                  r    = mix32((uint32) seed ^ i * 0x9E3779B1)
+ *                  bits = mix32((r ^ ((uint32)(seed >> 32) + (b * 8 + h) * 0x85EBCA77)) + j * 0xC2B2AE3D)      (mod 2^32)
+ *              A pure function of those four values -- not of the tile shape, the launch geometry or B.  The backward
+ *              regenerates it; clm_attn_train_mask writes it out as bytes keep [B, 8, L, L] (0 / 1) for the tests and is the only
+ *              place a mask is ever stored.
+ * CLM_E_INVALID, and nothing is launched: B < 1 or L < 1; dropout_p outside [0, 1) (NaN included); a pointer that is NULL or off 16
+ * bytes; more than 2^31 - 1 workgroups in any launch (ceil(L / 128) * 8 * B for the passes, ceil(B * 8 * L * L / 256) for the mask).
+ * clm_attn_train_workspace_bytes returns the (negative) code instead of a size.  Asynchronous on `stream`; nothing is written
+ * beyond the stated extents. */
+int64_t clm_attn_train_workspace_bytes(int B, int L);
+int clm_attn_train_forward(const float* qkv, float* out, float* lse, int B, int L, float dropout_p, uint64_t seed, void* stream);
+int clm_attn_train_backward(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv, void* workspace,
+                            int B, int L, float dropout_p, uint64_t seed, void* stream);
+int clm_attn_train_mask(uint8_t* keep, int B, int L, float dropout_p, uint64_t seed, void* stream);
+
 /* The whole SequenceCNNTransformer forward (transformer.py:88-104; configuration of configs/model/transformer.yaml:3-12:
  * vocab 12, d_model 256, kernel 3, 8 heads, feed-forward 1024, `n_layers` encoder layers) behind the same `net` boundary as
  * HyenaDna: forward(input_ids[B, L], input_quals=None) -> logits fp32 [B, 2].  Same conventions as the clm_* calls above;
