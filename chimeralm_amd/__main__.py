@@ -309,10 +309,19 @@ def finetune(
     ckpt_path: Path | None = typer.Option(None, "--ckpt", "-c", help="Path to the checkpoint file to start from"),
     weights: str = typer.Option("yangliz5/chimeralm", "--weights", help="Directory/file with model.safetensors to start from"),
     verbose: bool = typer.Option(False, "--verbose", "-v", help="Enable verbose output"),
+    train_backbone: bool = typer.Option(False, "--train-backbone", help="Train the backbone together with the head (the reference's "
+                                        "freeze_backbone=False): every parameter, in exact fp32; --precision then only names the "
+                                        "arithmetic of the validation forwards"),
+    hyena_core: str = typer.Option("engine", "--hyena-core", help="With --train-backbone, the Hyena operator's core: engine (the HIP "
+                                   "op; reads beyond 8,193 tokens take torch) | torch (conv1d and rfft / irfft)"),
 ):
-    """Fine-tune the classifier head on labelled reads with the backbone frozen (writes model.safetensors and metrics.tsv)."""
+    """Fine-tune the classifier head on labelled reads with the backbone frozen, or with --train-backbone the whole net (writes
+    model.safetensors and metrics.tsv)."""
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
     from .headtrain import TRAIN_PRECISIONS
+
+    if hyena_core not in ("engine", "torch"):
+        raise typer.BadParameter("--hyena-core must be engine or torch")
 
     if precision not in TRAIN_PRECISIONS:
         raise typer.BadParameter("--precision must be fp16x3 or fp32: the head trains on the rows of the exact kernels")
@@ -339,6 +348,8 @@ def finetune(
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
     kw = dict(precision=precision, selfcheck=False, freeze_backbone=True)
+    if train_backbone:
+        kw = dict(precision=precision, selfcheck=False, freeze_backbone=False, trainable=True, hyena_core=hyena_core)
     if ckpt_path is not None:
         log.info(f"Loading model from {ckpt_path}")
         model = lm.ChimeraLM.new(**kw).load_reference_checkpoint(ckpt_path)
@@ -347,7 +358,12 @@ def finetune(
         model = lm.ChimeraLM.from_pretrained(weights, **kw)
     model.to(device)
     train_rows, val_rows = headtrain.split_rows(train_path, val_path)
-    hist = headtrain.fit_head(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
+    if train_backbone:
+        from .hyenatrain import fit_hyena
+
+        hist = fit_hyena(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
+    else:
+        hist = headtrain.fit_head(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 
 

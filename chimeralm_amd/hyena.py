@@ -211,8 +211,11 @@ class HyenaDna(nn.Module):
     def __init__(self, number_of_classes: int, head: nn.Module, backbone_name: str = "hyenadna-small-32k-seqlen", *,
                  freeze_backbone: bool = False, precision: str = "fp16c", chunk_reads: int = 256,
                  selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
-                 attention_top_k: int | None = None, trajectory_stride: int | None = None):
+                 attention_top_k: int | None = None, trajectory_stride: int | None = None, trainable: bool = False,
+                 hyena_core: str = "engine"):
         super().__init__()
+        if hyena_core not in ("engine", "torch"):
+            raise ValueError('hyena_core must be "engine" (the HIP op, csrc/hyena_train.hip) or "torch" (conv1d and rfft / irfft)')
         if number_of_classes != 2:
             raise NotImplementedError("the engine implements the binary (2-class) head only")
         missing = [k for k in _HEAD_KEYS if k not in head.state_dict()]
@@ -244,6 +247,14 @@ class HyenaDna(nn.Module):
         if freeze_backbone:
             for p in self.backbone.parameters():
                 p.requires_grad = False
+        # training of the whole net (hyenatrain.py): with `trainable` and an unfrozen backbone, in train() and under
+        # autograd, the forward builds a graph to every parameter, in exact fp32 whatever `precision` says.  `hyena_core`: the
+        # operator's core on the engine or in torch; `embed_dropout`: the backbone's only dropout, on the embedding output, drawn from
+        # `dropout_generator` (None: torch's default generator); `last_train_core`: the core the last training forward took
+        self.trainable, self.hyena_core = bool(trainable), hyena_core
+        self.embed_dropout = 0.1
+        self.dropout_generator = None
+        self.last_train_core = None
         self._engine: Engine | None = None
         self._engine_sig = None
         # when the mode is measured again since the last weight load (`heard`: the seeded samples ran); knobs: `guard_due`
@@ -411,9 +422,15 @@ class HyenaDna(nn.Module):
 
         `freeze_backbone=True`, in training mode with autograd on: the logits carry a graph to the head's parameters (the fine-tune,
         headtrain.py: the backbone runs as in inference, the attention pooling forward and backward in the engine, the classifier in
-        torch); `precision` must be "fp32" or "fp16x3".  Every other call is inference and returns logits without a graph -- also a
-        module with an unfrozen backbone in training mode, which is how a freshly built module is called everywhere: its backbone does
-        not train on this engine, and `ClassificationLit.training_step` says so."""
+        torch); `precision` must be "fp32" or "fp16x3".  `trainable=True` with an unfrozen backbone, in training mode with autograd on:
+        the logits carry a graph to EVERY parameter (hyenatrain.py: the Hyena operator's core forward and backward in the engine,
+        everything around it in torch; exact fp32).  Every other call is inference and returns logits without a graph -- also a
+        module with an unfrozen backbone and without `trainable` in training mode, which is how a freshly built module is called
+        everywhere: it does not train, and `ClassificationLit.training_step` says so."""
+        if self.trainable and not self.freeze_backbone and self.training and torch.is_grad_enabled():
+            from .hyenatrain import train_forward
+
+            return train_forward(self, input_ids)
         if self.freeze_backbone and self.training and torch.is_grad_enabled():
             from .headtrain import check_train_precision, differentiable_logits
 

@@ -309,6 +309,34 @@ int clm_attn_train_backward(const float* qkv, const float* out, const float* lse
                             int B, int L, float dropout_p, uint64_t seed, void* stream);
 int clm_attn_train_mask(uint8_t* keep, int B, int L, float dropout_p, uint64_t seed, void* stream);
 
+/* ---- the Hyena operator's core for training (csrc/hyena_train.hip; additive under ABI 6) -------------
+ * The causal 3-tap filter, the two gates and the long convolution with its skip term, forward and backward, exact fp32.
+ * Stateless, no handle: the caller owns every tensor.  All tensors are device fp32, contiguous, channel-major, rows of exactly L
+ * floats (no padded pitch; 4-byte alignment is all that is asked):
+ *   zc [B, 768, L]   the raw in_proj output, rows x0 | x1 | v          sw [768, 3], sb [768]   short_filter weight and bias
+ *   k  [256, L]      the modulated implicit filter                      D  [256]                filter_fn.bias
+ *   c, y, dy [B, 256, L]
+ *   forward    u_r[t] = sb[r] + sum_j sw[r, j] zc[r, t - 2 + j] (zc = 0 before t = 0; r = ch, 256 + ch, 512 + ch -> x0, x1, v),
+ *              g = v x1,  c = causal_conv(g, k[ch]) + D[ch] g,  y = c x0.  Writes c_out and y_out.
+ *   backward   from zc, the parameters, the forward's c and dy: dzc [B, 768, L], dsw [768, 3], dsb [768], dk [256, L], dD [256],
+ *              every element written.  g, x0, x1, v are recomputed.
+ * Covered: 1 <= L <= 8193 (one power-of-two transform of N = 2^logn >= 2 L - 2 points, logn 8 ... 14, held in LDS).  No
+ * floating-point atomics: two identical calls give identical bits; dk, dsw, dsb and dD are added over the reads in read order;
+ * c, y and dzc of a read do not depend on the other reads of the batch.
+ * `workspace`: clm_hyena_train_workspace_bytes(B, L) bytes, with N as above,
+ *       4 * (N + 512 * (N / 2 + 1) + B * 256 * L + B * 256 * 16)   rounded up to 16
+ * (the twiddle table, the filter spectra -- computed once per call from k --, the per-read dk rows and the per-read parameter
+ * partials; the forward uses the first two).  It holds nothing between calls.
+ * CLM_E_INVALID, and nothing is launched: B < 1, L < 1 or B > 65535; a pointer that is NULL or off 4 bytes.  CLM_E_UNSUPPORTED:
+ * L > 8193.  clm_hyena_train_workspace_bytes returns the (negative) code instead of a size.  Asynchronous on `stream`; nothing is
+ * written beyond the stated extents. */
+int64_t clm_hyena_train_workspace_bytes(int B, int L);
+int clm_hyena_train_forward(const float* zc, const float* sw, const float* sb, const float* k, const float* D, int B, int L,
+                            float* c_out, float* y_out, void* workspace, void* stream);
+int clm_hyena_train_backward(const float* zc, const float* sw, const float* sb, const float* k, const float* D, const float* c,
+                             const float* dy, int B, int L, float* dzc, float* dsw, float* dsb, float* dk, float* dD, void* workspace,
+                             void* stream);
+
 /* The whole SequenceCNNTransformer forward (transformer.py:88-104; configuration of configs/model/transformer.yaml:3-12:
  * vocab 12, d_model 256, kernel 3, 8 heads, feed-forward 1024, `n_layers` encoder layers) behind the same `net` boundary as
  * HyenaDna: forward(input_ids[B, L], input_quals=None) -> logits fp32 [B, 2].  Same conventions as the clm_* calls above;
