@@ -130,7 +130,8 @@ class DNAConvNet(nn.Module):
         return out
 
     def debug_fetch(self, name: str, shape) -> np.ndarray:
-        """Intermediates of the last forward: "block0" [B, L/4, 256], "block1" [B, L/16, 256], "pooled" [B, 256]."""
+        """Intermediates of the last forward: "block0" [B, L/4, 256], "block1" [B, L/16, 256], "partial" [B, ceil((L/64) / 16), 256]
+        (block 2's pooled rows summed per tile of 16), "pooled" [B, 256]."""
         arr = np.empty(shape, dtype=np.float32)
         self._check(N.load().clm_cnn_debug_fetch(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes))
         return arr

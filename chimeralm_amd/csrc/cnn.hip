@@ -309,11 +309,12 @@ int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, siz
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     const std::string n(name);
-    const size_t B = (size_t)h->last_B, L4 = (size_t)(h->last_L / 4), L16 = L4 / 4;
+    const size_t B = (size_t)h->last_B, L4 = (size_t)(h->last_L / 4), L16 = L4 / 4, L64 = L16 / 4;
     const void* src = nullptr;
     size_t have = 0;
     if (n == "block0") { src = h->x1.get(); have = B * L4 * D * 4; }
     else if (n == "block1") { src = h->x2.get(); have = B * L16 * D * 4; }
+    else if (n == "partial") { src = h->part.get(); have = B * ((L64 + cnn::ROWS2 - 1) / cnn::ROWS2) * D * 4; }
     else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; }
     else return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: unknown name " + n);
     if (bytes > have) return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: more bytes requested than the last forward produced");

@@ -416,8 +416,9 @@ int clm_tf_destroy(clm_tf_handle* h);
  *   ids         i64, i32 or u8; an id outside [0, 12) is clamped into it (no read outside the table; the reference's nn.Embedding
  *               would raise IndexError).
  * The forward is bitwise deterministic (no atomics) and a read's logits do not depend on the other reads of its batch.
- * clm_cnn_debug_fetch names (the last forward): "block0" fp32 [B, L/4, 256], "block1" fp32 [B, L/16, 256], "pooled" fp32 [B, 256]
- * (the mean of block 2's output). */
+ * clm_cnn_debug_fetch names (the last forward): "block0" fp32 [B, L/4, 256], "block1" fp32 [B, L/16, 256], "partial" fp32
+ * [B, ceil((L/64) / 16), 256] (block 2's pooled rows summed per tile of 16; block 2 stores nothing else), "pooled" fp32 [B, 256]
+ * (the mean of block 2's output: the partials added in order, over L/64). */
 typedef struct clm_cnn_handle clm_cnn_handle;
 int clm_cnn_create(int device, int precision, clm_cnn_handle** out);
 int clm_cnn_load_weight(clm_cnn_handle* h, const char* key, const void* data, int dtype, const int64_t* shape, int ndim);
