@@ -295,6 +295,25 @@ def explain(
     log.info(f"{n} reads scanned; results saved to {output_path}")
 
 
+def _checked_fit_options(train_path: Path, val_path: Path | None, output_path: Path | None, ckpt_path: Path | None, epochs: int,
+                         batch_size: int, lr: float, *, min_batch: int, batch_note: str, suffix: str) -> Path:
+    """What `finetune` and `train` refuse alike, before a model is built or a GPU touched; returns the output directory."""
+    if epochs < 1:
+        raise typer.BadParameter("--epochs must be >= 1")
+    if not min_batch <= batch_size <= 65535:
+        raise typer.BadParameter(f"--batch-size must be {min_batch} ... 65535{batch_note}")
+    if not lr > 0:
+        raise typer.BadParameter("--lr must be > 0")
+    for f in (train_path, val_path):
+        if f is not None and f.suffix != ".parquet":
+            raise typer.BadParameter(f"{f} is not in Parquet format")
+        if f is not None and not f.is_file():
+            raise typer.BadParameter(f"{f}: no such file")
+    if ckpt_path is not None and not ckpt_path.is_file():
+        raise typer.BadParameter(f"--ckpt {ckpt_path}: no such file")
+    return output_path if output_path is not None else train_path.with_suffix(suffix)
+
+
 @app.command()
 def finetune(
     train_path: Path = typer.Argument(..., help="Labelled reads (parquet; ids end in |0 or |1)"),
@@ -325,25 +344,13 @@ def finetune(
 
     if precision not in TRAIN_PRECISIONS:
         raise typer.BadParameter("--precision must be fp16x3 or fp32: the head trains on the rows of the exact kernels")
-    if epochs < 1:
-        raise typer.BadParameter("--epochs must be >= 1")
-    if not 1 <= batch_size <= 65535:
-        raise typer.BadParameter("--batch-size must be 1 ... 65535")
-    if not lr > 0:
-        raise typer.BadParameter("--lr must be > 0")
-    for f in (train_path, val_path):
-        if f is not None and f.suffix != ".parquet":
-            raise typer.BadParameter(f"{f} is not in Parquet format")
-        if f is not None and not f.is_file():
-            raise typer.BadParameter(f"{f}: no such file")
     if ckpt_path is not None and weights != "yangliz5/chimeralm":
         raise typer.BadParameter("--ckpt and --weights exclude each other: the fit starts from one set of weights")
-    if ckpt_path is not None and not ckpt_path.is_file():
-        raise typer.BadParameter(f"--ckpt {ckpt_path}: no such file")
-    if output_path is None:
-        output_path = train_path.with_suffix(".finetune")
+    output_path = _checked_fit_options(train_path, val_path, output_path, ckpt_path, epochs, batch_size, lr, min_batch=1, batch_note="",
+                                       suffix=".finetune")
 
     from . import headtrain, lm
+    from .fit import split_rows
 
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
@@ -357,7 +364,7 @@ def finetune(
         log.info(f"Loading model weights {weights}")
         model = lm.ChimeraLM.from_pretrained(weights, **kw)
     model.to(device)
-    train_rows, val_rows = headtrain.split_rows(train_path, val_path)
+    train_rows, val_rows = split_rows(train_path, val_path)
     if train_backbone:
         from .hyenatrain import fit_hyena
 
@@ -392,26 +399,12 @@ def train(
     logging.basicConfig(level=logging.DEBUG if verbose else logging.INFO, format="%(message)s")
     if net not in TRAIN_NET_CHOICES:
         raise typer.BadParameter(f"--net must be one of {', '.join(TRAIN_NET_CHOICES)}")
-    if epochs < 1:
-        raise typer.BadParameter("--epochs must be >= 1")
-    if net != "cnn" and not 1 <= batch_size <= 65535:
-        raise typer.BadParameter("--batch-size must be 1 ... 65535")
-    if net == "cnn" and not 2 <= batch_size <= 65535:
-        raise typer.BadParameter("--batch-size must be 2 ... 65535: BatchNorm needs two reads")
-    if not lr > 0:
-        raise typer.BadParameter("--lr must be > 0")
-    for f in (train_path, val_path):
-        if f is not None and f.suffix != ".parquet":
-            raise typer.BadParameter(f"{f} is not in Parquet format")
-        if f is not None and not f.is_file():
-            raise typer.BadParameter(f"{f}: no such file")
-    if ckpt_path is not None and not ckpt_path.is_file():
-        raise typer.BadParameter(f"--ckpt {ckpt_path}: no such file")
-    if output_path is None:
-        output_path = train_path.with_suffix(".train")
+    output_path = _checked_fit_options(train_path, val_path, output_path, ckpt_path, epochs, batch_size, lr, min_batch=2 if net == "cnn" else 1,
+                                       batch_note=": BatchNorm needs two reads" if net == "cnn" else "", suffix=".train")
 
-    from . import cnntrain, headtrain
+    from . import cnntrain, mambatrain, tftrain
     from .config import compose, instantiate
+    from .fit import split_rows
 
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
@@ -422,13 +415,8 @@ def train(
         log.info(f"Loading model from {ckpt_path}")
         model.load_reference_checkpoint(ckpt_path)
     model.to(device)
-    train_rows, val_rows = headtrain.split_rows(train_path, val_path)
-    if net == "cnn":
-        fit = cnntrain.fit_cnn
-    elif net == "transformer":
-        from .tftrain import fit_transformer as fit
-    else:
-        from .mambatrain import fit_mamba as fit
+    train_rows, val_rows = split_rows(train_path, val_path)
+    fit = {"cnn": cnntrain.fit_cnn, "mamba": mambatrain.fit_mamba, "mambasp": mambatrain.fit_mamba, "transformer": tftrain.fit_transformer}[net]
     hist = fit(model, train_rows, val_rows, output_path, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device)
     log.info(f"{len(hist)} epochs; best val/f1 {hist[-1]['val/f1_best']:.4f}; model.safetensors and metrics.tsv saved to {output_path}")
 

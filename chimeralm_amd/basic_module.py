@@ -4,9 +4,10 @@ Same constructor (`net, optimizer, scheduler, criterion, *, compile`), `forward(
 `predict_step(batch, batch_idx) -> (logits, labels)` (:177-187), `model_step(batch) -> (loss, preds, targets)` (:87-104) and
 `test_step(batch, batch_idx)` (:153-170).  The reference's `test_step` feeds torchmetrics objects on the host; here it queues the
 batch's sums on the device (eval_metrics.EvalMetrics, attached by `Trainer.test`).  When `lightning` is importable the class is a
-`LightningModule`; otherwise a plain `nn.Module`.  Of the reference's training hooks `training_step` exists, for the two nets this
-engine can differentiate: the Hyena head on a frozen backbone (headtrain.py) and DNAConvNet end to end (cnntrain.py); the Lightning
-hooks around it (`on_train_start`, `configure_optimizers`, the epoch-end logging) are out of scope: `fit_head` / `fit_cnn` are the loops.
+`LightningModule`; otherwise a plain `nn.Module`.  Of the reference's training hooks `training_step` exists, for the five paths this
+engine can differentiate: the Hyena head on a frozen backbone (headtrain.py) and, end to end, DNAConvNet (cnntrain.py), the two Mamba
+nets (mambatrain.py), SequenceCNNTransformer (tftrain.py) and the whole HyenaDna net (hyenatrain.py); the Lightning hooks around it
+(`on_train_start`, `configure_optimizers`, the epoch-end logging) are out of scope: `fit.fit` is the loop, under each module's `fit_*`.
 """
 from __future__ import annotations
 
@@ -50,8 +51,9 @@ class ClassificationLit(_Base):
 
     def training_step(self, batch: dict[str, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         """The batch's loss with a graph to the trained parameters (basic_module.py `training_step`): for a net built with
-        `freeze_backbone=True` (the head's) or `trainable=True` (DNAConvNet: all of them), in training mode.  No other backward exists
-        on this engine."""
+        `freeze_backbone=True` (HyenaDna: the head's) or `trainable=True` (DNAConvNet, the Mamba nets, SequenceCNNTransformer, HyenaDna
+        with an unfrozen backbone: all of them), in training mode.  No other backward exists on this engine; the error's wording
+        dates from when only the head trained and is matched by tests."""
         if not getattr(self.net, "freeze_backbone", False) and not getattr(self.net, "trainable", False):
             raise NotImplementedError("only the head trains on this engine: freeze_backbone=True")
         loss, _, _ = self.model_step(batch)

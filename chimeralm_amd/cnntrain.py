@@ -13,17 +13,14 @@ inference `precision`.
 from __future__ import annotations
 
 import ctypes as C
-import logging
-import time
-from pathlib import Path
 
 import numpy as np
 import torch
 
 from . import _native as N
+from ._trainop import is_plain_fp32, stream_of
 from .engine import IDS_DT
 
-log = logging.getLogger("chimeralm_amd")
 N_PARAMS = 13                                # embedding, then (W, b, g, beta) of blocks 0, 1, 2: CLM_CNN_TRAIN_PARAMS
 
 
@@ -64,18 +61,14 @@ class CnnTrainEngine:
         if rc != 0:
             raise CnnTrainError(self.lib.clm_cnn_train_last_error(self._h).decode())
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def generation(self) -> int:
         return int(self.lib.clm_cnn_train_generation(self._h))
 
     def forward(self, ids: torch.Tensor, params: list[torch.Tensor], keeps: list[torch.Tensor] | None, scale: float):
         """-> pooled [B, 256], batch means [3, 256], biased batch variances [3, 256], the generation to hand to `backward`."""
         B, L = ids.shape
-        for p in params:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != ids.device:
-                raise ValueError("the engine trains contiguous fp32 parameters on the batch's device")
+        if not all(is_plain_fp32(p, ids.device) for p in params):
+            raise ValueError("the engine trains contiguous fp32 parameters on the batch's device")
         pooled = torch.empty((B, 256), dtype=torch.float32, device=ids.device)
         mean, var = torch.empty((3, 256), dtype=torch.float32, device=ids.device), torch.empty((3, 256), dtype=torch.float32, device=ids.device)
         pp = (C.c_void_p * N_PARAMS)(*[p.data_ptr() for p in params])
@@ -88,7 +81,7 @@ class CnnTrainEngine:
             kp = (C.c_void_p * 3)(*[k.data_ptr() for k in keeps])
         self._check(self.lib.clm_cnn_train_forward(self._h, C.c_void_p(ids.data_ptr()), IDS_DT[ids.dtype], ids.stride(0), B, L, pp, kp, float(scale),
                                                    C.c_void_p(pooled.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()),
-                                                   self._stream()))
+                                                   stream_of(self.device)))
         self.shape = (B, L)
         return pooled, mean, var, self.generation()
 
@@ -97,7 +90,7 @@ class CnnTrainEngine:
         """The 13 gradients (shaped like `like`); with `out` and beta = 1 they are added to what `out` holds."""
         grads = [torch.empty_like(p) for p in like] if out is None else out
         gp = (C.c_void_p * N_PARAMS)(*[g.data_ptr() for g in grads])
-        self._check(self.lib.clm_cnn_train_backward(self._h, generation, C.c_void_p(dpooled.data_ptr()), gp, float(beta), self._stream()))
+        self._check(self.lib.clm_cnn_train_backward(self._h, generation, C.c_void_p(dpooled.data_ptr()), gp, float(beta), stream_of(self.device)))
         return grads
 
     def debug_fetch(self, name: str) -> np.ndarray:
@@ -181,101 +174,14 @@ def train_forward(net, input_ids: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------------------- the loop
 def fit_cnn(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_size: int = 8, lr: float | None = None, seed: int = 12345,
             device: torch.device | str = "cuda", tokenizer=None, metrics_factory=None) -> list[dict]:
-    """Train every parameter of `model.net` (a `ClassificationLit` over `DNAConvNet(trainable=True)`) on one GPU.
+    """Train every parameter of `model.net` (a `ClassificationLit` over `DNAConvNet(trainable=True)`) on one GPU: `fit.fit` with
+    `fit.whole_batch_step` at the reference's batch of 8 -- a batch is never split, BatchNorm couples its reads, and a last batch of
+    one read is skipped, as it has no batch statistics.  Optimizer and scheduler are the reference's Adam 1e-4 and ReduceLROnPlateau
+    (configs/model/cnn.yaml); the dropout masks follow `seed` through `net.dropout_generator`."""
+    from . import fit
 
-    Per epoch: the training rows in `headtrain.epoch_order(n, seed, epoch)`, batches of `batch_size` (the reference's 8), ONE
-    optimizer step per batch over all parameters -- a batch is never split, BatchNorm couples its reads; a last batch of one read is
-    skipped, as it has no batch statistics -- then validation in file order, in eval mode through the inference kernels, into
-    `EvalMetrics` (or `metrics_factory()`), `scheduler.step(val/loss)`.  Optimizer and scheduler are the model's factories (the
-    reference's Adam 1e-4 and ReduceLROnPlateau, configs/model/cnn.yaml); `lr` overrides the rate.  Writes `out_dir/metrics.tsv`
-    (headtrain.METRIC_COLUMNS) and, for the epoch of the best `val/f1` (ties: the earlier), `out_dir/model.safetensors`; on return the
-    model holds that epoch's weights too.  Returns the rows of metrics.tsv as dicts, with `val/f1_best`."""
     if epochs < 1 or batch_size < 2:
         raise ValueError("epochs must be >= 1 and batch_size >= 2 (BatchNorm needs two reads)")
-    return fit_all_parameters(model, train_rows, val_rows, out_dir, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
-                              tokenizer=tokenizer, metrics_factory=metrics_factory, min_reads=2, config="configs/model/cnn.yaml")
-
-
-def fit_all_parameters(model, train_rows, val_rows, out_dir, *, epochs: int, batch_size: int, lr: float | None, seed: int,
-                       device: torch.device | str, tokenizer, metrics_factory, min_reads: int, config: str) -> list[dict]:
-    """The loop of `fit_cnn` and `mambatrain.fit_mamba`: one optimizer step per batch over every parameter of `model.net`, validation
-    through the inference kernels, the best-`val/f1` checkpoint and metrics.tsv.  A last batch of fewer than `min_reads` reads is
-    skipped (2 where BatchNorm needs batch statistics, else 1: none is)."""
-    from .headtrain import METRIC_COLUMNS, _f1, _load_reads, epoch_order, save_checkpoint
-    from .tokenizer import DataCollator, load_tokenizer_from_hyena_model
-
-    device = torch.device(device)
-    tok = tokenizer if tokenizer is not None else load_tokenizer_from_hyena_model("hyenadna-small-32k-seqlen")
-    collate = DataCollator(tok).torch_call
-    train, val = _load_reads(train_rows, tok), _load_reads(val_rows, tok)
-    out_dir = Path(out_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    params = [p for p in model.net.parameters() if p.requires_grad]
-    if not params:
-        raise ValueError("the net has no trainable parameter")
-    if model.optimizer_factory is None:
-        raise ValueError(f"the model has no optimizer factory ({config}: optimizer)")
-    opt = model.optimizer_factory(params=params)
-    if lr is not None:
-        for g in opt.param_groups:
-            g["lr"] = float(lr)
-    sched = model.scheduler_factory(optimizer=opt) if model.scheduler_factory is not None else None
-    if hasattr(model.net, "dropout_generator"):              # the dropout masks: a generator of the net's own, seeded here
-        model.net.dropout_generator = torch.Generator(device=device).manual_seed(int(seed))
-    if metrics_factory is None:
-        from .eval_metrics import EvalMetrics
-
-        metrics_factory = lambda: EvalMetrics(device, n_classes=2, ignore_index=-100)   # noqa: E731
-    history, best = [], -1.0
-    with (out_dir / "metrics.tsv").open("w") as tsv:
-        tsv.write("\t".join(METRIC_COLUMNS) + "\n")
-        for epoch in range(epochs):
-            t0 = time.perf_counter()
-            model.train()
-            order = epoch_order(len(train), seed, epoch)
-            loss_sum = torch.zeros((), dtype=torch.float64, device=device)
-            counts = torch.zeros(3, dtype=torch.float64, device=device)      # tp, fp, fn of the training predictions
-            seen = 0
-            for i0 in range(0, len(order), batch_size):
-                rows = order[i0:i0 + batch_size]
-                if len(rows) < min_reads:
-                    continue
-                batch = collate([train[i] for i in rows])
-                ids, y = batch["input_ids"].to(device), batch["labels"].to(device)
-                opt.zero_grad(set_to_none=True)
-                logits = model(ids)
-                loss = model.criterion(logits, y.long().view(-1))
-                loss.backward()
-                opt.step()
-                pred = logits.detach().argmax(dim=-1)
-                loss_sum += loss.detach().double() * len(rows)
-                counts += torch.stack([((pred == 1) & (y == 1)).sum(), ((pred == 1) & (y == 0)).sum(), ((pred == 0) & (y == 1)).sum()]).double()
-                seen += len(rows)
-            model.eval()
-            sums = metrics_factory()
-            try:
-                with torch.no_grad():
-                    for i0 in range(0, len(val), batch_size):
-                        batch = collate(val[i0:i0 + batch_size])
-                        sums.update(model(batch["input_ids"].to(device)), batch["labels"].to(device))
-                r = sums.read()
-            finally:
-                sums.close()
-            tp, fp, fn = counts.tolist()
-            row = {"epoch": epoch, "train/loss": float(loss_sum) / max(seen, 1), "train/f1": _f1(tp, fp, fn),
-                   "val/loss": r["sum_batch_mean_loss"] / r["n_batches"], "val/f1": _f1(r["tp"], r["fp"], r["fn"]),
-                   "lr": opt.param_groups[0]["lr"]}
-            if sched is not None:
-                sched.step(row["val/loss"])
-            if row["val/f1"] > best:
-                best = row["val/f1"]
-                save_checkpoint(model, out_dir)
-            row["seconds"] = time.perf_counter() - t0
-            tsv.write("\t".join(f"{row[c]:.9g}" if isinstance(row[c], float) else str(row[c]) for c in METRIC_COLUMNS) + "\n")
-            tsv.flush()
-            row["val/f1_best"] = best
-            history.append(row)
-            log.info("epoch %d: train/loss %.6f train/f1 %.4f val/loss %.6f val/f1 %.4f (best %.4f) lr %.3g  %.1f s", epoch,
-                     row["train/loss"], row["train/f1"], row["val/loss"], row["val/f1"], best, row["lr"], row["seconds"])
-    model.load_reference_checkpoint(out_dir / "model.safetensors")       # the model in memory is the one on disk: the best epoch's
-    return history
+    return fit.fit(model, train_rows, val_rows, out_dir, params=fit.trainable_parameters(model.net, "net"), step=fit.whole_batch_step,
+                   min_reads=2, config="configs/model/cnn.yaml", epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
+                   tokenizer=tokenizer, metrics_factory=metrics_factory)

@@ -20,21 +20,20 @@ HyenaDNA algorithm, not the Hub's remote code, which th
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 
 import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from ._trainop import abi_error, inverted_dropout, is_plain_fp32, stream_of
+from .headtrain import head_mlp
 
 log = logging.getLogger("chimeralm_amd")
 DM = 256
 MAX_ENGINE_TOKENS = 8193                     # one power-of-two transform of at most 16384 points (include/chimeralm_hip.h)
 MOD_SHIFT = 0.05                             # HyenaExponentialModulation.shift
 CORES = ("engine", "torch")
-_ABI_ERRORS = {-1: "CLM_E_INVALID: bad argument / shape", -2: "CLM_E_HIP: a HIP runtime call failed",
-               -4: "CLM_E_UNSUPPORTED: shape or mode outside what the kernels cover"}
 _long_read_logged = False
 
 
@@ -44,7 +43,7 @@ class HyenaTrainError(RuntimeError):
 
 def _check(rc: int, what: str, B: int, L: int):
     if rc < 0:
-        raise HyenaTrainError(f"{what}(B = {B}, L = {L}): {_ABI_ERRORS.get(int(rc), f'error {rc}')} (include/chimeralm_hip.h)")
+        raise HyenaTrainError(f"{what}(B = {B}, L = {L}): {abi_error(rc)} (include/chimeralm_hip.h)")
 
 
 def workspace_bytes(B: int, L: int) -> int:
@@ -54,16 +53,12 @@ def workspace_bytes(B: int, L: int) -> int:
     return n
 
 
-def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _checked(B: int, L: int, **tensors):
     """The op takes contiguous fp32 GPU tensors of exactly these shapes, on one device; anything else raises before a launch."""
     shapes = {"zc": (B, 3 * DM, L), "sw": (3 * DM, 3), "sb": (3 * DM,), "k": (DM, L), "D": (DM,), "c": (B, DM, L), "dy": (B, DM, L)}
     dev = tensors["zc"].device
     for name, t in tensors.items():
-        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != dev or tuple(t.shape) != shapes[name]:
+        if not is_plain_fp32(t, dev) or not t.is_cuda or tuple(t.shape) != shapes[name]:
             raise ValueError(f"{name} must be a contiguous fp32 tensor {shapes[name]} on the GPU of zc, got {t.dtype} {tuple(t.shape)} "
                              f"(contiguous: {t.is_contiguous()}) on {t.device}")
 
@@ -77,7 +72,7 @@ def core_forward(zc, sw, sb, k, D):
     ws = torch.empty(workspace_bytes(B, L), dtype=torch.uint8, device=zc.device)
     c, y = torch.empty((B, DM, L), dtype=torch.float32, device=zc.device), torch.empty((B, DM, L), dtype=torch.float32, device=zc.device)
     _check(N.load().clm_hyena_train_forward(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), B, L, c.data_ptr(),
-                                            y.data_ptr(), ws.data_ptr(), _stream(zc)), "clm_hyena_train_forward", B, L)
+                                            y.data_ptr(), ws.data_ptr(), stream_of(zc)), "clm_hyena_train_forward", B, L)
     return c, y
 
 
@@ -91,7 +86,7 @@ def core_backward(zc, sw, sb, k, D, c, dy):
     dzc, dsw, dsb, dk, dD = (torch.empty_like(t) for t in (zc, sw, sb, k, D))
     _check(N.load().clm_hyena_train_backward(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), c.data_ptr(),
                                              dy.data_ptr(), B, L, dzc.data_ptr(), dsw.data_ptr(), dsb.data_ptr(), dk.data_ptr(),
-                                             dD.data_ptr(), ws.data_ptr(), _stream(zc)), "clm_hyena_train_backward", B, L)
+                                             dD.data_ptr(), ws.data_ptr(), stream_of(zc)), "clm_hyena_train_backward", B, L)
     return dzc, dsw, dsb, dk, dD
 
 
@@ -161,28 +156,17 @@ def hyena_operator(net, mixer, u: torch.Tensor, core: str) -> torch.Tensor:
     return torch.matmul(y.transpose(1, 2), mixer.out_proj.weight.t()) + mixer.out_proj.bias
 
 
-def _embed_drop(net, h: torch.Tensor) -> torch.Tensor:
-    """Inverted dropout at `net.embed_dropout` with a mask from `net.dropout_generator` (None: torch's default generator)."""
-    p = float(net.embed_dropout)
-    if p <= 0.0:
-        return h
-    keep = torch.rand(h.shape, device=h.device, generator=net.dropout_generator) >= p
-    return h * (keep.to(h.dtype) * (1.0 / (1.0 - p)))
-
-
 def train_forward(net, input_ids: torch.Tensor) -> torch.Tensor:
     """logits [B, 2] of `net` (a `HyenaDna(trainable=True, freeze_backbone=False)` in training mode) with a graph to every parameter:
     the HyenaDNA backbone (embedding -> 4 x [LN, Hyena operator, LN, GELU-tanh MLP] -> LN) and the attention-pooling head on the
     module's own tensors.  No mask: pads count, as in the reference."""
-    from .headtrain import head_mlp
-
     if input_ids.dim() != 2:
         raise ValueError("input_ids must be [batch, length]")
     bb = net.backbone.backbone
     L = input_ids.shape[1]
     core = _core_for(net, L, input_ids.device)
     net.last_train_core = core
-    h = _embed_drop(net, bb.embeddings.word_embeddings(input_ids.long()))
+    h = inverted_dropout(bb.embeddings.word_embeddings(input_ids.long()), net.embed_dropout, net.dropout_generator)
     for blk in bb.layers:
         r = hyena_operator(net, blk.mixer, blk.norm1(h), core) + h
         h = blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(r)), approximate="tanh")) + r
@@ -196,11 +180,10 @@ def train_forward(net, input_ids: torch.Tensor) -> torch.Tensor:
 def fit_hyena(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_size: int = 8, lr: float | None = None, seed: int = 12345,
               device: torch.device | str = "cuda", tokenizer=None, metrics_factory=None) -> list[dict]:
     """Train every parameter of `model.net` (a `ClassificationLit` over `HyenaDna(trainable=True, freeze_backbone=False)`) on one GPU:
-    `fit_cnn`'s loop (cnntrain.fit_all_parameters: `epoch_order`, one optimizer step per batch, validation through the inference
-    kernels into `EvalMetrics`, the best-`val/f1` checkpoint, metrics.tsv) without its two-read rule.  Optimizer and scheduler are
-    the model's factories (ChimeraLM.new: AdamW 1e-4, weight decay 0.01, ReduceLROnPlateau); the embedding dropout follows `seed`
-    through `net.dropout_generator`, the head's dropouts through torch's generator, seeded here."""
-    from .cnntrain import fit_all_parameters
+    `fit.fit` with `fit.whole_batch_step`; a batch of one read trains.  Optimizer and scheduler are the model's factories
+    (ChimeraLM.new: AdamW 1e-4, weight decay 0.01, ReduceLROnPlateau); the embedding dropout follows `seed` through
+    `net.dropout_generator`, the head's dropouts through torch's generator, seeded here."""
+    from . import fit
 
     if epochs < 1 or batch_size < 1:
         raise ValueError("epochs and batch_size must be >= 1")
@@ -208,5 +191,6 @@ def fit_hyena(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_s
     if not getattr(net, "trainable", False) or getattr(net, "freeze_backbone", False):
         raise ValueError("fit_hyena trains HyenaDna(trainable=True, freeze_backbone=False); the head alone is headtrain.fit_head")
     torch.manual_seed(int(seed))                                     # the head's dropout masks
-    return fit_all_parameters(model, train_rows, val_rows, out_dir, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
-                              tokenizer=tokenizer, metrics_factory=metrics_factory, min_reads=1, config="lm.ChimeraLM.new")
+    return fit.fit(model, train_rows, val_rows, out_dir, params=fit.trainable_parameters(net, "net"), step=fit.whole_batch_step,
+                   min_reads=1, config="lm.ChimeraLM.new", epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
+                   tokenizer=tokenizer, metrics_factory=metrics_factory)

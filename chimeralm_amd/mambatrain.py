@@ -17,15 +17,14 @@ the training arithmetic is exact fp32 whatever the module's inference `precision
 from __future__ import annotations
 
 import ctypes as C
-import logging
 
 import torch
 import torch.nn.functional as F
 
 from . import _native as N
-from .mamba import HEADDIM, PAD, VOCAB
+from ._trainop import is_plain_fp32, stream_of
+from .mamba import HEADDIM, VOCAB
 
-log = logging.getLogger("chimeralm_amd")
 N_PARAMS = 6                                 # conv1d.weight, conv1d.bias, dt_bias, A_log, D, norm.weight: CLM_MAMBA_TRAIN_PARAMS
 Q = 64                                       # tokens per scan chunk: one entry state each (csrc/mamba_common.h)
 
@@ -60,18 +59,14 @@ class MambaTrainEngine:
         if rc != 0:
             raise MambaTrainError(self.lib.clm_mamba_train_last_error(self._h).decode())
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     @staticmethod
     def _ptrs(ts):
         return (C.c_void_p * N_PARAMS)(*[t.data_ptr() for t in ts])
 
     @staticmethod
     def _checked(zx, params):
-        for t in [zx, *params]:
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != zx.device:
-                raise ValueError("the engine trains contiguous fp32 tensors on one device")
+        if not all(is_plain_fp32(t, zx.device) for t in [zx, *params]):
+            raise ValueError("the engine trains contiguous fp32 tensors on one device")
 
     def forward(self, zx: torch.Tensor, params: list[torch.Tensor], d_model: int, expand: int, d_state: int):
         """-> out [B, L, di] and what the backward needs: (xc [B, L, di + 2 N], dt [B, L, H], ys [B, L, di], states [B, H, chunks, N, 64])."""
@@ -83,7 +78,7 @@ class MambaTrainEngine:
         xc, dt, ys, out = new(B, L, di + 2 * d_state), new(B, L, H), new(B, L, di), new(B, L, di)
         states = new(B, H, (L + Q - 1) // Q, d_state, HEADDIM)
         self._check(self.lib.clm_mamba_train_forward(self._h, zx.data_ptr(), self._ptrs(params), B, L, d_model, expand, d_state, xc.data_ptr(),
-                                                     dt.data_ptr(), ys.data_ptr(), states.data_ptr(), out.data_ptr(), self._stream()))
+                                                     dt.data_ptr(), ys.data_ptr(), states.data_ptr(), out.data_ptr(), stream_of(self.device)))
         return out, (xc, dt, ys, states)
 
     def backward(self, zx, params, saved, dout, d_model: int, expand: int, d_state: int):
@@ -95,7 +90,7 @@ class MambaTrainEngine:
         grads = [torch.empty_like(p) for p in params]
         self._check(self.lib.clm_mamba_train_backward(self._h, zx.data_ptr(), self._ptrs(params), B, L, d_model, expand, d_state, xc.data_ptr(),
                                                       dt.data_ptr(), ys.data_ptr(), states.data_ptr(), dout.data_ptr(), dzx.data_ptr(),
-                                                      self._ptrs(grads), self._stream()))
+                                                      self._ptrs(grads), stream_of(self.device)))
         return dzx, grads
 
     def close(self):
@@ -164,16 +159,14 @@ def train_forward(net, input_ids: torch.Tensor, mask: torch.Tensor | None = None
 # ------------------------------------------------------------------------------------------------------------- the loop
 def fit_mamba(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_size: int = 8, lr: float | None = None, seed: int = 12345,
               device: torch.device | str = "cuda", tokenizer=None, metrics_factory=None) -> list[dict]:
-    """Train every parameter of `model.net` (a `ClassificationLit` over a Mamba net with `trainable=True`) on one GPU: `fit_cnn`'s loop
-    (cnntrain.fit_all_parameters: `epoch_order`, one optimizer step per batch, validation through the inference kernels into
-    `EvalMetrics`, the best-`val/f1` checkpoint, metrics.tsv) without its two-read rule -- nothing here couples the reads of a batch, so
-    a batch of one read trains.  Optimizer and scheduler are the model's factories (configs/model/mamba.yaml, mambasp.yaml); dropout
-    draws from torch's generator, seeded here with `seed`."""
-    from .cnntrain import fit_all_parameters
+    """Train every parameter of `model.net` (a `ClassificationLit` over a Mamba net with `trainable=True`) on one GPU: `fit.fit` with
+    `fit.whole_batch_step` -- nothing here couples the reads of a batch, so a batch of one read trains.  Optimizer and scheduler are
+    the model's factories (configs/model/mamba.yaml, mambasp.yaml); dropout draws from torch's generator, seeded here with `seed`."""
+    from . import fit
 
     if epochs < 1 or batch_size < 1:
         raise ValueError("epochs and batch_size must be >= 1")
     torch.manual_seed(int(seed))                                     # the dropout masks
-    return fit_all_parameters(model, train_rows, val_rows, out_dir, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
-                              tokenizer=tokenizer, metrics_factory=metrics_factory, min_reads=1,
-                              config="configs/model/mamba.yaml, mambasp.yaml")
+    return fit.fit(model, train_rows, val_rows, out_dir, params=fit.trainable_parameters(model.net, "net"), step=fit.whole_batch_step,
+                   min_reads=1, config="configs/model/mamba.yaml, mambasp.yaml", epochs=epochs, batch_size=batch_size, lr=lr, seed=seed,
+                   device=device, tokenizer=tokenizer, metrics_factory=metrics_factory)

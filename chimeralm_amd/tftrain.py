@@ -17,15 +17,12 @@ the module's inference `precision`; `nn.TransformerEncoderLayer`'s forward (post
 """
 from __future__ import annotations
 
-import ctypes as C
-import logging
-
 import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from ._trainop import abi_error, inverted_dropout, stream_of
 
-log = logging.getLogger("chimeralm_amd")
 NH, HD, DM = 8, 32, 256
 CORES = ("engine", "torch")
 _M64 = (1 << 64) - 1
@@ -39,7 +36,7 @@ def workspace_bytes(B: int, L: int) -> int:
     """Bytes of scratch one backward of that shape takes (include/chimeralm_hip.h); raises for a shape the op refuses."""
     n = int(N.load().clm_attn_train_workspace_bytes(B, L))
     if n < 0:
-        raise TransformerTrainError(f"clm_attn_train_workspace_bytes({B}, {L}): error {n}")
+        raise TransformerTrainError(f"clm_attn_train_workspace_bytes({B}, {L}): error {n}, {abi_error(n)}")
     return n
 
 
@@ -57,13 +54,9 @@ def _aligned(t: torch.Tensor) -> torch.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def _stream(t: torch.Tensor):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _check(rc: int, what: str, *args):
     if rc != 0:
-        raise TransformerTrainError(f"{what}{args}: error {rc} (include/chimeralm_hip.h: what the op refuses)")
+        raise TransformerTrainError(f"{what}{args}: error {rc}, {abi_error(rc)} (include/chimeralm_hip.h: what the op refuses)")
 
 
 def attention_forward(qkv: torch.Tensor, dropout_p: float, seed: int):
@@ -73,7 +66,7 @@ def attention_forward(qkv: torch.Tensor, dropout_p: float, seed: int):
     B, L, _ = qkv.shape
     out = torch.empty((B, L, DM), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, NH, L), dtype=torch.float32, device=qkv.device)
-    _check(N.load().clm_attn_train_forward(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, float(dropout_p), int(seed), _stream(qkv)),
+    _check(N.load().clm_attn_train_forward(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, float(dropout_p), int(seed), stream_of(qkv)),
            "clm_attn_train_forward", B, L, dropout_p)
     return out, lse
 
@@ -84,14 +77,14 @@ def attention_backward(qkv, out, lse, dout, dropout_p: float, seed: int) -> torc
     dqkv = torch.empty_like(qkv)
     ws = torch.empty(workspace_bytes(B, L), dtype=torch.uint8, device=qkv.device)
     _check(N.load().clm_attn_train_backward(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), ws.data_ptr(),
-                                            B, L, float(dropout_p), int(seed), _stream(qkv)), "clm_attn_train_backward", B, L, dropout_p)
+                                            B, L, float(dropout_p), int(seed), stream_of(qkv)), "clm_attn_train_backward", B, L, dropout_p)
     return dqkv
 
 
 def attention_mask(B: int, L: int, dropout_p: float, seed: int, device) -> torch.Tensor:
     """keep [B, 8, L, L] uint8 of that seed: what forward and backward regenerate (tests)."""
     keep = torch.empty((B, NH, L, L), dtype=torch.uint8, device=device)
-    _check(N.load().clm_attn_train_mask(keep.data_ptr(), B, L, float(dropout_p), int(seed), _stream(keep)), "clm_attn_train_mask", B, L, dropout_p)
+    _check(N.load().clm_attn_train_mask(keep.data_ptr(), B, L, float(dropout_p), int(seed), stream_of(keep)), "clm_attn_train_mask", B, L, dropout_p)
     return keep
 
 
@@ -124,13 +117,8 @@ def torch_core(qkv: torch.Tensor, dropout_p: float) -> torch.Tensor:
     return F.scaled_dot_product_attention(q, k, v, dropout_p=float(dropout_p)).transpose(1, 2).reshape(B, L, DM)
 
 
-def _drop(net, t: torch.Tensor) -> torch.Tensor:
-    """Inverted dropout at `net.dropout` with a mask from `net.dropout_generator`."""
-    p = float(net.dropout)
-    if p <= 0.0:
-        return t
-    keep = torch.rand(t.shape, device=t.device, generator=net.dropout_generator) >= p
-    return t * (keep.to(t.dtype) * (1.0 / (1.0 - p)))
+def dropout(net, t: torch.Tensor) -> torch.Tensor:
+    return inverted_dropout(t, net.dropout, net.dropout_generator)
 
 
 def encoder_layer(net, layer, x: torch.Tensor) -> torch.Tensor:
@@ -142,9 +130,9 @@ def encoder_layer(net, layer, x: torch.Tensor) -> torch.Tensor:
         a = AttentionCore.apply(qkv, float(net.dropout), net.next_attention_seed())
     else:
         a = torch_core(qkv, net.dropout)
-    x = layer.norm1(x + _drop(net, sa.out_proj(a)))
-    f = layer.linear2(_drop(net, F.relu(layer.linear1(x))))
-    return layer.norm2(x + _drop(net, f))
+    x = layer.norm1(x + dropout(net, sa.out_proj(a)))
+    f = layer.linear2(dropout(net, F.relu(layer.linear1(x))))
+    return layer.norm2(x + dropout(net, f))
 
 
 def stem(net, x: torch.Tensor) -> torch.Tensor:
@@ -176,21 +164,21 @@ def train_forward(net, input_ids: torch.Tensor) -> torch.Tensor:
     w = torch.softmax(net.attn_pool(x), dim=1)
     pooled = torch.sum(w * x, dim=1)
     c = net.classifier
-    return c[3](_drop(net, c[1](c[0](pooled))))
+    return c[3](dropout(net, c[1](c[0](pooled))))
 
 
 # ------------------------------------------------------------------------------------------------------------- the loop
 def fit_transformer(model, train_rows, val_rows, out_dir, *, epochs: int = 10, batch_size: int = 8, lr: float | None = None,
                     seed: int = 12345, device: torch.device | str = "cuda", tokenizer=None, metrics_factory=None) -> list[dict]:
-    """Train every parameter of `model.net` (a `ClassificationLit` over `SequenceCNNTransformer(trainable=True)`) on one GPU: `fit_cnn`'s
-    loop (cnntrain.fit_all_parameters) without its two-read rule -- nothing here couples the reads of a batch.  Optimizer and
+    """Train every parameter of `model.net` (a `ClassificationLit` over `SequenceCNNTransformer(trainable=True)`) on one GPU:
+    `fit.fit` with `fit.whole_batch_step` -- nothing here couples the reads of a batch, so a batch of one read trains.  Optimizer and
     scheduler are the model's factories (configs/model/transformer.yaml: AdamW 1e-4, weight decay 0.01, ReduceLROnPlateau); the
-    dropout masks and the attention seeds follow `seed`."""
-    from .cnntrain import fit_all_parameters
+    dropout masks and the attention seeds follow `seed` through `net.dropout_generator`."""
+    from . import fit
 
     if epochs < 1 or batch_size < 1:
         raise ValueError("epochs and batch_size must be >= 1")
     torch.manual_seed(int(seed))                                     # (the torch core's dropout stream)
-    return fit_all_parameters(model, train_rows, val_rows, out_dir, epochs=epochs, batch_size=batch_size, lr=lr, seed=seed, device=device,
-                              tokenizer=tokenizer, metrics_factory=metrics_factory, min_reads=1,
-                              config="configs/model/transformer.yaml")
+    return fit.fit(model, train_rows, val_rows, out_dir, params=fit.trainable_parameters(model.net, "net"), step=fit.whole_batch_step,
+                   min_reads=1, config="configs/model/transformer.yaml", epochs=epochs, batch_size=batch_size, lr=lr, seed=seed,
+                   device=device, tokenizer=tokenizer, metrics_factory=metrics_factory)

@@ -5,8 +5,9 @@ one process per GPU (torchrun environment), the datamodule set up for this rank,
 (`chimeralm_amd.predict.run_predict`), the prediction-writer callbacks.  `test` is `trainer.test(model=model, datamodule=datamodule,
 ckpt_path=cfg.ckpt_path)` of the same file: the test loop (`run_test`) with the metric sums kept on the device, one read of them at
 the end, one all-gather of that small struct across ranks, and the reference's metric names in `callback_metrics`.  Training keywords
-(`min_epochs`, `max_epochs`, `check_val_every_n_epoch`, ...) are accepted and ignored: this class has no `fit`; the one training path
-of the engine, the head fine-tune with the backbone frozen, is `chimeralm_amd.headtrain.fit_head` (`python -m chimeralm_amd finetune`).
+(`min_epochs`, `max_epochs`, `check_val_every_n_epoch`, ...) are accepted and ignored: this class has no `fit`; the engine's five
+training paths -- the Hyena head on a frozen backbone, DNAConvNet, the two Mamba nets, SequenceCNNTransformer and the whole HyenaDna
+net -- are the `fit_*` functions over `chimeralm_amd.fit.fit` (`python -m chimeralm_amd finetune` / `train`).
 `explain` has no Lightning counterpart: the predict datamodule's reads through the mutagenesis scan (`run_explain`), for any net.
 """
 from __future__ import annotations

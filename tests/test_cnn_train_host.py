@@ -16,7 +16,7 @@ from torch import nn
 
 import cnn_reference as cr
 import cnn_train_reference as ctr
-from test_headtrain_host import PARQUET, _HostSums
+from test_fit_host import PARQUET, _HostSums
 
 REPO = Path(__file__).resolve().parent.parent
 CFG = dict(vocab_size=12, embedding_dim=256, num_filters=[256, 256, 256], kernel_sizes=[7, 7, 7], pool_sizes=[4, 4, 4], hidden_dim=512,
@@ -220,7 +220,7 @@ def _fit(tmp, seed=12345, epochs=2, rows=17):
 def test_fit_cnn_on_a_stub_net(tmp_path):
     from safetensors.torch import load_file
 
-    from chimeralm_amd import headtrain
+    from chimeralm_amd import fit
 
     m, h, steps = _fit(tmp_path / "a")
     mb, hb, _ = _fit(tmp_path / "b")
@@ -232,7 +232,7 @@ def test_fit_cnn_on_a_stub_net(tmp_path):
     assert m.net.order[:2] != m.net.order[2:]                              # ... and another one per epoch,
     assert _fit(tmp_path / "c", seed=7)[0].net.order != m.net.order        # and per seed
     lines = (tmp_path / "a" / "metrics.tsv").read_text().splitlines()
-    assert lines[0].split("\t") == list(headtrain.METRIC_COLUMNS) and len(lines) == 3 and all(len(ln.split("\t")) == 7 for ln in lines[1:])
+    assert lines[0].split("\t") == list(fit.METRIC_COLUMNS) and len(lines) == 3 and all(len(ln.split("\t")) == 7 for ln in lines[1:])
     assert h[-1]["val/f1_best"] == max(r["val/f1"] for r in h)
     # the best epoch (ties: the earlier) on disk and in memory
     saved, own = load_file(str(tmp_path / "a" / "model.safetensors")), m.state_dict()

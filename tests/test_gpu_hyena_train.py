@@ -256,10 +256,10 @@ def test_long_reads_take_the_torch_core(sd, built_lib):
 def test_fit_hyena_on_the_golden_reads(sd, built_lib, golden_dir, tmp_path):
     """4 epochs at batch 4, dropout 0, at the model's own AdamW rate 1e-4 (chosen on the CPU with the torch core, where train/loss
     went 0.733, 0.714, 0.686, 0.696; 3e-4 and 1e-3 fell too, less smoothly)."""
-    from chimeralm_amd import headtrain, hyenatrain
+    from chimeralm_amd import fit, hyenatrain
 
     lit = _module(sd)
-    train_rows, val_rows = headtrain.split_rows(golden_dir / "tests.parquet", None)
+    train_rows, val_rows = fit.split_rows(golden_dir / "tests.parquet", None)
     hist = hyenatrain.fit_hyena(lit, train_rows, val_rows, tmp_path / "fit", epochs=4, batch_size=4, lr=1e-4, seed=12345, device="cuda:0")
     print([(r["train/loss"], r["val/loss"], r["val/f1"]) for r in hist])
     assert len(hist) == 4 and hist[-1]["train/loss"] < hist[0]["train/loss"]
@@ -271,9 +271,9 @@ def test_the_finetune_command_and_eval_py(sd, built_lib, golden_dir, tmp_path):
     """`finetune --train-backbone` in a child process from a checkpoint saved here writes a checkpoint eval.py loads; its logits equal
     the in-memory model's."""
     import eval as ev
-    from chimeralm_amd import headtrain, lm
+    from chimeralm_amd import fit, lm
 
-    start = headtrain.save_checkpoint(_module(sd), tmp_path / "start")
+    start = fit.save_checkpoint(_module(sd), tmp_path / "start")
     data, out = golden_dir / "tests.parquet", tmp_path / "cli"
     r = subprocess.run([sys.executable, "-m", "chimeralm_amd", "finetune", str(data), "-o", str(out), "--epochs", "1", "-b", "4", "--seed", "3",
                         "--train-backbone", "--weights", str(start.parent)], capture_output=True, text=True,

@@ -252,7 +252,7 @@ def test_inference_sees_the_step(precision, built_lib):
 
 # ------------------------------------------------------------------------------------------------------------- loop and command
 def test_fit_mamba_on_the_golden_reads(built_lib, golden_dir, tmp_path):
-    from chimeralm_amd import headtrain, mambatrain
+    from chimeralm_amd import fit, mambatrain
     from chimeralm_amd.basic_module import ClassificationLit
     from chimeralm_amd.mamba import MambaSequenceClassificationSP
 
@@ -260,7 +260,7 @@ def test_fit_mamba_on_the_golden_reads(built_lib, golden_dir, tmp_path):
     net = MambaSequenceClassificationSP(vocab_size=12, number_of_classes=2, dropout=0.0, trainable=True, **NETS["mambasp"][0])
     lit = ClassificationLit(net, optimizer=partial(torch.optim.AdamW, lr=1e-4, weight_decay=0.01),
                             scheduler=partial(torch.optim.lr_scheduler.ReduceLROnPlateau, mode="min", factor=0.1, patience=6)).cuda()
-    train_rows, val_rows = headtrain.split_rows(golden_dir / "tests.parquet", None)
+    train_rows, val_rows = fit.split_rows(golden_dir / "tests.parquet", None)
     hist = mambatrain.fit_mamba(lit, train_rows, val_rows, tmp_path / "fit", epochs=4, batch_size=4, lr=1e-3, seed=12345, device="cuda:0")
     print([(r["train/loss"], r["val/loss"], r["val/f1"]) for r in hist])
     assert len(hist) == 4 and hist[-1]["train/loss"] < hist[0]["train/loss"]

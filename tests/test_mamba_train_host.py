@@ -14,7 +14,7 @@ import torch.nn.functional as F
 from torch import nn
 
 import mamba_train_reference as R
-from test_headtrain_host import PARQUET, _HostSums
+from test_fit_host import PARQUET, _HostSums
 
 REPO = Path(__file__).resolve().parent.parent
 SYMBOLS = ("clm_mamba_train_create", "clm_mamba_train_workspace_bytes", "clm_mamba_train_forward", "clm_mamba_train_backward",
@@ -172,7 +172,7 @@ def _fit(tmp, batch_size, epochs=2, rows=17):
 def test_fit_mamba_on_a_stub_net(tmp_path):
     from safetensors.torch import load_file
 
-    from chimeralm_amd import headtrain, mambatrain
+    from chimeralm_amd import fit, mambatrain
 
     m, h = _fit(tmp_path / "a", 8)
     assert m.net.seen == [8, 8, 1] * 2                                          # no two-read rule: the last read, alone, trains too
@@ -182,7 +182,7 @@ def test_fit_mamba_on_a_stub_net(tmp_path):
     strip = lambda hist: [{k: v for k, v in r.items() if k != "seconds"} for r in hist]   # noqa: E731
     assert strip(h) == strip(hb)
     lines = (tmp_path / "a" / "metrics.tsv").read_text().splitlines()
-    assert lines[0].split("\t") == list(headtrain.METRIC_COLUMNS) and len(lines) == 3
+    assert lines[0].split("\t") == list(fit.METRIC_COLUMNS) and len(lines) == 3
     assert h[-1]["val/f1_best"] == max(r["val/f1"] for r in h)
     saved, own = load_file(str(tmp_path / "a" / "model.safetensors")), m.state_dict()
     assert sorted(saved) == sorted(own) and all(torch.equal(saved[k], own[k]) for k in own)
