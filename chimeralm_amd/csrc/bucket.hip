@@ -9,7 +9,7 @@
 #include <cstring>
 #include <string>
 
-#include "clm_common.h"
+#include "handle_host.h"
 
 namespace clm {
 namespace bucket {
@@ -152,8 +152,7 @@ int clm_bucket_scatter(clm_bucket_handle* h, const unsigned char* ids, int64_t r
         const int chunks = (max_width + 15) / 16;                                // (<= 2049: dst_width <= 32769)
         hipLaunchKernelGGL(bucket::bucket_scatter_kernel, dim3((chunks + bucket::THREADS - 1) / bucket::THREADS, n), dim3(bucket::THREADS),
                            0, st, ids, row_stride, (int64_t)B * row_stride, dev, pool, pool_bytes);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(h, CLM_E_HIP, std::string("clm_bucket_scatter: launch failed: ") + hipGetErrorString(e));
+        if (int rc = launched(h, "clm_bucket_scatter")) return rc;
         HIPCHK(h, hipEventRecord(ring.done[slot], st));
         ring.used[slot] = true;
         ring.next = (slot + 1) % bucket::SLOTS;
@@ -164,14 +163,11 @@ int clm_bucket_scatter(clm_bucket_handle* h, const unsigned char* ids, int64_t r
 const char* clm_bucket_last_error(const clm_bucket_handle* h) { return h ? h->err.c_str() : create_error<clm_bucket_handle>().c_str(); }
 
 int clm_bucket_destroy(clm_bucket_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    if (h->ring.host) (void)hipHostFree(h->ring.host);
-    for (hipEvent_t e : h->ring.done)
-        if (e) (void)hipEventDestroy(e);
-    delete h;
-    return CLM_OK;
+    return destroy_handle(h, [h] {
+        if (h->ring.host) (void)hipHostFree(h->ring.host);
+        for (hipEvent_t e : h->ring.done)
+            if (e) (void)hipEventDestroy(e);
+    });
 }
 
 }  // extern "C"

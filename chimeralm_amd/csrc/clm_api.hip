@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "chimeralm_hip.h"
-#include "clm_common.h"
+#include "handle_host.h"
 
 using namespace clm;
 
@@ -56,11 +56,6 @@ struct FilterSet {
     DevBuf ktime[NLAYER], kf[NLAYER], tw;
     DevBuf kfp[NLAYER];           // 16384-point class only: kf lane-packed for the persistent kernel (launch_spectrum_lanepack)
     std::vector<ReversedFilter> krev;
-};
-
-struct ProfRec {
-    int stage;
-    hipEvent_t e0, e1;
 };
 
 // Weights as the kernels take them: device pointers resolved ONCE, by clm_finalize (a key that is not there fails there, with
@@ -179,7 +174,7 @@ struct clm_handle {
     } rows;
     DevBuf pt_w1s, pt_w1t, pt_partial;    // clm_pool_forward / _backward: W1 packed for the score GEMM / the tiles, partials
     // How forwards run right now.  clm_selfcheck / clm_set_fallback: the exact-fp32 kernels of the same handle as referee of, and
-    // replacement for, the 16-bit path; clm_selfcheck and the build of a [PAD] table change it for a scope (ScopedRun)
+    // replacement for, the 16-bit path; clm_selfcheck and the build of a [PAD] table change it for a scope (RunScope)
     struct RunMode {
         int force_prec = -1;      // >= 0 inside clm_selfcheck / a table build: the arithmetic forward_chunk runs in, whatever the length
         // clm_set_fallback: 0 = the handle's own mode; 1 = the next arithmetic INSIDE the gate (a 16-bit handle: fp16x3 -- fp32-class
@@ -197,10 +192,7 @@ struct clm_handle {
     bool x3 = false;              // CLM_PREC_F16X3: cfg.precision is PREC_F32 inside the engine, the fused tails run on hi + lo halfs (tail32.hip AR_X3)
     float x3_wmax = 0.f;          // largest |w| of the hi + lo packed weights (clm_finalize; NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32
     bool unfused_fp32 = false;    // CLM_DEBUG=unfused_fp32: exact fp32 through the separate GEMM kernels of rounds 1-3 (tests cross-check the fused tail)
-    std::vector<ProfRec> recs;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
-    double prof_ms[CLM_N_STAGES] = {};
-    int64_t prof_n[CLM_N_STAGES] = {};
+    StageProfile<CLM_N_STAGES> profile;
 };
 
 namespace {
@@ -338,15 +330,6 @@ bool fp32_path_is_x3(const clm_handle* h) {
 }
 bool is_exact(const clm_handle* h) { return h->cfg.precision == PREC_F32 && !h->x3; }   // the handle IS its own referee
 bool stop_here(const clm_handle* h, int layer, int stage) { return h->stop_layer == layer && h->stop_stage == stage; }
-
-// "Run forwards in this arithmetic, with profiling off / as referee / capturing into this table": what the scope changes in
-// h->run is put back as it stood on every way out of it.  Profiling is off inside: not part of anybody's timed region.
-struct ScopedRun {
-    clm_handle* const h;
-    const clm_handle::RunMode saved;
-    explicit ScopedRun(clm_handle* h_) : h(h_), saved(h_->run) { h->run.prof = false; }
-    ~ScopedRun() { h->run = saved; }
-};
 
 // Everything the engine decides about a chunk of Bc reads of L tokens, each decision once and under one name (plan_chunk says what
 // each means).  The stages read these fields; none looks at the precision, the CLM_DEBUG switches or the kind of a debug stop again.
@@ -533,32 +516,6 @@ int ensure_filters(clm_handle* h, int L, hipStream_t st, FilterSet** out, const 
     return CLM_OK;
 }
 
-struct StageTimer {
-    clm_handle* h;
-    hipStream_t st;
-    int stage;
-    bool on;
-    hipEvent_t e0{}, e1{};
-    StageTimer(clm_handle* h_, hipStream_t st_, int stage_) : h(h_), st(st_), stage(stage_), on(h_->run.prof) {
-        if (!on) return;
-        if (h->recs.size() > 200000) { on = false; return; }
-        if (!h->free_events.empty()) {
-            e0 = h->free_events.back().first;
-            e1 = h->free_events.back().second;
-            h->free_events.pop_back();
-        } else if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-            on = false;
-            return;
-        }
-        (void)hipEventRecord(e0, st);
-    }
-    ~StageTimer() {
-        if (!on) return;
-        (void)hipEventRecord(e1, st);
-        h->recs.push_back({stage, e0, e1});
-    }
-};
-
 // Asynchronous error of an EARLIER forward (the call itself returned before its kernels ran): reported once, by the next
 // forward / stage_wait / profile_read / clm_check call.  The reference raises IndexError inside nn.Embedding for such ids.
 int check_bad_ids(clm_handle* h) {
@@ -629,7 +586,7 @@ int ensure_pad_table(clm_handle* h, const ChunkPlan& p, hipStream_t st, clm_hand
     clm_handle::PadTable* tp = &h->pad_tables.back();
     int rc;
     {
-        ScopedRun scope(h);
+        RunScope<clm_handle> scope(h);
         h->run.force_prec = p.prec;                          // (fp16c: the class length may lie on the other side of the length switch)
         h->run.capture = tp;
         rc = forward_chunk(h, h->pad_ids.get(), CLM_DT_U8, tp->Lp, 1, LT, h->pad_logits.get<float>(), st);
@@ -669,12 +626,9 @@ int size_workspace(ChunkCtx& c, const clm_traj_out* traj = nullptr) {
     auto& [h, p, st, fs, kr, ptab] = c;
     if (int rc = ensure_workspace(h, p, st)) return rc;
     if (traj) {
-        const size_t need = (size_t)p.Bc * traj_points(p.L, traj->stride) * D * 4;
-        if (need > h->traj_pooled.bytes() || (size_t)p.Bc * 4 > h->traj_npad.bytes()) {
-            HIPCHK(h, hipStreamSynchronize(st));
-            HIPCHK(h, h->traj_pooled.reserve(need));
-            HIPCHK(h, h->traj_npad.reserve((size_t)p.Bc * 4));
-        }
+        if (int rc = grow(h, Sync::Stream(st), {{&h->traj_pooled, (size_t)p.Bc * traj_points(p.L, traj->stride) * D * 4},
+                                                {&h->traj_npad, (size_t)p.Bc * 4}}))
+            return rc;
     }
     h->last_B = p.Bc; h->last_L = p.L; h->last_Lp = p.Lp;
     h->last_hreg_Lmain = p.hreg ? p.Lmain : 0;
@@ -886,8 +840,7 @@ int stage_head(ChunkCtx& c, float* logits) {
         StageTimer t(h, st, CLM_STAGE_HEADMLP);
         launch_head_mlp(partial, h->hw, h->pooled.get<float>(), logits, p.Bc, st);
     }
-    HIPCHK(h, hipGetLastError());
-    return CLM_OK;
+    return launched(h, "stage_head");
 }
 
 // The chunk's attention outputs (clm_forward_attn), at the rows of its reads [b0, b0 + Bc) in the caller's buffers: one kernel behind
@@ -899,8 +852,7 @@ int stage_attn(ChunkCtx& c, const clm_attn_out& a, int b0) {
                         a.weights ? a.weights + r * (size_t)a.weights_row_stride : nullptr, a.weights_row_stride,
                         a.summary ? a.summary + r : nullptr, a.summary ? a.peak_pos + r * a.top_k : nullptr,
                         a.summary ? a.peak_weight + r * a.top_k : nullptr, a.top_k, st);
-    HIPCHK(h, hipGetLastError());
-    return CLM_OK;
+    return launched(h, "stage_attn");
 }
 
 // The chunk's running verdict (clm_forward_traj), at the rows of its reads [b0, b0 + Bc) in the caller's buffers: the prefix merge of
@@ -918,8 +870,7 @@ int stage_traj(ChunkCtx& c, const clm_traj_out& t, int b0, const float* logits) 
     launch_traj_classifier(h->traj_pooled.get<float>(), K, rows, h->hw, out, t.point_stride, st);
     launch_traj_summary(logits, out, t.point_stride, p.Bc, K, t.stride, p.L, h->traj_npad.get<int>(), h->ids8.get<unsigned char>(), p.Lp,
                         t.summary ? t.summary + b0 : nullptr, st);
-    HIPCHK(h, hipGetLastError());
-    return CLM_OK;
+    return launched(h, "stage_traj");
 }
 
 int forward_chunk(clm_handle* h, const void* ids, int ids_dtype, int64_t row_stride, int Bc, int L, float* logits, hipStream_t st,
@@ -974,13 +925,8 @@ int check_attn_arg(clm_handle* h, const char* who, const clm_attn_out* a, int L)
 // The trajectory request of clm_forward_traj / clm_forward_staged_traj for reads of L tokens (null: none, nothing to check)
 int check_traj_arg(clm_handle* h, const char* who, const clm_traj_out* t, int L) {
     if (!t) return CLM_OK;
+    if (int rc = check_traj_request(h, who, t, L)) return rc;   // what holds for every net; then what the Hyena engine adds
     const std::string w(who);
-    if (t->struct_size != (int32_t)sizeof(clm_traj_out)) return fail(h, CLM_E_INVALID, w + ": clm_traj_out size mismatch");
-    if (t->stride < 128 || t->stride > 4096 || t->stride % 128)
-        return fail(h, CLM_E_INVALID, w + ": the trajectory's stride must be a multiple of 128 in 128 ... 4096");
-    if (!t->logits) return fail(h, CLM_E_INVALID, w + ": the trajectory request has no logits buffer");
-    if (t->point_stride < traj_points(L, t->stride))
-        return fail(h, CLM_E_INVALID, w + ": point_stride is shorter than the " + std::to_string(traj_points(L, t->stride)) + " points of a read");
     if (L > ATTN_MAX_L)
         return fail(h, CLM_E_UNSUPPORTED, w + ": trajectories exist for reads of up to " + std::to_string(ATTN_MAX_L) + " tokens");
     if (h->stop_stage >= 0)
@@ -991,13 +937,6 @@ int check_traj_arg(clm_handle* h, const char* who, const clm_traj_out* t, int L)
 }
 
 size_t ids_elem_size(int dtype) { return dtype == CLM_DT_I64 ? 8 : (dtype == CLM_DT_I32 ? 4 : 1); }
-// The ids argument of `who` (clm_forward, clm_stage_ids, clm_selfcheck); out: the pointer that call writes its result through
-int check_ids_arg(clm_handle* h, const char* who, const void* ids, const void* out, int ids_dtype, int64_t row_stride, int B, int L) {
-    if (!ids || !out || B < 1 || L < 1 || row_stride < L) return fail(h, CLM_E_INVALID, std::string(who) + ": bad argument");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
-    return CLM_OK;
-}
 
 // `attn`, `traj`: the caller's attention and trajectory outputs for all B reads, or null -- the self-check, the [PAD]-table build and
 // every other forward the engine runs for itself pass none
@@ -1279,13 +1218,10 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
     *max_abs_diff = 0.f;
     if (labels_differ) *labels_differ = 0;
     if (is_exact(h)) return CLM_OK;
-    if ((size_t)2 * B * NCLS * 4 > h->sc_logits.bytes()) {
-        HIPCHK(h, hipStreamSynchronize(st));
-        HIPCHK(h, h->sc_logits.reserve((size_t)2 * B * NCLS * 4));
-    }
+    if (int rc = grow(h, Sync::Stream(st), {{&h->sc_logits, (size_t)2 * B * NCLS * 4}})) return rc;
     int rc = CLM_OK;
     {
-        ScopedRun scope(h);
+        RunScope<clm_handle> scope(h);
         h->run.fallback = 0;                                    // the MODE is on trial (short reads of fp16c: its fp16x3 kernels)
         // pass 0: the arithmetic the handle's mode runs reads of this length in (whatever clm_set_fallback says); pass 1: exact fp32
         for (int pass = 0; pass < 2 && !rc; ++pass) {
@@ -1295,15 +1231,7 @@ int clm_selfcheck(clm_handle* h, const void* ids, int ids_dtype, int64_t ids_row
         }
     }
     if (rc) return rc;
-    std::vector<float> host((size_t)2 * B * NCLS);
-    HIPCHK(h, hipMemcpyAsync(host.data(), h->sc_logits.get<float>(), host.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    float worst = 0.f;
-    int differ = 0;
-    (void)clm_logit_deviation(host.data(), host.data() + (size_t)B * NCLS, B, NCLS, &worst, &differ);
-    *max_abs_diff = worst;
-    if (labels_differ) *labels_differ = differ;
-    return CLM_OK;
+    return logits_deviation(h, st, h->sc_logits.get<float>(), B, max_abs_diff, labels_differ);
 }
 
 int clm_logit_deviation(const float* a, const float* b, int B, int n_classes, float* max_abs_diff, int* labels_differ) {
@@ -1384,8 +1312,7 @@ int clm_debug_fetch(clm_handle* h, const char* name, void* host_out, size_t byte
             if (f.key == key && i >= 0 && i < NLAYER && (int)L <= f.Lf) { src = f.ktime[i].get(); have = L * D * 4; }
     }
     if (!src) return fail(h, CLM_E_INVALID, "clm_debug_fetch: unknown or empty buffer " + n);
-    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_debug_fetch: " + n + " holds only " + std::to_string(have) + " bytes");
-    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
+    if (int rc = fetch_bytes(h, "clm_debug_fetch", n, src, have, host_out, bytes)) return rc;
     if (src == h->h.get<float>() && h->last_hreg_Lmain > 0) {
         // the tail kernels left the whole tiles in register order (gemm16.hip HREG): [mt][q][thread][4 floats] inside each tile's
         // 128 KiB, thread = (wave, lhalf, lrow), value = token 32 mt + lrow, feature 32 wave + 8 q + 4 lhalf + j -- back to rows here
@@ -1449,11 +1376,7 @@ int check_pool_args(clm_handle* h, const char* who, bool any_null, bool aligned,
 }
 // the call's workspace: W1 in the packing its kernels read, and the partials -- grown behind the stream's queued work
 int pool_workspace(clm_handle* h, DevBuf& w1, size_t partial_bytes, hipStream_t st) {
-    if (w1 && partial_bytes <= h->pt_partial.bytes()) return CLM_OK;
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, w1.reserve((size_t)D * D * 4));
-    HIPCHK(h, h->pt_partial.reserve(partial_bytes));
-    return CLM_OK;
+    return grow(h, Sync::Stream(st), {{&w1, (size_t)D * D * 4}, {&h->pt_partial, partial_bytes}});
 }
 }  // namespace
 
@@ -1472,8 +1395,7 @@ int clm_pool_forward(clm_handle* h, const float* rows, int B, int L, const float
     launch_softmax_stats(scores_out, stats_out, B, L, st);
     launch_pool(rows, h->net.lnf_g, h->net.lnf_b, scores_out, stats_out, h->pt_partial.get<float>(), B, L, eps, st);
     launch_pool_combine(h->pt_partial.get<float>(), pooled_out, B, st);
-    HIPCHK(h, hipGetLastError());
-    return CLM_OK;
+    return launched(h, "clm_pool_forward");
 }
 
 int clm_pool_backward(clm_handle* h, const float* rows, int B, int L, const float* w1, const float* b1, const float* w2,
@@ -1489,8 +1411,7 @@ int clm_pool_backward(clm_handle* h, const float* rows, int B, int L, const floa
     launch_pack_f32t(w1, h->pt_w1t.get(), D, D, st);
     launch_pool_bwd(rows, h->net.lnf_g, h->net.lnf_b, h->pt_w1t.get(), b1, w2, scores, stats, pooled, dpooled, h->pt_partial.get<float>(),
                     d_w1, d_b1, d_w2, d_b2, beta, B, L, h->cfg.ln_eps, st);
-    HIPCHK(h, hipGetLastError());
-    return CLM_OK;
+    return launched(h, "clm_pool_backward");
 }
 
 int clm_profile_enable(clm_handle* h, int on) {
@@ -1503,20 +1424,7 @@ int clm_profile_read(clm_handle* h, double* ms_out, int64_t* launches_out, int r
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    for (auto& r : h->recs) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) {
-            h->prof_ms[r.stage] += ms;
-            h->prof_n[r.stage] += 1;
-        }
-        h->free_events.push_back({r.e0, r.e1});
-    }
-    h->recs.clear();
-    for (int i = 0; i < CLM_N_STAGES; ++i) {
-        if (ms_out) ms_out[i] = h->prof_ms[i];
-        if (launches_out) launches_out[i] = h->prof_n[i];
-        if (reset) { h->prof_ms[i] = 0; h->prof_n[i] = 0; }
-    }
+    h->profile.read(ms_out, launches_out, reset != 0);
     return CLM_OK;
 }
 
@@ -1530,21 +1438,16 @@ const char* clm_profile_stage_name(int stage) {
 const char* clm_last_error(const clm_handle* h) { return h ? h->err.c_str() : create_error<clm_handle>().c_str(); }
 
 int clm_destroy(clm_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    tail16_dump_stamps();
-    conv_dump_stamps();
-    for (auto& r : h->recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    for (auto& e : h->free_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (auto& sg : h->stage) {
-        if (sg.copied) (void)hipEventDestroy(sg.copied);
-        if (sg.consumed) (void)hipEventDestroy(sg.consumed);
-    }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->bad_ids) (void)hipHostFree(h->bad_ids);
-    delete h;                                                // (its device buffers free themselves)
-    return CLM_OK;
+    return destroy_handle(h, [h] {                           // (with the device idle: bad_ids is written by queued kernels)
+        tail16_dump_stamps();
+        conv_dump_stamps();
+        for (auto& sg : h->stage) {
+            if (sg.copied) (void)hipEventDestroy(sg.copied);
+            if (sg.consumed) (void)hipEventDestroy(sg.consumed);
+        }
+        if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
+        if (h->bad_ids) (void)hipHostFree(h->bad_ids);
+    });
 }
 
 }  // extern "C"

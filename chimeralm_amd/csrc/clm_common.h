@@ -7,11 +7,8 @@
 #include <array>
 #include <atomic>
 #include <cstdio>
-#include <map>
-#include <string>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "chimeralm_hip.h"
 
@@ -175,172 +172,6 @@ void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
     hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
 }
 
-// ---- host side of the engine handles (clm_api.hip, tf_model.hip, cnn.hip) ------------------------------------------------------
-// One device allocation and its size, freed by its owner.  Nothing here synchronises: whoever replaces memory that queued kernels
-// may still read synchronises first.
-class DevBuf {
-  public:
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            reset();
-            std::swap(p_, o.p_);
-            std::swap(n_, o.n_);
-        }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    hipError_t alloc(size_t bytes) {              // what it held is freed first
-        reset();
-        const hipError_t e = hipMalloc(&p_, bytes);
-        if (e == hipSuccess) n_ = bytes;
-        else p_ = nullptr;
-        return e;
-    }
-    hipError_t reserve(size_t bytes) { return bytes > n_ ? alloc(bytes) : hipSuccess; }   // grows, never shrinks
-    void reset() {
-        if (p_) (void)hipFree(p_);
-        p_ = nullptr;
-        n_ = 0;
-    }
-    size_t bytes() const { return n_; }
-    template <class T = void>
-    T* get() const { return static_cast<T*>(p_); }
-    explicit operator bool() const { return p_ != nullptr; }
-
-  private:
-    void* p_ = nullptr;
-    size_t n_ = 0;
-};
-
-// The last error of a handle is its `err`; before a handle exists (its *_create), one string per handle type.
-template <class H>
-std::string& create_error() {
-    static std::string s;
-    return s;
-}
-template <class H>
-int fail(H* h, int code, const std::string& msg) {
-    (h ? h->err : create_error<H>()) = msg;
-    return code;
-}
-#define HIPCHK(h, expr)                                                                                   \
-    do {                                                                                                  \
-        const hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return clm::fail(h, CLM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// *_create: `device` exists, is made current and is a gfx950
-template <class H>
-int use_gfx950(int device, const char* who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": no such HIP device " + std::to_string(device));
-    if (hipSetDevice(device) != hipSuccess) return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return fail<H>(nullptr, CLM_E_HIP, std::string(who) + ": hipGetDeviceProperties failed");
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail<H>(nullptr, CLM_E_UNSUPPORTED, std::string(who) + ": this engine is built for gfx950 (MI355X) only, found " + prop.gcnArchName);
-    return CLM_OK;
-}
-
-// ---- expected weights of the transformer, CNN and Mamba engines: a handle's `expected` table, built ONCE by its *_create --------
-// canonical key -> shape and where *_finalize puts the device pointer (a field of the handle; null: read by finalize alone).
-// Sorted by key: the first missing weight finalize names is the first in key order.
-struct WeightSpec {
-    std::vector<int64_t> shape;
-    const float** dst;
-};
-using WeightTable = std::map<std::string, WeightSpec>;
-
-inline std::string canonical_weight_key(const char* key) {       // a Lightning checkpoint's "net." prefix is optional
-    const std::string k(key);
-    return k.rfind("net.", 0) == 0 ? k.substr(4) : k;
-}
-// `n` fp32 values as tensor `k` of the handle's `w`: a device copy, replacing the one loaded before
-template <class H>
-int store_f32(H* h, const std::string& k, const void* data, size_t n) {
-    HIPCHK(h, hipSetDevice(h->device));
-    h->w.erase(k);
-    DevBuf d;
-    HIPCHK(h, d.alloc(n * 4));
-    HIPCHK(h, hipMemcpy(d.get(), data, n * 4, hipMemcpyDefault));
-    h->w.emplace(k, std::move(d));
-    h->finalized = false;
-    return CLM_OK;
-}
-// *_load_weight: an fp32 tensor `k` of the handle's table, checked against it
-template <class H>
-int load_f32(H* h, const char* who, const std::string& k, const void* data, const int64_t* shape, int ndim) {
-    const auto it = h->expected.find(k);
-    if (it == h->expected.end()) return fail(h, CLM_E_INVALID, std::string(who) + ": unknown key " + k);
-    if (it->second.shape != std::vector<int64_t>(shape, shape + ndim)) return fail(h, CLM_E_INVALID, std::string(who) + ": wrong shape for " + k);
-    size_t n = 1;
-    for (int64_t s : it->second.shape) n *= (size_t)s;
-    return store_f32(h, k, data, n);
-}
-// *_finalize: every tensor of the table is loaded (else CLM_E_MISSING) and its device pointer stands where the forward reads it
-template <class H>
-int resolve_weights(H* h, const char* who) {
-    for (const auto& kv : h->expected) {
-        const auto it = h->w.find(kv.first);
-        if (it == h->w.end()) return fail(h, CLM_E_MISSING, std::string(who) + ": missing weight " + kv.first);
-        if (kv.second.dst) *kv.second.dst = it->second.template get<float>();
-    }
-    return CLM_OK;
-}
-// *_finalize: loaded tensor `k` back on the host (what finalize computes in fp64 or repacks there), and a product of it up again
-template <class H>
-int host_f32(H* h, const char* who, const std::string& k, std::vector<float>& out) {
-    const auto it = h->w.find(k);
-    if (it == h->w.end()) return fail(h, CLM_E_MISSING, std::string(who) + ": missing weight " + k);
-    out.resize(it->second.bytes() / 4);
-    HIPCHK(h, hipMemcpy(out.data(), it->second.get(), it->second.bytes(), hipMemcpyDeviceToHost));
-    return CLM_OK;
-}
-template <class H>
-int upload_f32(H* h, DevBuf& d, const std::vector<float>& src) {
-    HIPCHK(h, d.alloc(src.size() * 4));
-    HIPCHK(h, hipMemcpy(d.get(), src.data(), src.size() * 4, hipMemcpyHostToDevice));
-    return CLM_OK;
-}
-// W [rows][cols] -> [cols][rows] on the host (a layer whose threads each own an output reads its weights coalesced)
-inline std::vector<float> transposed(const std::vector<float>& W, int rows, int cols) {
-    std::vector<float> t((size_t)rows * cols);
-    for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = W[(size_t)r * cols + c];
-    return t;
-}
-// A convolution's taps, split as [taps][co][ci] fp32 on the device, each packed by pack(tap, dst) into tap_bytes of `out`.
-// Synchronises before it returns: the caller reuses or frees `split` next.
-template <class H, class Pack>
-int pack_taps(H* h, const float* split, int taps, size_t tap_bytes, DevBuf& out, Pack pack) {
-    HIPCHK(h, out.alloc(taps * tap_bytes));
-    for (int dk = 0; dk < taps; ++dk) pack(split + (size_t)dk * D * D, out.get<char>() + dk * tap_bytes);
-    HIPCHK(h, hipDeviceSynchronize());
-    return CLM_OK;
-}
-
-// fp16x3 packs a weight x 2^10 as fp16 hi + lo (tail32.hip pack_x3_kernel): from |w| = 65504 / 2^10 ~ 63.97 the hi half saturates
-// and the packing no longer holds the weight, so a handle whose x3-packed weights reach this runs its exact-fp32 kernels instead.
-constexpr float X3_WEIGHT_LIMIT = 64.f;
-// Largest |w| of `n` fp32 values in device memory (read back to the host; NaN as soon as one of them is NaN).
-inline hipError_t device_max_abs(const float* d, size_t n, float& out) {
-    std::vector<float> host(n);
-    const hipError_t e = hipMemcpy(host.data(), d, n * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    out = 0.f;
-    for (const float x : host) {
-        if (x != x) { out = x; break; }
-        out = __builtin_fabsf(x) > out ? __builtin_fabsf(x) : out;
-    }
-    return hipSuccess;
-}
-
 // ---- kernel launchers (definitions in the .hip files); all are asynchronous on `st` --------------------
 // PREC_F16C ("fp16c"): fp16 activations x weights held as hi + lo (in_proj, out_proj, score layer; the MLP weights are plain fp16
 // since round 3: MLP_PREC, gemm_common.h), hi = fp16(w), lo = e4m3((w - hi) * 2^17): per 64-deep group
@@ -402,14 +233,7 @@ struct TfLayerF32 {               // one encoder layer's tensors as loaded, fp32
 struct TfNetF32 {                 // ... and what belongs to no layer: embedding, pe, norm, the stem convolutions, pooling, classifier
     const float *emb, *pe, *norm_g, *norm_b, *conv_w[3], *conv_b[3], *pool_w, *pool_b, *cls0_w, *cls0_b, *cls3_w, *cls3_b;
 };
-struct TfPacking {                // one packing of the matrices the MFMA kernels read (16-bit mode, t32 or x3)
-    std::vector<std::array<DevBuf, 4>> mat;   // per layer
-    DevBuf conv[3];                           // stem convolutions: three taps [dk][co][ci], each tap packed
-};
-// tf_fp32.hip: the forward with exact-fp32 products (the reference's precision; x3: on hi + lo halfs), up to the encoder output h
-size_t tf32_workspace_floats(int B, int L);
-int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
-                 const TfLayerF32* lay, const TfPacking& pk /*t32, or x3's*/, hipStream_t st, bool unfused, bool x3, int stop_after = -1);
+// (their packings, TfPacking, and the exact forward's host side, tf32_forward: handle_host.h)
 
 // GEMM family (gemm.hip): exact fp32, the unfused path (CLM_DEBUG=unfused_fp32, debug stops); activations fp32.
 // z  = in_proj(LN1(h))      -> channel-major [B, 768, Lp]

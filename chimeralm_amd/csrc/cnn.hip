@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "chimeralm_hip.h"
-#include "clm_common.h"
+#include "handle_host.h"
 #include "cnn_common.h"
 
 namespace clm {
@@ -266,23 +266,15 @@ int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t i
                     void* stream) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_cnn_forward before clm_cnn_finalize");
-    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return fail(h, CLM_E_INVALID, "clm_cnn_forward: bad argument");
-    if (L < 64)
-        return fail(h, CLM_E_INVALID, "clm_cnn_forward: DNAConvNet needs reads of at least 64 tokens (three max-pools of 4; "
-                                          "the reference raises 'Invalid computed output size: 0'), got L = " + std::to_string(L));
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, "clm_cnn_forward: ids dtype must be i64, i32 or u8");
+    // (64 tokens: three max-pools of 4; the reference raises 'Invalid computed output size: 0' below that)
+    if (int rc = check_ids_arg(h, "clm_cnn_forward", ids, logits_out, ids_dtype, ids_row_stride, B, L, 64)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int Lp = (L + 63) / 64 * 64, L4 = L / 4, L16 = L4 / 4, L64 = L16 / 4;
     const int tiles2 = (L64 + cnn::ROWS2 - 1) / cnn::ROWS2;
-    const size_t need[5] = {(size_t)B * Lp, (size_t)B * L4 * D * 4, (size_t)B * L16 * D * 4, (size_t)B * tiles2 * D * 4, (size_t)B * D * 4};
-    DevBuf* buf[5] = {&h->ids8, &h->x1, &h->x2, &h->part, &h->pooled};
-    for (int i = 0; i < 5; ++i)
-        if (need[i] > buf[i]->bytes()) {
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, buf[i]->reserve(need[i]));
-        }
+    if (int rc = grow(h, Sync::Device(), {{&h->ids8, (size_t)B * Lp}, {&h->x1, (size_t)B * L4 * D * 4}, {&h->x2, (size_t)B * L16 * D * 4},
+                                          {&h->part, (size_t)B * tiles2 * D * 4}, {&h->pooled, (size_t)B * D * 4}}))
+        return rc;
     const CnnF32& f = h->f;
     const CnnDev& dv = h->dev;
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
@@ -300,8 +292,7 @@ int clm_cnn_forward(clm_cnn_handle* h, const void* ids, int ids_dtype, int64_t i
     hipLaunchKernelGGL(cnn::cnn_head_kernel, dim3((unsigned)B), dim3(512), 0, st, part, tiles2, L64, dv.fc0t.get<float>(), f.fc0_b,
                        dv.bn[3].scale.get<float>(), dv.bn[3].shift.get<float>(), f.fc4_w, f.fc4_b, h->pooled.get<float>(), logits_out);
     h->last_B = B; h->last_L = L;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_cnn_forward: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_cnn_forward");
 }
 
 int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, size_t bytes) {
@@ -317,19 +308,11 @@ int clm_cnn_debug_fetch(clm_cnn_handle* h, const char* name, void* host_out, siz
     else if (n == "partial") { src = h->part.get(); have = B * ((L64 + cnn::ROWS2 - 1) / cnn::ROWS2) * D * 4; }
     else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; }
     else return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: unknown name " + n);
-    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_cnn_debug_fetch: more bytes requested than the last forward produced");
-    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
-    return CLM_OK;
+    return fetch_bytes(h, "clm_cnn_debug_fetch", n, src, have, host_out, bytes);
 }
 
 const char* clm_cnn_last_error(const clm_cnn_handle* h) { return h ? h->err.c_str() : create_error<clm_cnn_handle>().c_str(); }
 
-int clm_cnn_destroy(clm_cnn_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;                                                  // (its device buffers free themselves)
-    return CLM_OK;
-}
+int clm_cnn_destroy(clm_cnn_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

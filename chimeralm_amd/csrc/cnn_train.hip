@@ -32,7 +32,7 @@
 #include <string>
 
 #include "chimeralm_hip.h"
-#include "clm_common.h"
+#include "handle_host.h"
 #include "cnn_common.h"
 #include "mfma32_common.h"
 
@@ -615,20 +615,14 @@ int clm_cnn_train_forward(clm_cnn_train_handle* h, const void* ids, int ids_dtyp
     int Ls[4];
     ct_lens(L, Ls);
     const int Lp = (L + 63) / 64 * 64;
-    {
-        std::pair<DevBuf*, size_t> want[] = {
+    if (int rc = grow(h, Sync::Device(), {
             {&h->ids8, (size_t)B * Lp},
             {&h->z[0], (size_t)B * Ls[0] * D * 4}, {&h->z[1], (size_t)B * Ls[1] * D * 4}, {&h->z[2], (size_t)B * Ls[2] * D * 4},
             {&h->dz[0], (size_t)B * Ls[0] * D * 4}, {&h->dz[1], (size_t)B * Ls[1] * D * 4}, {&h->dz[2], (size_t)B * Ls[2] * D * 4},
             {&h->xn[0], (size_t)B * Ls[1] * D * 4}, {&h->xn[1], (size_t)B * Ls[2] * D * 4}, {&h->xn[2], (size_t)B * Ls[3] * D * 4},
             {&h->choice[0], (size_t)B * Ls[1] * D}, {&h->choice[1], (size_t)B * Ls[2] * D}, {&h->choice[2], (size_t)B * Ls[3] * D},
-            {&h->dyp, (size_t)B * Ls[1] * D * 4}, {&h->dx, (size_t)B * Ls[1] * D * 4}, {&h->part, CT_PART_BYTES}, {&h->small, Small::END * 4}};
-        for (auto& w : want)
-            if (w.second > w.first->bytes()) {
-                HIPCHK(h, hipDeviceSynchronize());
-                HIPCHK(h, w.first->reserve(w.second));
-            }
-    }
+            {&h->dyp, (size_t)B * Ls[1] * D * 4}, {&h->dx, (size_t)B * Ls[1] * D * 4}, {&h->part, CT_PART_BYTES}, {&h->small, Small::END * 4}}))
+        return rc;
     float* const sm = h->small.get<float>();
     const float* E = params[0];
     const float *W[3], *bias[3], *g[3], *beta[3];
@@ -669,8 +663,7 @@ int clm_cnn_train_forward(clm_cnn_train_handle* h, const void* ids, int ids_dtyp
     hipLaunchKernelGGL(cnn_train_mean_kernel, dim3(B), dim3(1024), 0, st, h->xn[2].get<float>(), Ls[3], pooled_out);
     h->B = B;
     h->L = L;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, CLM_E_HIP, std::string("clm_cnn_train_forward: launch failed: ") + hipGetErrorString(e));
+    if (int rc = launched(h, "clm_cnn_train_forward")) return rc;
     h->pending = true;
     return CLM_OK;
 }
@@ -733,8 +726,7 @@ int clm_cnn_train_backward(clm_cnn_train_handle* h, int64_t generation, const fl
         }
     }
     h->pending = false;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, CLM_E_HIP, std::string("clm_cnn_train_backward: launch failed: ") + hipGetErrorString(e));
+    if (int rc = launched(h, "clm_cnn_train_backward")) return rc;
     h->have_dz = true;
     return CLM_OK;
 }
@@ -768,9 +760,7 @@ int clm_cnn_train_debug_fetch(clm_cnn_train_handle* h, const char* name, void* h
         HIPCHK(h, hipDeviceSynchronize());
         src = h->fetch.get();
     }
-    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_cnn_train_debug_fetch: more bytes requested than the last forward produced");
-    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
-    return CLM_OK;
+    return fetch_bytes(h, "clm_cnn_train_debug_fetch", n, src, have, host_out, bytes);
 }
 
 int64_t clm_cnn_train_workspace_bytes(int B, int L) { return B < 1 || L < 64 ? (int64_t)CLM_E_INVALID : (int64_t)ct_workspace_bytes(B, L); }
@@ -779,12 +769,6 @@ const char* clm_cnn_train_last_error(const clm_cnn_train_handle* h) {
     return h ? h->err.c_str() : create_error<clm_cnn_train_handle>().c_str();
 }
 
-int clm_cnn_train_destroy(clm_cnn_train_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;
-    return CLM_OK;
-}
+int clm_cnn_train_destroy(clm_cnn_train_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

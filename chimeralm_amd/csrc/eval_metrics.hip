@@ -7,7 +7,7 @@
 #include <cmath>
 #include <string>
 
-#include "clm_common.h"
+#include "handle_host.h"
 
 namespace clm {
 namespace eval {
@@ -140,8 +140,7 @@ int clm_eval_update(clm_eval_handle* h, const float* logits, const int64_t* labe
     HIPCHK(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(eval::eval_update_kernel, dim3(1), dim3(eval::THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<const float2*>(logits), labels, B, h->ignore_index, h->acc.get<clm_eval_result>());
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_eval_update: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_eval_update");
 }
 
 int clm_eval_read(clm_eval_handle* h, clm_eval_result* out, void* stream) {
@@ -179,14 +178,9 @@ int clm_eval_reset(clm_eval_handle* h, void* stream) {
 const char* clm_eval_last_error(const clm_eval_handle* h) { return h ? h->err.c_str() : create_error<clm_eval_handle>().c_str(); }
 
 int clm_eval_destroy(clm_eval_handle* h) {
-    if (!h) return CLM_OK;
-    if (h->device >= 0) {
-        (void)hipSetDevice(h->device);
-        (void)hipDeviceSynchronize();
-    }
-    if (h->staging) (void)hipHostFree(h->staging);
-    delete h;                                                  // (its device buffer frees itself)
-    return CLM_OK;
+    return destroy_handle(h, [h] {
+        if (h->staging) (void)hipHostFree(h->staging);
+    });
 }
 
 }  // extern "C"

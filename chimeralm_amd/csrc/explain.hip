@@ -15,7 +15,7 @@
 #include <cmath>
 #include <string>
 
-#include "clm_common.h"
+#include "handle_host.h"
 
 namespace clm {
 namespace explain {
@@ -247,11 +247,6 @@ int bad_options(clm_explain_handle* h, const char* who, int n_bases, int window,
     return CLM_OK;
 }
 
-int launched(clm_explain_handle* h, const char* who) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string(who) + ": launch failed: " + hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
@@ -361,12 +356,6 @@ const char* clm_explain_last_error(const clm_explain_handle* h) {
     return h ? h->err.c_str() : create_error<clm_explain_handle>().c_str();
 }
 
-int clm_explain_destroy(clm_explain_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;                                                  // (its device buffer frees itself)
-    return CLM_OK;
-}
+int clm_explain_destroy(clm_explain_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // bitwise the same from run to run.
 #include <string>
 
-#include "clm_common.h"
+#include "handle_host.h"
 #include "longread_plan.h"
 
 namespace clm {
@@ -158,8 +158,7 @@ int clm_longread_rows(clm_longread_handle* h, const unsigned char* ids, int64_t 
     hipLaunchKernelGGL(longread::longread_rows_kernel, dim3((chunks + longread::ROWS_THREADS - 1) / longread::ROWS_THREADS, rows),
                        dim3(longread::ROWS_THREADS), 0, reinterpret_cast<hipStream_t>(stream), ids, row_stride, (int64_t)B * row_stride, spans,
                        s0, out, out_stride, width);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail_lr(h, CLM_E_HIP, std::string("clm_longread_rows: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_longread_rows");
 }
 
 int clm_longread_reduce(clm_longread_handle* h, const float* logits, const int32_t* first, int B, float* logits_out, int32_t* chosen,
@@ -173,18 +172,11 @@ int clm_longread_reduce(clm_longread_handle* h, const float* logits, const int32
     hipLaunchKernelGGL(longread::longread_reduce_kernel, dim3((B + longread::REDUCE_THREADS - 1) / longread::REDUCE_THREADS),
                        dim3(longread::REDUCE_THREADS), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint2*>(logits), first, B,
                        reinterpret_cast<uint2*>(logits_out), chosen, gap, nonfinite);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail_lr(h, CLM_E_HIP, std::string("clm_longread_reduce: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_longread_reduce");
 }
 
 const char* clm_longread_last_error(const clm_longread_handle* h) { return h ? h->err.c_str() : longread::host_error().c_str(); }
 
-int clm_longread_destroy(clm_longread_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;
-    return CLM_OK;
-}
+int clm_longread_destroy(clm_longread_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

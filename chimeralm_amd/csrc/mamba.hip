@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "chimeralm_hip.h"
-#include "clm_common.h"
+#include "handle_host.h"
 #include "mamba_common.h"
 #include "mfma32_common.h"
 
@@ -566,20 +566,6 @@ int mamba_pack(clm_mamba_handle* h, DevBuf& dst, const std::vector<float>& W, in
     return CLM_OK;
 }
 
-// The trajectory request of clm_mamba_forward_traj for reads of L tokens (null: none, nothing to check)
-int check_verdict_arg(clm_mamba_handle* h, const clm_traj_out* t, int L) {
-    if (!t) return CLM_OK;
-    const std::string w = "clm_mamba_forward_traj";
-    if (t->struct_size != (int32_t)sizeof(clm_traj_out)) return fail(h, CLM_E_INVALID, w + ": clm_traj_out size mismatch");
-    if (t->stride < 128 || t->stride > 4096 || t->stride % 128)
-        return fail(h, CLM_E_INVALID, w + ": the trajectory's stride must be a multiple of 128 in 128 ... 4096");
-    if (!t->logits) return fail(h, CLM_E_INVALID, w + ": the trajectory request has no logits buffer");
-    const int K = (L + t->stride - 1) / t->stride;
-    if (t->point_stride < K)
-        return fail(h, CLM_E_INVALID, w + ": point_stride is shorter than the " + std::to_string(K) + " points of a read");
-    return CLM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -679,14 +665,12 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
                            int64_t mask_row_stride, float* logits_out, const clm_traj_out* traj, void* stream) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return fail(h, CLM_E_STATE, "clm_mamba_forward before clm_mamba_finalize");
-    if (!ids || !logits_out || B < 1 || L < 1 || ids_row_stride < L) return fail(h, CLM_E_INVALID, "clm_mamba_forward: bad argument");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, "clm_mamba_forward: ids dtype must be i64, i32 or u8");
+    if (int rc = check_ids_arg(h, "clm_mamba_forward", ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
     if (h->variant == CLM_MAMBA_SEQ && L > h->max_len)
         return fail(h, CLM_E_INVALID, "clm_mamba_forward: read length " + std::to_string(L) + " exceeds model_max_length " +
                                           std::to_string(h->max_len) + " (the positional embedding's length)");
     if (mask && mask_row_stride < L) return fail(h, CLM_E_INVALID, "clm_mamba_forward: mask row stride shorter than the read");
-    if (int rc = check_verdict_arg(h, traj, L)) return rc;
+    if (int rc = check_traj_request(h, "clm_mamba_forward_traj", traj, L)) return rc;
     if (h->variant == CLM_MAMBA_SP) mask = nullptr;              // (the reference's mambasp ignores its second argument)
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -695,21 +679,13 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
     const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, cap_tok / (size_t)L));
     const size_t T = (size_t)nb * L;
     const bool dbg = (size_t)B * L * d * 4 <= DBG_CAP;
-    const size_t need[10] = {(size_t)B * Lp, T * d * 4, T * NP * 4, T * h->conv_dim * 4, T * di * 4, T * H * 4,
-                             (size_t)nb * tiles_x * 2 * d * 4, (size_t)B * d * 4, dbg ? (size_t)B * L * d * 4 : 0,
-                             dbg ? (size_t)B * L * d * 4 : 0};
-    DevBuf* buf[10] = {&h->ids8, &h->h, &h->zx, &h->xc, &h->g, &h->ssq, &h->part, &h->pooled, &h->dbg_front, &h->dbg_layer0};
-    for (int i = 0; i < 10; ++i)
-        if (need[i] > buf[i]->bytes()) {
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, buf[i]->reserve(need[i]));
-        }
+    const size_t taps = dbg ? (size_t)B * L * d * 4 : 0;
     const int vK = traj ? (L + traj->stride - 1) / traj->stride : 0;          // points per read of the request
-    if (traj && ((size_t)nb * vK * d * 4 > h->verdict_pooled.bytes() || (size_t)nb * 4 > h->verdict_npad.bytes())) {
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, h->verdict_pooled.reserve((size_t)nb * vK * d * 4));
-        HIPCHK(h, h->verdict_npad.reserve((size_t)nb * 4));
-    }
+    if (int rc = grow(h, Sync::Device(), {{&h->ids8, (size_t)B * Lp}, {&h->h, T * d * 4}, {&h->zx, T * NP * 4}, {&h->xc, T * h->conv_dim * 4},
+                                          {&h->g, T * di * 4}, {&h->ssq, T * H * 4}, {&h->part, (size_t)nb * tiles_x * 2 * d * 4},
+                                          {&h->pooled, (size_t)B * d * 4}, {&h->dbg_front, taps}, {&h->dbg_layer0, taps},
+                                          {&h->verdict_pooled, (size_t)nb * vK * d * 4}, {&h->verdict_npad, traj ? (size_t)nb * 4 : 0}}))
+        return rc;
     const MambaNetF32& net = h->net;
     unsigned char* const ids8 = h->ids8.get<unsigned char>();
     float *const hs = h->h.get<float>(), *const zx = h->zx.get<float>(), *const g = h->g.get<float>(), *const ssq = h->ssq.get<float>();
@@ -773,8 +749,7 @@ int clm_mamba_forward_traj(clm_mamba_handle* h, const void* ids, int ids_dtype, 
         }
     }
     h->last_B = B, h->last_L = L, h->last_nb = nb, h->last_dbg = dbg;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_mamba_forward: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_mamba_forward");
 }
 
 int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out, size_t bytes) {
@@ -806,19 +781,11 @@ int clm_mamba_debug_fetch(clm_mamba_handle* h, const char* name, void* host_out,
     } else {
         return fail(h, CLM_E_INVALID, "clm_mamba_debug_fetch: unknown name " + n);
     }
-    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_mamba_debug_fetch: more bytes requested than the last forward produced");
-    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
-    return CLM_OK;
+    return fetch_bytes(h, "clm_mamba_debug_fetch", n, src, have, host_out, bytes);
 }
 
 const char* clm_mamba_last_error(const clm_mamba_handle* h) { return h ? h->err.c_str() : create_error<clm_mamba_handle>().c_str(); }
 
-int clm_mamba_destroy(clm_mamba_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;                                                  // (its device buffers free themselves)
-    return CLM_OK;
-}
+int clm_mamba_destroy(clm_mamba_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -23,7 +23,7 @@
 #include <string>
 
 #include "chimeralm_hip.h"
-#include "clm_common.h"
+#include "handle_host.h"
 #include "mamba_common.h"
 #include "mfma32_common.h"
 
@@ -667,8 +667,7 @@ int clm_mamba_train_forward(clm_mamba_train_handle* h, const float* zxbcdt, cons
     mtrain::launch_scan<false>(s, q.N, B, st);
     hipLaunchKernelGGL(mtrain::mtrain_gate_fwd_kernel, dim3((unsigned)((q.rows + 3) / 4)), dim3(256), 0, st, ys, zxbcdt, q.ldz, q.di, nw, out,
                        q.rows);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_mamba_train_forward: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_mamba_train_forward");
 }
 
 int clm_mamba_train_backward(clm_mamba_train_handle* h, const float* zxbcdt, const float* const* params, int B, int L, int d_model,
@@ -682,11 +681,7 @@ int clm_mamba_train_backward(clm_mamba_train_handle* h, const float* zxbcdt, con
     for (int i = 0; i < CLM_MAMBA_TRAIN_PARAMS; ++i)
         if (!params[i] || !dparams[i]) return fail(h, CLM_E_INVALID, "clm_mamba_train_backward: null parameter or gradient");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t need = ws_floats(q) * 4;
-    if (need > h->ws.bytes()) {
-        HIPCHK(h, hipDeviceSynchronize());                     // (queued kernels of an earlier call may still read the old scratch)
-        HIPCHK(h, h->ws.reserve(need));
-    }
+    if (int rc = grow(h, Sync::Device(), {{&h->ws, ws_floats(q) * 4}})) return rc;   // (queued kernels of an earlier call may still read the old scratch)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const float *cw = params[0], *cbias = params[1], *dtb = params[2], *alog = params[3], *Dp = params[4], *nw = params[5];
     float* p = h->ws.get<float>();
@@ -720,20 +715,13 @@ int clm_mamba_train_backward(clm_mamba_train_handle* h, const float* zxbcdt, con
     reduce(pA, (size_t)B, (size_t)q.H, dparams[3]);
     reduce(pD, (size_t)B, (size_t)q.H, dparams[4]);
     reduce(pnw, t64, (size_t)q.di, dparams[5]);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, std::string("clm_mamba_train_backward: launch failed: ") + hipGetErrorString(e));
+    return launched(h, "clm_mamba_train_backward");
 }
 
 const char* clm_mamba_train_last_error(const clm_mamba_train_handle* h) {
     return h ? h->err.c_str() : create_error<clm_mamba_train_handle>().c_str();
 }
 
-int clm_mamba_train_destroy(clm_mamba_train_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;
-    return CLM_OK;
-}
+int clm_mamba_train_destroy(clm_mamba_train_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 // conv32_kernel and enc32_kernel in tail32.hip, the MFMA attention (attention32_kernel, attention_x3_kernel) in attention.hip.
 #include <utility>
 
-#include "clm_common.h"
+#include "handle_host.h"
 
 namespace clm {
 namespace tf32 {
@@ -193,11 +193,11 @@ size_t tf32_workspace_floats(int B, int L) {
 
 // net / lay / pk: the weights as clm_tf_finalize resolved them (pk: the packing the caller chose, t32 or x3).  h [M][256] receives the
 // encoder output (the residual stream the pooling head reads), exactly where the 16-bit path leaves it.  stop_after >= 0 (fused form
-// only): return right after the launch of that CLM_TF_STAGE_* (clm_tf_debug_stop_after).
-int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
-                 const TfLayerF32* lay, const TfPacking& pk, hipStream_t st, bool unfused, bool x3, int stop_after) {
+// only): return right after the launch of that CLM_TF_STAGE_* (clm_tf_debug_stop_after).  false: the attention refused the shape
+// and nothing behind it was launched; the launch error is the caller's to read.
+bool tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_layers, float* ws, float* h, const TfNetF32& net,
+                  const TfLayerF32* lay, const TfPacking& pk, hipStream_t st, bool unfused, bool x3, int stop_after) {
     using namespace tf32;
-    auto done = [] { return hipGetLastError() == hipSuccess ? 0 : -1; };
     const int L1 = L / 2, L2 = L1 / 2, L3 = L2 / 2;
     const size_t M = (size_t)B * L3;
     float* x = ws;
@@ -207,7 +207,7 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
     float* u = att + M * D;
     float* t = u + M * 1024;
     hipLaunchKernelGGL(embed_kernel, dim3((unsigned)(((size_t)B * L + 3) / 4)), dim3(256), 0, st, ids8, ids_stride, net.emb, x, B, L);
-    if (stop_after == CLM_TF_STAGE_EMBED) return done();
+    if (stop_after == CLM_TF_STAGE_EMBED) return true;
     // 3 x [Conv1d(k = 3, padding = 1) -> ReLU -> MaxPool1d(2)]; a trailing odd position is dropped by the pooling, as in torch
     int Lin = L;
     for (int c = 0; c < 3; ++c) {
@@ -215,7 +215,7 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
         if (!unfused) {      // round 4: convolution + ReLU + pooling in one kernel on the fp32 MFMA (tail32.hip conv32_kernel)
             launch_conv32(x, pk.conv[c].get(), net.conv_b[c], y, B, Lin, st, x3);
             std::swap(x, y);
-            if (stop_after == CLM_TF_STAGE_CONV1 + c) return done();
+            if (stop_after == CLM_TF_STAGE_CONV1 + c) return true;
         } else {
             gemm<true, true>(x, D, net.conv_w[c], net.conv_b[c], nullptr, y, D, (size_t)B * Lin, D, 3 * D, Lin, st);
             hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)(((size_t)B * Lout * (D / 4) + 255) / 256)), dim3(256), 0, st, y, x, B, Lin, Lout);
@@ -224,23 +224,23 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
     }
     // + positional encoding, LayerNorm -> residual stream
     hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, net.pe, net.norm_g, net.norm_b, h, M, L3, 1e-5f);
-    if (stop_after == CLM_TF_STAGE_PE_LN) return done();
+    if (stop_after == CLM_TF_STAGE_PE_LN) return true;
     // Round 4: the dense layers of an encoder layer run fused on the fp32 MFMA (tail32.hip enc32_kernel: out_proj + LN1 + FFN + LN2 +
     // the next layer's in_proj on 64-token tiles; weights in its packing, pk.mat[layer]).  CLM_DEBUG=unfused_fp32: the seven separate
     // launches per layer of round 2 (the tests cross-check the two).
     if (!unfused && n_layers > 0)
         launch_enc32(nullptr, h, nullptr, nullptr, nullptr, pk.mat[0][0].get(), nullptr, nullptr, nullptr, lay[0].b_in, nullptr, nullptr,
                      nullptr, nullptr, qkv, M, 1e-5f, st, x3);
-    if (stop_after == CLM_TF_STAGE_IN_PROJ) return done();
+    if (stop_after == CLM_TF_STAGE_IN_PROJ) return true;
     for (int i = 0; i < n_layers; ++i) {
         const TfLayerF32& l = lay[i];
         if (!unfused) {
-            if (!launch_attention_exact(x3, qkv, att, B, L3, st)) return -1;                  // attention.hip, on the MFMA
-            if (stop_after == CLM_TF_STAGE_ATTENTION(i)) return done();
+            if (!launch_attention_exact(x3, qkv, att, B, L3, st)) return false;                 // attention.hip, on the MFMA
+            if (stop_after == CLM_TF_STAGE_ATTENTION(i)) return true;
             const bool more = i + 1 < n_layers;
             launch_enc32(att, h, pk.mat[i][1].get(), pk.mat[i][2].get(), pk.mat[i][3].get(), more ? pk.mat[i + 1][0].get() : nullptr, l.b_out,
                          l.b_ff1, l.b_ff2, more ? lay[i + 1].b_in : nullptr, l.ln1_g, l.ln1_b, l.ln2_g, l.ln2_b, qkv, M, 1e-5f, st, x3);
-            if (stop_after == CLM_TF_STAGE_LAYER(i)) return done();
+            if (stop_after == CLM_TF_STAGE_LAYER(i)) return true;
             continue;
         }
         gemm<false, false>(h, D, l.w[0], l.b_in, nullptr, qkv, 768, M, 768, D, 0, st);
@@ -251,7 +251,7 @@ int tf32_forward(const unsigned char* ids8, int ids_stride, int B, int L, int n_
         gemm<false, false>(u, 1024, l.w[3], l.b_ff2, h, t, D, M, D, 1024, 0, st);
         hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, t, (const float*)nullptr, l.ln2_g, l.ln2_b, h, M, 1, 1e-5f);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return true;
 }
 
 }  // namespace clm

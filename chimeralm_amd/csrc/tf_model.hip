@@ -26,6 +26,7 @@
 
 #include "chimeralm_hip.h"
 #include "gemm16_common.h"
+#include "handle_host.h"
 
 namespace clm {
 namespace tf {
@@ -467,49 +468,38 @@ struct clm_tf_handle {
     DevBuf ids8;
     DevBuf x1, x2, x3, hx, qkv, att;              // 16-bit activations
     DevBuf h, scores, pooled;                     // fp32; pooled [B][256] scales with B alone
-    bool referee = false;                         // inside clm_tf_selfcheck's second pass: an fp16x3 handle runs its exact-fp32 kernels
     bool arith_x3 = false;                        // CLM_PREC_F16X3: prec is PREC_F32, the fused fp32-path kernels run on hi + lo halfs
     bool unfused_fp32 = false;                    // CLM_DEBUG=unfused_fp32 at creation: the separate fp32 launches of round 2 (tests cross-check the fused kernels)
     DevBuf ws32;                                  // fp32 mode: activations of tf_fp32.hip
-    int last_B = 0, last_L3 = 0;
-    // clm_tf_debug_stop_after (tests): a forward returns right after the launch of this CLM_TF_STAGE_* (< 0: the whole forward).
-    // What the last forward was -- its length, its path, where it stopped -- decides which clm_tf_debug_fetch names it produced.
-    int stop_after = -1;
-    int last_L = 0, last_stop = -1;
-    bool last_path32 = false;
-    // clm_tf_set_fallback (as clm_set_fallback): 0 = the handle's mode; 1 = the next arithmetic inside the gate (16-bit handle: the
-    // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
-    int fallback = 0;
+    // How forwards run right now, read by plan_tf alone; clm_tf_selfcheck changes it for a scope (RunScope)
+    struct RunMode {
+        // clm_tf_set_fallback (as clm_set_fallback): 0 = the handle's mode; 1 = the next arithmetic inside the gate (16-bit handle: the
+        // fp32-path kernels on hi + lo halfs = fp16x3; fp16x3 handle: exact fp32); 2 = exact fp32 (the raw fp32 tensors stay loaded)
+        int fallback = 0;
+        bool referee = false;                     // inside clm_tf_selfcheck's second pass: exact fp32, whatever the mode or fall-back level
+        bool prof = false;                        // clm_tf_profile_enable: StageTimer records its spans
+        // clm_tf_debug_stop_after (tests): a forward returns right after the launch of this CLM_TF_STAGE_* (< 0: the whole forward)
+        int stop_after = -1;
+    } run;
+    // Everything a forward of B reads of L tokens decides, each decision once (plan_tf); `last`: the plan of the last forward, which
+    // says what clm_tf_debug_fetch may hand out (B = 0: none yet)
+    struct Plan {
+        int B, L, L3, Lp;                         // L3 = L / 8 positions behind the stem, Lp = the row pitch of ids8
+        size_t M, es;                             // M = B * L3 rows; bytes per element of the path's activations
+        int prec;                                 // PREC_* of the kernels that run: the handle's 16-bit mode, or PREC_F32
+        bool path32, x3, unfused;                 // the fp32-path kernels; ... on hi + lo halfs (fp16x3); ... as CLM_DEBUG=unfused_fp32's separate launches
+        int stop;                                 // the CLM_TF_STAGE_* the forward ends behind (< 0: none)
+    } last = {};
     bool have_x3 = false;                         // pk_x3 is filled (fp16x3 and 16-bit handles, fused kernels only)
     float x3_wmax = 0.f;                          // largest |w| they hold (NaN if any is NaN): from X3_WEIGHT_LIMIT on, exact fp32 instead
     DevBuf sc_logits;                             // clm_tf_selfcheck: [2][B][2] fp32 logits of the two forwards
     // profiling taps (clm_tf_profile_*): HIP events on the launch stream around each stage, stages: 0 conv stack + pe/LN,
     // 1 attention, 2 encoder layer kernel (out_proj + LN1 + FFN + LN2 + next QKV; the unfused pieces count here too), 3 pooling head
-    bool prof = false;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> recs;
-    double prof_ms[4] = {};
-    int64_t prof_n[4] = {};
+    StageProfile<4> profile;
 };
+using TfPlan = clm_tf_handle::Plan;
 
 namespace {
-
-struct TfTimer {                                   // RAII: one event pair per stage span when profiling is on
-    clm_tf_handle* h;
-    hipStream_t st;
-    int stage;
-    hipEvent_t e0{}, e1{};
-    bool on;
-    TfTimer(clm_tf_handle* h_, hipStream_t st_, int stage_) : h(h_), st(st_), stage(stage_), on(h_->prof && h_->recs.size() < 100000) {
-        if (!on) return;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(e0, st);
-    }
-    ~TfTimer() {
-        if (!on) return;
-        (void)hipEventRecord(e1, st);
-        h->recs.push_back({stage, {e0, e1}});
-    }
-};
 
 // clm_tf_create: the state-dict keys of an n_layers-deep net, their shapes and the field of h->net / h->lay each resolves into
 void tf_expect(clm_tf_handle* h) {
@@ -543,58 +533,73 @@ void tf_pool_head(clm_tf_handle* h, int B, int L3, float* logits, hipStream_t st
                        n.cls3_b, h->scores.get<float>(), h->pooled.get<float>(), logits, L3);
 }
 
-// what clm_tf_debug_fetch may hand out after this forward
-void tf_note(clm_tf_handle* h, int B, int L, bool path32, int stop) {
-    h->last_B = B; h->last_L = L; h->last_L3 = L / 8;
-    h->last_path32 = path32; h->last_stop = stop;
+// How a forward of B reads of L tokens runs on this handle right now: every decision once and under one name.  tf_run, the
+// effective precision and (through h->last) the debug fetch read these fields; none looks at the handle's flags again.
+TfPlan plan_tf(const clm_tf_handle* h, int B, int L) {
+    TfPlan p{};
+    const clm_tf_handle::RunMode& r = h->run;
+    p.B = B; p.L = L; p.L3 = L / 8;
+    p.Lp = (L + 63) / 64 * 64;
+    p.M = (size_t)B * p.L3;
+    // the fp32-path kernels: an fp32 / fp16x3 handle's own, a 16-bit handle's fall-back, the referee pass of a self-check
+    p.path32 = h->prec == PREC_F32 || r.fallback > 0 || r.referee;
+    // ... on hi + lo halfs: an fp16x3 handle unless told to fall back, a 16-bit handle at fall-back level 1.  Never as referee, and
+    // exact fp32 instead where the weights are beyond the packing's range
+    p.x3 = p.path32 && !r.referee && h->have_x3 && h->x3_wmax < X3_WEIGHT_LIMIT && (h->arith_x3 ? r.fallback == 0 : r.fallback < 2);
+    p.unfused = p.path32 && h->unfused_fp32;
+    p.prec = p.path32 ? (int)PREC_F32 : h->prec;
+    p.es = p.path32 ? 4 : 2;
+    p.stop = r.stop_after;
+    return p;
 }
 
+// The launches of the handle's 16-bit mode.  false: the attention refused the shape and nothing behind it was launched; the launch
+// error is the caller's to read.
 template <int PREC>
-int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t stride, int B, int L, float* logits, hipStream_t st) {
+bool tf_forward_t(clm_tf_handle* h, const TfPlan& p, const void* ids, int ids_dtype, int64_t stride, float* logits, hipStream_t st) {
     using elem = typename CT<PREC>::elem;
-    const int L1 = L / 2, L2 = L1 / 2, L3 = L2 / 2, Lp = (L + 63) / 64 * 64;
-    const size_t M = (size_t)B * L3;
+    const int B = p.B, L = p.L, L1 = L / 2, L2 = L1 / 2, L3 = p.L3, Lp = p.Lp;
+    const size_t M = p.M;
     const TfNetF32& n = h->net;
     const TfPacking& pk = h->pk_mode;
-    const int stop = h->stop_after;                            // (< 0: never equal to a stage)
-    auto done = [] { return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP; };
+    const int stop = p.stop;                                   // (< 0: never equal to a stage)
     {
-        TfTimer t(h, st, 0);
+        StageTimer t(h, st, 0);
         launch_embed(ids, ids_dtype, stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);   // ids of any dtype -> clamped uint8
-        if (stop == CLM_TF_STAGE_EMBED) return done();         // (this path has no embedding launch: the first convolution reads the ids)
+        if (stop == CLM_TF_STAGE_EMBED) return true;          // (this path has no embedding launch: the first convolution reads the ids)
         constexpr size_t conv_lds = (size_t)(130 * RS16 + 8 * 64 * tf::ZRS) * 2;
         constexpr auto k1 = tf::conv3_relu_pool_kernel<PREC, true>;
         constexpr auto k2 = tf::conv3_relu_pool_kernel<PREC, false>;
         launch_lds<k1>(dim3((2 * L1 + 127) / 128, B), dim3(512), conv_lds, st, h->ids8.get<unsigned char>(), Lp, n.emb,
                        (const elem*)nullptr, pk.conv[0].get(), n.conv_b[0], h->x1.get<elem>(), L, L1);
-        if (stop == CLM_TF_STAGE_CONV1) return done();
+        if (stop == CLM_TF_STAGE_CONV1) return true;
         launch_lds<k2>(dim3((2 * L2 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
                        (const float*)nullptr, h->x1.get<const elem>(), pk.conv[1].get(), n.conv_b[1], h->x2.get<elem>(), L1, L2);
-        if (stop == CLM_TF_STAGE_CONV2) return done();
+        if (stop == CLM_TF_STAGE_CONV2) return true;
         launch_lds<k2>(dim3((2 * L3 + 127) / 128, B), dim3(512), conv_lds, st, (const unsigned char*)nullptr, 0,
                        (const float*)nullptr, h->x2.get<const elem>(), pk.conv[2].get(), n.conv_b[2], h->x3.get<elem>(), L2, L3);
-        if (stop == CLM_TF_STAGE_CONV3) return done();
+        if (stop == CLM_TF_STAGE_CONV3) return true;
         hipLaunchKernelGGL(tf::pe_ln_kernel<PREC>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, h->x3.get<const elem>(), n.pe, n.norm_g,
                            n.norm_b, h->h.get<float>(), h->hx.get<elem>(), M, L3, 1e-5f);
-        if (stop == CLM_TF_STAGE_PE_LN) return done();
+        if (stop == CLM_TF_STAGE_PE_LN) return true;
     }
     for (int i = 0; i < h->n_layers; ++i) {
         const TfLayerF32& l = h->lay[i];
         const std::array<DevBuf, 4>& m = pk.mat[i];
         if (i == 0) {   // later layers: computed at the end of the previous layer's feed-forward kernel
-            TfTimer t(h, st, 2);
+            StageTimer t(h, st, 2);
             const tf::LinArgs a{h->hx.get(), m[0].get(), l.b_in, h->qkv.get(), M, 0};
             constexpr size_t lds = (size_t)(128 * RS16 + 8 * 128 * tf::ZRS) * 2;
             launch_lds<tf::linear16_kernel<PREC, tf::E_ACT, D, tf::TQKV>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, a);
-            if (stop == CLM_TF_STAGE_IN_PROJ) return done();
+            if (stop == CLM_TF_STAGE_IN_PROJ) return true;
         }
         {
-            TfTimer t(h, st, 1);
+            StageTimer t(h, st, 1);
             if (!launch_attention_fwd(PREC, h->qkv.get(), h->att.get(), B, L3, st, PREC == PREC_F16C))   // fp16c: hi and lo planes (attention.hip)
-                return CLM_E_INVALID;
-            if (stop == CLM_TF_STAGE_ATTENTION(i)) return done();
+                return false;
+            if (stop == CLM_TF_STAGE_ATTENTION(i)) return true;
         }
-        TfTimer tl(h, st, 2);
+        StageTimer tl(h, st, 2);
         // the rest of the layer -- out_proj + LN1 at its head -- and the next layer's in_proj: one kernel
         const bool more = i + 1 < h->n_layers;
         const tf::FfnArgs f{h->hx.get(), m[2].get(), m[3].get(), l.b_ff1, l.b_ff2, l.ln2_g, l.ln2_b, h->h.get<float>(), h->hx.get(), M, 1e-5f,
@@ -602,13 +607,13 @@ int tf_forward_t(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t strid
                             h->att.get(), m[1].get(), l.b_out, l.ln1_g, l.ln1_b};
         constexpr size_t lds = (size_t)2 * 128 * RS16 * 2 + (size_t)2 * 16 * 128 * 4;
         launch_lds<tf::enc_ffn16_kernel<PREC>>(dim3((unsigned)((M + 127) / 128)), dim3(512), lds, st, f);
-        if (stop == CLM_TF_STAGE_LAYER(i)) return done();
+        if (stop == CLM_TF_STAGE_LAYER(i)) return true;
     }
     {
-        TfTimer t(h, st, 3);
+        StageTimer t(h, st, 3);
         tf_pool_head(h, B, L3, logits, st);
     }
-    return hipGetLastError() == hipSuccess ? CLM_OK : CLM_E_HIP;
+    return true;
 }
 
 }  // namespace
@@ -705,71 +710,39 @@ int clm_tf_finalize(clm_tf_handle* h) {
     return CLM_OK;
 }
 
-static bool tf_fp32_path_is_x3(const clm_tf_handle* h) {
-    if (h->referee || !h->have_x3 || !(h->x3_wmax < X3_WEIGHT_LIMIT)) return false;   // (weights beyond the packing's range: exact fp32)
-    return h->arith_x3 ? h->fallback == 0 : h->fallback < 2;
-}
-
-// One forward in the arithmetic `prec32 ? the fp32 path (exact, or fp16x3: tf_fp32_path_is_x3) : the handle's 16-bit mode` (workspaces of BOTH kinds may be live: the
-// self-check runs one after the other on the same ids).
-static int tf_run(clm_tf_handle* h, bool prec32, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L,
-                  float* logits_out, hipStream_t st) {
-    const int L3 = L / 8;
-    const size_t M = (size_t)B * L3, tok = (size_t)B * ((L + 63) / 64 * 64);
-    if (tok > h->ids8.bytes() || M * D * 4 > h->h.bytes() || M * 4 > h->scores.bytes()) {   // shared pieces: ids, residual stream, pooling scores
-        HIPCHK(h, hipDeviceSynchronize());
-        for (DevBuf* b : {&h->ids8, &h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att, &h->h, &h->scores, &h->pooled, &h->ws32})
-            b->reset();                                        // (the whole workspace: what is regrown below follows this shape)
-        HIPCHK(h, h->ids8.alloc(tok));
-        HIPCHK(h, h->h.alloc(M * D * 4));
-        HIPCHK(h, h->scores.alloc(M * 4));
+// One forward as `p` plans it (workspaces of BOTH paths may be live on one handle: the self-check runs one after the other on the
+// same ids).  Every buffer the path takes grows on its own: a handle holds the per-buffer maxima of the shapes it has seen.
+static int tf_run(clm_tf_handle* h, const TfPlan& p, const void* ids, int ids_dtype, int64_t ids_row_stride, float* logits_out, hipStream_t st) {
+    const size_t B = (size_t)p.B, L = (size_t)p.L, M = p.M;
+    const size_t e16 = p.path32 ? 0 : 2;                       // the 16-bit activations: none on the fp32 path
+    if (int rc = grow(h, Sync::Device(), {{&h->ids8, B * p.Lp}, {&h->h, M * D * 4}, {&h->scores, M * 4}, {&h->pooled, B * D * 4},
+                                          {&h->ws32, p.path32 ? tf32_workspace_floats(p.B, p.L) * 4 : 0},
+                                          {&h->x1, B * (L / 2) * D * e16}, {&h->x2, B * (L / 4) * D * e16}, {&h->x3, M * D * e16},
+                                          {&h->hx, M * D * e16}, {&h->qkv, M * tf::TQKV * e16},
+                                          {&h->att, M * D * e16 * (p.prec == PREC_F16C ? 2 : 1) /* hi + lo planes */}}))
+        return rc;
+    bool ran;
+    if (p.path32) {
+        launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8.get<unsigned char>(), p.B, p.L, p.Lp, st);
+        ran = tf32_forward(h->ids8.get<unsigned char>(), p.Lp, p.B, p.L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), h->net,
+                           h->lay.data(), p.x3 ? h->pk_x3 : h->pk_t32, st, p.unfused, p.x3, p.stop);
+        if (ran && p.stop < 0) tf_pool_head(h, p.B, p.L3, logits_out, st);   // (stopped: nothing behind that launch, the pooling head included)
+    } else {
+        ran = p.prec == PREC_BF16   ? tf_forward_t<PREC_BF16>(h, p, ids, ids_dtype, ids_row_stride, logits_out, st)
+              : p.prec == PREC_F16C ? tf_forward_t<PREC_F16C>(h, p, ids, ids_dtype, ids_row_stride, logits_out, st)
+                                    : tf_forward_t<PREC_F16>(h, p, ids, ids_dtype, ids_row_stride, logits_out, st);
     }
-    if ((size_t)B * D * 4 > h->pooled.bytes()) {               // pooled [B][256] on its own -- a batch of MORE, SHORTER reads fits the
-        HIPCHK(h, hipDeviceSynchronize());                     // shared pieces and must still regrow this one
-        HIPCHK(h, h->pooled.reserve((size_t)B * D * 4));
-    }
-    if (prec32) {
-        const size_t need = tf32_workspace_floats(B, L) * 4;
-        if (need > h->ws32.bytes()) {
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, h->ws32.reserve(need));
-        }
-        const int Lp = (L + 63) / 64 * 64;
-        launch_embed(ids, ids_dtype, ids_row_stride, nullptr, nullptr, h->ids8.get<unsigned char>(), B, L, Lp, st);
-        // hi + lo halfs on the fp32 path: an fp16x3 handle unless told to fall back; a 16-bit handle at fall-back level 1
-        const bool use_x3 = tf_fp32_path_is_x3(h);
-        if (tf32_forward(h->ids8.get<unsigned char>(), Lp, B, L, h->n_layers, h->ws32.get<float>(), h->h.get<float>(), h->net, h->lay.data(),
-                         use_x3 ? h->pk_x3 : h->pk_t32, st, h->unfused_fp32, use_x3, h->stop_after))
-            return fail(h, CLM_E_HIP, std::string("clm_tf_forward (fp32): ") + hipGetErrorString(hipGetLastError()));
-        tf_note(h, B, L, true, h->stop_after);
-        if (h->stop_after >= 0) return CLM_OK;                 // stopped: nothing behind that launch, the pooling head included
-        tf_pool_head(h, B, L3, logits_out, st);
-        return hipGetLastError() == hipSuccess ? CLM_OK : fail(h, CLM_E_HIP, "clm_tf_forward (fp32): launch failed");
-    }
-    {   // the 16-bit activations, each buffer grown on its own (x1 / x2 scale with B * (L / 2), B * (L / 4), not with M)
-        const size_t need[6] = {(size_t)B * (L / 2) * D * 2, (size_t)B * (L / 4) * D * 2, M * D * 2, M * D * 2, M * tf::TQKV * 2,
-                                M * D * 2 * (h->prec == PREC_F16C ? 2 : 1) /* hi + lo planes */};
-        DevBuf* buf[6] = {&h->x1, &h->x2, &h->x3, &h->hx, &h->qkv, &h->att};
-        bool grow = false;
-        for (int i = 0; i < 6; ++i) grow |= need[i] > buf[i]->bytes();
-        if (grow) {
-            HIPCHK(h, hipDeviceSynchronize());
-            for (int i = 0; i < 6; ++i) HIPCHK(h, buf[i]->reserve(need[i]));
-        }
-    }
-    const int rc = h->prec == PREC_BF16   ? tf_forward_t<PREC_BF16>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st)
-                   : h->prec == PREC_F16C ? tf_forward_t<PREC_F16C>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st)
-                                          : tf_forward_t<PREC_F16>(h, ids, ids_dtype, ids_row_stride, B, L, logits_out, st);
-    if (rc) return fail(h, rc, std::string("clm_tf_forward: ") + hipGetErrorString(hipGetLastError()));
-    tf_note(h, B, L, false, h->stop_after);
+    if (!ran)
+        return fail(h, CLM_E_INVALID, "clm_tf_forward: the attention refused " + std::to_string(p.B) + " reads of " + std::to_string(p.L3) +
+                                          " positions: more workgroups than a grid takes");
+    if (int rc = launched(h, p.path32 ? "clm_tf_forward (fp32)" : "clm_tf_forward")) return rc;
+    h->last = p;                                               // what clm_tf_debug_fetch may hand out after this forward
     return CLM_OK;
 }
 
-static int tf_check_args(clm_tf_handle* h, const char* who, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L) {
+static int tf_check_args(clm_tf_handle* h, const char* who, const void* ids, const void* out, int ids_dtype, int64_t ids_row_stride, int B, int L) {
     if (!h->finalized) return fail(h, CLM_E_STATE, std::string(who) + " before clm_tf_finalize");
-    if (!ids || B < 1 || L < 8 || ids_row_stride < L) return fail(h, CLM_E_INVALID, std::string(who) + ": bad argument (L >= 8)");
-    if (ids_dtype != CLM_DT_I64 && ids_dtype != CLM_DT_I32 && ids_dtype != CLM_DT_U8)
-        return fail(h, CLM_E_INVALID, std::string(who) + ": ids dtype must be i64, i32 or u8");
+    if (int rc = check_ids_arg(h, who, ids, out, ids_dtype, ids_row_stride, B, L, 8)) return rc;   // (three max-pools of 2)
     if (L / 8 > h->max_len)
         return fail(h, CLM_E_INVALID, std::string(who) + ": Sequence too long (" + std::to_string(L / 8) + " > max_len of pos_encoder.pe)");
     return CLM_OK;
@@ -778,11 +751,9 @@ static int tf_check_args(clm_tf_handle* h, const char* who, const void* ids, int
 int clm_tf_forward(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, float* logits_out,
                    void* stream) {
     if (!h) return CLM_E_INVALID;
-    if (!logits_out) return fail(h, CLM_E_INVALID, "clm_tf_forward: bad argument (L >= 8)");
-    if (int rc = tf_check_args(h, "clm_tf_forward", ids, ids_dtype, ids_row_stride, B, L)) return rc;
+    if (int rc = tf_check_args(h, "clm_tf_forward", ids, logits_out, ids_dtype, ids_row_stride, B, L)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    return tf_run(h, h->prec == PREC_F32 || h->fallback > 0, ids, ids_dtype, ids_row_stride, B, L, logits_out,
-                  reinterpret_cast<hipStream_t>(stream));
+    return tf_run(h, plan_tf(h, B, L), ids, ids_dtype, ids_row_stride, logits_out, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The handle's 16-bit mode on trial against the exact-fp32 kernels of the same handle, on the caller's ids (chimeralm_hip.h;
@@ -790,35 +761,25 @@ int clm_tf_forward(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids
 int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t ids_row_stride, int B, int L, void* stream,
                      float* max_abs_diff_out, int* labels_differ_out) {
     if (!h) return CLM_E_INVALID;
-    if (int rc = tf_check_args(h, "clm_tf_selfcheck", ids, ids_dtype, ids_row_stride, B, L)) return rc;
+    if (int rc = tf_check_args(h, "clm_tf_selfcheck", ids, h, ids_dtype, ids_row_stride, B, L)) return rc;   // (both outputs are optional)
     if (B > 4096) return fail(h, CLM_E_INVALID, "clm_tf_selfcheck: at most 4096 reads per call");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float diff = 0.f;
     int differ = 0;
     if (h->prec != PREC_F32 || h->arith_x3) {                  // (an fp16x3 handle: its own exact-fp32 kernels are the referee)
-        if ((size_t)2 * B * NCLS * 4 > h->sc_logits.bytes()) {
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, h->sc_logits.reserve((size_t)2 * B * NCLS * 4));
+        if (int rc = grow(h, Sync::Device(), {{&h->sc_logits, (size_t)2 * B * NCLS * 4}})) return rc;
+        float* const pair = h->sc_logits.get<float>();
+        {
+            RunScope<clm_tf_handle> scope(h);
+            h->run.fallback = 0;                               // the MODE is on trial, whatever clm_tf_set_fallback says
+            h->run.stop_after = -1;                            // ... on whole forwards, whatever clm_tf_debug_stop_after says
+            for (int pass = 0; pass < 2; ++pass) {             // pass 0: the handle's mode; pass 1: exact fp32
+                h->run.referee = pass == 1;
+                if (int rc = tf_run(h, plan_tf(h, B, L), ids, ids_dtype, ids_row_stride, pair + (size_t)pass * B * NCLS, st)) return rc;
+            }
         }
-        float* lm = h->sc_logits.get<float>();
-        float* lx = lm + (size_t)B * NCLS;
-        const int fallback = h->fallback, stop = h->stop_after;
-        h->fallback = 0;                                       // the MODE is on trial, whatever clm_tf_set_fallback says
-        h->stop_after = -1;                                    // ... on whole forwards, whatever clm_tf_debug_stop_after says
-        const int rc1 = tf_run(h, h->arith_x3, ids, ids_dtype, ids_row_stride, B, L, lm, st);
-        h->fallback = fallback;
-        if (rc1) { h->stop_after = stop; return rc1; }
-        h->referee = true;
-        const int rc2 = tf_run(h, true, ids, ids_dtype, ids_row_stride, B, L, lx, st);
-        h->referee = false;
-        h->stop_after = stop;
-        if (rc2) return rc2;
-        std::vector<float> a((size_t)B * NCLS), b((size_t)B * NCLS);
-        HIPCHK(h, hipMemcpyAsync(a.data(), lm, a.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(b.data(), lx, b.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        (void)clm_logit_deviation(a.data(), b.data(), B, NCLS, &diff, &differ);   // (shared with clm_selfcheck: a non-finite logit is sticky +inf)
+        if (int rc = logits_deviation(h, st, pair, B, &diff, &differ)) return rc;
     }
     if (max_abs_diff_out) *max_abs_diff_out = diff;
     if (labels_differ_out) *labels_differ_out = differ;
@@ -828,15 +789,15 @@ int clm_tf_selfcheck(clm_tf_handle* h, const void* ids, int ids_dtype, int64_t i
 int clm_tf_set_fallback(clm_tf_handle* h, int on) {
     if (!h) return CLM_E_INVALID;
     if (on < 0 || on > 2) return fail(h, CLM_E_INVALID, "clm_tf_set_fallback: level must be 0, 1 or 2");
-    h->fallback = (h->prec == PREC_F32 && !h->arith_x3) ? 0 : on;
+    h->run.fallback = (h->prec == PREC_F32 && !h->arith_x3) ? 0 : on;
     return CLM_OK;
 }
 
 int clm_tf_effective_precision(const clm_tf_handle* h) {
     if (!h) return CLM_E_INVALID;
     if (!h->finalized) return CLM_E_STATE;
-    if (h->prec != PREC_F32 && h->fallback == 0) return h->prec;
-    return tf_fp32_path_is_x3(h) ? CLM_PREC_F16X3 : CLM_PREC_F32;
+    const TfPlan p = plan_tf(h, 1, 8);                         // (the arithmetic does not depend on the shape)
+    return p.x3 ? CLM_PREC_F16X3 : p.prec;
 }
 
 int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_t bytes) {
@@ -844,18 +805,18 @@ int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     const std::string n(name);
-    const size_t B = (size_t)h->last_B, M = B * h->last_L3;
-    const int L = h->last_L, s = h->last_stop;
-    const bool p32 = h->last_path32;
-    const bool fused32 = p32 && !h->unfused_fp32;              // the exact path's names below describe the fused launches' workspace
-    const size_t es = p32 ? 4 : 2;                             // bytes per element of the path's activations
-    auto ran = [&](int stage) { return h->last_B > 0 && (s < 0 || s >= stage); };   // the last forward launched `stage`
+    const TfPlan& p = h->last;                                 // the last forward: its shape, its path, where it stopped
+    const size_t B = (size_t)p.B, M = p.M, es = p.es;
+    const int L = p.L, s = p.stop;
+    const bool p32 = p.path32;
+    const bool fused32 = p32 && !p.unfused;                    // the exact path's names below describe the fused launches' workspace
+    auto ran = [&](int stage) { return p.B > 0 && (s < 0 || s >= stage); };   // the last forward launched `stage`
     const void* src = nullptr;
     size_t have = 0;
     bool produced = true;
     if (n == "hidden") { src = h->h.get(); have = M * D * 4; produced = ran(CLM_TF_STAGE_PE_LN); }
-    else if (n == "scores") { src = h->scores.get(); have = M * 4; produced = h->last_B > 0 && s < 0; }
-    else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; produced = h->last_B > 0 && s < 0; }
+    else if (n == "scores") { src = h->scores.get(); have = M * 4; produced = p.B > 0 && s < 0; }
+    else if (n == "pooled") { src = h->pooled.get(); have = B * D * 4; produced = p.B > 0 && s < 0; }
     else if (n == "x0") {       // exact path: the embedding rows, gone once the second convolution has written over them
         src = h->ws32.get(); have = B * L * D * 4; produced = fused32 && (s == CLM_TF_STAGE_EMBED || s == CLM_TF_STAGE_CONV1);
     } else if (n == "x1") {     // exact path: the other half of the ping-pong, until the third convolution
@@ -871,25 +832,23 @@ int clm_tf_debug_fetch(clm_tf_handle* h, const char* name, void* host_out, size_
         produced = (fused32 || !p32) && ran(CLM_TF_STAGE_IN_PROJ);
     } else if (n == "att") {    // fp16c: both planes
         src = p32 ? (const void*)(h->ws32.get<float>() + (size_t)2 * B * L * D + M * tf::TQKV) : h->att.get();
-        have = M * D * es * (!p32 && h->prec == PREC_F16C ? 2 : 1); produced = (fused32 || !p32) && ran(CLM_TF_STAGE_ATTENTION(0));
+        have = M * D * es * (p.prec == PREC_F16C ? 2 : 1); produced = (fused32 || !p32) && ran(CLM_TF_STAGE_ATTENTION(0));
     } else return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: unknown name " + n);
     if (!produced) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: the last forward did not produce (or has overwritten) " + n);
-    if (bytes > have) return fail(h, CLM_E_INVALID, "clm_tf_debug_fetch: more bytes requested than the last forward produced");
-    HIPCHK(h, hipMemcpy(host_out, src, bytes, hipMemcpyDeviceToHost));
-    return CLM_OK;
+    return fetch_bytes(h, "clm_tf_debug_fetch", n, src, have, host_out, bytes);
 }
 
 int clm_tf_debug_stop_after(clm_tf_handle* h, int stage) {
     if (!h) return CLM_E_INVALID;
     if (stage >= 0 && h->unfused_fp32) return fail(h, CLM_E_UNSUPPORTED, "clm_tf_debug_stop_after: the fused launches only (CLM_DEBUG=unfused_fp32 is set)");
     if (stage > CLM_TF_STAGE_LAYER(h->n_layers - 1)) return fail(h, CLM_E_INVALID, "clm_tf_debug_stop_after: no such stage in this net");
-    h->stop_after = stage < 0 ? -1 : stage;
+    h->run.stop_after = stage < 0 ? -1 : stage;
     return CLM_OK;
 }
 
 int clm_tf_profile_enable(clm_tf_handle* h, int on) {
     if (!h) return CLM_E_INVALID;
-    h->prof = on != 0;
+    h->run.prof = on != 0;
     return CLM_OK;
 }
 
@@ -897,33 +856,12 @@ int clm_tf_profile_read(clm_tf_handle* h, double* ms_out /*[4]*/, int64_t* spans
     if (!h) return CLM_E_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
-    for (auto& r : h->recs) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.second.first, r.second.second) == hipSuccess) {
-            h->prof_ms[r.first] += ms;
-            h->prof_n[r.first] += 1;
-        }
-        (void)hipEventDestroy(r.second.first);
-        (void)hipEventDestroy(r.second.second);
-    }
-    h->recs.clear();
-    for (int i = 0; i < 4; ++i) {
-        if (ms_out) ms_out[i] = h->prof_ms[i];
-        if (spans_out) spans_out[i] = h->prof_n[i];
-        if (reset) h->prof_ms[i] = 0, h->prof_n[i] = 0;
-    }
+    h->profile.read(ms_out, spans_out, reset != 0);
     return CLM_OK;
 }
 
 const char* clm_tf_last_error(const clm_tf_handle* h) { return h ? h->err.c_str() : create_error<clm_tf_handle>().c_str(); }
 
-int clm_tf_destroy(clm_tf_handle* h) {
-    if (!h) return CLM_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    for (auto& r : h->recs) { (void)hipEventDestroy(r.second.first); (void)hipEventDestroy(r.second.second); }
-    delete h;                                                  // (its device buffers free themselves)
-    return CLM_OK;
-}
+int clm_tf_destroy(clm_tf_handle* h) { return destroy_handle(h); }
 
 }  // extern "C"

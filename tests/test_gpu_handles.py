@@ -1,11 +1,12 @@
-"""Lifecycle of the three engine handles (clm_*, clm_tf_*, clm_cnn_*): create, load, forwards whose second shape regrows the
-workspace, close -- three times over.  Every device buffer a handle owns must go with it (free device memory after cycle 3 within
-128 MiB of cycle 1), and a fresh handle on the same weights must compute the same bits."""
+"""Lifecycle of the four engine handles (clm_*, clm_tf_*, clm_cnn_*, clm_mamba_*): create, load, forwards whose second shape
+regrows the workspace, close -- three times over.  Every device buffer a handle owns must go with it (free device memory after
+cycle 3 within 128 MiB of cycle 1), and a fresh handle on the same weights must compute the same bits."""
 import numpy as np
 import pytest
 import torch
 
 import cnn_reference as cr
+import mamba_reference as mr
 from oracle import hyena_oracle as ho
 from oracle import transformer_oracle as to
 
@@ -89,6 +90,25 @@ def test_cnn_lifecycle(built_lib):
     def cycle():
         net = DNAConvNet(vocab_size=12, embedding_dim=256, num_filters=[256, 256, 256], kernel_sizes=[7, 7, 7], pool_sizes=[4, 4, 4],
                          hidden_dim=512, number_of_classes=2, dropout=0.1, precision="fp16x3")
+        net.load_state_dict(sd, strict=True)
+        out = [net(short), net(long)]
+        torch.cuda.synchronize()
+        net.close()
+        return out
+
+    _three_cycles(cycle)
+
+
+def test_mamba_lifecycle(built_lib):
+    from chimeralm_amd.mamba import MambaSequenceClassificationSP
+
+    sd = mr.make_mamba_state_dict("mambasp", 5, n_layers=2, d_model=256)
+    short = torch.from_numpy(mr.synthetic_ids(1, 2, 300, 30)).cuda()
+    long = torch.from_numpy(mr.synthetic_ids(2, 4, 2100, 100)).cuda()
+
+    def cycle():
+        net = MambaSequenceClassificationSP(vocab_size=12, embedding_dim=256, number_of_layers=2, number_of_classes=2, dropout=0.2,
+                                            d_state=mr.VARIANTS["mambasp"][2], expand=mr.VARIANTS["mambasp"][3], precision="fp16x3")
         net.load_state_dict(sd, strict=True)
         out = [net(short), net(long)]
         torch.cuda.synchronize()

@@ -113,6 +113,63 @@ def test_more_shorter_reads_after_a_long_batch_regrow_the_pooled_buffer(built_li
     net.close()
 
 
+TWO_LAYERS = to.Config(max_len=512, num_encoder_layers=2)
+
+
+def _two_layers(sd, prec):
+    from chimeralm_amd.transformer import SequenceCNNTransformer
+
+    net = SequenceCNNTransformer(vocab_size=12, max_len=TWO_LAYERS.max_len, num_encoder_layers=2, precision=prec, selfcheck=False)
+    net.load_state_dict(sd, strict=True)
+    return net
+
+
+@pytest.mark.parametrize("prec", ["fp16c", "fp32", "fp16x3"])
+def test_workspace_follows_a_sequence_of_shapes(built_lib, prec):
+    """Every workspace buffer grows on its own and none is ever reset: 2 x 1000, 9 x 64, 1 x 2048, 2 x 1000 tokens on ONE handle,
+    each batch bit for bit what a fresh handle computes.  The family of the `pooled` overrun at its smallest sizes: 9 > 2 reads with
+    fewer tokens and rows than the first batch (only the per-read buffers regrow); 64 tokens are L3 = 8 positions, one tile;
+    1 x 2048 has about the tokens of 2 x 1000 in one read (every buffer regrows a little, next to `pooled`, which does not); the last
+    batch runs in buffers that are all larger than it needs."""
+    sd = to.make_state_dict(9, TWO_LAYERS, scale=1.0)
+    net = _two_layers(sd, prec)
+    for seed, (B, L) in enumerate([(2, 1000), (9, 64), (1, 2048), (2, 1000)]):
+        ids = torch.from_numpy(to.synthetic_ids(900 + seed, B, L, 3)).cuda()
+        got = net(ids).cpu()
+        fresh = _two_layers(sd, prec)
+        want = fresh(ids).cpu()
+        fresh.close()
+        assert torch.isfinite(want).all() and torch.equal(got, want), f"{prec}: batch {seed} ({B} x {L}) differs from a fresh handle's"
+    net.close()
+
+
+def test_run_mode_survives_a_selfcheck(built_lib):
+    """clm_tf_selfcheck runs whole forwards in the handle's mode and in exact fp32 whatever the fall-back level and the debug stop
+    say -- and leaves both as it found them: afterwards the handle still reports fp16x3 (fp16c at fall-back level 1), a forward
+    still ends behind pe_ln, and with the stop cleared it computes what a handle that never ran a self-check does."""
+    from chimeralm_amd import _native as N
+    from chimeralm_amd.transformer import TransformerEngineError
+
+    sd = to.make_state_dict(10, TWO_LAYERS, scale=1.0)
+    ids = torch.from_numpy(to.synthetic_ids(910, 2, 64, 0)).cuda()
+    net, plain = _two_layers(sd, "fp16c"), _two_layers(sd, "fp16c")
+    lib = N.load()
+    for m in (net, plain):
+        m(ids)                                                  # (creates the engine)
+        m._check(lib.clm_tf_set_fallback(m._h, 1))
+    net.debug_stop_after("pe_ln")
+    diff, differ = net._selfcheck_call(lib, ids)
+    assert np.isfinite(diff) and diff > 0                       # whole forwards of the MODE against exact fp32 ran
+    assert net._arith(lib) == "fp16x3"
+    net(ids)
+    with pytest.raises(TransformerEngineError, match="did not produce"):
+        net.debug_fetch("scores", (2, 8))
+    net.debug_stop_after(None)
+    assert torch.equal(net(ids).cpu(), plain(ids).cpu())
+    net.close()
+    plain.close()
+
+
 def test_arguments_and_errors(built_lib):
     from chimeralm_amd.transformer import SequenceCNNTransformer, TransformerEngineError
 

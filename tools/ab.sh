@@ -10,7 +10,7 @@ for i in 1 2 3; do
     python3 - <<PY
 import json
 d=json.loads([l for l in open("$R/gpurun_out/ab_$v.log") if l.startswith("{")][-1])
-print("$v", round(d["value"]), round(d["ms_per_step"],2), {k: round(x*d["ms_per_step"],2) for k,x in d["stage_ms_share"].items()})
+print("$v", round(d["value"]), round(d["ms_per_step"],2), {k: round(x*d["ms_per_step"],2) for k,x in d.get("stage_ms_share", {}).items()})   # (--net transformer reports no stages)
 PY
   done
 done
