@@ -6,6 +6,14 @@ the numpy restatement of the keep mask's `bits`, and the score patterns the GPU 
     p_ij = exp(s_ij - lse_i)           O_i = sum_j keep_ij p_ij v_j / (1 - p)
     delta_i = sum_d dO_id O_id         dP_ij = dO_i . v_j           dS_ij = p_ij (keep_ij dP_ij / (1 - p) - delta_i)
     dQ_i = sum_j dS_ij k_j / sqrt(32)  dK_j = sum_i dS_ij q_i / sqrt(32)      dV_j = sum_i keep_ij p_ij dO_i / (1 - p)
+
+dS = p (dP - delta) cancels, so a row of dq, dk or dv can be far smaller than its terms.  `backward` returns, next to each of them,
+the row's sum of the absolute terms per (read, head, position) -- `dq_abs`, `dk_abs`, `dv_abs` [B, 8, L], the largest of the 32
+components -- the denominator of the row-wise comparison (tests/grad_rows.py):
+    |dP|_ij = |dO_i| . |v_j|     |delta|_i = sum_d |dO_id| |O_id|     T_ij = p_ij (keep_ij |dP|_ij / (1 - p) + |delta|_i)
+    dq_abs_i = max_d sum_j T_ij |k_jd| / sqrt(32)    dk_abs_j = max_d sum_i T_ij |q_id| / sqrt(32)
+    dv_abs_j = max_d sum_i keep_ij p_ij |dO_id| / (1 - p)
+`DEFECTS` are wrong variants of the formulas, planted by tests/test_grad_rows_host.py into the float32 evaluation only.
 """
 from __future__ import annotations
 
@@ -16,6 +24,9 @@ import torch
 
 HD, NH, D = 32, 8, 256
 PATTERNS = ("normal", "large", "flat", "first_tile_max", "ragged_max")
+# delta_unscaled: delta_i = sum_j p_ij dP_ij, without keep / (1 - p) | phantom_key: one more key behind the last, s = 0 instead of
+# masked (k = v = 0), in the softmax's sum | skip_last_query_tile: the dk | dv pass leaves out the last (ragged) tile of 64 queries
+DEFECTS = ("delta_unscaled", "phantom_key", "skip_last_query_tile")
 
 
 # ------------------------------------------------------------------------------------------------------------- the keep mask
@@ -69,30 +80,44 @@ def rscale(p: float, dt) -> torch.Tensor:
     return one / (one - torch.tensor(p, dtype=torch.float32).to(dt))
 
 
-def forward(qkv: torch.Tensor, keep: torch.Tensor | None, p: float):
+def _with_zero_key(s: torch.Tensor) -> torch.Tensor:
+    """The scores with one more key of score 0 behind the last."""
+    return torch.cat([s, torch.zeros_like(s[..., :1])], dim=-1)
+
+
+def forward(qkv: torch.Tensor, keep: torch.Tensor | None, p: float, defect: str | None = None):
     """-> out [B, L, 256], lse [B, 8, L] (natural units), P [B, 8, L, L], in qkv's dtype.  keep: [B, 8, L, L] bool or None."""
     dt = qkv.dtype
     q, k, v = (heads(qkv[..., o: o + D]) for o in (0, D, 2 * D))
     s = (q @ k.transpose(-1, -2)) * torch.tensor(1.0 / math.sqrt(HD), dtype=dt)
-    lse = torch.logsumexp(s, dim=-1)
+    lse = torch.logsumexp(_with_zero_key(s) if defect == "phantom_key" else s, dim=-1)
     P = torch.exp(s - lse[..., None])
     Pd = P if keep is None else P * (keep.to(dt) * rscale(p, dt))
     return merge(Pd @ v), lse, P
 
 
-def backward(qkv: torch.Tensor, keep: torch.Tensor | None, p: float, dout: torch.Tensor):
-    """-> dict out, lse, dq, dk, dv ([B, L, 256] each but lse) by the hand formulas, in qkv's dtype."""
+def backward(qkv: torch.Tensor, keep: torch.Tensor | None, p: float, dout: torch.Tensor, defect: str | None = None):
+    """-> dict out, lse, dq, dk, dv ([B, L, 256] each but lse) by the hand formulas, in qkv's dtype, and dq_abs, dk_abs, dv_abs
+    [B, 8, L], the rows' sums of the absolute terms.  `defect`: one of DEFECTS, planted."""
     dt = qkv.dtype
     q, k, v = (heads(qkv[..., o: o + D]) for o in (0, D, 2 * D))
-    out, lse, P = forward(qkv, keep, p)
+    out, lse, P = forward(qkv, keep, p, defect)
     g = heads(dout)
     scale = torch.tensor(1.0, dtype=dt) if keep is None else keep.to(dt) * rscale(p, dt)
-    delta = (g * heads(out)).sum(dim=-1, keepdim=True)
     dP = g @ v.transpose(-1, -2)
+    delta = (P * dP).sum(dim=-1, keepdim=True) if defect == "delta_unscaled" else (g * heads(out)).sum(dim=-1, keepdim=True)
     dS = P * (scale * dP - delta)
     c = torch.tensor(1.0 / math.sqrt(HD), dtype=dt)
-    return {"out": out, "lse": lse, "dq": merge(dS @ k) * c, "dk": merge(dS.transpose(-1, -2) @ q) * c,
-            "dv": merge((P * scale).transpose(-1, -2) @ g)}
+    T = P * (scale * (g.abs() @ v.abs().transpose(-1, -2)) + (g.abs() * heads(out).abs()).sum(dim=-1, keepdim=True))
+    dSt, Pt = dS.transpose(-1, -2), (P * scale).transpose(-1, -2)
+    if defect == "skip_last_query_tile":
+        L = qkv.shape[1]
+        dSt, Pt = dSt.clone(), Pt.clone()
+        dSt[..., (L - 1) // 64 * 64:] = 0
+        Pt[..., (L - 1) // 64 * 64:] = 0
+    return {"out": out, "lse": lse, "dq": merge(dS @ k) * c, "dk": merge(dSt @ q) * c, "dv": merge(Pt @ g),
+            "dq_abs": ((T @ k.abs()) * c).amax(-1), "dk_abs": ((T.transpose(-1, -2) @ q.abs()) * c).amax(-1),
+            "dv_abs": ((P * scale).transpose(-1, -2) @ g.abs()).amax(-1)}
 
 
 def autograd(qkv: torch.Tensor, keep: torch.Tensor | None, p: float, dout: torch.Tensor):

@@ -5,7 +5,9 @@
   project's bound), with the denominators of the batch-reduced gradients (the sums of the absolute terms).
 * `circular_pairs`: the circular form at N >= 2 L - 2 with two READS packed as real / imaginary part, its three alias corrections and
   the `Re IFFT(X conj Y)` identity for dk.
-* `circular_mirror`: the form the kernels run -- two real sequences of ONE read packed, separated through the mirrored bin.
+* `circular_mirror`: the form the kernels run -- two real sequences of ONE read packed, separated through the mirrored bin -- with
+  the kernels' balancing of the two packed sequences, every output of the op, and `DEFECTS`: wrong variants planted by
+  tests/test_grad_rows_host.py into the float32 evaluation only.
 * `net_step`: one training step of the whole net in torch autograd over `hyena_oracle.backbone_forward` + `head_forward`.
 """
 from __future__ import annotations
@@ -17,6 +19,9 @@ from oracle import hyena_oracle as ho
 
 C = ho.D_MODEL
 CORE_GRADS = ("dzc", "dsw", "dsb", "dk", "dD")
+# no_alias: the three corrections at N == 2 L - 2 left out | unbalanced: the two sequences of a transform packed as they come |
+# short_tail: the transposed 3-tap filter reads du[L - 2] and du[L - 1] as 0
+DEFECTS = ("no_alias", "unbalanced", "short_tail")
 
 
 def logn_for(L: int) -> int:
@@ -168,29 +173,48 @@ def circular_pairs(zc, sw, sb, k, D, dy, n: int | None = None):
     return {"c": c, "dg": dg + D[None, :, None] * dc, "dk": dk}
 
 
+def _balance(a, b):
+    """csrc/hyena_train.hip hyena_train_balance per sequence pair: the power of two that brings b's sum of squares to a's."""
+    n1, n2 = a.pow(2).sum(-1, keepdim=True), b.pow(2).sum(-1, keepdim=True)
+    ok = (n1 > 0) & (n2 > 0) & torch.isfinite(n1) & torch.isfinite(n2)
+    one = torch.ones_like(n1)
+    sh = torch.div(torch.frexp(torch.where(ok, n1, one))[1] - torch.frexp(torch.where(ok, n2, one))[1], 2, rounding_mode="trunc")
+    return torch.ldexp(one, sh.clamp(-40, 40))
+
+
 def _split_spectra(Z):
     """A, B of Z = FFT(a + i b), a and b real: A[m] = (Z[m] + conj Z[n - m]) / 2, B[m] = (Z[m] - conj Z[n - m]) / 2i."""
     Zr = torch.roll(Z.flip(-1), 1, -1).conj()
     return (Z + Zr) / 2, (Z - Zr) / 2j
 
 
-def circular_mirror(zc, sw, sb, k, D, dy, n: int | None = None):
-    """The kernels' form: per read, c of two channels from one transform and (dg, dk of the read) from one transform of dc + i g."""
+def circular_mirror(zc, sw, sb, k, D, dy, n: int | None = None, defect: str | None = None):
+    """The kernels' form: per read, c of two channels from one transform and (dg, dk of the read) from one transform of dc + i g,
+    the imaginary sequence of each packing scaled by `_balance` (inputs in the time domain, product spectra by Parseval) and the dk
+    rows of the reads summed in read order.  Same keys as `hand_core`, without `den`.  `defect`: one of DEFECTS, planted."""
     L, ch = zc.shape[-1], zc.shape[1] // 3
     n = max(2 * L - 2, L) if n is None else n
-    alias = n == 2 * L - 2 and L > 1
-    u, _ = _short(zc, sw, sb)
+    alias = n == 2 * L - 2 and L > 1 and defect != "no_alias"
+    bal = (lambda a, b_: torch.ones_like(a[..., :1])) if defect == "unbalanced" else _balance
+    spec_norm = lambda S: (S.real ** 2 + S.imag ** 2)                              # noqa: E731
+    u, taps = _short(zc, sw, sb)
     x0, x1, v = u.split(ch, dim=1)
     g = v * x1
     K = _fftn(k, n)
-    A, Bs = _split_spectra(_fftn(torch.complex(g[:, 0::2], g[:, 1::2]), n))
-    r = torch.fft.ifft(A * K[0::2] + 1j * Bs * K[1::2])[..., :L]
+    rin = bal(g[:, 0::2], g[:, 1::2])
+    A, Bs = _split_spectra(_fftn(torch.complex(g[:, 0::2], g[:, 1::2] * rin), n))
+    S1, S2 = A * K[0::2], Bs * K[1::2]
+    rout = bal(spec_norm(S1).sqrt(), spec_norm(S2).sqrt())
+    r = torch.fft.ifft(S1 + 1j * S2 * rout)[..., :L]
     c = torch.zeros_like(g)
-    c[:, 0::2], c[:, 1::2] = r.real, r.imag
+    c[:, 0::2], c[:, 1::2] = r.real, r.imag / (rin * rout)
     dc = dy * x0
-    X, Y = _split_spectra(_fftn(torch.complex(dc, g), n))
-    r = torch.fft.ifft(X * K.conj() + 1j * X * Y.conj())[..., :L]
-    dg, dkr = r.real.clone(), r.imag.clone()
+    rin = bal(dc, g)
+    X, Y = _split_spectra(_fftn(torch.complex(dc, g * rin), n))
+    S1, S2 = X * K.conj(), X * Y.conj()
+    rout = bal(spec_norm(S1).sqrt(), spec_norm(S2).sqrt())
+    r = torch.fft.ifft(S1 + 1j * S2 * rout)[..., :L]
+    dg, dkr = r.real.clone(), r.imag / (rin * rout)
     if alias:
         c[..., 0] -= g[..., L - 1] * k[..., L - 1]
         dg[..., L - 1] -= dc[..., 0] * k[..., L - 1]
@@ -198,7 +222,14 @@ def circular_mirror(zc, sw, sb, k, D, dy, n: int | None = None):
     dk = torch.zeros_like(k)
     for b in range(zc.shape[0]):                                                   # read order
         dk = dk + dkr[b]
-    return {"c": c + D[None, :, None] * g, "dg": dg + D[None, :, None] * dc, "dk": dk}
+    c, dg = c + D[None, :, None] * g, dg + D[None, :, None] * dc
+    du = torch.cat([dy * c, dg * v, dg * x1], dim=1)
+    dup = F.pad(du, (0, 2))
+    if defect == "short_tail":
+        dup[..., L - 2:L] = 0
+    dzc = sum(sw[None, :, j, None] * dup[..., 2 - j:2 - j + L] for j in range(3))
+    return {"c": c, "y": c * x0, "dg": dg, "dzc": dzc, "dsw": (du[..., None] * taps).sum((0, 2)), "dsb": du.sum((0, 2)), "dk": dk,
+            "dD": (dc * g).sum((0, 2))}
 
 
 # ------------------------------------------------------------------------------------------------------------- the net

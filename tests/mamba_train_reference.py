@@ -6,7 +6,10 @@
   float32 on the CPU it gives the error those formulas have in the engine's number format, which sets the tests' bound.
 
 `dA_log`, `d dt_bias` and the `dt` columns of `dzxbcdt` are differences of large sums; `core_backward` returns, next to each of them,
-the sum of the absolute terms (`*_abs`): the size of what cancels, which is the denominator of their relative error.
+the sum of the absolute terms (`*_abs`): the size of what cancels, which is the denominator of their relative error.  The other
+batch-reduced gradients (`conv1d.weight`, `conv1d.bias`, `norm.weight`, `D`) carry theirs too, per channel or head, for the row-wise
+comparison (tests/grad_rows.py).  `DEFECTS` are wrong variants of the formulas, planted by tests/test_grad_rows_host.py into the
+float32 evaluation only.
 
 `net_forward` is the whole net (either variant) around `core_forward`, differentiable in every parameter, with the max-pool routed by
 a given argmax (`route`), so that a near-tie cannot turn a rounding difference into another gradient.
@@ -20,6 +23,11 @@ from mamba_reference import D_CONV, PAD, scan_chunked, _layer_prefix
 
 EPS = 1e-5
 CORE_PARAMS = ("conv1d.weight", "conv1d.bias", "dt_bias", "A_log", "D", "norm.weight")
+# carry_no_decay: dS crosses a chunk boundary without its exp(s_last) | carry_reset: dS of the chunks behind is dropped at every
+# boundary but the first one crossed | pad_dt: the last chunk is staged as Q rows and its rows t >= L keep the dt of the rows that
+# follow in memory (x, B, C, dy are 0 there) | conv_across_reads: the conv backward's taps reach from the end of read b into read
+# b + 1 | no_ub: ddt without its ub term
+DEFECTS = ("carry_no_decay", "carry_reset", "pad_dt", "conv_across_reads", "no_ub")
 
 
 def dims_of(p: dict) -> tuple[int, int, int]:
@@ -60,9 +68,9 @@ def _rcumsum(v, dim):
     return torch.flip(torch.cumsum(torch.flip(v, (dim,)), dim), (dim,))
 
 
-def scan_backward(x, dt, A, Bm, Cm, Dv, dy, Q: int = 64) -> dict:
+def scan_backward(x, dt, A, Bm, Cm, Dv, dy, Q: int = 64, defect: str | None = None) -> dict:
     """The chunked backward of `scan_chunked` (y includes D x).  x, dy [B, L, H, P], dt [B, L, H], A, Dv [H], Bm, Cm [B, L, N].
-    -> dx, ddt, dA, dB, dC, dD and ddt_abs, dA_abs (sums of the absolute terms)."""
+    -> dx, ddt, dA, dB, dC, dD and ddt_abs, dA_abs, dD_abs (sums of the absolute terms)."""
     Bn, L, H, P = x.shape
     zero = torch.zeros((), dtype=x.dtype)
     states, S = [], x.new_zeros(Bn, H, Bm.shape[-1], P)
@@ -102,7 +110,7 @@ def scan_backward(x, dt, A, Bm, Cm, Dv, dy, Q: int = 64) -> dict:
         ds = K.sum(2) - K.sum(1) + r - u
         ds[:, -1] = ds[:, -1] + u.sum(1) + e_last * dot
         da = _rcumsum(ds, 1)
-        ddt[:, c0:c1] = Kl.sum(1) + ub + A * da
+        ddt[:, c0:c1] = Kl.sum(1) + (0 if defect == "no_ub" else ub) + A * da
         dA = dA + (da * dtc).sum((0, 1))
         ub_a = f * torch.einsum("bjn,bjhn->bjh", Bc.abs(), XdS.abs())
         ds_a = K.abs().sum(2) + K.abs().sum(1) + torch.einsum("bin,bihn->bih", Cc.abs(), dCi.abs()) + ub_a * dtc
@@ -110,12 +118,29 @@ def scan_backward(x, dt, A, Bm, Cm, Dv, dy, Q: int = 64) -> dict:
         da_a = _rcumsum(ds_a, 1)
         ddt_abs[:, c0:c1] = Kl.abs().sum(1) + ub_a + A.abs() * da_a
         dA_abs = dA_abs + (da_a * dtc).sum((0, 1))
-        dS = e_last[:, :, None, None] * dS + torch.einsum("bin,bih,bihp->bhnp", Cc, e, dyc)
-    return {"dx": dx, "ddt": ddt, "dA": dA, "dB": dB, "dC": dC, "dD": (dy * x).sum((0, 1, 3)), "ddt_abs": ddt_abs, "dA_abs": dA_abs}
+        carried = e_last[:, :, None, None] * dS
+        if defect == "carry_no_decay":
+            carried = dS
+        elif defect == "carry_reset" and ci < len(states) - 1:
+            carried = torch.zeros_like(dS)
+        dS = carried + torch.einsum("bin,bih,bihp->bhnp", Cc, e, dyc)
+    return {"dx": dx, "ddt": ddt, "dA": dA, "dB": dB, "dC": dC, "dD": (dy * x).sum((0, 1, 3)), "ddt_abs": ddt_abs, "dA_abs": dA_abs,
+            "dD_abs": (dy * x).abs().sum((0, 1, 3))}
 
 
-def core_backward(zx: torch.Tensor, p: dict, dout: torch.Tensor, Q: int = 64) -> dict:
-    """The hand formulas: -> "out", "dzxbcdt", one entry per CORE_PARAMS key, and "A_log_abs", "dt_bias_abs", "dzxbcdt_dt_abs"."""
+def _scan_backward_padded(x, dt, A, Bm, Cm, Dv, dy, Q: int) -> dict:
+    """`scan_backward` with the last chunk staged as Q rows: x, B, C, dy zero past L, dt that of the rows that follow in the flattened
+    [B L] rows (read b + 1's first ones; behind the last read, read 0's)."""
+    L = x.shape[1]
+    n = -L % Q
+    zp = lambda t: torch.cat([t, torch.zeros_like(t[:, :n])], dim=1)           # noqa: E731
+    sb = scan_backward(zp(x), torch.cat([dt, torch.roll(dt, -1, 0)[:, :n]], dim=1), A, zp(Bm), zp(Cm), Dv, zp(dy), Q=Q)
+    return {k: (v[:, :L] if v.dim() > 1 else v) for k, v in sb.items()}
+
+
+def core_backward(zx: torch.Tensor, p: dict, dout: torch.Tensor, Q: int = 64, defect: str | None = None) -> dict:
+    """The hand formulas: -> "out", "dzxbcdt", one entry per CORE_PARAMS key, "dzxbcdt_dt_abs" and "<key>_abs" for every CORE_PARAMS
+    key.  `defect`: one of DEFECTS, planted."""
     di, H, N = dims_of(p)
     Bn, L, _ = zx.shape
     P = di // H
@@ -128,18 +153,26 @@ def core_backward(zx: torch.Tensor, p: dict, dout: torch.Tensor, Q: int = 64) ->
     out = g * r * w
     dg = r * w * dout - g * r ** 3 * (g * w * dout).mean(-1, keepdim=True)
     dys, dz = dg * sz, dg * ys * dsilu(z)
-    sb = scan_backward(x.reshape(Bn, L, H, P), dt, A, Bm, Cm, p["D"], dys.reshape(Bn, L, H, P), Q=Q)
+    if defect == "pad_dt":
+        sb = _scan_backward_padded(x.reshape(Bn, L, H, P), dt, A, Bm, Cm, p["D"], dys.reshape(Bn, L, H, P), Q)
+    else:
+        sb = scan_backward(x.reshape(Bn, L, H, P), dt, A, Bm, Cm, p["D"], dys.reshape(Bn, L, H, P), Q=Q, defect=defect)
     sg = torch.sigmoid(raw + p["dt_bias"])
     draw, draw_abs = sb["ddt"] * sg, sb["ddt_abs"] * sg
     du = torch.cat([sb["dx"].reshape(Bn, L, di), sb["dB"], sb["dC"]], dim=-1) * dsilu(u)
     xpad = F.pad(xBC, (0, 0, D_CONV - 1, 0))                                             # [B, L + 3, conv_dim]
     dupad = F.pad(du, (0, 0, 0, D_CONV - 1))
+    if defect == "conv_across_reads":
+        dupad[:-1, L:] = du[1:, :D_CONV - 1]
     cw = p["conv1d.weight"][:, 0, :]                                                      # [conv_dim, 4]
     dcw = torch.stack([(du * xpad[:, k:k + L]).sum((0, 1)) for k in range(D_CONV)], dim=-1)
+    dcw_abs = torch.stack([(du * xpad[:, k:k + L]).abs().sum((0, 1)) for k in range(D_CONV)], dim=-1)
     dxBC = sum(cw[:, k] * dupad[:, D_CONV - 1 - k:D_CONV - 1 - k + L] for k in range(D_CONV))
     return {"out": out, "dzxbcdt": torch.cat([dz, dxBC, draw], dim=-1), "conv1d.weight": dcw[:, None, :], "conv1d.bias": du.sum((0, 1)),
             "dt_bias": draw.sum((0, 1)), "A_log": A * sb["dA"], "D": sb["dD"], "norm.weight": (dout * g * r).sum((0, 1)),
-            "A_log_abs": A.abs() * sb["dA_abs"], "dt_bias_abs": draw_abs.sum((0, 1)), "dzxbcdt_dt_abs": draw_abs}
+            "A_log_abs": A.abs() * sb["dA_abs"], "dt_bias_abs": draw_abs.sum((0, 1)), "dzxbcdt_dt_abs": draw_abs,
+            "conv1d.weight_abs": dcw_abs[:, None, :], "conv1d.bias_abs": du.abs().sum((0, 1)), "D_abs": sb["dD_abs"],
+            "norm.weight_abs": (dout * g * r).abs().sum((0, 1))}
 
 
 def autograd_core(zx: torch.Tensor, p: dict, dout: torch.Tensor, sequential: bool = False) -> dict:

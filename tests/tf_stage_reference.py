@@ -188,12 +188,15 @@ def forward(sd: dict, ids, dtype=torch.float64, fmt: Fmt = EXACT, trace: dict | 
 def statistic(got, ref, den=None) -> torch.Tensor:
     """The per-position error [B, n] (float64) of `got` against the float64 `ref`.
       rows [B, n, C]:   max_c |got - ref| / max_c |ref|, the position's own row maximum as denominator;
-      `den` [B] given:  |got - ref| / den[b] per entry of [B, n] (the pooling scores, over the read's max |score|).
+      `den` [B] given:  |got - ref| / den[b] per entry of [B, n] (the pooling scores, over the read's max |score|);
+      `den` [B, n] given with rows [B, n, C]:  max_c |got - ref| / den[b, n], a row's own sum of absolute terms (tests/grad_rows.py).
     A zero denominator demands an exact result: 0 where got == ref, inf elsewhere."""
     got, ref = got.double(), ref.double()
     diff = (got - ref).abs()
     if den is None:
         num, d = diff.amax(-1), ref.abs().amax(-1)
+    elif den.dim() == 2:
+        num, d = diff.amax(-1), den.double()
     else:
         num, d = diff, den.double()[:, None].expand_as(diff)
     return torch.where(d > 0, num / d.clamp_min(1e-300), torch.where(num == 0, torch.zeros_like(num), torch.full_like(num, float("inf"))))
