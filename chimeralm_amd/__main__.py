@@ -333,6 +333,8 @@ def finetune(
                                         "arithmetic of the validation forwards"),
     hyena_core: str = typer.Option("engine", "--hyena-core", help="With --train-backbone, the Hyena operator's core: engine (the HIP "
                                    "op; reads beyond 8,193 tokens take torch) | torch (conv1d and rfft / irfft)"),
+    hyena_long_core: str = typer.Option("torch", "--hyena-long-core", help="With --train-backbone and --hyena-core engine, the core of "
+                                        "reads of 8,194 to 32,769 tokens: torch | engine (the segmented HIP op)"),
 ):
     """Fine-tune the classifier head on labelled reads with the backbone frozen, or with --train-backbone the whole net (writes
     model.safetensors and metrics.tsv)."""
@@ -341,6 +343,8 @@ def finetune(
 
     if hyena_core not in ("engine", "torch"):
         raise typer.BadParameter("--hyena-core must be engine or torch")
+    if hyena_long_core not in ("torch", "engine"):
+        raise typer.BadParameter("--hyena-long-core must be torch or engine")
 
     if precision not in TRAIN_PRECISIONS:
         raise typer.BadParameter("--precision must be fp16x3 or fp32: the head trains on the rows of the exact kernels")
@@ -356,7 +360,8 @@ def finetune(
     torch.cuda.set_device(device)
     kw = dict(precision=precision, selfcheck=False, freeze_backbone=True)
     if train_backbone:
-        kw = dict(precision=precision, selfcheck=False, freeze_backbone=False, trainable=True, hyena_core=hyena_core)
+        kw = dict(precision=precision, selfcheck=False, freeze_backbone=False, trainable=True, hyena_core=hyena_core,
+                  hyena_long_core=hyena_long_core)
     if ckpt_path is not None:
         log.info(f"Loading model from {ckpt_path}")
         model = lm.ChimeraLM.new(**kw).load_reference_checkpoint(ckpt_path)

@@ -135,6 +135,9 @@ SYMBOLS = {
     "clm_hyena_train_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "clm_hyena_train_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
     "clm_hyena_train_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7),
+    "clm_hyena_longtrain_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "clm_hyena_longtrain_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "clm_hyena_longtrain_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 7),
     "clm_tf_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     "clm_tf_load_weight": (C.c_int, [_H, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "clm_tf_finalize": (C.c_int, [_H]),

@@ -16,8 +16,8 @@ LIB = CSRC / "libchimeralm_hip.so"
 # hipcc's per-kernel resource remarks of the last build (registers, scratch, LDS): tests/test_kernel_resources.py holds the hot
 # kernels to "no scratch" -- spills there are vector-memory traffic inside loops that were tuned to hide it (HISTORY.md section 4.7)
 RESOURCES = CSRC / "kernel_resources.txt"
-SOURCES = ["clm_api.hip", "gemm.hip", "gemm16.hip", "tail32.hip", "hyena_conv.hip", "hyena_train.hip", "head.hip", "pool_train.hip", "attn_weights.hip", "trajectory.hip", "pad_prefix.hip", "lone_token.hip", "attention.hip", "attention_train.hip", "tf_model.hip", "tf_fp32.hip", "cnn.hip", "cnn_train.hip", "mamba.hip", "mamba_verdict.hip", "mamba_train.hip", "eval_metrics.hip", "explain.hip", "longread.hip", "longread_plan.cpp", "bucket.hip", "bucket_plan.cpp", "bam_feeder.cpp", "bam_filter.cpp"]
-HEADERS = ["clm_common.h", "handle_host.h", "clm_lab.h", "head_dense.h", "mfma32_common.h", "attention_tiles.h", "mamba_common.h", "cnn_common.h", "gemm_common.h", "gemm16_common.h", "fft_core.h", "fft_passes.h", "bgzf.h", "longread_plan.h"]
+SOURCES = ["clm_api.hip", "gemm.hip", "gemm16.hip", "tail32.hip", "hyena_conv.hip", "hyena_train.hip", "hyena_longtrain.hip", "head.hip", "pool_train.hip", "attn_weights.hip", "trajectory.hip", "pad_prefix.hip", "lone_token.hip", "attention.hip", "attention_train.hip", "tf_model.hip", "tf_fp32.hip", "cnn.hip", "cnn_train.hip", "mamba.hip", "mamba_verdict.hip", "mamba_train.hip", "eval_metrics.hip", "explain.hip", "longread.hip", "longread_plan.cpp", "bucket.hip", "bucket_plan.cpp", "bam_feeder.cpp", "bam_filter.cpp"]
+HEADERS = ["clm_common.h", "handle_host.h", "clm_lab.h", "head_dense.h", "mfma32_common.h", "attention_tiles.h", "mamba_common.h", "cnn_common.h", "gemm_common.h", "gemm16_common.h", "fft_core.h", "fft_passes.h", "hyena_train_blocks.h", "bgzf.h", "longread_plan.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 

@@ -212,8 +212,11 @@ class HyenaDna(nn.Module):
                  freeze_backbone: bool = False, precision: str = "fp16c", chunk_reads: int = 256,
                  selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
                  attention_top_k: int | None = None, trajectory_stride: int | None = None, trainable: bool = False,
-                 hyena_core: str = "engine"):
+                 hyena_core: str = "engine", hyena_long_core: str = "torch"):
         super().__init__()
+        if hyena_long_core not in ("torch", "engine"):
+            raise ValueError('hyena_long_core must be "torch" (reads beyond 8,193 tokens train on conv1d and rfft / irfft) or "engine" '
+                             "(the segmented HIP op up to 32,769 tokens, csrc/hyena_longtrain.hip)")
         if hyena_core not in ("engine", "torch"):
             raise ValueError('hyena_core must be "engine" (the HIP op, csrc/hyena_train.hip) or "torch" (conv1d and rfft / irfft)')
         if number_of_classes != 2:
@@ -250,8 +253,10 @@ class HyenaDna(nn.Module):
         # training of the whole net (hyenatrain.py): with `trainable` and an unfrozen backbone, in train() and under
         # autograd, the forward builds a graph to every parameter, in exact fp32 whatever `precision` says.  `hyena_core`: the
         # operator's core on the engine or in torch; `embed_dropout`: the backbone's only dropout, on the embedding output, drawn from
-        # `dropout_generator` (None: torch's default generator); `last_train_core`: the core the last training forward took
-        self.trainable, self.hyena_core = bool(trainable), hyena_core
+        # `dropout_generator` (None: torch's default generator); `last_train_core`: the core the last training forward took.
+        # `hyena_long_core`: with hyena_core="engine", where reads of 8,194 ... 32,769 tokens train -- "torch", or "engine": the segmented
+        # op (last_train_core "engine-long")
+        self.trainable, self.hyena_core, self.hyena_long_core = bool(trainable), hyena_core, hyena_long_core
         self.embed_dropout = 0.1
         self.dropout_generator = None
         self.last_train_core = None

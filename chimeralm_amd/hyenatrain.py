@@ -14,6 +14,10 @@ The op is stateless: four layers make four live autograd nodes that keep zc, c a
 path, the path of reads beyond the op's 8,193 tokens (taken automatically, logged once, visible in `net.last_train_core`) and a
 forward that runs on CPU tensors.
 
+`hyena_long_core="engine"` (default "torch") sends reads of 8,194 ... 32,769 tokens to the segmented op instead
+(csrc/hyena_longtrain.hip, `clm_hyena_longtrain_*`, `HyenaLongCore`; `net.last_train_core == "engine-long"`): the same operator over
+8,192-token segments.
+
 Deliberate differences from the reference: the embedding dropout is drawn from `net.dropout_generator`, not the
 reference's stream; the training arithmetic is exact fp32 whatever the module's inference `precision`; the backbone is the restated
 HyenaDNA algorithm, not the Hub's remote code, which the reference does not pin either.
@@ -32,8 +36,10 @@ from .headtrain import head_mlp
 log = logging.getLogger("chimeralm_amd")
 DM = 256
 MAX_ENGINE_TOKENS = 8193                     # one power-of-two transform of at most 16384 points (include/chimeralm_hip.h)
+MAX_LONG_TOKENS = 32769                      # the segmented op: up to five 8192-token segments (csrc/hyena_longtrain.hip)
 MOD_SHIFT = 0.05                             # HyenaExponentialModulation.shift
 CORES = ("engine", "torch")
+LONG_CORES = ("torch", "engine")
 _long_read_logged = False
 
 
@@ -46,11 +52,20 @@ def _check(rc: int, what: str, B: int, L: int):
         raise HyenaTrainError(f"{what}(B = {B}, L = {L}): {abi_error(rc)} (include/chimeralm_hip.h)")
 
 
+def _workspace_bytes(op: str, B: int, L: int) -> int:
+    n = int(getattr(N.load(), f"clm_{op}_workspace_bytes")(int(B), int(L)))
+    _check(n, f"clm_{op}_workspace_bytes", B, L)
+    return n
+
+
 def workspace_bytes(B: int, L: int) -> int:
     """Bytes of scratch one call of that shape takes (the formula of include/chimeralm_hip.h); raises for a shape the op refuses."""
-    n = int(N.load().clm_hyena_train_workspace_bytes(int(B), int(L)))
-    _check(n, "clm_hyena_train_workspace_bytes", B, L)
-    return n
+    return _workspace_bytes("hyena_train", B, L)
+
+
+def long_workspace_bytes(B: int, L: int) -> int:
+    """The same for the segmented op (`clm_hyena_longtrain_*`, 1 <= L <= 32,769)."""
+    return _workspace_bytes("hyena_longtrain", B, L)
 
 
 def _checked(B: int, L: int, **tensors):
@@ -63,31 +78,50 @@ def _checked(B: int, L: int, **tensors):
                              f"(contiguous: {t.is_contiguous()}) on {t.device}")
 
 
-def core_forward(zc, sw, sb, k, D):
-    """-> c, y [B, 256, L] of zc [B, 768, L], sw [768, 3], sb [768], k [256, L], D [256] (csrc/hyena_train.hip)."""
+def _forward(op: str, zc, sw, sb, k, D):
     if zc.dim() != 3:
         raise ValueError("zc must be [B, 768, L]")
     B, _, L = zc.shape
     _checked(B, L, zc=zc, sw=sw, sb=sb, k=k, D=D)
-    ws = torch.empty(workspace_bytes(B, L), dtype=torch.uint8, device=zc.device)
+    ws = torch.empty(_workspace_bytes(op, B, L), dtype=torch.uint8, device=zc.device)
     c, y = torch.empty((B, DM, L), dtype=torch.float32, device=zc.device), torch.empty((B, DM, L), dtype=torch.float32, device=zc.device)
-    _check(N.load().clm_hyena_train_forward(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), B, L, c.data_ptr(),
-                                            y.data_ptr(), ws.data_ptr(), stream_of(zc)), "clm_hyena_train_forward", B, L)
+    fn = getattr(N.load(), f"clm_{op}_forward")
+    _check(fn(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), B, L, c.data_ptr(), y.data_ptr(), ws.data_ptr(),
+              stream_of(zc)), f"clm_{op}_forward", B, L)
     return c, y
 
 
-def core_backward(zc, sw, sb, k, D, c, dy):
-    """-> dzc, dsw, dsb, dk, dD."""
+def _backward(op: str, zc, sw, sb, k, D, c, dy):
     if zc.dim() != 3:
         raise ValueError("zc must be [B, 768, L]")
     B, _, L = zc.shape
     _checked(B, L, zc=zc, sw=sw, sb=sb, k=k, D=D, c=c, dy=dy)
-    ws = torch.empty(workspace_bytes(B, L), dtype=torch.uint8, device=zc.device)
+    ws = torch.empty(_workspace_bytes(op, B, L), dtype=torch.uint8, device=zc.device)
     dzc, dsw, dsb, dk, dD = (torch.empty_like(t) for t in (zc, sw, sb, k, D))
-    _check(N.load().clm_hyena_train_backward(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), c.data_ptr(),
-                                             dy.data_ptr(), B, L, dzc.data_ptr(), dsw.data_ptr(), dsb.data_ptr(), dk.data_ptr(),
-                                             dD.data_ptr(), ws.data_ptr(), stream_of(zc)), "clm_hyena_train_backward", B, L)
+    fn = getattr(N.load(), f"clm_{op}_backward")
+    _check(fn(zc.data_ptr(), sw.data_ptr(), sb.data_ptr(), k.data_ptr(), D.data_ptr(), c.data_ptr(), dy.data_ptr(), B, L, dzc.data_ptr(),
+              dsw.data_ptr(), dsb.data_ptr(), dk.data_ptr(), dD.data_ptr(), ws.data_ptr(), stream_of(zc)), f"clm_{op}_backward", B, L)
     return dzc, dsw, dsb, dk, dD
+
+
+def core_forward(zc, sw, sb, k, D):
+    """-> c, y [B, 256, L] of zc [B, 768, L], sw [768, 3], sb [768], k [256, L], D [256] (csrc/hyena_train.hip)."""
+    return _forward("hyena_train", zc, sw, sb, k, D)
+
+
+def core_backward(zc, sw, sb, k, D, c, dy):
+    """-> dzc, dsw, dsb, dk, dD."""
+    return _backward("hyena_train", zc, sw, sb, k, D, c, dy)
+
+
+def long_core_forward(zc, sw, sb, k, D):
+    """`core_forward` by the segmented op (csrc/hyena_longtrain.hip): every 1 <= L <= 32,769."""
+    return _forward("hyena_longtrain", zc, sw, sb, k, D)
+
+
+def long_core_backward(zc, sw, sb, k, D, c, dy):
+    """`core_backward` by the segmented op."""
+    return _backward("hyena_longtrain", zc, sw, sb, k, D, c, dy)
 
 
 class HyenaCore(torch.autograd.Function):
@@ -104,6 +138,22 @@ class HyenaCore(torch.autograd.Function):
     def backward(ctx, dy):
         zc, sw, sb, k, D, c = ctx.saved_tensors
         return core_backward(zc, sw, sb, k, D, c, dy.float().contiguous())
+
+
+class HyenaLongCore(torch.autograd.Function):
+    """`HyenaCore` on the segmented op: reads of up to 32,769 tokens."""
+
+    @staticmethod
+    def forward(ctx, zc, sw, sb, k, D):
+        args = [t.detach().float().contiguous() for t in (zc, sw, sb, k, D)]
+        c, y = long_core_forward(*args)
+        ctx.save_for_backward(*args, c)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        zc, sw, sb, k, D, c = ctx.saved_tensors
+        return long_core_backward(zc, sw, sb, k, D, c, dy.float().contiguous())
 
 
 def torch_core(zc, sw, sb, k, D):
@@ -135,13 +185,15 @@ def implicit_filter(mixer, L: int) -> torch.Tensor:
 def _core_for(net, L: int, device) -> str:
     global _long_read_logged
     core = net.hyena_core
-    if core == "engine" and L > MAX_ENGINE_TOKENS:
+    if core == "engine" and MAX_ENGINE_TOKENS < L <= MAX_LONG_TOKENS and getattr(net, "hyena_long_core", "torch") == "engine":
+        core = "engine-long"
+    elif core == "engine" and L > MAX_ENGINE_TOKENS:
         if not _long_read_logged:
             log.warning("chimeralm_amd: reads of %d tokens are beyond the engine's Hyena training op (%d): they train on the torch core",
                         L, MAX_ENGINE_TOKENS)
             _long_read_logged = True
         core = "torch"
-    if core == "engine" and device.type != "cuda":
+    if core != "torch" and device.type != "cuda":
         raise RuntimeError('hyena_core="engine" runs on an MI355X only (move the batch to \'cuda\', or build the net with hyena_core="torch")')
     return core
 
@@ -152,7 +204,7 @@ def hyena_operator(net, mixer, u: torch.Tensor, core: str) -> torch.Tensor:
     zc = torch.matmul(mixer.in_proj.weight, u.transpose(1, 2)) + mixer.in_proj.bias.unsqueeze(-1)      # [B, 768, L]
     sw, sb = mixer.short_filter.weight.squeeze(1), mixer.short_filter.bias
     k, D = implicit_filter(mixer, L), mixer.filter_fn.bias
-    y = HyenaCore.apply(zc, sw, sb, k, D) if core == "engine" else torch_core(zc, sw, sb, k, D)
+    y = {"engine": HyenaCore.apply, "engine-long": HyenaLongCore.apply, "torch": torch_core}[core](zc, sw, sb, k, D)
     return torch.matmul(y.transpose(1, 2), mixer.out_proj.weight.t()) + mixer.out_proj.bias
 
 

@@ -16,7 +16,8 @@ class ChimeraLM:
     def new(cls, *, save_attention: bool = False, precision: str = "fp16c", chunk_reads: int = 256,
             selfcheck: bool | None = None, selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
             attention_top_k: int | None = None, freeze_backbone: bool = False,
-            trajectory_stride: int | None = None, trainable: bool = False, hyena_core: str = "engine") -> ClassificationLit:
+            trajectory_stride: int | None = None, trainable: bool = False, hyena_core: str = "engine",
+            hyena_long_core: str = "torch") -> ClassificationLit:
         """Randomly initialised model of the production architecture (lm.py:39-61).  `precision` / `selfcheck`: see
         `chimeralm_amd.hyena.HyenaDna` -- the default "fp16c" is measured against the exact-fp32 kernels on the loaded weights
         before the first batch and replaced by them if it is more than `selfcheck_tol` off."""
@@ -30,6 +31,7 @@ class ChimeraLM:
                 precision=precision, chunk_reads=chunk_reads, selfcheck=selfcheck, selfcheck_tol=selfcheck_tol,
                 selfcheck_every=selfcheck_every, attention_top_k=attention_top_k, freeze_backbone=freeze_backbone,
                 trajectory_stride=trajectory_stride, trainable=trainable, hyena_core=hyena_core,
+                hyena_long_core=hyena_long_core,
             ),
             optimizer=partial(torch.optim.AdamW, lr=0.0001, weight_decay=0.01),
             scheduler=partial(torch.optim.lr_scheduler.ReduceLROnPlateau, mode="min", factor=0.1, patience=10),
@@ -43,13 +45,13 @@ class ChimeraLM:
                         selfcheck_tol: float = 5e-4, selfcheck_every: int = 16,
                         attention_top_k: int | None = None, freeze_backbone: bool = False,
                         trajectory_stride: int | None = None, trainable: bool = False,
-                        hyena_core: str = "engine") -> ClassificationLit:
+                        hyena_core: str = "engine", hyena_long_core: str = "torch") -> ClassificationLit:
         """Released weights (lm.py:12-37).  `model_name` is a local directory / file holding `model.safetensors`
         or a Lightning `.ckpt`; a Hub repo id is resolved through the local HF cache only (no network here)."""
         model = cls.new(save_attention=save_attention, precision=precision, chunk_reads=chunk_reads, selfcheck=selfcheck,
                         selfcheck_tol=selfcheck_tol, selfcheck_every=selfcheck_every, attention_top_k=attention_top_k,
                         freeze_backbone=freeze_backbone, trajectory_stride=trajectory_stride, trainable=trainable,
-                        hyena_core=hyena_core)
+                        hyena_core=hyena_core, hyena_long_core=hyena_long_core)
         p = Path(model_name)
         if p.is_dir():
             p = p / "model.safetensors"

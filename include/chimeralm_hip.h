@@ -337,6 +337,28 @@ int clm_hyena_train_backward(const float* zc, const float* sw, const float* sb, 
                              const float* dy, int B, int L, float* dzc, float* dsw, float* dsb, float* dk, float* dD, void* workspace,
                              void* stream);
 
+/* ---- the same core for reads of up to 32,769 tokens (csrc/hyena_longtrain.hip; additive under ABI 6) ----
+ * The operator, the tensors, the outputs and the promises of clm_hyena_train_* above (no floating-point atomics, identical bits
+ * from identical calls, sums over the reads in read order, c, y and dzc of a read independent of the other reads), computed as a
+ * uniformly partitioned convolution: S = ceil(L / 8192) segments of P = 8192 tokens, overlap-save transforms of N = 16384 points
+ * held in LDS, the spectra of the segments kept in the workspace and their products added per segment before one inverse.
+ * Covered: every 1 <= L <= 32769 (S = 1 ... 5; a lone last token, L = 8192 n + 1, is a segment of its own).  The results agree
+ * with clm_hyena_train_* to rounding where both cover L, not bit for bit.
+ * `workspace`: clm_hyena_longtrain_workspace_bytes(B, L) bytes, with H = 8193 bins per spectrum,
+ *       4 * (16384 + 512 * S * H + 1024 * B * S * H + B * 256 * L + B * 256 * 16)   rounded up to 16
+ * (the twiddle table; the S filter spectra of the 256 channels, computed once per call from k; two spectra per (read, channel,
+ * segment) -- the backward's FFT([dc_m ; dc_m+1]) and FFT([g_m ; 0]); the forward keeps one per channel there --; the per-read dk
+ * rows; the per-read parameter partials).  It holds nothing between calls.
+ * CLM_E_INVALID, and nothing is launched: B < 1, L < 1 or B > 65535; a pointer that is NULL or off 4 bytes.  CLM_E_UNSUPPORTED:
+ * L > 32769.  clm_hyena_longtrain_workspace_bytes returns the (negative) code instead of a size.  Asynchronous on `stream`; nothing
+ * is written beyond the stated extents. */
+int64_t clm_hyena_longtrain_workspace_bytes(int B, int L);
+int clm_hyena_longtrain_forward(const float* zc, const float* sw, const float* sb, const float* k, const float* D, int B, int L,
+                                float* c_out, float* y_out, void* workspace, void* stream);
+int clm_hyena_longtrain_backward(const float* zc, const float* sw, const float* sb, const float* k, const float* D, const float* c,
+                                 const float* dy, int B, int L, float* dzc, float* dsw, float* dsb, float* dk, float* dD,
+                                 void* workspace, void* stream);
+
 /* The whole SequenceCNNTransformer forward (transformer.py:88-104; configuration of configs/model/transformer.yaml:3-12:
  * vocab 12, d_model 256, kernel 3, 8 heads, feed-forward 1024, `n_layers` encoder layers) behind the same `net` boundary as
  * HyenaDna: forward(input_ids[B, L], input_quals=None) -> logits fp32 [B, 2].  Same conventions as the clm_* calls above;

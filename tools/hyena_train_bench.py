@@ -1,15 +1,17 @@
 """What a training step of the whole HyenaDna net costs on one MI355X, with the Hyena operator's core on the engine and in torch
-(chimeralm_amd/hyenatrain.py, csrc/hyena_train.hip).
+(chimeralm_amd/hyenatrain.py, csrc/hyena_train.hip, csrc/hyena_longtrain.hip).
 
     python tools/hyena_train_bench.py [--cases 8x8193,2x32769] [--dropout 0.1] [--warmup 2] [--steps 10] [-o FILE]
 
 The production architecture (lm.ChimeraLM.new), the module's own seeded initialisation, token ids uniform over A/C/G/T.  Timed with
 device events on the launch stream.  Where both cores cover the length they run in the same job on the same weights, ALTERNATING step by step (engine, torch, engine, ...), so that clocks and neighbours move both alike; reported per core:
 the median of the timed steps and their spread (min .. max).  A step is zero_grad, forward, loss, backward; no optimizer.  Reads of
-more than 8,193 tokens run the torch core alone.  Then, on one layer's tensors: the core forward and backward of the engine
-(clm_hyena_train_forward / _backward) and of torch (conv1d, rfft / irfft at n = 2 L, autograd), and the fp32 INFERENCE forward of the
+8,194 to 32,769 tokens alternate the segmented engine op ("engine-long", hyena_long_core="engine") with the torch core in the same
+way; longer ones run the torch core alone.  Then, on one layer's tensors: the core forward and backward of the engine
+(clm_hyena_train_* or clm_hyena_longtrain_*) and of torch (conv1d, rfft / irfft at n = 2 L, autograd), and the fp32 INFERENCE forward of the
 same batch.  Live bytes: torch's peak allocation over one step of each core (the engine's scratch is a torch tensor, so it is
-counted).  One line per case, also appended to FILE (profiles/hyena_train_bench.txt is one)."""
+counted).  One line per case, also appended to FILE (profiles/hyena_train_bench.txt is one; profiles/hyena_longtrain_bench.txt is
+`--cases 2x32769,4x16385,2x32768`)."""
 from __future__ import annotations
 
 import argparse
@@ -73,12 +75,12 @@ def main():
         labels = torch.arange(B, device=dev) % 2
 
         def step(core):
-            net.hyena_core = core
+            net.hyena_core, net.hyena_long_core = ("engine", "engine") if core == "engine-long" else (core, "torch")
             lit.zero_grad(set_to_none=True)
             lit.training_step({"input_ids": ids, "labels": labels}).backward()
 
         lit.train()
-        wanted = ht.CORES if L <= ht.MAX_ENGINE_TOKENS else ("torch",)
+        wanted = ht.CORES if L <= ht.MAX_ENGINE_TOKENS else ("engine-long", "torch") if L <= ht.MAX_LONG_TOKENS else ("torch",)
         live, failed = {}, {}
         for core in wanted:                                           # one step each, alone: peak live bytes, and whether it fits at all
             torch.cuda.empty_cache()
@@ -99,7 +101,7 @@ def main():
             for core in cores:
                 ts[core].append(event_ms(lambda: step(core)))
         lit.zero_grad(set_to_none=True)
-        net.hyena_core = "engine"
+        net.hyena_core, net.hyena_long_core = "engine", "torch"
         # one layer's core, on tensors of its shapes and the layer's own filter
         mixer = net.backbone.backbone.layers[0].mixer
         with torch.no_grad():
@@ -107,11 +109,13 @@ def main():
             sw, sb, D = mixer.short_filter.weight.squeeze(1).contiguous(), mixer.short_filter.bias.detach(), mixer.filter_fn.bias.detach()
         zc, dy = torch.randn(B, 768, L, device=dev), torch.randn(B, 256, L, device=dev)
         part = ""
-        if "engine" in cores:
-            c, _ = ht.core_forward(zc, sw, sb, k, D)
-            t_ef = timed(lambda: ht.core_forward(zc, sw, sb, k, D), a.steps, a.warmup)
-            t_eb = timed(lambda: ht.core_backward(zc, sw, sb, k, D, c, dy), a.steps, a.warmup)
-            part += (f"engine core per layer: forward {fmt(t_ef)}, backward {fmt(t_eb)}, backward / forward "
+        for name, fwd, bwd in (("engine", ht.core_forward, ht.core_backward), ("engine-long", ht.long_core_forward, ht.long_core_backward)):
+            if name not in cores:
+                continue
+            c, _ = fwd(zc, sw, sb, k, D)
+            t_ef = timed(lambda: fwd(zc, sw, sb, k, D), a.steps, a.warmup)
+            t_eb = timed(lambda: bwd(zc, sw, sb, k, D, c, dy), a.steps, a.warmup)
+            part += (f"{name} core per layer: forward {fmt(t_ef)}, backward {fmt(t_eb)}, backward / forward "
                      f"{statistics.median(t_eb) / statistics.median(t_ef):.2f} | ")
             del c
         if "torch" in cores:
