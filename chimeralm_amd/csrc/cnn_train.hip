@@ -49,8 +49,13 @@ constexpr int CT_SLICES = 4;                       // the small reductions: 1,02
 constexpr int CT_TSIZE = cnn::K * cnn::VOC * D;        // floats of T / dT
 constexpr float CT_INV_SQRT2 = 0.7071067811865476f, CT_INV_SQRT_2PI = 0.3989422804014327f;
 
+// The normal cdf as 0.5 erfc(-u / sqrt 2), not 0.5 (1 + erf): the sum 1 + erf is a multiple of 2^-24, so below u = -5.4 it is 0 or a
+// few quanta next to a true 1e-8, and y, the pooling choice among such values, dy and every sum over dy of a channel whose BatchNorm
+// bias sits in GELU's far tail were good to a few per cent only.  erfc keeps its relative accuracy there; for u >= 0
+// the two agree to rounding.
+__device__ __forceinline__ float ct_cdf(float u) { return 0.5f * erfcf(-u * CT_INV_SQRT2); }
 __device__ __forceinline__ float ct_gelu_grad(float u) {
-    const float cdf = 0.5f * (1.0f + erff(u * CT_INV_SQRT2));
+    const float cdf = ct_cdf(u);
     const float pdf = CT_INV_SQRT_2PI * expf(-0.5f * u * u);
     return fmaf(u, pdf, cdf);
 }
@@ -64,7 +69,10 @@ __device__ __forceinline__ double ct_combine(double v, double* red, int slice, i
     __syncthreads();
     return t;
 }
-__device__ __forceinline__ float ct_y(float z, float mu, float rstd, float g, float beta) { return gelu_erf(g * ((z - mu) * rstd) + beta); }
+__device__ __forceinline__ float ct_y(float z, float mu, float rstd, float g, float beta) {
+    const float u = g * ((z - mu) * rstd) + beta;
+    return u * ct_cdf(u);
+}
 
 }  // namespace
 

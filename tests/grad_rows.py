@@ -237,3 +237,51 @@ def worst(stat: torch.Tensor) -> float:
 
 def summary(ratios: dict) -> list[str]:
     return [f"RATIO {k:18s} worst engine / yardstick {v[0]:8.2f}   above the floor {v[1]:8.2f}" for k, v in ratios.items()]
+
+
+# ------------------------------------------------------------------------------------------------------------- the host files' comparisons
+# (tests/test_grad_rows_host.py and tests/test_cnn_train_rows_host.py: the yardstick's ceiling, a second evaluation, planted defects)
+CEILING = 1e-4
+K_SECOND = 32
+K_DEFECT = 16
+
+
+def ceiling(tag, rows):
+    lines = [f"CEILING {tag:44s} {name:16s} yardstick max {worst(st):.3e}  worst: {loc(*argmax_row(st))}" for name, st, loc in rows]
+    print("\n".join(lines))
+    bad = [ln for ln, (_, st, _) in zip(lines, rows) if not worst(st) < CEILING]
+    assert not bad, "\n".join(bad)
+
+
+def argmax_row(st):
+    b = int(st.amax(1).argmax())
+    return b, int(st[b].argmax())
+
+
+def second(tag, second_rows, yard_rows, assert_it=True):
+    names = {n for n, _, _ in second_rows}
+    lines, bad = [], []
+    hold(tag, second_rows, [r for r in yard_rows if r[0] in names], K_SECOND, lines, bad)
+    print("\n".join(lines))
+    if assert_it:
+        assert not bad, "\n".join(bad)
+    elif bad:
+        print("(reported only)\n" + "\n".join(bad))
+
+
+
+def planted(tag, defect_rows, yard_rows, old, expect_seen=True):
+    """The row gate's verdict on a planted variant (asserted) and the tensor-wide gate's (printed)."""
+    seen = []
+    for (name, d, loc), (_, y, _) in zip(defect_rows, yard_rows):
+        over = d / torch.clamp(K_DEFECT * y, min=FLOOR)
+        if float(over.max()) > 1.0:
+            b, i = argmax_row(over)
+            seen.append(f"{name}: {float(d[b, i]):.3e} against max(16 x {float(y[b, i]):.3e}, floor) at {loc(b, i)}; "
+                        f"{int((over > 1).sum())} of {over.numel()} rows")
+    old_seen = [f"{n} {e:.3e} > {bnd:.3e}" for n, e, bnd in old if not e <= bnd]
+    print(f"PLANTED {tag}\n  row gate:         " + ("SEES " + "\n                    ".join(seen) if seen else "blind") +
+          "\n  tensor-wide gate: " + ("SEES " + "; ".join(old_seen) if old_seen else "blind (worst " +
+                                      max((f"{e / bnd:.3f} of its bound, {n}" for n, e, bnd in old), key=lambda s: float(s.split()[0])) + ")"))
+    assert bool(seen) == expect_seen, tag
+    return bool(old_seen)

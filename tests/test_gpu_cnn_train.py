@@ -6,6 +6,9 @@ The bound of every comparison: err = max |engine - fp64| / max |fp64| must be <=
 float32 on the CPU for the same inputs, 32 x 2^-24) -- tests/test_gpu_headtrain.py's bound and floor (the factor covers the kernels'
 nested partial sums against torch's one level, the floor keeps a lucky CPU run from failing the test).
 
+Every tensor is held as a whole here, and the largest case stays below the grid caps of `ct_split`; tests/test_gpu_cnn_train_rows.py
+holds the same kernels row by row, under shaped inputs and at the capped grids.
+
 CLM_CNN_TRAIN_PARITY=<file> appends the measured ratios to that file (profiles/cnn_train_parity.txt is one).
 """
 from __future__ import annotations

@@ -27,32 +27,10 @@ import grad_rows as G
 import hyena_train_reference as HR
 import mamba_train_reference as MR
 
-CEILING = 1e-4
-K_SECOND = 32
-K_DEFECT = 16
-
-
-def _ceiling(tag, rows):
-    lines = [f"CEILING {tag:44s} {name:16s} yardstick max {G.worst(st):.3e}  worst: {loc(*_argmax(st))}" for name, st, loc in rows]
-    print("\n".join(lines))
-    bad = [ln for ln, (_, st, _) in zip(lines, rows) if not G.worst(st) < CEILING]
-    assert not bad, "\n".join(bad)
-
-
-def _argmax(st):
-    b = int(st.amax(1).argmax())
-    return b, int(st[b].argmax())
-
-
-def _second(tag, second_rows, yard_rows, assert_it=True):
-    names = {n for n, _, _ in second_rows}
-    lines, bad = [], []
-    G.hold(tag, second_rows, [r for r in yard_rows if r[0] in names], K_SECOND, lines, bad)
-    print("\n".join(lines))
-    if assert_it:
-        assert not bad, "\n".join(bad)
-    elif bad:
-        print("(reported only)\n" + "\n".join(bad))
+# the ceiling, the second evaluation's factor, the planted defects' factor and the three comparisons live in tests/grad_rows.py
+# (tests/test_cnn_train_rows_host.py shares them)
+CEILING, K_SECOND, K_DEFECT = G.CEILING, G.K_SECOND, G.K_DEFECT
+_ceiling, _argmax, _second, _planted = G.ceiling, G.argmax_row, G.second, G.planted
 
 
 # ------------------------------------------------------------------------------------------------------------- (a), (b)
@@ -118,23 +96,6 @@ def _old_mamba(ev, r64, r32):
 
 def _old_hyena(ev, r64, r32):
     return [(k,) + G.old_gate(ev[k], r64[k], r32[k], r64["den"].get(k)) for k in ("c", "y") + HR.CORE_GRADS]
-
-
-def _planted(tag, defect_rows, yard_rows, old, expect_seen=True):
-    """The row gate's verdict on a planted variant (asserted) and the tensor-wide gate's (printed)."""
-    seen = []
-    for (name, d, loc), (_, y, _) in zip(defect_rows, yard_rows):
-        over = d / torch.clamp(K_DEFECT * y, min=G.FLOOR)
-        if float(over.max()) > 1.0:
-            b, i = _argmax(over)
-            seen.append(f"{name}: {float(d[b, i]):.3e} against max(16 x {float(y[b, i]):.3e}, floor) at {loc(b, i)}; "
-                        f"{int((over > 1).sum())} of {over.numel()} rows")
-    old_seen = [f"{n} {e:.3e} > {bnd:.3e}" for n, e, bnd in old if not e <= bnd]
-    print(f"PLANTED {tag}\n  row gate:         " + ("SEES " + "\n                    ".join(seen) if seen else "blind") +
-          "\n  tensor-wide gate: " + ("SEES " + "; ".join(old_seen) if old_seen else "blind (worst " +
-                                      max((f"{e / bnd:.3f} of its bound, {n}" for n, e, bnd in old), key=lambda s: float(s.split()[0])) + ")"))
-    assert bool(seen) == expect_seen, tag
-    return bool(old_seen)
 
 
 MAMBA_PLANTED = [  # (defect, case): what reaches which rows
