@@ -116,6 +116,12 @@ __device__ __forceinline__ f32x2 gelu_tanh2(f32x2 x) {
 }
 // exact gelu (erf form): nn.GELU() of the head (hyena.py:38,47,162)
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.7071067811865476f)); }
+// The normal cdf of the TRAINING kernels (cnn_train.hip, pool_train.hip: g = u cdf and gelu' = cdf + u pdf feed sums over tokens), as
+// 0.5 erfc(-u / sqrt 2), not 0.5 (1 + erf): the sum 1 + erf is a multiple of 2^-24, so below u = -5.4 it is 0 or a few quanta next to
+// a true 1e-8, and y, the pooling choice among such values, dy and every sum over dy of a channel whose bias sits in GELU's far tail
+// were good to a few per cent only.  erfc keeps its relative accuracy there; for u >= 0 the two agree to
+// rounding.  gelu_erf above stays as it is: a forward value's absolute error of 2^-25 |u| is below the floor of the sum it enters.
+__device__ __forceinline__ float normal_cdf(float u) { return 0.5f * erfcf(-u * 0.7071067811865476f); }
 
 // ---- round 4: lo bytes of 16-bit activations (fp16c) -----------------------------------------------------------------------------
 // x = fp16(x) + lo, |lo| <= 2^-11 |x|: one e5m2 byte carries lo to 3 significant bits, i.e. x to ~15 bits instead of fp16's 11.

@@ -47,15 +47,11 @@ constexpr int CT_DT_GRID = 256;                    // dt: workgroups at most
 constexpr int CT_DT_SUB = 512;                     // dt: positions whose table rows are staged in LDS at a time
 constexpr int CT_SLICES = 4;                       // the small reductions: 1,024 threads = 256 columns x 4 slices of the summed index
 constexpr int CT_TSIZE = cnn::K * cnn::VOC * D;        // floats of T / dT
-constexpr float CT_INV_SQRT2 = 0.7071067811865476f, CT_INV_SQRT_2PI = 0.3989422804014327f;
+constexpr float CT_INV_SQRT_2PI = 0.3989422804014327f;
 
-// The normal cdf as 0.5 erfc(-u / sqrt 2), not 0.5 (1 + erf): the sum 1 + erf is a multiple of 2^-24, so below u = -5.4 it is 0 or a
-// few quanta next to a true 1e-8, and y, the pooling choice among such values, dy and every sum over dy of a channel whose BatchNorm
-// bias sits in GELU's far tail were good to a few per cent only.  erfc keeps its relative accuracy there; for u >= 0
-// the two agree to rounding.
-__device__ __forceinline__ float ct_cdf(float u) { return 0.5f * erfcf(-u * CT_INV_SQRT2); }
+// (the cdf is clm_common.h normal_cdf, 0.5 erfc(-u / sqrt 2), shared with pool_train.hip; the comment there says why)
 __device__ __forceinline__ float ct_gelu_grad(float u) {
-    const float cdf = ct_cdf(u);
+    const float cdf = normal_cdf(u);
     const float pdf = CT_INV_SQRT_2PI * expf(-0.5f * u * u);
     return fmaf(u, pdf, cdf);
 }
@@ -71,7 +67,7 @@ __device__ __forceinline__ double ct_combine(double v, double* red, int slice, i
 }
 __device__ __forceinline__ float ct_y(float z, float mu, float rstd, float g, float beta) {
     const float u = g * ((z - mu) * rstd) + beta;
-    return u * ct_cdf(u);
+    return u * normal_cdf(u);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // pool_train.hip -- the attention pooling of the Hyena head as a trainable layer: forward and backward on caller-supplied weights
 // (the frozen-backbone fine-tune, chimeralm_amd/headtrain.py).  Reference arithmetic:
 //   /root/reference/chimeralm/models/components/hyena.py:117-132, per read, with x_t = ln_f(h_t) (ln_f is backbone: frozen)
-//     u_t = W1 x_t + b1,  g_t = gelu_erf(u_t),  s_t = w2 . g_t + b2,  a = softmax_t(s) over ALL L positions,  p = sum_t a_t x_t
+//     u_t = W1 x_t + b1,  g_t = gelu_erf(u_t) (the backward: u_t normal_cdf(u_t)),  s_t = w2 . g_t + b2,  a = softmax_t(s) over ALL L,  p = sum_t a_t x_t
 //   backward, given dp = dloss/dp:
 //     ds_t = a_t ((x_t - p) . dp)          (sum_t a_t (x_t . dp) = p . dp: no reduction pass of its own)
 //     dw2 = sum ds_t g_t,  db2 = sum ds_t,  du_t = ds_t w2 * gelu'(u_t),  gelu'(u) = Phi(u) + u phi(u)
@@ -29,7 +29,7 @@ namespace {
 
 constexpr int RSD = 68;           // row stride (floats) of the feature-major du tile [256][64 tokens]: 16 rows of a ds_read_b128 lane
                                   // group fall on 16 different 16-byte bank groups (68 = 4 mod 64)
-constexpr float INV_SQRT2 = 0.7071067811865476f, INV_SQRT_2PI = 0.3989422804014327f;
+constexpr float INV_SQRT_2PI = 0.3989422804014327f;
 
 struct PoolBwdArgs {
     const float* rows;            // [B, L, 256] final residual rows (before ln_f)
@@ -149,12 +149,12 @@ __global__ __launch_bounds__(512) void pool_bwd_kernel(PoolBwdArgs m) {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
                         const float u = acc[mt][4 * q + e] + bq[e];
-                        const float cdf = 0.5f * (1.0f + erff(u * INV_SQRT2));
+                        const float cdf = normal_cdf(u);           // 0.5 erfc(-u / sqrt 2): exact in the far tail (clm_common.h)
                         const float pdf = INV_SQRT_2PI * expf(-0.5f * u * u);
                         Du[(c0 + 8 * q + e) * RSD + mt * 32 + lrow] = ds[mt] * (u * cdf);
                         acc[mt][4 * q + e] = ds[mt] * wq[e] * fmaf(u, pdf, cdf);
                     }
-                __builtin_amdgcn_sched_barrier(0);          // (one feature quad at a time: erff's temporaries of all 32 elements do not fit)
+                __builtin_amdgcn_sched_barrier(0);          // (one feature quad at a time: erfcf's temporaries of all 32 elements do not fit)
             }
         }
         __syncthreads();

@@ -162,7 +162,7 @@ DEFECTS = ("small_row", "m_covered", "dz_uncovered", "dz_unchosen", "across_read
 
 
 def _cdf(u):
-    """The normal cdf as 0.5 erfc(-u / sqrt 2), as the kernels take it (csrc/cnn_train.hip ct_cdf): 0.5 (1 + erf) is a multiple of
+    """The normal cdf as 0.5 erfc(-u / sqrt 2), as the kernels take it (csrc/clm_common.h normal_cdf): 0.5 (1 + erf) is a multiple of
     2^-25 in float32 and of 2^-54 in float64, and under `dead` (u near -6, cdf 1e-9) that left y, the choice among such values, dy
     and every sum over dy of the odd channels good to a few per cent in ANY float32 evaluation -- the yardstick read 3.4e-2 there."""
     return 0.5 * torch.special.erfc(u * -0.7071067811865476)

@@ -5,6 +5,11 @@ The bound of every comparison: err = max |engine - fp64| / max |fp64| must be <=
 float32 on the CPU for the same inputs, 32 x 2^-24).  The factor 8 covers the kernel's three nested levels of partial sums (tile,
 workgroup, grid) against torch's one; the floor of 32 fp32 roundoffs keeps a lucky CPU run from failing the test.
 
+The reference takes the normal cdf as 0.5 erfc(-u / sqrt 2) in both precisions (tests/headtrain_reference.py `cdf`), as the kernel does.
+db2 keeps dw2's bound and scale: the row file's sum |ds_t| denominator gives a LOOSER bound at nine of this file's ten shapes (float32
+yardstick on the CPU: 2.4e-5 - 1.3e-4 against 3.9e-6 - 1.8e-5; tighter only at 2 x 200 with w2 x 40).  tests/test_gpu_headtrain_rows.py
+holds the same kernels row by row.
+
 CLM_HEADTRAIN_PARITY=<file> appends the measured ratios of the parity cases to that file (profiles/headtrain_parity.txt is one).
 """
 from __future__ import annotations
